@@ -10,11 +10,20 @@ With N > 1 every rank runs its own [32,512] batch (utterances are independent: w
 data-path collective); value = N*K steps / max-over-ranks time.
 
 Sequence per rank: an untimed 3-step set-up call (builds the chain's conditioning table for all remaining timesteps and
-captures the step graph), W untimed warm-up steps, barrier, EXACTLY K timed steps of the same chain, barrier.  The
-once-per-chain table build is reported separately ("chain_setup_ms", ~4 ms against a 998-step chain of ~5.7 s).
+captures the step graph), W untimed warm-up steps, barrier, EXACTLY K timed steps of the same chain, barrier.  When the
+set-up, warm-up and timed steps together outrun the chain (998 steps at 1000 timesteps), a new chain starts from t = 998 on
+the latents as they stand, its conditioning table rebuilt as at the start of any chain.
 
-Extra objects: "roofline" (dominant kernel = the FFN causal-conv contraction, timed live with HIP
-events) and "cpu_baseline" (the CPU oracle timed on the host cores on a bounded sample, rank 0, N=1).
+A plain run does only that and prints the line (metric, value, unit, higher_is_better, dtype, ms_per_step and the workload's
+description).  --dump-outputs DIR then writes what the timed path computed -- the latents after the last timed step -- as
+DIR/latents.npy (fp32; other ranks' as latents_rank<r>.npy; --mode train: the last update's loss statistics and gradient
+norm and a fixed sample of the parameters it left); inputs and weights are seeded, so two builds compare output for output.
+
+--full adds the secondary figures of the same line (rank 0): "chain_setup_ms" (the once-per-chain table build, ~4 ms
+against a 998-step chain of ~5.7 s), "roofline" (dominant kernel = the FFN causal-conv contraction, timed live with HIP
+events), the committed PMC step traffic, the ancestral (DDPM) chain, and at N = 1 the other-precision, full-chain,
+conditional, refinement and training legs and "cpu_baseline" (the CPU oracle timed on the host cores on a bounded sample);
+the --no-* options below leave single legs out of a --full run.
 """
 import argparse
 import json
@@ -42,6 +51,11 @@ def parse():
     ap.add_argument("--timesteps", type=int, default=1000)
     ap.add_argument("--dtype", default="f16", choices=["f16", "bf16", "bf16x3", "f32"],
                     help="arithmetic of the contractions; f16 (default) = IEEE-half MFMA operands, the 2-byte mode inside north_star's 1e-2 budget")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary figures (chain set-up, roofline, profiles' traffic, DDPM chain, other precisions, full "
+                         "chain, conditional / refinement / training legs, CPU baseline); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (fp32)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-split", action="store_true", help="one stream per chain instead of two forked half-batches")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -49,12 +63,35 @@ def parse():
     ap.add_argument("--cpu-threads", type=int, default=0, help="cap on host threads of the CPU baseline (0 = every core this process may use)")
     ap.add_argument("--no-full-chain", action="store_true", help="skip the end-to-end 998-evaluation chain leg")
     ap.add_argument("--no-x3", action="store_true", help="skip the split-operand (bf16x3) leg")
-    ap.add_argument("--no-train", action="store_true", help="skip the two training legs of the default line")
+    ap.add_argument("--no-train", action="store_true", help="skip the two training legs of the --full line")
     ap.add_argument("--no-refine", action="store_true", help="skip the mask-predict refinement leg (SURVEY 8 f4)")
     ap.add_argument("--no-cond", action="store_true", help="skip the conditional-variant (guided chain) leg (SURVEY 8 f3)")
     ap.add_argument("--train-loss", default="vae", choices=["vae", "diffusion"], help="--mode train: which loss's update is the step")
     ap.add_argument("--no-f32", action="store_true", help="skip the exact-fp32 legs (20 steps + the full chain for the unit agreement)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_LIMIT = 64 << 20  # bytes of --dump-outputs in all
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array (torch tensor or numpy) as out_dir/<name>.npy, fp32 (fp64 stays fp64)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        if hasattr(a, "detach"):
+            a = a.detach().cpu()
+            a = (a.double() if a.dtype == torch.float64 else a.float()).numpy()
+        a = np.asarray(a, dtype=np.float64 if np.asarray(a).dtype == np.float64 else np.float32)
+        total += a.nbytes
+        assert total <= DUMP_LIMIT, f"--dump-outputs: more than {DUMP_LIMIT >> 20} MB"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def time_dominant_kernel(ops, _lib, packing, dev, B, T, dtype, iters=20):
@@ -489,7 +526,8 @@ def run_sampling(args, ctx):
     sched = scheduler.DDPMScheduler(args.timesteps)
     coef = sched.ddim_coef_table(dev)
     start = args.timesteps - 1  # "full 1000-step" chain: t = 998 ... 1 (last bullet)
-    assert W + K + 10 <= start - 1, "steps + warmup exceed the chain length"
+    if args.full:  # (the secondary legs below continue the chain for 7 more steps)
+        assert W + K + 10 <= start - 1, "--full: steps + warmup exceed the chain length"
     x = ops.randn((B, T, cfg.latent_dim), seed=1234 + rank, device=dev)  # x_T ~ N(0, I): the build's Philox
     lengths = torch.full((B,), T, dtype=torch.int32, device=dev)
 
@@ -501,32 +539,57 @@ def run_sampling(args, ctx):
             dist.barrier()
         torch.cuda.synchronize()
 
+    def chain_steps(n, pos, new_chain=False):
+        """n more steps of the chain whose next call starts at `pos`; -> the position after them.  A chain keeps its conditioning
+        table (built once per chain, for all its steps); one that has run out (its t = 1 update done) is followed by a new chain
+        from `start` on the latents as they stand, which builds its table again."""
+        while n > 0:
+            if pos <= 1:
+                pos, new_chain = start, True
+            k = min(n, pos - 1)
+            got = eng.ddim_loop(x, lengths, pos, coef, use_graph=not args.no_graph, max_evals=k, split=not args.no_split, keep_table=not new_chain)
+            assert got == k, (got, k)
+            n, pos, new_chain = n - k, pos - k, False
+        return pos
+
     SETUP = 3  # untimed: builds the chain's conditioning table and captures the step graph (the analogue of loading / compiling)
     with torch.cuda.stream(stream):
-        assert eng.ddim_loop(x, lengths, start, coef, use_graph=not args.no_graph, max_evals=SETUP, split=not args.no_split) == SETUP
-        pos = start - SETUP
-        if W > 0:
-            n = eng.ddim_loop(x, lengths, pos, coef, use_graph=not args.no_graph, max_evals=W, split=not args.no_split, keep_table=True)
-            assert n == W
-            pos -= W
+        pos = chain_steps(SETUP, start, new_chain=True)
+        pos = chain_steps(W, pos)
         barrier()
         t0 = time.perf_counter()
         # the timed K steps continue the same chain: its conditioning table (built once per chain, for all 998 steps) is
         # kept, as it would be for the rest of a real chain
-        n = eng.ddim_loop(x, lengths, pos, coef, use_graph=not args.no_graph, max_evals=K, split=not args.no_split, keep_table=True)
+        pos = chain_steps(K, pos)
         barrier()
         dt = time.perf_counter() - t0
-        assert n == K
         assert torch.isfinite(x).all().item(), "state diverged"
-        pos -= K
+    if args.dump_outputs:  # (before the --full legs, which continue the chain)
+        dump_outputs(args.dump_outputs, {"latents" if rank == 0 else f"latents_rank{rank}": x})
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = tmax.item()
 
-    result = None
     if rank == 0:
         step_flops = synthetic.eps_step_flops(B, T)
+        peak = MFMA_PEAK_TFLOPS[args.dtype]
+        result = {
+            "metric": "denoising-steps/sec (BxT latents)", "value": world * K / dt, "unit": "denoising-steps/s",
+            "n_gpus": world, "backend": ctx["backend"], "rccl_ranks": rccl_ranks, "process_group_ranks": ctx["group_ranks"], "steps": K, "warmup": W,
+            "ms_per_step": dt / K * 1e3, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "config": {"workload": f"configs[2]: DDIM/DDPM-schedule reverse chain, eps-predictor Model(512, z=128) on "
+                                   f"[B={B},T={T}] latents per GPU, {args.timesteps}-step cosine schedule, random-init weights",
+                       "batch_per_gpu": B, "frames": T, "latent_dim": cfg.latent_dim, "timesteps": args.timesteps,
+                       "hip_graph": not args.no_graph, "half_batch_streams": 1 if args.no_split else 2, "parallelism": f"batch-sharded x{world} (no collective)"},
+            "frame_steps_per_s": world * K * B * T / dt,
+            "step_tflops_per_gpu": step_flops * K / dt / 1e12,
+            "step_mfma_frac": step_flops * K / dt / 1e12 / peak,
+        }
+        if not args.full:
+            print(json.dumps(result), flush=True)
+            return
         # once-per-chain work that the timed window (which continues the warm-up's chain) does not contain: the conditioning
         # table for all remaining timesteps.  Timed here: one call that rebuilds it and runs 2 steps, minus 2 steps.
         with torch.cuda.stream(stream):
@@ -545,28 +608,16 @@ def run_sampling(args, ctx):
             avg_ms, n_l = ctypes.c_float(), ctypes.c_int32()
             _lib.check(lib.dn_profile_stop(ctypes.byref(avg_ms), ctypes.byref(n_l)), "dn_profile_stop")
             ksec = avg_ms.value * 1e-3
-        peak = MFMA_PEAK_TFLOPS[args.dtype]
         achieved = kflops / ksec / 1e12
-        result = {
-            "metric": "denoising-steps/sec (BxT latents)", "value": world * K / dt, "unit": "denoising-steps/s",
-            "n_gpus": world, "backend": ctx["backend"], "rccl_ranks": rccl_ranks, "process_group_ranks": ctx["group_ranks"], "steps": K, "warmup": W,
-            "ms_per_step": dt / K * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": f"configs[2]: DDIM/DDPM-schedule reverse chain, eps-predictor Model(512, z=128) on "
-                                   f"[B={B},T={T}] latents per GPU, {args.timesteps}-step cosine schedule, random-init weights",
-                       "batch_per_gpu": B, "frames": T, "latent_dim": cfg.latent_dim, "timesteps": args.timesteps,
-                       "hip_graph": not args.no_graph, "half_batch_streams": 1 if args.no_split else 2, "parallelism": f"batch-sharded x{world} (no collective)"},
-            "frame_steps_per_s": world * K * B * T / dt,
+        result.update({
             "chain_setup_ms": chain_setup_ms,  # conditioning table of a whole chain, built once per chain (not per step)
-            "step_tflops_per_gpu": step_flops * K / dt / 1e12,
-            "step_mfma_frac": step_flops * K / dt / 1e12 / peak,
             "roofline": {"bound": "mfma", "kernel": f"{'conv_gemm_fat_kernel' if args.dtype in ('bf16', 'f16') else 'conv_gemm_big_kernel'}<{args.dtype}, BIAS> FFN causal conv k=3 "
                                                     f"[{B * T} x 4095] x [4095 x 1365]",
                          "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
                          "flops_per_launch": kflops, "avg_launch_ms": ksec * 1e3, "launches_timed": n_l.value,
                          "avg_launch_ms_isolated_back_to_back": ksec_iso * 1e3, "traffic": traffic_from_profiles(args.dtype)[0],
                          "traffic_profile_matches_build": traffic_from_profiles(args.dtype)[1]},
-        }
+        })
         # BASELINE config 2 asks for an HBM rate beside steps/s: the measured fabric-side bytes of one step (PMC, committed under
         # profiles/; an upper bound on HBM bytes, Infinity-Cache hits included) x the measured step rate.  Only for the shape and
         # dtype the passes were collected on.
@@ -653,7 +704,7 @@ def eps_train_flops(B, T):
     return 3.0 * eps_lin + 3.5 * eps_attn + 2.0 * dec_lin + 3.5 * dec_attn + M * 4849664.0
 
 
-def measure_training(kind, dtype, max_tokens, K, W, ctx, stream):
+def measure_training(kind, dtype, max_tokens, K, W, ctx, stream, dump=None):
     """K timed updates of one of the two training losses on this rank's `max_tokens` batches (4 batch shapes cycled, lengths
     U[64,512]); one update = forward, backward, bucketed gradient all-reduce (RCCL when world > 1), clip + Adam, refresh, attention
     dropout on as in the reference's train mode.  kind = "vae": speech_vae_decoder_loss (BASELINE configs[3]); "diffusion":
@@ -713,6 +764,10 @@ def measure_training(kind, dtype, max_tokens, K, W, ctx, stream):
         fl = vae_train_flops if kind == "vae" else (lambda B, T, _n: eps_train_flops(B, T))
         flops = sum(fl(b["nsentences"], b["frames"] // b["nsentences"], b["ntokens"]) for b in used)
         assert torch.isfinite(logged).all().item() and torch.isfinite(norm).item(), "training diverged"
+        if dump:  # what the last timed update returned, and a fixed sample of the parameters it left (before the kernel timing below)
+            idx = torch.randint(0, eng.n_params, (1 << 20,), generator=torch.Generator().manual_seed(0)).sort().values.to(dev)
+            sfx = "" if rank == 0 else f"_rank{rank}"
+            dump_outputs(dump, {"loss_stats" + sfx: logged, "grad_norm" + sfx: norm.reshape(1), "params_sample" + sfx: eng.master[idx]})
         # the dominant backward kernel, timed where it runs: HIP events around the FFN causal conv's weight-gradient contraction
         # (one per transformer layer of the trained model) inside two more updates of the first batch shape
         # Twice: as the updates above ran it (on the second stream beside the data-gradient chain -- train_engine.hip: WgSide -- so
@@ -793,7 +848,8 @@ def run_training(args, ctx):
     stream = torch.cuda.Stream(device=dev)
     if args.dtype not in ("bf16", "f32"):
         args.dtype = "bf16"  # the training engines run bf16 / f32 (the reference trains in fp32); the line's dtype says which ran
-    m = measure_training(args.train_loss, args.dtype, args.max_tokens, K, W, ctx, stream)
+    torch.manual_seed(rank)  # (the diffusion loss draws its timesteps with torch's generator)
+    m = measure_training(args.train_loss, args.dtype, args.max_tokens, K, W, ctx, stream, dump=args.dump_outputs)
     keys = ["dt", "sent", "toks", "frames", "flops", "ar_ms"]
     vals = torch.tensor([m[k] for k in keys], dtype=torch.float64, device=dev if world > 1 and dist.get_backend() == "nccl" else "cpu")
     if world > 1:

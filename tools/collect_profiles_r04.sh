@@ -10,9 +10,9 @@ O=gpurun_out/r04
 rm -rf $O && mkdir -p $O
 BID=$(python tools/build_id.py)
 echo "build $BID" > $O/build_id.txt
-python bench.py > $O/bench_line.json 2> $O/bench_line.err
+python bench.py --full > $O/bench_line.json 2> $O/bench_line.err
 echo "bench line done"
-LEGS="--no-cpu-baseline --no-full-chain --no-f32 --no-x3 --no-train --no-refine --no-cond"
+LEGS="--full --no-cpu-baseline --no-full-chain --no-f32 --no-x3 --no-train --no-refine --no-cond"
 prof() {  # name, bench flags
   rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_$1 -o bench -- python3 $R/bench.py $2 > $O/rocprof_$1.json 2> $O/rocprof_$1.err
   python tools/summarize_trace.py $(find $O/prof_$1 -name "*kernel_trace.csv" | head -1) > $O/per_shape_$1.txt

@@ -43,7 +43,7 @@ for dt, (a, b, kernel) in NAMES.items():
     raw = json.load(open(os.path.join(SRC, a)))
     f, w = raw["FETCH_SIZE"]["mean_per_launch"], raw["WRITE_SIZE"]["mean_per_launch"]
     d = {"kernel": kernel,
-         "command": "rocprofv3 --pmc FETCH_SIZE (pass 1) / --pmc WRITE_SIZE (pass 2) --kernel-trace --output-format csv -- python3 bench.py --no-split "
+         "command": "rocprofv3 --pmc FETCH_SIZE (pass 1) / --pmc WRITE_SIZE (pass 2) --kernel-trace --output-format csv -- python3 bench.py --full --no-split "
                     "--steps 30 [--dtype bf16x3] (tools/collect_profiles_r03.sh); tools/pmc_summary.py <kernel>[@grid] <dirs>: mean per launch over "
                     f"{raw['FETCH_SIZE']['launches']} launches INSIDE the chain",
          "FETCH_SIZE_KB": f, "WRITE_SIZE_KB": w,

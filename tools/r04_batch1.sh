@@ -4,11 +4,12 @@ timeout -k 10 900 python -m pytest tests/test_hip_mirror.py tests/test_hip_refin
 grep -E "^(FAILED|ERROR)|passed|failed|cosines|worst relative" gpurun_out/b1_tests.log | head -40
 timeout -k 10 120 python tools/cond_gemm_bench.py > gpurun_out/b1_cond_gemm.log 2>&1 || true
 cat gpurun_out/b1_cond_gemm.log | tail -6
-timeout -k 10 300 python bench.py --no-cpu-baseline --no-full-chain --no-x3 --no-train --no-f32 > gpurun_out/b1_bench.json 2> gpurun_out/b1_bench.err || { tail -20 gpurun_out/b1_bench.err; }
+export BL=${BL:-$(mktemp -d)}  # where the bench line goes
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-full-chain --no-x3 --no-train --no-f32 > $BL/b1_bench.json 2> $BL/b1_bench.err || { tail -20 $BL/b1_bench.err; }
 python - <<'PY'
-import json
+import json, os
 try:
-    d=json.loads(open('gpurun_out/b1_bench.json').read().strip().splitlines()[-1])
+    d=json.loads(open(os.path.join(os.environ['BL'], 'b1_bench.json')).read().strip().splitlines()[-1])
     print({k:d[k] for k in ('value','dtype','ms_per_step','bf16_steps_per_s') if k in d}); print(d.get('refine')); print(d.get('cond'))
 except Exception as e: print('bench parse', e)
 PY

@@ -1,6 +1,6 @@
 set -e
 cd $GRAFT_REPO_ROOT
-LEGS="--no-cpu-baseline --no-full-chain --no-f32 --no-x3 --no-train --no-cond --steps 20 --warmup 5"
+LEGS="--full --no-cpu-baseline --no-full-chain --no-f32 --no-x3 --no-train --no-cond --steps 20 --warmup 5"
 DN_TILE_192=0 python bench.py $LEGS > gpurun_out/b15_t0.json 2>/dev/null
 python bench.py $LEGS > gpurun_out/b15_t1.json 2>/dev/null
 python - <<'PY'

@@ -2,7 +2,7 @@ set -e
 cd $GRAFT_REPO_ROOT
 timeout -k 10 600 python -m pytest tests/test_hip_f16.py tests/test_hip_train.py -m gpu -q -k "every_tile or fullsize_diffusion or bench_shape" > gpurun_out/b2_tests.log 2>&1 || true
 grep -E "^(FAILED|ERROR)|passed|failed" gpurun_out/b2_tests.log | head -20
-F="--no-cpu-baseline --no-full-chain --no-x3 --no-train --no-f32 --no-refine --no-cond"
+F="--full --no-cpu-baseline --no-full-chain --no-x3 --no-train --no-f32 --no-refine --no-cond"
 for i in 1 2; do
   python bench.py $F > gpurun_out/b2_a$i.json 2>/dev/null
   DN_QKV_192=1 python bench.py $F > gpurun_out/b2_b$i.json 2>/dev/null

@@ -1,11 +1,12 @@
 set -e
 cd $GRAFT_REPO_ROOT
 S=$(date +%s)
-python bench.py > gpurun_out/b5_bench_line.json 2> gpurun_out/b5_bench_line.err || { tail -30 gpurun_out/b5_bench_line.err; exit 1; }
+export BL=${BL:-$(mktemp -d)}  # where the bench line goes
+python bench.py --full > $BL/b5_bench_line.json 2> $BL/b5_bench_line.err || { tail -30 $BL/b5_bench_line.err; exit 1; }
 echo "default bench wall: $(( $(date +%s) - S )) s"
 python - <<'PY'
-import json
-d=json.loads(open('gpurun_out/b5_bench_line.json').read().strip().splitlines()[-1])
+import json, os
+d=json.loads(open(os.path.join(os.environ['BL'], 'b5_bench_line.json')).read().strip().splitlines()[-1])
 keys=['value','dtype','ms_per_step','step_mfma_frac','bf16_steps_per_s','bf16x3_steps_per_s','ddpm_steps_per_s','backend','rccl_ranks','f32_steps_per_s']
 print({k:d.get(k) for k in keys})
 print('roofline', {k:d['roofline'][k] for k in ('frac','avg_launch_ms','traffic')})

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Fabric-side bytes per denoising step from rocprofv3 --pmc passes of `bench.py --no-split --no-cpu-baseline` at two step
+"""Fabric-side bytes per denoising step from rocprofv3 --pmc passes of `bench.py --full --no-split --no-cpu-baseline` at two step
 counts: everything that is not a timed step (set-up, warm-up, the roofline legs) is the same in both runs and cancels in the
 difference.  bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024 (gfx950: FETCH_SIZE counts 128-byte requests as 64, MI355X_MICROARCH.md).
 Usage: step_traffic.py <root with {FETCH_SIZE,WRITE_SIZE}_{stepsA,stepsB}/ dirs> stepsA stepsB  -> JSON on stdout"""
@@ -22,7 +22,7 @@ write = (total("WRITE_SIZE", sb) - total("WRITE_SIZE", sa)) / (sb - sa)
 print(json.dumps({
     "what": "fabric-side traffic of ONE denoising step of bench.py's workload ([B=32,T=512], the dtype of the runs, single stream), from the "
             f"difference of two PMC runs with --steps {sa} and --steps {sb}",
-    "command": "rocprofv3 --pmc <FETCH_SIZE|WRITE_SIZE> --kernel-trace --output-format csv -- python3 bench.py --no-split "
+    "command": "rocprofv3 --pmc <FETCH_SIZE|WRITE_SIZE> --kernel-trace --output-format csv -- python3 bench.py --full --no-split "
                "--no-cpu-baseline --steps <n>   (4 passes); tools/step_traffic.py",
     "FETCH_SIZE_KB_per_step": fetch, "WRITE_SIZE_KB_per_step": write,
     "correction": "gfx950: FETCH_SIZE counts 128-B requests at 64 B -> x2; WRITE_SIZE exact; both in KiB",
