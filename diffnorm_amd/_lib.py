@@ -14,6 +14,13 @@ DN_F32, DN_BF16, DN_BF16X3, DN_F16 = 0, 1, 2, 3
 EPI_BIAS, EPI_SILU, EPI_GEGLU, EPI_FILM_GATE, EPI_RESADD, EPI_POSEMB, EPI_RELU = range(7)
 DN_MAX_TERMS = 8
 TAG_FFN_CONV, TAG_WN_DILATED, TAG_FFN_CONV_WGRAD = 1, 2, 3
+# DnGemmParams.flags (DN_GEMM_*)
+GEMM_NARROW_STORES, GEMM_NO_RES_PREFETCH, GEMM_RELU, GEMM_TWIN = 1 << 4, 1 << 5, 1 << 6, 1 << 7
+GEMM_TAG_SHIFT, GEMM_TILE_SHIFT, GEMM_BAND_SHIFT = 8, 16, 24
+GEMM_FAT_STAMPS, GEMM_NO_SHARED_ROWS, GEMM_TAPS_INNER, GEMM_TERM_OUTER = 1 << 20, 1 << 21, 1 << 22, 1 << 23
+# tile variants of dn_conv_gemm (DN_TILE_*)
+(TILE_128X128, TILE_256X128, TILE_256X256, TILE_256X352, TILE_ROW, TILE_256X256_W4, TILE_256X256_W8, TILE_256X192,
+ TILE_256X128_2WG) = range(1, 10)
 
 
 class DiffNormHipError(RuntimeError):
@@ -38,7 +45,7 @@ class GemmParams(C.Structure):
                 ("ldr", C.c_int32), ("res_dtype", C.c_int32), ("res_gstride", C.c_int64),
                 ("gamma_beta", C.c_void_p), ("gb_ld", C.c_int32), ("gb_half", C.c_int32),
                 ("gb_gstride", C.c_int64), ("pos_table", C.c_void_p), ("pos_ld", C.c_int32),
-                ("pad_", C.c_int32), ("lengths", C.c_void_p),
+                ("flags", C.c_int32), ("lengths", C.c_void_p),
                 ("norm_out", C.c_void_p), ("norm_ld", C.c_int32), ("norm_dtype", C.c_int32), ("norm_D", C.c_int32),
                 ("norm_gb_ld", C.c_int32), ("norm_gamma", C.c_void_p), ("norm_gb", C.c_void_p),
                 ("norm_gb_half", C.c_int32), ("out_layout", C.c_int32),
@@ -46,6 +53,12 @@ class GemmParams(C.Structure):
                 ("row_ssq", C.c_void_p), ("row_ssq_ld", C.c_int32), ("row_ssq_parts", C.c_int32),
                 ("row_D", C.c_float), ("row_bias_ld", C.c_int32), ("row_bias", C.c_void_p),
                 ("pre_out", C.c_void_p), ("pre_ld", C.c_int32), ("pre_pad_", C.c_int32)]
+    # the former name of `flags` (same offset): callers that still write p.pad_ keep reaching the field
+    pad_ = property(lambda self: self.flags, lambda self, v: setattr(self, "flags", v))
+
+
+class GemmRoute(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("tile", "taps_inner", "shared_rows", "band")]
 
 
 class AdamParams(C.Structure):
@@ -125,6 +138,7 @@ class EpsTrainBatch(C.Structure):
 _vp, _i32, _i64, _u64, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t
 SYMBOLS = {
     "dn_conv_gemm": (C.c_int, [C.POINTER(GemmParams), _vp]),
+    "dn_conv_gemm_route": (C.c_int, [C.POINTER(GemmParams), C.POINTER(GemmRoute)]),
     "dn_conv_gemm_kblocked_ok": (C.c_int, [C.POINTER(GemmParams)]),
     "dn_conv_gemm_tile": (C.c_int, [C.POINTER(GemmParams)]),
     "dn_grad_sumsq": (C.c_int, [_vp, C.c_int64, _vp, _vp, C.c_int32, _vp]),

@@ -44,6 +44,7 @@ const OptDef kOpts[dn::OPT_COUNT] = {
     {"wgrad_prio", "DN_WGRAD_PRIO", nullptr},              // 1: the weight-gradient stream at the lowest priority (read when the stream is created; measured level, default off)
 };
 std::atomic<int> g_opt[dn::OPT_COUNT];
+std::atomic<int> g_opt_gen{0};
 std::once_flag g_opt_once;
 int env_value(const OptDef& d) {
   const char* e = getenv(d.env);
@@ -71,8 +72,11 @@ extern "C" int dn_set_option(const char* name, int32_t value) {
   DN_CHECK_ARG(i >= 0, "dn_set_option: unknown option '%s'", name ? name : "(null)");
   std::call_once(g_opt_once, init_options);
   g_opt[i].store(value == DN_OPTION_DEFAULT ? env_value(kOpts[i]) : value, std::memory_order_relaxed);
+  g_opt_gen.fetch_add(1, std::memory_order_relaxed);
   return DN_OK;
 }
+
+int dn::option_generation() { return g_opt_gen.load(std::memory_order_relaxed); }
 
 extern "C" int dn_get_option(const char* name, int32_t* value, int32_t* is_set) {
   const int i = find_option(name);

@@ -226,10 +226,6 @@ struct LaunchProfile {
   hipEvent_t* ev = nullptr;  // 2*cap events
 };
 extern LaunchProfile g_prof;  // defined in gemm.hip
-// Set by the two-stream sampling loop while it enqueues (or captures) a step: every contraction it launches has an identical
-// half-batch twin running beside it, which fills the idle part of a ragged round -- tile choices that even out the rounds of ONE
-// launch (the 256 x 192 tile) lose there.  Defined in gemm.hip.
-extern thread_local bool g_gemm_twin;
 
 }  // namespace dn
 
@@ -244,6 +240,7 @@ enum Opt { OPT_TAPS_INNER = 0, OPT_FUSE_NORM, OPT_NO_SPLIT_NORM, OPT_KBLOCK, OPT
 constexpr int DN_OPT_UNSET = -2147483647 - 1;
 int option(Opt o);                       // current value or DN_OPT_UNSET
 inline int option_or(Opt o, int dflt) { const int v = option(o); return v == DN_OPT_UNSET ? dflt : v; }
+int option_generation();                 // counts dn_set_option calls: a change means cached routes may be stale
 }  // namespace dn
 #define DN_CHECK_ARG(cond, ...)  \
   do {                           \

@@ -24,9 +24,10 @@ inline int esize(int dtype) { return dtype == DN_BF16 || dtype == DN_F16 ? 2 : 4
     if (rc__ != DN_OK) return rc__; \
   } while (0)
 
-inline DnGemmParams gemm_base(int dtype, int M, int N, int K, int T) {
+inline DnGemmParams gemm_base(int dtype, int M, int N, int K, int T, int32_t flags = 0) {
   DnGemmParams p;
   memset(&p, 0, sizeof(p));
+  p.flags = flags;
   p.dtype = dtype;
   p.M = M; p.N = N; p.K = K; p.T = T;
   p.groups = 1;
@@ -117,6 +118,7 @@ struct DnEps {
   const float* graph_coef;
   int graph_flags;
   uint64_t graph_seed;  // dn_ddpm_loop: the Philox key baked into the captured step
+  int graph_opt_gen;    // dn::option_generation() at capture: the run-time options its routes were chosen under
   void *side_stream, *ev_fork, *ev_join;  // DN_LOOP_SPLIT2: second half-batch stream and its fork/join events
   // DN_LOOP_KEEP_TABLE: the conditioning table built by the previous dn_ddim_loop call on this workspace
   void* table_ws;

@@ -22,9 +22,6 @@ inline bool fuse_norm_enabled(int Dp, int dtype) {
   return on && Dp <= 512 && dtype != DN_BF16X3;  // (the whole-row tile is not built for split operands)
 }
 
-// set by the two-stream sampling loop while it enqueues (or captures) a step: dn_conv_gemm's tile choice counts the twin launch
-static thread_local bool g_twin_launches = false;
-
 // Split RMSNorm (DnGemmParams.norm_split / row_ssq): every RMSNorm of the transformer is divided between the residual-
 // closing contraction that produces its input and the projection that consumes its output, so the 2*depth+1 norm passes
 // over the residual stream disappear (measured: -6 % per denoising step at [32,512] x dim 512).  DN_NO_SPLIT_NORM=1 runs
@@ -57,9 +54,10 @@ WaveBufs plan_wave(const WavenetW& w, int M, int es, Arena& ar) {
   return b;
 }
 
-// `fin` carries the destination of the final 1x1 conv (out, ldo, out_dtype, N, epilogue and its extras).
+// `fin` carries the destination of the final 1x1 conv (out, ldo, out_dtype, N, epilogue and its extras).  gemm_flags: DnGemmParams.flags
+// of every contraction issued (DN_GEMM_TWIN from the two-stream sampler).
 int run_wavenet(const WavenetW& w, int dtype, const void* in, int M, int T, const float* gb, int gb_ld, const WaveBufs& wb,
-                DnGemmParams fin, hipStream_t s) {
+                DnGemmParams fin, hipStream_t s, int32_t gemm_flags = 0) {
   const int es = esize(dtype);
   const int cinp = padk(w.cin), cp = padk(w.cout), cn = padn(w.cout), L = w.layers, S = w.stacks;
   const size_t mat = (size_t)cn * cp;
@@ -69,15 +67,15 @@ int run_wavenet(const WavenetW& w, int dtype, const void* in, int M, int T, cons
   // dilated conv, -11 % on the res conv at [32,512]).  The last stack's outputs stay row-major for the skip contraction.
   bool kb = false;
   if (kblock_mode() != 0 && dn::dn_is16(dtype) && w.conv_Wkb && w.res_Wkb) {
-    DnGemmParams q = gemm_base(dtype, M, cp, cp, T);
+    DnGemmParams q = gemm_base(dtype, M, cp, cp, T, gemm_flags);
     q.groups = L;
     const int t_res = dn_conv_gemm_tile(&q);
     q.n_terms = 3; q.epilogue = DN_EPI_FILM_GATE;
-    kb = kblock_mode() == 1 || (t_res == 3 && dn_conv_gemm_tile(&q) == 3);
+    kb = kblock_mode() == 1 || (t_res == DN_TILE_256X256 && dn_conv_gemm_tile(&q) == DN_TILE_256X256);
   }
   const int a_layout = kb ? (DN_LAYOUT_A_KBLOCKED | DN_LAYOUT_W_KBLOCKED) : 0;
   {  // init conv, k=3, dilation 1 (latent_module.py:596,614 / 1014,1029)
-    DnGemmParams p = gemm_base(dtype, M, cp, cinp, T);
+    DnGemmParams p = gemm_base(dtype, M, cp, cinp, T, gemm_flags);
     p.n_terms = 3;
     for (int j = 0; j < 3; ++j) {
       p.terms[j].A = in; p.terms[j].lda = cinp; p.terms[j].shift = 2 - j;
@@ -92,7 +90,7 @@ int run_wavenet(const WavenetW& w, int dtype, const void* in, int M, int T, cons
     const int64_t a_gs = st == 0 ? 0 : plane;  // stack 0 feeds one tensor to all blocks (:570-571)
     void* out_s = (st & 1) ? wb.blk1 : wb.blk0;
     {  // res_conv 1x1 of the L blocks (:510,521)
-      DnGemmParams p = gemm_base(dtype, M, cp, cp, T);
+      DnGemmParams p = gemm_base(dtype, M, cp, cp, T, gemm_flags);
       p.groups = L;
       p.terms[0].A = in_s; p.terms[0].lda = cp; p.terms[0].a_gstride = a_gs;
       p.terms[0].W = eoff(kb ? w.res_Wkb : w.res_W, (size_t)st * L * mat, es); p.terms[0].w_gstride = (int64_t)mat;
@@ -102,7 +100,7 @@ int run_wavenet(const WavenetW& w, int dtype, const void* in, int M, int T, cons
       DN_TRY(dn_conv_gemm(&p, s));
     }
     {  // dilated conv k=3 (dilation 2^block) + FiLM + tanh*sigmoid + residual (:509,523-530)
-      DnGemmParams p = gemm_base(dtype, M, cp, cp, T);
+      DnGemmParams p = gemm_base(dtype, M, cp, cp, T, gemm_flags);
       p.groups = L;
       p.n_terms = 3;
       for (int j = 0; j < 3; ++j) {
@@ -119,13 +117,13 @@ int run_wavenet(const WavenetW& w, int dtype, const void* in, int M, int T, cons
       }
       p.out = out_s; p.ldo = cp; p.out_gstride = plane;
       p.out_layout = kb && st + 1 < S ? DN_LAYOUT_OUT_KBLOCKED : 0;
-      p.pad_ = DN_TAG_WN_DILATED << 8;
+      p.flags |= DN_TAG_WN_DILATED << DN_GEMM_TAG_SHIFT;
       DN_TRY(dn_conv_gemm(&p, s));
     }
   }
   const void* last = ((S - 1) & 1) ? wb.blk1 : wb.blk0;
   {  // sum over blocks of skip_conv(out_i): one contraction with L terms (:511,534,617)
-    DnGemmParams p = gemm_base(dtype, M, cp, cp, T);
+    DnGemmParams p = gemm_base(dtype, M, cp, cp, T, gemm_flags);
     p.n_terms = L;
     for (int i = 0; i < L; ++i) {
       p.terms[i].A = eoff(last, (size_t)i * plane, es); p.terms[i].lda = cp;
@@ -134,7 +132,7 @@ int run_wavenet(const WavenetW& w, int dtype, const void* in, int M, int T, cons
     p.bias = w.skip_b; p.out = wb.sk; p.ldo = cp;
     DN_TRY(dn_conv_gemm(&p, s));
   }
-  fin.dtype = dtype; fin.M = M; fin.K = cp; fin.T = T; fin.groups = 1; fin.n_terms = 1;
+  fin.dtype = dtype; fin.M = M; fin.K = cp; fin.T = T; fin.groups = 1; fin.n_terms = 1; fin.flags |= gemm_flags;
   fin.terms[0].A = wb.sk; fin.terms[0].lda = cp; fin.terms[0].W = w.final_W;
   fin.bias = w.final_b;
   return dn_conv_gemm(&fin, s);
@@ -196,10 +194,11 @@ struct CrossAttn { const void* q_W; const void* out_W; const void* kv; int n_kv;
 // supplies the first one (`xn_ready`: tb.xn already holds layer 0's attention norm) or it runs standalone once.
 // `rb` (split RMSNorm with adaptive norms only): fp32 rows [Bc, rb_ld] of beta . W^T, layer l at columns
 // l * (3 hd [+ hd] + 2 padk(inner)): first the q/kv projection's, [then the cross-attention query projection's,] then the GEGLU
-// projection's (packed column order).  `cx`: the cross-attention block between the two (NULL: the unconditional model).
+// projection's (packed column order).  `cx`: the cross-attention block between the two (NULL: the unconditional model).  gemm_flags: as in
+// run_wavenet.
 int run_transformer(const TransformerW& w, int dtype, float* xres, int B, int T, const int32_t* lengths, const float* gb, int gb_ld,
                     const float* rb, int rb_ld, const TfBufs& tb, void* pred, int pred_ld, int pred_dtype, bool xn_ready, hipStream_t s,
-                    const CrossAttn* cx = nullptr) {
+                    const CrossAttn* cx = nullptr, int32_t gemm_flags = 0) {
   const int es = esize(dtype), M = B * T;
   const int D = w.dim, Dp = padk(D), Dn = padn(D), hd = w.heads * w.dim_head, ip = padk(w.inner), in_n = padn(w.inner);
   const bool fuse = fuse_norm_enabled(Dp, dtype);
@@ -218,36 +217,36 @@ int run_transformer(const TransformerW& w, int dtype, float* xres, int B, int T,
   bool geglu_kb = false;
   static const bool geglu_kb_off = getenv("DN_GEGLU_KB") && atoi(getenv("DN_GEGLU_KB")) == 0;  // A/B timing
   if (!geglu_kb_off && split && !fuse && kblock_mode() != 0 && dn::dn_is16(dtype) && w.ffin_Wkb && Dp % 32 == 0) {
-    DnGemmParams q = gemm_base(dtype, M, ip, Dp, T);
+    DnGemmParams q = gemm_base(dtype, M, ip, Dp, T, gemm_flags);
     q.epilogue = DN_EPI_GEGLU;
-    if (mid2 & 2) q.pad_ |= 9 << 16;
+    if (mid2 & 2) q.flags |= DN_TILE_256X128_2WG << DN_GEMM_TILE_SHIFT;
     const int gt = dn_conv_gemm_tile(&q);
-    geglu_kb = kblock_mode() == 1 || gt == 3 || gt == 9;
+    geglu_kb = kblock_mode() == 1 || gt == DN_TILE_256X256 || gt == DN_TILE_256X128_2WG;
   }
   // The same for the q/kv projection of layers >= 1 (layer 0's norm comes from the caller, row-major): its activations are the
   // attention norm's row * gamma, written by the previous layer's feed-forward-out contraction and read by nothing else.
   bool qkv_kb = false;
   static const bool qkv_kb_off = getenv("DN_QKV_KB") && atoi(getenv("DN_QKV_KB")) == 0;  // A/B timing
   if (!qkv_kb_off && split && !fuse && kblock_mode() != 0 && dn::dn_is16(dtype) && w.qkv_Wkb && Dp % 32 == 0) {
-    DnGemmParams q = gemm_base(dtype, M, 3 * hd, Dp, T);
-    if (mid2 & 1) q.pad_ |= 9 << 16;
+    DnGemmParams q = gemm_base(dtype, M, 3 * hd, Dp, T, gemm_flags);
+    if (mid2 & 1) q.flags |= DN_TILE_256X128_2WG << DN_GEMM_TILE_SHIFT;
     const int qt = dn_conv_gemm_tile(&q);
-    qkv_kb = kblock_mode() == 1 || qt == 3 || qt == 9;
+    qkv_kb = kblock_mode() == 1 || qt == DN_TILE_256X256 || qt == DN_TILE_256X128_2WG;
   }
   // option qkv_192: the projection's 3 x 512 columns are 8 x 192 but 6 x 256 -- at [32,512] 512 tiles of 256 x 192 are two full rounds
   // of the chip, 384 tiles of 256 x 256 one and a half
   const bool qkv_192 = option_or(OPT_QKV_192, 0) != 0 && dn::dn_is16(dtype) && (3 * hd) % 192 == 0 && M >= 2048;
   for (int l = 0; l < w.depth; ++l) {
     {  // to_q ; to_kv in one contraction (:930-931,945)
-      DnGemmParams p = gemm_base(dtype, M, 3 * hd, Dp, T);
+      DnGemmParams p = gemm_base(dtype, M, 3 * hd, Dp, T, gemm_flags);
       p.terms[0].A = tb.xn; p.terms[0].lda = Dp; p.terms[0].W = eoff(w.qkv_W, (size_t)l * padn(3 * hd) * Dp, es);
       if (qkv_kb && l >= 1) {
         p.terms[0].W = eoff(w.qkv_Wkb, (size_t)l * padn(3 * hd) * Dp, es);
         p.terms[0].layout = DN_LAYOUT_A_KBLOCKED | DN_LAYOUT_W_KBLOCKED;
       }
       p.out = tb.qkv; p.ldo = 3 * hd; p.out_dtype = side_dtype(dtype);
-      if (qkv_192) p.pad_ |= 8 << 16;
-      else if (mid2 & 1) p.pad_ |= 9 << 16;
+      if (qkv_192) p.flags |= DN_TILE_256X192 << DN_GEMM_TILE_SHIFT;
+      else if (mid2 & 1) p.flags |= DN_TILE_256X128_2WG << DN_GEMM_TILE_SHIFT;
       if (scaled) set_row_scale(p, tb, Dp, D, rb ? rb + (size_t)l * rb_layer : nullptr, rb_ld);
       DN_TRY(dn_conv_gemm(&p, s));
     }
@@ -261,7 +260,7 @@ int run_transformer(const TransformerW& w, int dtype, float* xres, int B, int T,
       DN_TRY(dn_attention(&a, s));
     }
     {  // to_out + residual (:932,692) [+ the feed-forward block's norm (:703)]
-      DnGemmParams p = gemm_base(dtype, M, Dp, hd, T);
+      DnGemmParams p = gemm_base(dtype, M, Dp, hd, T, gemm_flags);
       p.terms[0].A = tb.ao; p.terms[0].lda = hd; p.terms[0].W = eoff(w.out_W, (size_t)l * Dn * hd, es);
       p.epilogue = DN_EPI_RESADD; p.res = xres; p.ldr = Dp; p.out = xres; p.ldo = Dp; p.out_dtype = DN_F32;
       const NormSrc ns = norm_src(w, gb, l, 1, nj);
@@ -274,7 +273,7 @@ int run_transformer(const TransformerW& w, int dtype, float* xres, int B, int T,
     scaled = split;
     if (cx) {  // cross-attention to the resampled prompt latents, no mask (:694-700)
       {
-        DnGemmParams p = gemm_base(dtype, M, hd, Dp, T);
+        DnGemmParams p = gemm_base(dtype, M, hd, Dp, T, gemm_flags);
         p.terms[0].A = tb.xn; p.terms[0].lda = Dp; p.terms[0].W = eoff(cx->q_W, (size_t)l * padn(hd) * Dp, es);
         p.out = cx->q; p.ldo = hd; p.out_dtype = side_dtype(dtype);
         if (scaled) set_row_scale(p, tb, Dp, D, rb ? rb + (size_t)l * rb_layer + 3 * hd : nullptr, rb_ld);
@@ -291,7 +290,7 @@ int run_transformer(const TransformerW& w, int dtype, float* xres, int B, int T,
         DN_TRY(dn_attention(&a, s));
       }
       {
-        DnGemmParams p = gemm_base(dtype, M, Dp, hd, T);
+        DnGemmParams p = gemm_base(dtype, M, Dp, hd, T, gemm_flags);
         p.terms[0].A = tb.ao; p.terms[0].lda = hd; p.terms[0].W = eoff(cx->out_W, (size_t)l * Dn * hd, es);
         p.epilogue = DN_EPI_RESADD; p.res = xres; p.ldr = Dp; p.out = xres; p.ldo = Dp; p.out_dtype = DN_F32;
         const NormSrc ns = norm_src(w, gb, l, 2, nj);
@@ -305,23 +304,24 @@ int run_transformer(const TransformerW& w, int dtype, float* xres, int B, int T,
     // CausalConv1d(inner, inner, 3) (:894), set up first: when it runs on one of the two 256-row tiles its operands go K-blocked --
     // the GEGLU projection writes its output that way and the weights come from their K-blocked copy (the tile then stages
     // 1 KiB pieces of whole cache lines instead of sixteen half-lines: -5 % on this contraction; DN_KBLOCK=0 disables)
-    DnGemmParams pc = gemm_base(dtype, M, ip, ip, T);
+    DnGemmParams pc = gemm_base(dtype, M, ip, ip, T, gemm_flags);
     pc.n_terms = 3;
     for (int j = 0; j < 3; ++j) {
       pc.terms[j].A = tb.gg; pc.terms[j].lda = ip; pc.terms[j].shift = 2 - j;
       pc.terms[j].W = eoff(w.ffconv_W, ((size_t)l * 3 + j) * in_n * ip, es);
     }
     pc.bias = w.ffconv_b + (size_t)l * ip; pc.out = tb.fc; pc.ldo = ip;
-    pc.pad_ = (DN_TAG_FFN_CONV << 8) | (g_twin_launches ? 128 : 0);  // (bit 7: an identical half-batch launch runs beside this one)
-    const int conv_tile = dn_conv_gemm_tile(&pc);  // 4 = 256 x 352 (the eps-predictor's width), 3 = 256 x 256 (the VAE's)
-    const bool kblocked = kblock_mode() != 0 && dn::dn_is16(dtype) && w.ffconv_Wkb && (kblock_mode() == 1 || conv_tile == 4 || conv_tile == 3);
+    pc.flags |= DN_TAG_FFN_CONV << DN_GEMM_TAG_SHIFT;
+    const int conv_tile = dn_conv_gemm_tile(&pc);  // 256 x 352 (the eps-predictor's width), 256 x 256 (the VAE's)
+    const bool kblocked = kblock_mode() != 0 && dn::dn_is16(dtype) && w.ffconv_Wkb &&
+                          (kblock_mode() == 1 || conv_tile == DN_TILE_256X352 || conv_tile == DN_TILE_256X256);
     if (kblocked)
       for (int j = 0; j < 3; ++j) {
         pc.terms[j].W = eoff(w.ffconv_Wkb, ((size_t)l * 3 + j) * in_n * ip, es);
         pc.terms[j].layout = DN_LAYOUT_A_KBLOCKED | DN_LAYOUT_W_KBLOCKED;
       }
     {  // Linear(D -> 2*inner) + GEGLU (:899,881-884)
-      DnGemmParams p = gemm_base(dtype, M, ip, Dp, T);
+      DnGemmParams p = gemm_base(dtype, M, ip, Dp, T, gemm_flags);
       p.terms[0].A = tb.xn; p.terms[0].lda = Dp; p.terms[0].W = eoff(w.ffin_W, (size_t)l * 2 * ip * Dp, es);
       if (geglu_kb) {
         p.terms[0].W = eoff(w.ffin_Wkb, (size_t)l * 2 * ip * Dp, es);
@@ -329,14 +329,14 @@ int run_transformer(const TransformerW& w, int dtype, float* xres, int B, int T,
       }
       p.bias = w.ffin_b + (size_t)l * 2 * ip;
       p.epilogue = DN_EPI_GEGLU; p.out = tb.gg; p.ldo = ip;
-      if (mid2 & 2) p.pad_ |= 9 << 16;
+      if (mid2 & 2) p.flags |= DN_TILE_256X128_2WG << DN_GEMM_TILE_SHIFT;
       p.out_layout = kblocked ? DN_LAYOUT_OUT_KBLOCKED : 0;
       if (scaled) set_row_scale(p, tb, Dp, D, rb ? rb + (size_t)l * rb_layer + 3 * hd + (cx ? hd : 0) : nullptr, rb_ld);
       DN_TRY(dn_conv_gemm(&p, s));
     }
     DN_TRY(dn_conv_gemm(&pc, s));
     {  // Linear(inner -> D) + residual (:902,704) [+ the next layer's attention norm (:691) or to_pred's norm (:677)]
-      DnGemmParams p = gemm_base(dtype, M, Dp, ip, T);
+      DnGemmParams p = gemm_base(dtype, M, Dp, ip, T, gemm_flags);
       p.terms[0].A = tb.fc; p.terms[0].lda = ip; p.terms[0].W = eoff(w.ffout_W, (size_t)l * Dn * ip, es);
       p.bias = w.ffout_b + (size_t)l * Dp;
       p.epilogue = DN_EPI_RESADD; p.res = xres; p.ldr = Dp; p.out = xres; p.ldo = Dp; p.out_dtype = DN_F32;
@@ -349,7 +349,7 @@ int run_transformer(const TransformerW& w, int dtype, float* xres, int B, int T,
     if (!fuse && !split) DN_TRY(standalone_norm(l + 1, 0));
   }
   // to_pred = RMSNorm(gamma) + Linear(D, D, no bias) (:676-679); its norm came out of the last contraction above
-  DnGemmParams p = gemm_base(dtype, M, Dp, Dp, T);
+  DnGemmParams p = gemm_base(dtype, M, Dp, Dp, T, gemm_flags);
   p.terms[0].A = tb.xn; p.terms[0].lda = Dp; p.terms[0].W = w.pred_W;
   p.out = pred; p.ldo = pred_ld; p.out_dtype = pred_dtype;
   if (pred_ld < Dp) p.N = pred_ld;  // dense fp32 destination narrower than the padded width
@@ -523,34 +523,35 @@ int eps_cond_rows(const DnEps* m, const int32_t* times, int n, float* cond, floa
   return eps_beta_rows(m, gb, m->n_row, n, gbh, gb + m->n_cond, m->n_row, s);
 }
 
-// Model.forward after the conditioning (latent_module.py:861-876); gb_ld == 0 -> one row for the batch.
+// Model.forward after the conditioning (latent_module.py:861-876); gb_ld == 0 -> one row for the batch.  gemm_flags: as in run_wavenet.
 int eps_core(const DnEps* m, const float* x, const float* gb, int gb_ld, const int32_t* lengths, int B, int T, float* eps_out,
-             const EpsBufs& b, hipStream_t s) {
+             const EpsBufs& b, hipStream_t s, int32_t gemm_flags = 0) {
   const DnEpsConfig& c = m->cfg;
   const int dtype = c.dtype, M = B * T;
   const int D = c.dim, Dp = padk(D), z = c.latent, zp = padk(z);
   DN_TRY(dn_convert_rows(x, DN_F32, z, b.xin, dtype, zp, M, z, s));
   {  // init_conv 1x1: latent -> dim (:734,864)
-    DnGemmParams p = gemm_base(dtype, M, Dp, zp, T);
+    DnGemmParams p = gemm_base(dtype, M, Dp, zp, T, gemm_flags);
     p.terms[0].A = b.xin; p.terms[0].lda = zp; p.terms[0].W = m->init_W;
     p.bias = m->init_b; p.out = b.h0; p.ldo = Dp;
     DN_TRY(dn_conv_gemm(&p, s));
   }
   {  // WaveNet; its final 1x1 conv also adds the positional embedding and opens the fp32 residual stream
-    DnGemmParams fin = gemm_base(dtype, M, Dp, Dp, T);
+    DnGemmParams fin = gemm_base(dtype, M, Dp, Dp, T, gemm_flags);
     fin.epilogue = DN_EPI_POSEMB; fin.pos_table = m->pos_table; fin.pos_ld = Dp; fin.lengths = lengths;
     fin.out = b.xres; fin.ldo = Dp; fin.out_dtype = DN_F32;
     // layer 0's attention norm rides on the contraction that opens the residual stream
     const float* gb0 = gb + (size_t)c.wn_stacks * c.wn_layers * 2 * Dp;
     if (fuse_norm_enabled(Dp, dtype)) set_norm(fin, b.tf.xn, Dp, D, dtype, nullptr, gb0, gb_ld);
     else if (split_norm_enabled(Dp, dtype)) set_split_norm(fin, b.tf, Dp, D, dtype, nullptr, gb0, gb_ld);
-    DN_TRY(run_wavenet(m->wn, dtype, b.h0, M, T, gb, gb_ld, b.wv, fin, s));
+    DN_TRY(run_wavenet(m->wn, dtype, b.h0, M, T, gb, gb_ld, b.wv, fin, s, gemm_flags));
   }
   const float* gb_tf = gb + (size_t)c.wn_stacks * c.wn_layers * 2 * Dp;
   const bool xn_ready = fuse_norm_enabled(Dp, dtype) || split_norm_enabled(Dp, dtype);
-  DN_TRY(run_transformer(m->tf, dtype, b.xres, B, T, lengths, gb_tf, gb_ld, gb + m->n_cond, gb_ld, b.tf, b.tp, Dp, dtype, xn_ready, s));
+  DN_TRY(run_transformer(m->tf, dtype, b.xres, B, T, lengths, gb_tf, gb_ld, gb + m->n_cond, gb_ld, b.tf, b.tp, Dp, dtype, xn_ready, s, nullptr,
+                         gemm_flags));
   // final_proj: dim -> latent (:807,875), dense fp32 out
-  DnGemmParams p = gemm_base(dtype, M, z, Dp, T);
+  DnGemmParams p = gemm_base(dtype, M, z, Dp, T, gemm_flags);
   p.terms[0].A = b.tp; p.terms[0].lda = Dp; p.terms[0].W = m->final_W;
   p.bias = m->final_b; p.out = eps_out; p.ldo = z; p.out_dtype = DN_F32;
   return dn_conv_gemm(&p, s);
@@ -671,8 +672,7 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
     m->table_ws = workspace; m->table_B = B; m->table_T = T; m->table_split = (int)split; m->table_rows = start_step;
   }
   const int noise_top = start_step - 1;  // injected noise: row (noise_top - t) belongs to step t
-  g_twin_launches = dn::g_gemm_twin = split;  // tile choice of the half-batch launches (host side, also at graph capture)
-  struct TwinReset { ~TwinReset() { g_twin_launches = dn::g_gemm_twin = false; } } twin_reset;
+  const int32_t twin = split ? DN_GEMM_TWIN : 0;  // every contraction of a half batch has its twin beside it (tile choice)
   auto one_step = [&]() -> int {
     hipLaunchKernelGGL(fill_t_kernel, dim3((B + 255) / 256), dim3(256), 0, s, tvec, B, counter);
     hipLaunchKernelGGL(copy_cond_row_kernel, dim3(32), dim3(256), 0, s, table, m->n_row, counter, bufs.gb);
@@ -682,14 +682,14 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
         dn_set_error("dn_ddim_loop: fork failed");
         return DN_ELAUNCH;
       }
-      DN_TRY(eps_core(m, x + off, bufs.gb, 0, lengths + B0, B1, T, eps + off, bufs1, s2));
+      DN_TRY(eps_core(m, x + off, bufs.gb, 0, lengths + B0, B1, T, eps + off, bufs1, s2, twin));
       if (op.ddpm)
         DN_TRY(dn_ddpm_step_launch(x + off, eps + off, B1 * T, z, T, coef, tvec + B0, op.clip, op.noise ? op.noise + off : nullptr, (int64_t)M * z,
                                    noise_top, op.seed ^ 0x9E3779B97F4A7C15ull, s2));  // (the second half draws from its own key)
       else
         DN_TRY(dn_ddim_step(x + off, eps + off, x + off, nullptr, DN_F32, z, B1 * T, z, z, T, coef, tvec + B0, s2));
     }
-    DN_TRY(eps_core(m, x, bufs.gb, 0, lengths, B0, T, eps, bufs, s));
+    DN_TRY(eps_core(m, x, bufs.gb, 0, lengths, B0, T, eps, bufs, s, twin));
     if (op.ddpm)
       DN_TRY(dn_ddpm_step_launch(x, eps, B0 * T, z, T, coef, tvec, op.clip, op.noise, (int64_t)M * z, noise_top, op.seed, s));
     else
@@ -710,9 +710,11 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
   if (use_graph && n_eval > 2) {
     const int gflags = (flags & ~DN_LOOP_KEEP_TABLE) | (op.ddpm ? 1 << 16 : 0) | (op.clip ? 1 << 17 : 0);
     // (an injected-noise chain bakes noise_top into the captured step: never served from the cache)
+    // (a dn_set_option since the capture may route the contractions differently: a miss)
+    const int opt_gen = dn::option_generation();
     const bool cached = m->graph_exec && m->graph_B == B && m->graph_T == T && m->graph_ws == workspace && m->graph_x == x &&
                         m->graph_len == lengths && m->graph_coef == coef && m->graph_flags == gflags && !op.noise &&
-                        m->graph_seed == op.seed;
+                        m->graph_seed == op.seed && m->graph_opt_gen == opt_gen;
     if (!cached) {
       DN_TRY(one_step());  // eager first step: also settles the per-kernel attributes outside capture
       done = 1;
@@ -741,6 +743,7 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
       }
       m->graph_exec = exec; m->graph_B = B; m->graph_T = T; m->graph_ws = workspace; m->graph_x = x;
       m->graph_len = lengths; m->graph_coef = coef; m->graph_flags = op.noise ? -1 : gflags; m->graph_seed = op.seed;
+      m->graph_opt_gen = opt_gen;
     }
     for (; done < n_eval; ++done) {
       hipError_t e = hipGraphLaunch((hipGraphExec_t)m->graph_exec, s);

@@ -4,14 +4,23 @@
 
 namespace dn {
 LaunchProfile g_prof;
-thread_local bool g_gemm_twin = false;
 }
 
+extern "C" int dn_conv_gemm_route(const DnGemmParams* pp, DnGemmRoute* route) {
+  DN_CHECK_ARG(pp && route, "dn_conv_gemm_route: null argument");
+  *route = dn::route(*pp);
+  return DN_OK;
+}
+
+extern "C" int dn_conv_gemm_tile(const DnGemmParams* pp) { return pp ? dn::route(*pp).tile : -1; }
+
+// Would the contraction with K-blocked operands (which no ldw comes with) run on the 256 x 352 tile?
 extern "C" int dn_conv_gemm_kblocked_ok(const DnGemmParams* pp) {
-  return pp && pp->K % 32 == 0 && dn::routes_to_352(*pp) ? 1 : 0;
+  if (!pp || pp->K % 32 != 0) return 0;
+  DnGemmParams q = *pp;
+  for (DnGemmTerm& t : q.terms) { t.layout = DN_LAYOUT_A_KBLOCKED | DN_LAYOUT_W_KBLOCKED; t.ldw = 0; }
+  return dn::route(q).tile == DN_TILE_256X352 ? 1 : 0;
 }
-
-extern "C" int dn_conv_gemm_tile(const DnGemmParams* pp) { return pp ? dn::choose_tile(*pp) : -1; }
 
 extern "C" int dn_conv_gemm(const DnGemmParams* pp, void* stream) {
   DN_CHECK_ARG(pp != nullptr, "dn_conv_gemm: null params");

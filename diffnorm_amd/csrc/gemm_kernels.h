@@ -352,7 +352,7 @@ __device__ __forceinline__ void wave_epilogue_wide(const DnGemmParams& p, const 
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         v[i] += bv[i];
-        if constexpr (EPI == DN_EPI_SILU) v[i] = (p.pad_ & 64) ? fmaxf(v[i], 0.f) : silu(v[i]);  // pad_ bit 6: DN_EPI_RELU rides on this epilogue
+        if constexpr (EPI == DN_EPI_SILU) v[i] = (p.flags & DN_GEMM_RELU) ? fmaxf(v[i], 0.f) : silu(v[i]);  // DN_EPI_RELU rides on this epilogue
       }
       store8_h16<H16>(out, out_off(p, m, n), v);
     }
@@ -513,7 +513,7 @@ __device__ __forceinline__ void wave_epilogue_impl(const DnGemmParams& p, const 
         }
         float v0 = a4.x + bv.x, v1 = a4.y + bv.y, v2 = a4.z + bv.z, v3 = a4.w + bv.w;
         if constexpr (EPI == DN_EPI_SILU) {
-          if (p.pad_ & 64) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }  // DN_EPI_RELU
+          if (p.flags & DN_GEMM_RELU) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }  // DN_EPI_RELU
           else { v0 = silu(v0); v1 = silu(v1); v2 = silu(v2); v3 = silu(v3); }
         } else if constexpr (EPI == DN_EPI_FILM_GATE) {
           if (gbb) {
@@ -579,7 +579,7 @@ __device__ __forceinline__ void wave_epilogue(const DnGemmParams& p, const float
   } else {
     if constexpr (EPI == DN_EPI_BIAS || EPI == DN_EPI_SILU || EPI == DN_EPI_GEGLU) {
       // 16-byte stores need 8-column granularity and 16-byte aligned rows (uniform: kernel arguments)
-      const bool wide = !SPLIT && !(p.pad_ & 16) && obf && (p.N & 7) == 0 && (p.ldo & 7) == 0 && (ncols & 7) == 0 && (p.out_gstride & 7) == 0 &&
+      const bool wide = !SPLIT && !(p.flags & DN_GEMM_NARROW_STORES) && obf && (p.N & 7) == 0 && (p.ldo & 7) == 0 && (ncols & 7) == 0 && (p.out_gstride & 7) == 0 &&
                         (reinterpret_cast<uintptr_t>(p.out) & 15) == 0;
       if (wide) {
         if (full) wave_epilogue_wide<EPI, true, H16>(p, ep, m_base, n_base, g, lane, ncols, prescaled);
@@ -630,7 +630,7 @@ __global__ __launch_bounds__(BM * 2, 1) void conv_gemm_kernel(const DnGemmParams
     logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
   }
   int mt_, nt_;
-  tile_coords(logical, n_tiles_n, (p.M + BM - 1) / BM, (p.pad_ >> 24) & 0xff, mt_, nt_);
+  tile_coords(logical, n_tiles_n, (p.M + BM - 1) / BM, (p.flags >> DN_GEMM_BAND_SHIFT) & 0xff, mt_, nt_);
   const int m0 = mt_ * BM;
   const int n0 = nt_ * BN;  // packed weight row of the tile
 
@@ -656,7 +656,7 @@ __global__ __launch_bounds__(BM * 2, 1) void conv_gemm_kernel(const DnGemmParams
   ResPre pre_res;
   pre_res.on = false;
   if constexpr (EPI == DN_EPI_RESADD && BM == 128) {  // (the 8-wave tile has no 64 registers to spare)
-    pre_res.on = !(p.pad_ & 32);  // pad_ bit 5: A/B timing without the prefetch
+    pre_res.on = !(p.flags & DN_GEMM_NO_RES_PREFETCH);  // A/B timing without the prefetch
     const int n_ = n0 + wn * 64 + (lane & 15) * 4;
     const char* resb = reinterpret_cast<const char*>(p.res) + p.res_gstride * g * 4;
 #pragma unroll
@@ -885,7 +885,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_big_kernel(const DnGemmParam
     logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
   }
   int mt_, nt_;
-  tile_coords(logical, n_tiles_n, (p.M + BMB - 1) / BMB, (p.pad_ >> 24) & 0xff, mt_, nt_);
+  tile_coords(logical, n_tiles_n, (p.M + BMB - 1) / BMB, (p.flags >> DN_GEMM_BAND_SHIFT) & 0xff, mt_, nt_);
   const int m0 = mt_ * BMB;
   const int n0 = nt_ * BNB;
   const int w_rows = (np_total + 127) / 128 * 128;  // rows the packed weight really has: clamp the ragged last tile
@@ -1283,7 +1283,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_mid2_kernel(const DnGemmPara
     logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
   }
   int mt_, nt_;
-  tile_coords(logical, n_tiles_n, (p.M + BMM - 1) / BMM, (p.pad_ >> 24) & 0xff, mt_, nt_);
+  tile_coords(logical, n_tiles_n, (p.M + BMM - 1) / BMM, (p.flags >> DN_GEMM_BAND_SHIFT) & 0xff, mt_, nt_);
   const int m0 = mt_ * BMM, n0 = nt_ * BNM;
   const int w_rows = (np_total + 127) / 128 * 128;
 
@@ -2202,7 +2202,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void conv_gemm_fat_kernel(const DnGe
 #endif
   __syncthreads();
 #ifdef DN_FAT_STAMPS
-  if ((p.pad_ & (1 << 20)) && tid == 0) {  // stamps go to a buffer of their own (pos_table is unused by this epilogue)
+  if ((p.flags & DN_GEMM_FAT_STAMPS) && tid == 0) {  // stamps go to a buffer of their own (pos_table is unused by this epilogue)
     uint64_t* d = reinterpret_cast<uint64_t*>(const_cast<float*>(p.pos_table)) + 4 * (blockIdx.x + gridDim.x * blockIdx.y);
     d[0] = dbg_c1 - dbg_c0; d[1] = dbg_c2 - dbg_c1; d[2] = __builtin_amdgcn_s_memrealtime() - dbg_r0; d[3] = dbg_r0;
   }
@@ -2247,40 +2247,21 @@ __global__ __launch_bounds__(64 * WAVES, 1) void conv_gemm_fat_kernel(const DnGe
   }
 }
 
-// In-chain launch timing (dn_profile_start / dn_profile_stop): HIP events recorded on the launch stream
-// around every dn_conv_gemm whose tag (bits 8..15 of DnGemmParams.pad_) matches.  Eager launches only.
-// (struct LaunchProfile / g_prof: common.h -- wgrad_tn.hip times its launches the same way)
+// ------------------------------------------------------------------------------------------ route
+// How dn_conv_gemm runs a contraction (DnGemmRoute: tile, K order, shared staged rows, band), decided once per call by route()
+// from the params and the run-time options alone; launch() and the dn_conv_gemm_route / _tile / _kblocked_ok queries read it.
+// The helpers up to route() are its rules and serve it only.  DN_EPI_RELU routes as DN_EPI_SILU: no rule tells them apart.
+using Route = DnGemmRoute;
 
-template <typename E, int EPI, int BM, int STAGES>
-static int launch_tile(const DnGemmParams& p, hipStream_t s) {
-  constexpr int ring = STAGES * (W_TILE_BYTES + BM * ROWB), slabs = (BM / 32) * 64 * 68 * 4;
-  constexpr int lds = ring > slabs ? ring : slabs;  // K-loop ring, reused as the epilogue's transpose slabs
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm_kernel<E, EPI, BM, STAGES>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
-  const int np = p.N * (EPI == DN_EPI_GEGLU ? 2 : 1);
-  dim3 grid(((p.M + BM - 1) / BM) * ((np + BN - 1) / BN), p.groups);
-  const bool timed = g_prof.cap > 0 && ((p.pad_ >> 8) & 0xff) == g_prof.tag && g_prof.n < g_prof.cap;
-  if (timed) (void)hipEventRecord(g_prof.ev[2 * g_prof.n], s);
-  hipLaunchKernelGGL((conv_gemm_kernel<E, EPI, BM, STAGES>), grid, dim3(BM * 2), lds, s, p);
-  if (timed) (void)hipEventRecord(g_prof.ev[2 * g_prof.n++ + 1], s);
-  DN_CHECK_LAUNCH("dn_conv_gemm");
-  return DN_OK;
-}
-
-// Are the terms the taps of one causal conv, to be run innermost in K by the two tiles with 32-deep K-tiles (256 x 352, 256 x 256)?
+// Are the terms the taps of one causal conv, to be run innermost in K by the tiles with 32-deep K-tiles (256 x 352, 256 x 256)?
 // Same activation tensor and layout, non-negative shifts and weight addresses in arithmetic progression.  That order is those
 // tiles' default: the activation panel crosses the fabric once instead of once per tap.  It changes the fp32 summation order, and
 // with it the last bits, relative to the 128-byte-K-tile variants (term-outer): a batch large enough to route to these tiles and
 // a smaller one do not agree to the last bit; equal-size shards do.  DN_TAPS_INNER=0 (or DN_FAT_TAPS_INNER=0, the older name)
-// or bit 23 of pad_ restores term-outer everywhere (bit 22 forces tap-inner).
-static inline bool taps_route_by_shape() { return option_or(OPT_TAPS_INNER, 1) == 2; }  // dn_set_option("taps_inner", 2)
+// or DN_GEMM_TERM_OUTER restores term-outer everywhere (DN_GEMM_TAPS_INNER forces tap-inner).
 static inline bool terms_are_taps(const DnGemmParams& p) {
   const bool env_taps = option_or(OPT_TAPS_INNER, 1) != 0;
-  bool taps = p.n_terms >= 2 && p.n_terms <= 4 && !((p.pad_ >> 23) & 1) && (env_taps || ((p.pad_ >> 22) & 1));
+  bool taps = p.n_terms >= 2 && p.n_terms <= 4 && !(p.flags & DN_GEMM_TERM_OUTER) && (env_taps || (p.flags & DN_GEMM_TAPS_INNER));
   for (int i = 0; i < p.n_terms; ++i) taps = taps && p.terms[i].layout == p.terms[0].layout && p.terms[i].shift >= 0;
   for (int i = 1; i < p.n_terms && taps; ++i) {
     const DnGemmTerm &a = p.terms[i], &b = p.terms[i - 1], &t0 = p.terms[0], &t1 = p.terms[1];
@@ -2291,137 +2272,33 @@ static inline bool terms_are_taps(const DnGemmParams& p) {
   return taps;
 }
 
-template <typename E, int EPI, bool TAPS, int BNB = 256, bool HALO = false>
-static void launch_big_variant(const DnGemmParams& p, dim3 grid, int lds, hipStream_t s) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm_big_kernel<E, EPI, TAPS, BNB, HALO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((conv_gemm_big_kernel<E, EPI, TAPS, BNB, HALO>), grid, dim3(512), lds, s, p);
-}
-
-// Shared staging of the taps' rows on the 256 x 256 tile: three taps with shifts (2d, d, 0) and at least two K-chunks; per group
-// (dilation = shift << group) and per tile the kernel falls back to shifted copies (halo over 128 rows, a sequence start inside the
-// tile).  DN_BIG_HALO=0 or bit 21 of pad_ switch it off.
+// Shared staging of the taps' rows on the 256 x 256 tile: three taps with shifts (2d, d, 0) and at least two K-chunks of kt_elems;
+// per group (dilation = shift << group) and per tile the kernel falls back to shifted copies (halo over 128 rows, a sequence start
+// inside the tile).  DN_BIG_HALO=0 or DN_GEMM_NO_SHARED_ROWS switch it off.
 static inline bool big_taps_share_rows(const DnGemmParams& p, int kt_elems) {
   static const bool env_off = getenv("DN_BIG_HALO") && atoi(getenv("DN_BIG_HALO")) == 0;
-  if (env_off || ((p.pad_ >> 21) & 1) || p.n_terms != 3 || p.K / kt_elems < 2) return false;
+  if (env_off || (p.flags & DN_GEMM_NO_SHARED_ROWS) || p.n_terms != 3 || p.K / kt_elems < 2) return false;
   const DnGemmTerm &t0 = p.terms[0], &t1 = p.terms[1], &t2 = p.terms[2];
   return t2.shift == 0 && t1.shift >= 1 && t0.shift == 2 * t1.shift && (t0.shift_by_group || 2 * t1.shift <= 128);
 }
 
-template <typename E, int EPI, int BNB = 256>
-static int launch_big(const DnGemmParams& p, hipStream_t s) {
-  constexpr int ring = 4 * (BNB + 256) * ROWB2, slabs = 8 * 64 * EP_LD * 4;
-  constexpr int lds = ring > slabs ? ring : slabs;
-  const int np = p.N * (EPI == DN_EPI_GEGLU ? 2 : 1);
-  dim3 grid(((p.M + 255) / 256) * ((np + BNB - 1) / BNB), p.groups);
-  const bool timed = g_prof.cap > 0 && ((p.pad_ >> 8) & 0xff) == g_prof.tag && g_prof.n < g_prof.cap;
-  if (timed) (void)hipEventRecord(g_prof.ev[2 * g_prof.n], s);
-  bool tapped = false;
-  if constexpr ((EPI == DN_EPI_BIAS || EPI == DN_EPI_FILM_GATE) && !std::is_same<E, BF16X3>::value && BNB == 256) {  // the epilogues a causal conv has (CausalConv1d + bias; the WaveNet block); split operands pair K-tiles along a row: term-outer only
-    if (terms_are_taps(p)) {
-      if (big_taps_share_rows(p, ROWB2 / Elem<E>::bytes)) launch_big_variant<E, EPI, true, 256, true>(p, grid, lds, s);
-      else launch_big_variant<E, EPI, true>(p, grid, lds, s);
-      tapped = true;
-    }
-  }
-  if (!tapped) launch_big_variant<E, EPI, false, BNB>(p, grid, lds, s);
-  if (timed) (void)hipEventRecord(g_prof.ev[2 * g_prof.n++ + 1], s);
-  DN_CHECK_LAUNCH("dn_conv_gemm");
-  return DN_OK;
-}
-
-template <typename E, int EPI>
-static int launch_mid2(const DnGemmParams& p, hipStream_t s) {
-  constexpr int ring = 3 * (BNM + 256) * ROWB2, slabs = 4 * 64 * EP_LD * 4;
-  constexpr int lds = ring > slabs ? ring : slabs;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm_mid2_kernel<E, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
-  const int np = p.N * (EPI == DN_EPI_GEGLU ? 2 : 1);
-  dim3 grid(((p.M + 255) / 256) * ((np + BNM - 1) / BNM), p.groups);
-  const bool timed = g_prof.cap > 0 && ((p.pad_ >> 8) & 0xff) == g_prof.tag && g_prof.n < g_prof.cap;
-  if (timed) (void)hipEventRecord(g_prof.ev[2 * g_prof.n], s);
-  hipLaunchKernelGGL((conv_gemm_mid2_kernel<E, EPI>), grid, dim3(256), lds, s, p);
-  if (timed) (void)hipEventRecord(g_prof.ev[2 * g_prof.n++ + 1], s);
-  DN_CHECK_LAUNCH("dn_conv_gemm (256 x 128 tile, two workgroups per CU)");
-  return DN_OK;
-}
-
-template <typename E, int EPI>
-static int launch_row(const DnGemmParams& p, hipStream_t s) {
-  constexpr int ring = 2 * (512 + 64) * ROWB, slabs = 8 * 64 * EP_LD * 4 + 64 * 8 * 4;
-  constexpr int lds = ring > slabs ? ring : slabs;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm_row_kernel<E, EPI>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
-  dim3 grid((p.M + 63) / 64, p.groups);
-  hipLaunchKernelGGL((conv_gemm_row_kernel<E, EPI>), grid, dim3(512), lds, s, p);
-  DN_CHECK_LAUNCH("dn_conv_gemm (row tile)");
-  return DN_OK;
-}
-
-template <typename E, int EPI, bool TAPS_INNER, int NTW, int WAVES, bool HALO = false>
-static void launch_fat_variant(const DnGemmParams& p, dim3 grid, int lds, hipStream_t s) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm_fat_kernel<E, EPI, TAPS_INNER, NTW, WAVES, HALO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((conv_gemm_fat_kernel<E, EPI, TAPS_INNER, NTW, WAVES, HALO>), grid, dim3(64 * WAVES), lds, s, p);
-}
-
 // Can the three taps share ONE staged copy of the activation rows (the HALO form of the 256 x 352 tile)?  Taps of one causal conv
 // with shifts (2d, d, 0), d <= 8; at least three K-chunks.  The kernel decides per tile: one with a sequence start inside runs the
-// shifted-copies loop (with sequences a multiple of 256 frames long no tile has one).  DN_FAT_HALO=0 or bit 21 of pad_ switch it
-// off (A/B timing, tests).
+// shifted-copies loop (with sequences a multiple of 256 frames long no tile has one).  DN_FAT_HALO=0 or DN_GEMM_NO_SHARED_ROWS
+// switch it off (A/B timing, tests).
 static inline bool taps_share_rows(const DnGemmParams& p) {
   static const bool env_off = getenv("DN_FAT_HALO") && atoi(getenv("DN_FAT_HALO")) == 0;
-  if (env_off || ((p.pad_ >> 21) & 1) || p.n_terms != 3 || p.K < 96) return false;
+  if (env_off || (p.flags & DN_GEMM_NO_SHARED_ROWS) || p.n_terms != 3 || p.K < 96) return false;
   const DnGemmTerm &t0 = p.terms[0], &t1 = p.terms[1], &t2 = p.terms[2];
   return !t0.shift_by_group && t2.shift == 0 && t1.shift >= 1 && t1.shift <= 8 && t0.shift == 2 * t1.shift;
 }
 
-// NTW = 11: the 256 x 352 tile (caller guarantees N % 352 == 0, BIAS epilogue); NTW = 8: the 256 x 256 tile, with one
-// (WAVES = 4) or two (WAVES = 8) waves per SIMD.
-template <typename E, int EPI, int NTW, int WAVES = 4>
-static int launch_fat(const DnGemmParams& p, hipStream_t s) {
-  constexpr int BNF = 32 * NTW;
-  constexpr int ring = 4 * (BNF + 256) * ROWB2, slabs = WAVES * 64 * EP_LD * 4;
-  constexpr int lds = ring > slabs ? ring : slabs;
-  const int np = p.N * (EPI == DN_EPI_GEGLU ? 2 : 1);
-  dim3 grid(((p.M + 255) / 256) * ((np + BNF - 1) / BNF), p.groups);
-  const bool timed = g_prof.cap > 0 && ((p.pad_ >> 8) & 0xff) == g_prof.tag && g_prof.n < g_prof.cap;
-  const bool taps = terms_are_taps(p);  // tap-inner K order for the taps of one causal conv (see the kernel and terms_are_taps)
-  if (timed) (void)hipEventRecord(g_prof.ev[2 * g_prof.n], s);
-  bool shared = false;
-  if constexpr (NTW == 11 && WAVES == 4 && EPI == DN_EPI_BIAS) {
-    if (taps && taps_share_rows(p)) {
-      launch_fat_variant<E, EPI, true, NTW, WAVES, true>(p, grid, lds, s);
-      shared = true;
-    }
-  }
-  if (shared) {}
-  else if (taps) launch_fat_variant<E, EPI, true, NTW, WAVES>(p, grid, lds, s);
-  else launch_fat_variant<E, EPI, false, NTW, WAVES>(p, grid, lds, s);
-  if (timed) (void)hipEventRecord(g_prof.ev[2 * g_prof.n++ + 1], s);
-  DN_CHECK_LAUNCH("dn_conv_gemm (one-wave-per-SIMD tile)");
-  return DN_OK;
-}
-
-// Tile variant forced for this call: DN_GEMM_TILE (process-wide) or bits 16..19 of pad_ (per call; tests); 0 = choose by shape.
+// Tile variant forced for this call: DN_GEMM_TILE (process-wide) or the DN_GEMM_TILE_SHIFT bits of flags (per call; tests);
+// 0 = choose by shape.
 static inline int forced_tile(const DnGemmParams& p) {
   static const int env_tile = getenv("DN_GEMM_TILE") ? atoi(getenv("DN_GEMM_TILE")) : 0;
-  return ((p.pad_ >> 16) & 15) ? ((p.pad_ >> 16) & 15) : env_tile;
+  const int bits = (p.flags >> DN_GEMM_TILE_SHIFT) & 15;
+  return bits ? bits : env_tile;
 }
 
 // Does this contraction run on the 256 x 352 one-wave-per-SIMD tile?  bf16, BIAS or GEGLU, packed columns a multiple of
@@ -2429,20 +2306,18 @@ static inline int forced_tile(const DnGemmParams& p) {
 // batches, +5 % on whole ones, against the 256 x 256 tile on the FFN conv).  Chosen by itself only for the long-K BIAS
 // contractions; on the GEGLU projection (K = 512: 16 K-tiles) it measured level with the 256 x 256 tile (67.6 vs 66.1
 // us), so there it runs only when forced.
-static inline bool routes_to_352(const DnGemmParams& p) {
+static inline bool routes_to_352(const DnGemmParams& p, int force) {
   if (!dn_is16(p.dtype) || (p.epilogue != DN_EPI_BIAS && p.epilogue != DN_EPI_GEGLU)) return false;
-  if ((p.epilogue == DN_EPI_RESADD || p.epilogue == DN_EPI_POSEMB) && p.norm_out && !p.norm_split) return false;
-  const int force = forced_tile(p);
   const int npk = p.N * (p.epilogue == DN_EPI_GEGLU ? 2 : 1);
   if (npk % 352 != 0) return false;
-  if (force == 4) return true;
+  if (force == DN_TILE_256X352) return true;
   if (force != 0 || p.epilogue != DN_EPI_BIAS) return false;
   // One workgroup per CU on both 256-row tiles, so what decides is how much of the chip a launch fills: the 352-wide tile is
   // ~1.3x the 256-wide one per flop on a full chip (1.33 vs 0.95-1.0 PFLOP/s on the FFN conv) but has 1/1.375 of its tiles.  A
-  // half-batch launch of the two-stream sampling chain (bit 7 of pad_: an identical twin runs beside it) counts double: 128 + 128
+  // half-batch launch of the two-stream sampling chain (DN_GEMM_TWIN: an identical twin runs beside it) counts double: 128 + 128
   // workgroups fill the chip.  Alone, a 128-tile launch leaves half the chip idle: the training step's FFN conv at M = 8192 takes
   // 138 us on this tile against 98 us on 192 tiles of 256 x 256.
-  const long twin = (p.pad_ & 128) ? 2 : 1;
+  const long twin = (p.flags & DN_GEMM_TWIN) ? 2 : 1;
   const long tiles_fat = (long)((p.M + 255) / 256) * (npk / 352) * p.groups * twin;
   const long tiles_big = (long)((p.M + 255) / 256) * ((npk + 255) / 256) * p.groups * twin;
   auto fill = [](long tiles) { const double r = (double)tiles / 256.0; return r / ceil(r); };
@@ -2451,29 +2326,28 @@ static inline bool routes_to_352(const DnGemmParams& p) {
   return tiles_fat >= 100 && 1.3 * fill(tiles_fat) >= fill(tiles_big);
 }
 
-// The tile variant a contraction runs on: 1 = 128 x 128, 2 = 256 x 128, 3 = 256 x 256, 4 = 256 x 352, 5 = whole-row (fused norm),
-// 6 / 7 = the forced-only hand-scheduled 256 x 256 forms; -1 = K-blocked operands with a tile forced that does not take them.
-static inline int choose_tile(const DnGemmParams& p) {
+// The tile variant a contraction runs on (DN_TILE_*); -1 = K-blocked operands with a tile forced that does not take them.
+// force: forced_tile(p); taps: terms_are_taps(p).
+static inline int choose_tile(const DnGemmParams& p, int force, bool taps) {
   const bool bf = dn_is16(p.dtype);
-  if ((p.epilogue == DN_EPI_RESADD || p.epilogue == DN_EPI_POSEMB) && p.norm_out && !p.norm_split && p.dtype != DN_BF16X3) return 5;
-  const int force = forced_tile(p);
+  if ((p.epilogue == DN_EPI_RESADD || p.epilogue == DN_EPI_POSEMB) && p.norm_out && !p.norm_split && p.dtype != DN_BF16X3) return DN_TILE_ROW;
   bool has_ldw = false;
   for (int i = 0; i < p.n_terms; ++i) has_ldw = has_ldw || p.terms[i].ldw != 0;
   // A handful of rows against a huge fp32 weight (the conditioning projections: B rows x [2048 -> 57 k], 470 MB of weights): the
   // launch is a weight stream, and what decides is how the rows of the weight are fetched -- the 128-byte K-tiles of the 128 x 128
   // tile take whole cache lines per row (64-byte K-tiles: half lines from rows 8 KiB apart), two workgroups per CU keep twice
   // the loads in flight.  Measured at B = 16 (tools/cond_gemm_bench.py): 282 us on that tile against 503-569 us on the others.
-  if (p.dtype == DN_F32 && p.M <= 128 && force == 0 && (long)p.N * p.K * p.groups >= (8L << 20)) return 1;
+  if (p.dtype == DN_F32 && p.M <= 128 && force == 0 && (long)p.N * p.K * p.groups >= (8L << 20)) return DN_TILE_128X128;
   if (has_ldw && p.dtype != DN_BF16X3) {  // a weight row stride other than K: the 128x128 / 256x128 / 256x256 tiles (row-major operands)
     const int npw = p.N * (p.epilogue == DN_EPI_GEGLU ? 2 : 1);
     const long tb = (long)((p.M + 255) / 256) * ((npw + 255) / 256) * p.groups, ts = (long)((p.M + 127) / 128) * ((npw + BN - 1) / BN) * p.groups;
-    if (force >= 1 && force <= 3) return force;
-    return tb >= 256 ? 3 : ts >= 512 ? 2 : 1;
+    if (force >= DN_TILE_128X128 && force <= DN_TILE_256X256) return force;
+    return tb >= 256 ? DN_TILE_256X256 : ts >= 512 ? DN_TILE_256X128 : DN_TILE_128X128;
   }
   if (p.dtype == DN_BF16X3) {  // split operands run on the two 128-byte-K-tile kernels (row-major operands only)
     for (int i = 0; i < p.n_terms; ++i)
       if (p.terms[i].layout != 0) return -1;
-    if ((force >= 1 && force <= 3) || (force == 8 && p.epilogue == DN_EPI_BIAS)) return force;
+    if ((force >= DN_TILE_128X128 && force <= DN_TILE_256X256) || (force == DN_TILE_256X192 && p.epilogue == DN_EPI_BIAS)) return force;
     const int npx = p.N * (p.epilogue == DN_EPI_GEGLU ? 2 : 1);
     const long mt2 = (p.M + 255) / 256, t_big = mt2 * ((npx + 255) / 256) * p.groups, t_mid = mt2 * ((npx + BN - 1) / BN) * p.groups,
                t_small = (long)((p.M + 127) / 128) * ((npx + BN - 1) / BN) * p.groups;
@@ -2481,7 +2355,7 @@ static inline int choose_tile(const DnGemmParams& p) {
     // three MFMAs per product against twice the staged bytes: the 256 x 256 tile is the one that stays matrix-bound (its fill
     // path needs 21 B/cycle per CU; 256 x 128 needs 31, two 128 x 128 workgroups 43 of the ~30 available)
     const double sb = 1.00 * fill2(t_big, 1), sm = 0.80 * fill2(t_mid, 1), ss = 0.70 * fill2(t_small, 2);
-    // The 256 x 192 tile (tile 8, BIAS epilogue; N = 1408 -> 512 workgroups = two full rounds instead of 1.5) is forced-only
+    // The 256 x 192 tile (BIAS epilogue; N = 1408 -> 512 workgroups = two full rounds instead of 1.5) is forced-only
     // (DN_X3_192=1 lets the score pick it): isolated, the FFN conv + q/kv pair of a layer drops 552 -> 513 us at [32,512], but
     // in the two-stream chain each half-batch launch is then exactly one round and the halves stop filling each other's ragged
     // rounds: 77.9 vs 80.4 steps/s, three alternating same-box runs.
@@ -2489,24 +2363,29 @@ static inline int choose_tile(const DnGemmParams& p) {
     if (p.epilogue == DN_EPI_BIAS && force == 0 && use192) {
       const int c192 = (npx + 191) / 192;
       const double s192 = 0.97 * fill2(mt2 * c192 * p.groups, 1) * npx / (192.0 * c192) / (npx / (256.0 * ((npx + 255) / 256)));
-      if (s192 > sb && s192 > sm && s192 > ss) return 8;
+      if (s192 > sb && s192 > sm && s192 > ss) return DN_TILE_256X192;
     }
-    if (sb >= sm && sb >= ss) return 3;
-    return sm > ss ? 2 : 1;
+    if (sb >= sm && sb >= ss) return DN_TILE_256X256;
+    return sm > ss ? DN_TILE_256X128 : DN_TILE_128X128;
   }
-  if (routes_to_352(p)) return 4;
+  if (routes_to_352(p, force)) return DN_TILE_256X352;
   // DN_TAPS_INNER=2: the taps of a causal conv run on the 64-byte-K-tile kernels (tap-inner order, shared rows) WHATEVER M is, so a
   // batch and its shards sum every output in the same order -- bit-for-bit sharding invariance at the fast order's speed on
   // large batches (small ones pay for 256-row tiles); the sharded driver's default (normalize.py).
-  if (force == 0 && (p.epilogue == DN_EPI_BIAS || p.epilogue == DN_EPI_FILM_GATE) && taps_route_by_shape() && terms_are_taps(p)) return 3;
+  const bool taps_route_by_shape = option_or(OPT_TAPS_INNER, 1) == 2;  // dn_set_option("taps_inner", 2)
+  if (force == 0 && (p.epilogue == DN_EPI_BIAS || p.epilogue == DN_EPI_FILM_GATE) && taps_route_by_shape && taps) return DN_TILE_256X256;
   bool kblocked = false;
   for (int i = 0; i < p.n_terms; ++i) kblocked = kblocked || p.terms[i].layout != 0;
-  const bool mid2_ok = bf && p.epilogue != DN_EPI_RESADD && p.epilogue != DN_EPI_POSEMB;  // tile 9: 256 x 128, two workgroups per CU (no residual prefetch / split-norm producer on it)
-  if (kblocked) return bf && force == 8 && p.epilogue == DN_EPI_BIAS ? 8 : mid2_ok && force == 9 ? 9 : bf && (force == 0 || force == 3) ? 3 : -1;  // the other tiles that take them (8: the 192-column form)
-  if (bf && force == 8 && (p.epilogue == DN_EPI_BIAS || (p.epilogue == DN_EPI_RESADD && !(p.norm_out && p.norm_split)))) return 8;
-  if (mid2_ok && force == 9) return 9;
-  if (p.dtype == DN_BF16 && (force == 6 || force == 7)) return force;
-  if (force >= 1 && force <= 3) return force;
+  const bool mid2_ok = bf && p.epilogue != DN_EPI_RESADD && p.epilogue != DN_EPI_POSEMB;  // 256 x 128, two workgroups per CU (no residual prefetch / split-norm producer on it)
+  if (kblocked)  // the other tiles that take them (and the 192-column form of the 256 x 256 kernel)
+    return bf && force == DN_TILE_256X192 && p.epilogue == DN_EPI_BIAS ? DN_TILE_256X192
+           : mid2_ok && force == DN_TILE_256X128_2WG                  ? DN_TILE_256X128_2WG
+           : bf && (force == 0 || force == DN_TILE_256X256)            ? DN_TILE_256X256
+                                                                       : -1;
+  if (bf && force == DN_TILE_256X192 && (p.epilogue == DN_EPI_BIAS || (p.epilogue == DN_EPI_RESADD && !(p.norm_out && p.norm_split)))) return DN_TILE_256X192;
+  if (mid2_ok && force == DN_TILE_256X128_2WG) return DN_TILE_256X128_2WG;
+  if (p.dtype == DN_BF16 && (force == DN_TILE_256X256_W4 || force == DN_TILE_256X256_W8)) return force;
+  if (force >= DN_TILE_128X128 && force <= DN_TILE_256X256) return force;
 
   const int np = p.N * (p.epilogue == DN_EPI_GEGLU ? 2 : 1);
   const long mt256 = (p.M + 255) / 256, mt128 = (p.M + 127) / 128;
@@ -2519,12 +2398,12 @@ static inline int choose_tile(const DnGemmParams& p) {
   // prologue and epilogue, which is what the short-K contractions (K = 512: 8 K-tiles) are made of.
   static const int heur = getenv("DN_GEMM_HEUR") ? atoi(getenv("DN_GEMM_HEUR")) : 1;
   if (heur == 0)  // previous rule, kept for A/B timing
-    return tiles_big >= 360 ? 3 : tiles_mid >= 192 ? 2 : 1;
+    return tiles_big >= 360 ? DN_TILE_256X256 : tiles_mid >= 192 ? DN_TILE_256X128 : DN_TILE_128X128;
   // The GEGLU projection goes to the 256 x 256 tile as soon as that gives every CU a tile: there the engine feeds it K-blocked
   // operands (whole cache lines), and in the two-stream chain the other half-batch's launches fill its partial last round, which
   // the fill model below cannot see.  Measured at M = 8192 (a half-batch stream of [32,512]): 38.7-40.9 us against 41.6-42.3 on
   // the 128 x 128 tile in isolation, +2.2 % per denoising step in the chain (176.9 vs 173.1 steps/s, two alternating runs).
-  if (bf && p.epilogue == DN_EPI_GEGLU && tiles_big >= 256 && heur != 3) return 3;  // DN_GEMM_HEUR=3: scored like the rest (A/B)
+  if (bf && p.epilogue == DN_EPI_GEGLU && tiles_big >= 256 && heur != 3) return DN_TILE_256X256;  // DN_GEMM_HEUR=3: scored like the rest (A/B)
   auto fill = [](long tiles, int per_cu) {
     const double rounds = (double)tiles / (256.0 * per_cu);
     return rounds / ceil(rounds);
@@ -2536,26 +2415,27 @@ static inline int choose_tile(const DnGemmParams& p) {
   // on 1536 of 128 x 128 (3 full rounds each); backward-data (negative shifts: no shared rows) 268 / 259 / 281.  M = 15360: 293
   // against 411.  DN_GEMM_HEUR=4: the short-K factors for every shape (A/B timing).
   const bool multi_long = heur != 4 && (p.epilogue == DN_EPI_BIAS || p.epilogue == DN_EPI_FILM_GATE) && p.n_terms >= 2 && (long)p.K * p.n_terms >= 1024;
-  const bool long_taps = multi_long && terms_are_taps(p);
+  const bool long_taps = multi_long && taps;
+  // (shared rows counted with the 2-byte types' 32-element K-tiles whatever the type: the score's quantity, not the launch's)
   const bool shares = long_taps && big_taps_share_rows(p, 32) && heur != 5;
   const bool long_k = heur == 5 ? long_taps : multi_long;  // DN_GEMM_HEUR=5: the rule before round 4's recalibration (taps only, no shared-row factor; A/B timing)
   const double s_big = 1.00 * fill(tiles_big, 1), s_mid = (shares ? 0.68 : long_k ? 0.78 : 0.90) * fill(tiles_mid, 1),
                s_small = (shares ? 0.60 : long_k ? 0.72 : 0.92) * fill(tiles_small, 2);
-  // The 256 x 192 form of the 256 x 256 kernel (tile 8; BIAS and RESADD epilogues, 2-byte operands, not the taps of a long conv: those
+  // The 256 x 192 form of the 256 x 256 kernel (BIAS and RESADD epilogues, 2-byte operands, not the taps of a long conv: those
   // share staged rows on the 256-wide form only): widths that are whole multiples of 192 but leave 256-wide tiles a ragged round --
   // the VAE's N = 768 contractions at M = 12288 are 144 tiles of 256 x 256 (0.56 of one round) but 192 of 256 x 192 (0.75 of one,
-  // each 3/4 of the work).  Scored only for a launch that has the chip to itself (see g_gemm_twin; option tile_192 = 0: never) and
+  // each 3/4 of the work).  Scored only for a launch that has the chip to itself (not DN_GEMM_TWIN; option tile_192 = 0: never) and
   // only from K = 768 up: the narrower tile saves MFMAs and weight-panel reads, not the activation panel's LDS traffic nor the
   // prologue and epilogue a short K loop is made of (measured in the training updates: N = 768, K = 768-4096: 75.5 -> 66.2 us;
   // N = 1408, K = 512 at M = 8192, 192 -> 256 workgroups: 77.2 -> 78.8 us).
-  if (bf && (p.epilogue == DN_EPI_BIAS || p.epilogue == DN_EPI_RESADD) && !long_taps && !g_gemm_twin && !(p.norm_out && p.norm_split) &&
+  if (bf && (p.epilogue == DN_EPI_BIAS || p.epilogue == DN_EPI_RESADD) && !long_taps && !(p.flags & DN_GEMM_TWIN) && !(p.norm_out && p.norm_split) &&
       (long)p.K * p.n_terms >= 768 && option_or(OPT_TILE_192, 1) != 0) {
     const int c192 = (np + 191) / 192, c256 = (np + 255) / 256;
     const double s_192 = 0.90 * fill(mt256 * c192 * p.groups, 1) * (256.0 * c256) / (192.0 * c192);
-    if (s_big >= s_mid && s_big >= s_small && s_192 > s_big) return 8;  // (against the same kernel's 256-wide form only: a pure fill gain)
+    if (s_big >= s_mid && s_big >= s_small && s_192 > s_big) return DN_TILE_256X192;  // (against the same kernel's 256-wide form only: a pure fill gain)
   }
-  if (s_big >= s_mid && s_big >= s_small) return 3;
-  return s_mid > s_small ? 2 : 1;
+  if (s_big >= s_mid && s_big >= s_small) return DN_TILE_256X256;
+  return s_mid > s_small ? DN_TILE_256X128 : DN_TILE_128X128;
 }
 
 // Row-tile band of the tile order (tile_coords) for the 128 x 128 / 256 x 128 / 256 x 256 tiles: 1 unless the weights of one
@@ -2567,7 +2447,8 @@ static inline int choose_band(const DnGemmParams& p, int tile) {
   static const int env_band = getenv("DN_GEMM_BAND") ? atoi(getenv("DN_GEMM_BAND")) : -1;
   if (env_band >= 0) return env_band < 255 ? env_band : 255;
   const int es = dn_is16(p.dtype) ? 2 : 4;
-  const int bm = tile == 1 ? 128 : 256, bn = tile == 3 ? 256 : 128, conc = 32 * (tile == 1 || tile == 9 ? 2 : 1);
+  const bool two_per_cu = tile == DN_TILE_128X128 || tile == DN_TILE_256X128_2WG;
+  const int bm = tile == DN_TILE_128X128 ? 128 : 256, bn = tile == DN_TILE_256X256 ? 256 : 128, conc = 32 * (two_per_cu ? 2 : 1);
   const int np = p.N * (p.epilogue == DN_EPI_GEGLU ? 2 : 1);
   const double w_total = (double)np * p.K * p.n_terms * es;
   if (w_total < 6.0e6) return 1;
@@ -2580,44 +2461,131 @@ static inline int choose_band(const DnGemmParams& p, int tile) {
   return band < 255 ? band : 255;
 }
 
+static inline Route route(const DnGemmParams& p) {
+  const bool taps = terms_are_taps(p);
+  Route r;
+  r.tile = choose_tile(p, forced_tile(p), taps);
+  // Taps-inner K order: the 256 x 256 tile runs it for the epilogues a causal conv has (CausalConv1d + bias; the WaveNet block) and
+  // not on split operands (they pair K-tiles along a row: term-outer only); the one-wave-per-SIMD tiles for every epilogue.  Shared
+  // staged rows: the 256 x 256 tile (its 64-byte K-tiles: 32 elements of a 2-byte type, 16 of fp32) and the BIAS form of 256 x 352.
+  const bool conv_epi = p.epilogue == DN_EPI_BIAS || p.epilogue == DN_EPI_FILM_GATE;
+  const bool big = r.tile == DN_TILE_256X256 && conv_epi && p.dtype != DN_BF16X3;
+  const bool fat = r.tile == DN_TILE_256X352 || r.tile == DN_TILE_256X256_W4 || r.tile == DN_TILE_256X256_W8;
+  r.taps_inner = taps && (big || fat);
+  r.shared_rows = r.taps_inner && (big ? big_taps_share_rows(p, ROWB2 / (dn_is16(p.dtype) ? 2 : 4))
+                                       : r.tile == DN_TILE_256X352 && p.epilogue == DN_EPI_BIAS && taps_share_rows(p));
+  const int forced_band = (p.flags >> DN_GEMM_BAND_SHIFT) & 0xff;  // a band forced by the caller (tests)
+  const bool banded = (r.tile >= DN_TILE_128X128 && r.tile <= DN_TILE_256X256) || r.tile == DN_TILE_256X128_2WG;
+  r.band = banded && forced_band == 0 ? choose_band(p, r.tile) : forced_band;
+  return r;
+}
+
+// ------------------------------------------------------------------------------------------ launch
+// One launch of a tile's kernel: its LDS attribute set once, HIP events around a tagged call while dn_profile_start is open
+// (eager launches only; struct LaunchProfile / g_prof: common.h -- wgrad_tn.hip times its launches the same way).
+template <auto KERNEL>
+static int launch_kernel(const DnGemmParams& p, dim3 grid, int threads, int lds, hipStream_t s) {
+  static bool attr_done = false;
+  if (!attr_done) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    attr_done = true;
+  }
+  const bool timed = g_prof.cap > 0 && ((p.flags >> DN_GEMM_TAG_SHIFT) & 0xff) == g_prof.tag && g_prof.n < g_prof.cap;
+  if (timed) (void)hipEventRecord(g_prof.ev[2 * g_prof.n], s);
+  hipLaunchKernelGGL(KERNEL, grid, dim3(threads), lds, s, p);
+  if (timed) (void)hipEventRecord(g_prof.ev[2 * g_prof.n++ + 1], s);
+  DN_CHECK_LAUNCH("dn_conv_gemm");
+  return DN_OK;
+}
+
+template <int EPI>
+static inline int packed_cols(const DnGemmParams& p) { return p.N * (EPI == DN_EPI_GEGLU ? 2 : 1); }
+
+template <typename E, int EPI, int BM, int STAGES>
+static int launch_tile(const DnGemmParams& p, hipStream_t s) {
+  constexpr int ring = STAGES * (W_TILE_BYTES + BM * ROWB), slabs = (BM / 32) * 64 * 68 * 4;
+  constexpr int lds = ring > slabs ? ring : slabs;  // K-loop ring, reused as the epilogue's transpose slabs
+  const dim3 grid(((p.M + BM - 1) / BM) * ((packed_cols<EPI>(p) + BN - 1) / BN), p.groups);
+  return launch_kernel<conv_gemm_kernel<E, EPI, BM, STAGES>>(p, grid, BM * 2, lds, s);
+}
+
+// BNB = 256: the 256 x 256 tile; 192: its 256 x 192 form
+template <typename E, int EPI, int BNB = 256>
+static int launch_big(const DnGemmParams& p, const Route& r, hipStream_t s) {
+  constexpr int ring = 4 * (BNB + 256) * ROWB2, slabs = 8 * 64 * EP_LD * 4;
+  constexpr int lds = ring > slabs ? ring : slabs;
+  const dim3 grid(((p.M + 255) / 256) * ((packed_cols<EPI>(p) + BNB - 1) / BNB), p.groups);
+  if constexpr ((EPI == DN_EPI_BIAS || EPI == DN_EPI_FILM_GATE) && !std::is_same<E, BF16X3>::value && BNB == 256) {
+    if (r.shared_rows) return launch_kernel<conv_gemm_big_kernel<E, EPI, true, 256, true>>(p, grid, 512, lds, s);
+    if (r.taps_inner) return launch_kernel<conv_gemm_big_kernel<E, EPI, true>>(p, grid, 512, lds, s);
+  }
+  return launch_kernel<conv_gemm_big_kernel<E, EPI, false, BNB>>(p, grid, 512, lds, s);
+}
+
+template <typename E, int EPI>
+static int launch_mid2(const DnGemmParams& p, hipStream_t s) {
+  constexpr int ring = 3 * (BNM + 256) * ROWB2, slabs = 4 * 64 * EP_LD * 4;
+  constexpr int lds = ring > slabs ? ring : slabs;
+  const dim3 grid(((p.M + 255) / 256) * ((packed_cols<EPI>(p) + BNM - 1) / BNM), p.groups);
+  return launch_kernel<conv_gemm_mid2_kernel<E, EPI>>(p, grid, 256, lds, s);
+}
+
+template <typename E, int EPI>
+static int launch_row(const DnGemmParams& p, hipStream_t s) {
+  constexpr int ring = 2 * (512 + 64) * ROWB, slabs = 8 * 64 * EP_LD * 4 + 64 * 8 * 4;
+  constexpr int lds = ring > slabs ? ring : slabs;
+  return launch_kernel<conv_gemm_row_kernel<E, EPI>>(p, dim3((p.M + 63) / 64, p.groups), 512, lds, s);
+}
+
+// NTW = 11: the 256 x 352 tile (BIAS / GEGLU epilogue, packed columns a multiple of 352); NTW = 8: the 256 x 256 tile, with one
+// (WAVES = 4) or two (WAVES = 8) waves per SIMD.
+template <typename E, int EPI, int NTW, int WAVES = 4>
+static int launch_fat(const DnGemmParams& p, const Route& r, hipStream_t s) {
+  constexpr int BNF = 32 * NTW;
+  constexpr int ring = 4 * (BNF + 256) * ROWB2, slabs = WAVES * 64 * EP_LD * 4;
+  constexpr int lds = ring > slabs ? ring : slabs;
+  const dim3 grid(((p.M + 255) / 256) * ((packed_cols<EPI>(p) + BNF - 1) / BNF), p.groups);
+  if constexpr (NTW == 11 && WAVES == 4 && EPI == DN_EPI_BIAS) {
+    if (r.shared_rows) return launch_kernel<conv_gemm_fat_kernel<E, EPI, true, NTW, WAVES, true>>(p, grid, 64 * WAVES, lds, s);
+  }
+  if (r.taps_inner) return launch_kernel<conv_gemm_fat_kernel<E, EPI, true, NTW, WAVES>>(p, grid, 64 * WAVES, lds, s);
+  return launch_kernel<conv_gemm_fat_kernel<E, EPI, false, NTW, WAVES>>(p, grid, 64 * WAVES, lds, s);
+}
+
 template <typename E, int EPI>
 static int launch(const DnGemmParams& p0, hipStream_t s) {
+  const Route r = route(p0);
+  DN_CHECK_ARG(r.tile > 0, "dn_conv_gemm: K-blocked operands are taken by the 256 x 352 and 256 x 256 tiles only (bf16; forced tile %d)",
+               forced_tile(p0));
   DnGemmParams p = p0;
-  const int tile = choose_tile(p);
   static const bool no_res_prefetch = getenv("DN_RES_PREFETCH") && atoi(getenv("DN_RES_PREFETCH")) == 0;  // A/B timing
-  if (no_res_prefetch) p.pad_ |= 32;
-  if (((tile >= 1 && tile <= 3) || tile == 9) && ((p.pad_ >> 24) & 0xff) == 0)  // bits 24..31 of pad_: a band forced by the caller (tests)
-    p.pad_ = (p.pad_ & 0x00ffffff) | (choose_band(p, tile) << 24);
-  DN_CHECK_ARG(tile > 0, "dn_conv_gemm: K-blocked operands are taken by the 256 x 352 and 256 x 256 tiles only (bf16; forced tile %d)",
-               forced_tile(p));
-  if constexpr (std::is_same<E, BF16X3>::value) {  // split operands: the 128-byte-K-tile kernels (both halves in one K-tile) and the 256 x 256 tile (K-tile pairs)
-    if constexpr (EPI == DN_EPI_BIAS) {
-      if (tile == 8) return launch_big<E, EPI, 192>(p, s);
-    }
-    if (tile == 3 || tile == 8) return launch_big<E, EPI>(p, s);
-    if (tile == 2) return launch_tile<E, EPI, 256, 3>(p, s);
-    return launch_tile<E, EPI, 128, 2>(p, s);
-  } else {
-  if constexpr (EPI == DN_EPI_RESADD || EPI == DN_EPI_POSEMB) {
-    if (tile == 5) return launch_row<E, EPI>(p, s);
+  if (no_res_prefetch) p.flags |= DN_GEMM_NO_RES_PREFETCH;
+  p.flags = (int32_t)(((uint32_t)p.flags & ~(0xffu << DN_GEMM_BAND_SHIFT)) | ((uint32_t)r.band << DN_GEMM_BAND_SHIFT));
+  constexpr bool x3 = std::is_same<E, BF16X3>::value, half = IsHalf<E>::value;  // x3: split operands (128-byte-K-tile kernels and K-tile pairs on 256 x 256)
+  switch (r.tile) {
+    case DN_TILE_256X256: return launch_big<E, EPI>(p, r, s);
+    case DN_TILE_256X128: return launch_tile<E, EPI, 256, 3>(p, s);
+    case DN_TILE_ROW:
+      if constexpr (!x3 && (EPI == DN_EPI_RESADD || EPI == DN_EPI_POSEMB)) return launch_row<E, EPI>(p, s);
+      break;
+    case DN_TILE_256X352:
+      if constexpr (half && (EPI == DN_EPI_BIAS || EPI == DN_EPI_GEGLU)) return launch_fat<E, EPI, 11>(p, r, s);
+      break;
+    case DN_TILE_256X192:  // widths that are whole multiples of 192 but ragged on 256
+      if constexpr ((x3 && EPI == DN_EPI_BIAS) || (half && (EPI == DN_EPI_BIAS || EPI == DN_EPI_RESADD))) return launch_big<E, EPI, 192>(p, r, s);
+      if constexpr (x3) return launch_big<E, EPI>(p, r, s);
+      break;
+    case DN_TILE_256X128_2WG:
+      if constexpr (half && EPI != DN_EPI_RESADD && EPI != DN_EPI_POSEMB) return launch_mid2<E, EPI>(p, s);
+      break;
+    case DN_TILE_256X256_W4:  // (the forced-only hand-scheduled 256 x 256 forms: kept for bf16)
+      if constexpr (std::is_same<E, BF16>::value) return launch_fat<E, EPI, 8>(p, r, s);
+      break;
+    case DN_TILE_256X256_W8:
+      if constexpr (std::is_same<E, BF16>::value) return launch_fat<E, EPI, 8, 8>(p, r, s);
+      break;
   }
-  if constexpr ((EPI == DN_EPI_BIAS || EPI == DN_EPI_GEGLU) && IsHalf<E>::value) {
-    if (tile == 4) return launch_fat<E, EPI, 11>(p, s);
-  }
-  if constexpr ((EPI == DN_EPI_BIAS || EPI == DN_EPI_RESADD) && IsHalf<E>::value) {
-    if (tile == 8) return launch_big<E, EPI, 192>(p, s);  // 256 x 192: widths that are whole multiples of 192 but ragged on 256
-  }
-  if constexpr (IsHalf<E>::value && EPI != DN_EPI_RESADD && EPI != DN_EPI_POSEMB) {
-    if (tile == 9) return launch_mid2<E, EPI>(p, s);
-  }
-  if constexpr (std::is_same<E, BF16>::value) {  // (the forced-only hand-scheduled 256 x 256 forms: kept for bf16)
-    if (tile == 6) return launch_fat<E, EPI, 8>(p, s);
-    if (tile == 7) return launch_fat<E, EPI, 8, 8>(p, s);
-  }
-  if (tile == 3) return launch_big<E, EPI>(p, s);
-  if (tile == 2) return launch_tile<E, EPI, 256, 3>(p, s);
   return launch_tile<E, EPI, 128, 2>(p, s);
-  }
 }
 
 template <typename E>
@@ -2625,10 +2593,10 @@ static int dispatch_epi(const DnGemmParams& p, hipStream_t s) {
   switch (p.epilogue) {
     case DN_EPI_BIAS: return launch<E, DN_EPI_BIAS>(p, s);
     case DN_EPI_SILU: return launch<E, DN_EPI_SILU>(p, s);
-    case DN_EPI_RELU: {  // the SILU kernels with the activation switched by pad_ bit 6 (no further instantiations)
+    case DN_EPI_RELU: {  // the SILU kernels with the activation switched by DN_GEMM_RELU (no further instantiations)
       DnGemmParams q = p;
       q.epilogue = DN_EPI_SILU;
-      q.pad_ |= 64;
+      q.flags |= DN_GEMM_RELU;
       return launch<E, DN_EPI_SILU>(q, s);
     }
     case DN_EPI_GEGLU: return launch<E, DN_EPI_GEGLU>(p, s);

@@ -384,7 +384,7 @@ int weight_grad(const Ctx& c0, const WgTap* taps, int n_taps, int cin, const voi
     p.terms[0].W = xT; p.terms[0].w_gstride = (int64_t)pl.rows_w * pl.chunk;
     p.epilogue = DN_EPI_RESADD; p.res = grad; p.ldr = Kp; p.res_gstride = (int64_t)Np * Kp;
     p.out = grad; p.ldo = Kp; p.out_dtype = DN_F32; p.out_gstride = (int64_t)Np * Kp;
-    p.pad_ = tag << 8;
+    p.flags = tag << DN_GEMM_TAG_SHIFT;
     return finish(dn_conv_gemm(&p, c.s));
   }
   DnGemmParams p = gemm_base(c.dtype, cout, pl.N, pl.chunk, cout);
@@ -392,7 +392,7 @@ int weight_grad(const Ctx& c0, const WgTap* taps, int n_taps, int cin, const voi
   p.terms[0].A = dyT; p.terms[0].lda = pl.chunk; p.terms[0].a_gstride = (int64_t)cout * pl.chunk;
   p.terms[0].W = xT; p.terms[0].w_gstride = (int64_t)pl.N * pl.chunk;
   p.out = part; p.ldo = pl.N; p.out_dtype = DN_F32; p.out_gstride = (int64_t)cout * pl.N;
-  p.pad_ = tag << 8;
+  p.flags = tag << DN_GEMM_TAG_SHIFT;
   DN_TRY(dn_conv_gemm(&p, c.s));
   return finish(dn_wgrad_reduce(part, pl.k_slices, cout, pl.N, pl.rows_w, n_taps, grad, padn(cout), padk(cin), c.s));
 }

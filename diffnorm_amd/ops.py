@@ -105,7 +105,10 @@ def conv_gemm(terms: Sequence[Tuple[torch.Tensor, torch.Tensor, int]], out: torc
     if pre_out is not None:  # GEGLU: the pre-activation (packed columns) kept for the backward pass
         assert pre_out.is_contiguous() and pre_out.dtype == out.dtype
         p.pre_out, p.pre_ld = pre_out.data_ptr(), pre_out.shape[-1]
-    p.pad_ = int(os.environ.get("DN_DEBUG_FLAGS", "0")) | (tile << 16) | (0 if taps_inner is None else (1 << 22) if taps_inner else (1 << 23)) | ((band & 0x7f) << 24) | ((1 << 21) if shared_rows is False else 0)  # ablation switches (tools/gemm_bench.py) | forced tile / K order / no shared staging of the taps' rows (tests; None = the library's default)
+    # ablation switches (tools/gemm_bench.py) | forced tile / K order / band / no shared staging of the taps' rows (tests; None = the library's default)
+    p.flags = (int(os.environ.get("DN_DEBUG_FLAGS", "0")) | (tile << _lib.GEMM_TILE_SHIFT) | ((band & 0x7f) << _lib.GEMM_BAND_SHIFT) |
+               (0 if taps_inner is None else _lib.GEMM_TAPS_INNER if taps_inner else _lib.GEMM_TERM_OUTER) |
+               (_lib.GEMM_NO_SHARED_ROWS if shared_rows is False else 0))
     _lib.check(lib.dn_conv_gemm(C.byref(p), _stream()), "dn_conv_gemm")
     return out
 

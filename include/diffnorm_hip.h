@@ -120,14 +120,8 @@ typedef struct {
   int64_t gb_gstride;
   const float* pos_table; /* POSEMB: fp32 [T+1, pos_ld] sinusoidal table, row 0 = zeros             */
   int32_t pos_ld;
-  int32_t pad_;        /* profiling / tests only.  bit4: 4-column instead of 8-column bf16 stores (the K-loop ablations that
-                          used bits 0..3 are compile-time now: -DDN_GEMM_ABL); 0 in every product call; bits 8..15: launch tag
-                          (DN_TAG_*) matched by dn_profile_start; bits 16..19: force a tile variant (tests: 1 = 128x128,
-                          2 = 256x128, 3 = 256x256, 4 = 256x352 when N % 352 == 0, 6 / 7 = hand-scheduled 256x256 with one / two waves per SIMD [bf16]),
-                          0 = chosen from the shape; bits 22 / 23: force the
-                          256x352 tile's K order for the taps of a causal conv -- 22 = taps innermost (its default: the
-                          activation panel crosses the fabric once, not once per tap), 23 = term-outer (the summation
-                          order of every other tile variant)                                                     */
+  int32_t flags;       /* DN_GEMM_* control bits: launch tag, twin launch, forced tile / K order / band (tests, A/B timing); 0 = the
+                          library's choice for everything                                                              */
   const int32_t* lengths; /* POSEMB: [B] valid frames per sequence                                  */
   /* RESADD / POSEMB with N <= 512 only: when norm_out != NULL one workgroup owns whole output rows and also emits
    * the NEXT block's RMSNorm of the row it just produced (latent_module.py:620-639, 691, 703):
@@ -160,13 +154,49 @@ typedef struct {
   int32_t pre_ld, pre_pad_;
 } DnGemmParams;
 
+/* DnGemmParams.flags.  Bits 0..3 are the compile-time K-loop ablations' (-DDN_GEMM_ABL builds only).                */
+enum {
+  DN_GEMM_NARROW_STORES = 1 << 4,    /* 4-column instead of 8-column 2-byte stores (A/B timing)                         */
+  DN_GEMM_NO_RES_PREFETCH = 1 << 5,  /* no prefetch of the residual rows before the K loop (A/B timing)                 */
+  DN_GEMM_RELU = 1 << 6,             /* set by the library: DN_EPI_RELU runs as the SILU kernels with this bit           */
+  DN_GEMM_TWIN = 1 << 7,             /* an identical launch runs beside this one (the half batches of DN_LOOP_SPLIT2)    */
+  DN_GEMM_TAG_SHIFT = 8,             /* bits 8..15: launch tag (DN_TAG_*) matched by dn_profile_start                     */
+  DN_GEMM_TILE_SHIFT = 16,           /* bits 16..19: force a tile variant (DN_TILE_*); 0 = chosen from the shape          */
+  DN_GEMM_FAT_STAMPS = 1 << 20,      /* in-kernel clock stamps of the 256 x 352 tile (-DDN_FAT_STAMPS builds only)        */
+  DN_GEMM_NO_SHARED_ROWS = 1 << 21,  /* the taps of a causal conv do not share one staged copy of their rows               */
+  DN_GEMM_TAPS_INNER = 1 << 22,      /* force the taps-innermost K order on the tiles with 32-deep K-tiles (3, 4, 6, 7)  */
+  DN_GEMM_TERM_OUTER = 1 << 23,      /* force the term-outer K order (the summation order of every other tile)            */
+  DN_GEMM_BAND_SHIFT = 24            /* bits 24..31: row-tile band of the tile order; 0 = chosen from the shape           */
+};
+
+/* Tile variants of dn_conv_gemm (rows x packed output columns per workgroup).                                         */
+enum {
+  DN_TILE_128X128 = 1,      /* two workgroups per CU, 128-byte K-tiles                                                 */
+  DN_TILE_256X128 = 2,      /* one workgroup per CU, 128-byte K-tiles                                                  */
+  DN_TILE_256X256 = 3,      /* one workgroup per CU, 64-byte K-tiles; takes K-blocked operands                        */
+  DN_TILE_256X352 = 4,      /* one wave per SIMD, 2-byte types, BIAS / GEGLU, packed columns a multiple of 352        */
+  DN_TILE_ROW = 5,          /* 64 whole output rows (the fused RMSNorm of RESADD / POSEMB with N <= 512)               */
+  DN_TILE_256X256_W4 = 6,   /* forced only, bf16: the hand-scheduled 256 x 256 form, one wave per SIMD                 */
+  DN_TILE_256X256_W8 = 7,   /* forced only, bf16: the same with two waves per SIMD                                     */
+  DN_TILE_256X192 = 8,      /* the 256 x 256 kernel on 192 columns: widths a multiple of 192 but ragged on 256         */
+  DN_TILE_256X128_2WG = 9   /* forced only, 2-byte types: 256 x 128 with two workgroups per CU                         */
+};
+
 int dn_conv_gemm(const DnGemmParams* p, void* stream);
+
+/* How dn_conv_gemm runs a contraction; reads the params and the run-time options only.                                */
+typedef struct {
+  int32_t tile;        /* DN_TILE_*; -1 = K-blocked operands with a tile forced that does not take them (dn_conv_gemm: DN_EINVAL) */
+  int32_t taps_inner;  /* 1: the taps of a causal conv run innermost in K (tiles 3, 4, 6, 7); 0: term-outer                 */
+  int32_t shared_rows; /* 1: the taps share one staged copy of the activation rows                                         */
+  int32_t band;        /* row-tile band of the tile order (0 / 1 = column tiles fastest)                                   */
+} DnGemmRoute;
+int dn_conv_gemm_route(const DnGemmParams* p, DnGemmRoute* route);
 /* 1 when dn_conv_gemm would run this contraction (M, N, K, groups, dtype, epilogue, n_terms are read) on the tile that
  * takes K-blocked A / W terms, else 0.                                                                            */
 int dn_conv_gemm_kblocked_ok(const DnGemmParams* p);
-/* The tile variant dn_conv_gemm would run this contraction on (1 = 128x128, 2 = 256x128, 3 = 256x256, 4 = 256x352,
- * 5 = whole-row fused norm, 6 / 7 forced-only forms; -1 = K-blocked operands with an unsuitable tile forced): lets a
- * caller lay its buffers out K-blocked only where the contraction lands on a tile that gains from it.              */
+/* The tile variant dn_conv_gemm would run this contraction on (DnGemmRoute.tile): lets a caller lay its buffers out
+ * K-blocked only where the contraction lands on a tile that gains from it.                                        */
 int dn_conv_gemm_tile(const DnGemmParams* p);
 
 /* launch tags set by the engine on its dominant contractions */

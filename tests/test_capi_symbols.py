@@ -50,9 +50,10 @@ def test_struct_layout_matches_header(lib, tmp_path):
         "DnGemmParams": (_lib.GemmParams, ["terms", "n_terms", "dtype", "M", "N", "K", "T", "groups", "epilogue", "bias",
                                            "bias_gstride", "out", "ldo", "out_dtype", "out_gstride", "res", "ldr", "res_dtype",
                                            "res_gstride", "gamma_beta", "gb_ld", "gb_half", "gb_gstride", "pos_table", "pos_ld",
-                                           "lengths", "norm_out", "norm_ld", "norm_dtype", "norm_D", "norm_gb_ld", "norm_gamma",
+                                           "flags", "lengths", "norm_out", "norm_ld", "norm_dtype", "norm_D", "norm_gb_ld", "norm_gamma",
                                            "norm_gb", "norm_gb_half", "out_layout", "norm_split", "norm_ssq_ld", "norm_ssq", "row_ssq",
                                            "row_ssq_ld", "row_ssq_parts", "row_D", "row_bias_ld", "row_bias"]),
+        "DnGemmRoute": (_lib.GemmRoute, ["tile", "taps_inner", "shared_rows", "band"]),
         "DnAdamParams": (_lib.AdamParams, ["lr", "beta1", "beta2", "eps", "weight_decay", "max_norm", "step", "grad_scale",
                                            "grad_scale_dev"]),
         "DnAttnParams": (_lib.AttnParams, ["q", "k", "v", "out", "ldq", "ldk", "ldv", "ldo", "B", "T", "heads", "dim_head",
@@ -143,7 +144,7 @@ def test_tile_choice_is_host_logic(lib, monkeypatch):
     def params(M, N, K, T=512, groups=1, n_terms=1, epi=_lib.EPI_BIAS, dtype=_lib.DN_BF16, tile=0, layout=0):
         p = _lib.GemmParams()
         p.M, p.N, p.K, p.T, p.groups, p.n_terms, p.epilogue, p.dtype = M, N, K, T, groups, n_terms, epi, dtype
-        p.pad_ = tile << 16
+        p.flags = tile << _lib.GEMM_TILE_SHIFT
         for i in range(n_terms):
             p.terms[i].layout = layout
         return p
@@ -151,26 +152,26 @@ def test_tile_choice_is_host_logic(lib, monkeypatch):
     tile = lambda p: lib.dn_conv_gemm_tile(C.byref(p))
     M = 32 * 512
     ffn_conv = params(M, 1408, 1408, n_terms=3)
-    assert tile(ffn_conv) == 4 and lib.dn_conv_gemm_kblocked_ok(C.byref(ffn_conv)) == 1      # 256 x 352: 1408 = 4 x 352
-    assert tile(params(M, 1408, 1408, n_terms=3, dtype=_lib.DN_F32)) != 4                      # bf16 only
-    assert tile(params(2 * 100, 1408, 1408, T=100, n_terms=3)) != 4                            # too few tiles to own whole CUs
+    assert tile(ffn_conv) == _lib.TILE_256X352 and lib.dn_conv_gemm_kblocked_ok(C.byref(ffn_conv)) == 1  # 1408 = 4 x 352
+    assert tile(params(M, 1408, 1408, n_terms=3, dtype=_lib.DN_F32)) != _lib.TILE_256X352                # bf16 only
+    assert tile(params(2 * 100, 1408, 1408, T=100, n_terms=3)) != _lib.TILE_256X352                      # too few tiles to own whole CUs
     assert lib.dn_conv_gemm_kblocked_ok(C.byref(params(2 * 100, 1408, 1408, T=100, n_terms=3))) == 0
-    assert tile(params(M, 512, 512, groups=8)) == 3                                            # WaveNet res conv: 256 x 256
-    assert tile(params(M, 512, 512, groups=8, n_terms=3, epi=_lib.EPI_FILM_GATE)) == 3         # dilated conv + FiLM gate
-    assert tile(params(M, 1408, 512, epi=_lib.EPI_GEGLU)) == 3                                 # GEGLU projection (2816 packed columns)
-    assert tile(params(M, 1536, 512)) == 1                                                     # q/kv: two 128 x 128 workgroups per CU
-    assert tile(params(M, 2048, 2048, n_terms=3)) == 3                                         # the VAE's FFN conv (not a multiple of 352)
+    assert tile(params(M, 512, 512, groups=8)) == _lib.TILE_256X256                                      # WaveNet res conv
+    assert tile(params(M, 512, 512, groups=8, n_terms=3, epi=_lib.EPI_FILM_GATE)) == _lib.TILE_256X256   # dilated conv + FiLM gate
+    assert tile(params(M, 1408, 512, epi=_lib.EPI_GEGLU)) == _lib.TILE_256X256                           # GEGLU projection (2816 packed columns)
+    assert tile(params(M, 1536, 512)) == _lib.TILE_128X128                                               # q/kv: two 128 x 128 workgroups per CU
+    assert tile(params(M, 2048, 2048, n_terms=3)) == _lib.TILE_256X256                                   # the VAE's FFN conv (not a multiple of 352)
     # a lone launch whose 256 x 256 tiles leave most of a round idle goes to the 256 x 192 form when the width divides (training)
-    assert tile(params(24 * 512, 768, 768)) == 8 and tile(params(24 * 512, 768, 2048, epi=_lib.EPI_RESADD)) == 8
+    assert tile(params(24 * 512, 768, 768)) == _lib.TILE_256X192 and tile(params(24 * 512, 768, 2048, epi=_lib.EPI_RESADD)) == _lib.TILE_256X192
     _lib.set_option("tile_192", 0)
     try:
-        assert tile(params(24 * 512, 768, 768)) == 3
+        assert tile(params(24 * 512, 768, 768)) == _lib.TILE_256X256
     finally:
         _lib.set_option("tile_192", None)
     # K-blocked operands: taken by the two 256-row tiles; a forced tile that cannot take them is an error (-1)
-    assert tile(params(M, 1536, 512, layout=3)) == 3
-    assert tile(params(M, 1408, 1408, n_terms=3, layout=3)) == 4
-    assert tile(params(M, 1536, 512, layout=3, tile=1)) == -1
+    assert tile(params(M, 1536, 512, layout=3)) == _lib.TILE_256X256
+    assert tile(params(M, 1408, 1408, n_terms=3, layout=3)) == _lib.TILE_256X352
+    assert tile(params(M, 1536, 512, layout=3, tile=_lib.TILE_128X128)) == -1
     assert tile(params(M, 1536, 512, layout=1, dtype=_lib.DN_F32)) == -1
-    for forced in (1, 2, 3):
+    for forced in (_lib.TILE_128X128, _lib.TILE_256X128, _lib.TILE_256X256):
         assert tile(params(M, 1536, 512, tile=forced)) == forced

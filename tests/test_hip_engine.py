@@ -372,3 +372,36 @@ def test_ddpm_loop_matches_reference_p_sample_steps(eng, golden, dtype, tol):
     two = run(7, 2, False)  # the second step's draw differs from the first's (counter = step)
     assert not torch.allclose((two - one).flatten()[:64], torch.zeros(64))
 
+
+
+def test_sampling_graph_observes_run_time_options(eng):
+    """A captured sampling step is not replayed after dn_set_option changed how its contractions route: the chain run under
+    taps_inner = 0 on the buffers of a chain captured under the default is bit-identical to the eager chain under taps_inner = 0."""
+    import ctypes as C
+
+    from diffnorm_amd import _lib
+
+    engine, scheduler = eng
+    cfg = O.EpsConfig(dim=512, latent_dim=128, depth=1, wavenet_layers=2, wavenet_stacks=1)
+    e = engine.EpsEngine(O.make_eps_state_dict(cfg, "graph_opts"), cfg, dtype="bf16", device=DEV)
+    B, T = 32, 512
+    p = _lib.GemmParams()  # the FFN causal conv of one half batch: on a tile that runs the taps innermost by default
+    p.M, p.N, p.K, p.T, p.groups, p.n_terms, p.epilogue, p.dtype = B // 2 * T, 1408, 1408, T, 1, 3, _lib.EPI_BIAS, _lib.DN_BF16
+    p.flags = _lib.GEMM_TWIN
+    for j in range(3):
+        p.terms[j].shift, p.terms[j].lda = 2 - j, 1408
+    assert _lib.load().dn_conv_gemm_tile(C.byref(p)) in (_lib.TILE_256X256, _lib.TILE_256X352)
+    coef = scheduler.DDPMScheduler(200).ddim_coef_table(DEV)
+    lens = torch.full((B,), T, dtype=torch.int32, device=DEV)
+    x0 = seeded((B, T, cfg.latent_dim), 5).to(DEV)
+    x = x0.clone()
+    with _lib.option("taps_inner", 1):  # (the library default, set explicitly: the suite may run with the environment's 0)
+        assert e.ddim_loop(x, lens, 5, coef, use_graph=True) == 4  # captured with the taps innermost
+    first = x.clone()
+    x.copy_(x0)  # same buffer, same pointer
+    with _lib.option("taps_inner", 0):
+        e.ddim_loop(x, lens, 5, coef, use_graph=True)
+        ref = x0.clone()
+        e.ddim_loop(ref, lens, 5, coef, use_graph=False)
+    assert not torch.equal(first, ref)  # the two K orders differ in the last bits here: the check below can tell them apart
+    assert torch.equal(x, ref)

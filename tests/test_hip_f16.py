@@ -95,12 +95,12 @@ def test_residual_epilogue_on_the_256x192_tile(ops, half, B, T, K, N):
     res = seeded((M, N), 24)
     xa, W = x.to(DEV, tdt).contiguous(), packing._mat(w, code).to(DEV)
     outs = []
-    for tile in (8, 1):
+    for tile in (_lib.TILE_256X192, _lib.TILE_128X128):
         stream = res.to(DEV).clone()
         ops_.conv_gemm([(xa, W, 0)], stream, T, N, bias=packing._vec(b, W.shape[0]).to(DEV), epilogue=_lib.EPI_RESADD, res=stream, tile=tile)
         outs.append(stream.cpu())
         p = _lib.GemmParams()
-        p.M, p.N, p.K, p.T, p.groups, p.n_terms, p.epilogue, p.dtype, p.pad_ = M, N, K, T, 1, 1, _lib.EPI_RESADD, code, tile << 16
+        p.M, p.N, p.K, p.T, p.groups, p.n_terms, p.epilogue, p.dtype, p.flags = M, N, K, T, 1, 1, _lib.EPI_RESADD, code, tile << _lib.GEMM_TILE_SHIFT
         assert _lib.load().dn_conv_gemm_tile(C.byref(p)) == tile
     assert torch.equal(outs[0], outs[1])
     want = res + x.to(tdt).float() @ w.to(tdt).float().t() + b

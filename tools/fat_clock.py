@@ -21,7 +21,7 @@ def run(flag, abl=0):
         t = p.terms[i]; t.A, t.W, t.lda, t.shift = a.data_ptr(), w[i].data_ptr(), K, 2 - i
     p.bias = bias.data_ptr(); p.out, p.ldo, p.out_dtype = out.data_ptr(), N, _lib.DN_BF16
     p.pos_table = dbg.data_ptr() if flag else 0
-    p.pad_ = (4 << 16) | ((1 << 20) if flag else 0) | abl
+    p.flags = (_lib.TILE_256X352 << _lib.GEMM_TILE_SHIFT) | (_lib.GEMM_FAT_STAMPS if flag else 0) | abl
     _lib.check(lib.dn_conv_gemm(C.byref(p), torch.cuda.current_stream().cuda_stream), "gemm")
 for _ in range(20): run(False)
 for abl in (0, 0, 0):  # repeats
