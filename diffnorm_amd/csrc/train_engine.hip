@@ -103,6 +103,20 @@ inline int64_t take(int64_t& cur, int64_t n) {
 }
 
 // ------------------------------------------------------------------------------------------ parameter layout
+// What both training engines are built on: the flat buffers dn_*_train_bind attaches and the sizes of their regions.
+//   master / work / grads: n_params elements each;   aux = [transposed matrices: n_trans elements of the arithmetic dtype, rounded
+//   up to 64][derived fp32 vectors: n_fderived floats][256 spare bytes]
+struct FlatParams {
+  int dtype;
+  int64_t n_params, n_trans, n_fderived;
+  float* master;
+  void* work;
+  char* aux;
+  float* grads;
+  float* fderived() const { return reinterpret_cast<float*>(aux + r64(n_trans) * esize(dtype)); }  // the derived-fp32 region
+  size_t aux_bytes() const { return (size_t)r64(n_trans) * esize(dtype) + (size_t)n_fderived * 4 + 256; }
+};
+
 struct WaveP {
   int cin, cout, S, L;
   int film_col;  // FiLM (eps-predictor): first column of block (stack 0, layer 0)'s [gamma ; beta] in the conditioning rows, -1 = none
@@ -171,21 +185,94 @@ void layout_tf(TfP& w, int64_t& cur, int64_t& tcur) {
   w.t_pred = take(tcur, (int64_t)padn(Dp) * Dp);
 }
 
+void tf_set_dims(TfP& w, int dim, int depth, int heads, int dim_head, int cond_col) {
+  w.dim = dim; w.depth = depth; w.heads = heads; w.dim_head = dim_head;
+  w.inner = (int)((double)dim * 4 * 2 / 3);
+  w.cond_col = cond_col;
+}
+
+// the offsets tables of dn_*_train_offsets: a WaveNet's 10 tensors; a transformer layer's 8, then its learned gammas if it has them
+void push_wave_offsets(const WaveP& w, int64_t* offsets, int& k) {
+  for (int64_t o : {w.init_W, w.init_b, w.conv_W, w.conv_b, w.res_W, w.res_b, w.skip_W, w.skip_b, w.final_W, w.final_b}) offsets[k++] = o;
+}
+
+void push_tf_layer_offsets(const TfP& t, int l, int64_t* offsets, int& k) {
+  for (int64_t o : {t.qkv_W(l), t.out_W(l), t.ffin_W(l), t.ffin_b(l), t.ffconv_W(l), t.ffconv_b(l), t.ffout_W(l), t.ffout_b(l)}) offsets[k++] = o;
+  if (t.cond_col < 0) {
+    offsets[k++] = t.g1(l); offsets[k++] = t.g2(l);
+  }
+}
+
+// Range of the flat gradient buffer that backward stage `stage` completes: 0 = everything behind the transformer layers, 1 .. depth =
+// layers depth-1 .. 0, depth + 1 = [front_end, first layer), depth + 2 = [0, front_end).
+int stage_range(const FlatParams& p, const TfP& tf, int64_t front_end, const char* who, int32_t stage, int64_t* offset, int64_t* count) {
+  DN_CHECK_ARG(offset && count, "%s: null argument", who);
+  const int depth = tf.depth;
+  DN_CHECK_ARG(stage >= 0 && stage <= depth + 2, "%s: stage %d", who, stage);
+  int64_t lo, hi;
+  if (stage == 0) {
+    lo = tf.pred_gamma; hi = p.n_params;
+  } else if (stage <= depth) {
+    lo = tf.layer0 + (int64_t)(depth - stage) * tf.layer_stride; hi = lo + tf.layer_stride;
+  } else if (stage == depth + 1) {
+    lo = front_end; hi = tf.layer0;
+  } else {
+    lo = 0; hi = front_end;
+  }
+  *offset = lo; *count = hi - lo;
+  return DN_OK;
+}
+
+int bind_flat(FlatParams& p, const char* who, float* master, void* work, void* aux, float* grads) {
+  DN_CHECK_ARG(master && work && aux && grads, "%s: null argument", who);
+  for (const void* q : {(const void*)master, (const void*)work, (const void*)aux, (const void*)grads})
+    DN_CHECK_ARG(((uintptr_t)q & 255) == 0, "%s: buffers must be 256-byte aligned", who);
+  DN_CHECK_ARG(p.dtype == DN_BF16 || (const void*)work == (const void*)master, "%s: in f32 mode work must be master", who);
+  p.master = master; p.work = work; p.aux = (char*)aux; p.grads = grads;
+  return DN_OK;
+}
+
+// aux <- work: the transposed copies the data-gradient contractions read.  A matrix [Np][Kp] (Np = padn(N)) becomes [padn(Kp)][padk(N)];
+// `count` of them, `src_stride` elements apart (packed back to back unless given), land back to back.
+struct Transposer {
+  const FlatParams& p;
+  hipStream_t s;
+  int strided(int64_t off, int64_t src_stride, int64_t toff, int count, int N, int Kp) const {
+    const int es = esize(p.dtype);
+    return dn_transpose_weights(static_cast<const char*>(p.work) + off * es, p.dtype, count, src_stride, padk(N), Kp, p.aux + toff * es,
+                                (int64_t)padn(Kp) * padk(N), padk(N), padn(Kp), s);
+  }
+  int operator()(int64_t off, int64_t toff, int count, int N, int Kp) const { return strided(off, (int64_t)padn(N) * Kp, toff, count, N, Kp); }
+};
+
+int refresh_wave(const Transposer& tr, const WaveP& w) {  // + the summed skip biases
+  const int cinp = padk(w.cin), cp = padk(w.cout);
+  DN_TRY(tr(w.init_W, w.t_init, 3, w.cout, cinp));
+  DN_TRY(tr(w.conv_W, w.t_conv, w.S * w.L * 3, w.cout, cp));
+  DN_TRY(tr(w.res_W, w.t_res, w.S * w.L, w.cout, cp));
+  DN_TRY(tr(w.skip_W, w.t_skip, w.L, w.cout, cp));
+  DN_TRY(tr(w.final_W, w.t_final, 1, w.cout, cp));
+  return dn_sum_groups(tr.p.master + w.skip_b, cp, w.L, tr.p.fderived() + w.skip_bsum, DN_F32, cp, tr.s);
+}
+
+int refresh_tf(const Transposer& tr, const TfP& t) {
+  const int Dp = padk(t.dim), hd = t.heads * t.dim_head, ip = padk(t.inner);
+  DN_TRY(tr.strided(t.qkv_W(0), t.layer_stride, t.t_qkv, t.depth, 3 * hd, Dp));
+  DN_TRY(tr.strided(t.out_W(0), t.layer_stride, t.t_out, t.depth, t.dim, hd));
+  DN_TRY(tr.strided(t.ffin_W(0), t.layer_stride, t.t_ffin, t.depth, 2 * ip, Dp));
+  for (int l = 0; l < t.depth; ++l) DN_TRY(tr(t.ffconv_W(l), t.t_ffconv + (int64_t)l * 3 * padn(ip) * ip, 3, t.inner, ip));
+  DN_TRY(tr.strided(t.ffout_W(0), t.layer_stride, t.t_ffout, t.depth, t.dim, ip));
+  return tr(t.pred_W, t.t_pred, 1, t.dim, Dp);
+}
+
 }  // namespace
 
-struct DnVaeTrain {
+struct DnVaeTrain : FlatParams {
   DnVaeConfig cfg;
   int n_wave;
   WaveP enc[4], dec[4];
   TfP tf;
   int64_t lm_W, lm_b, t_lm;
-  int64_t n_params;   // elements of master / work / grads
-  int64_t n_trans;    // elements (arithmetic dtype) of the transposed region of aux
-  int64_t n_fderived; // floats of the derived-fp32 region of aux (behind the transposed region)
-  float* master;
-  void* work;
-  char* aux;
-  float* grads;
 };
 
 namespace {
@@ -235,9 +322,9 @@ struct Ctx {
   WgSide* side = nullptr;  // weight gradients that pass a handle run here (transformer layers)
   const float* master;  // fp32 parameters (vectors are read from here in every mode)
   const void* work;     // the same layout in the arithmetic dtype (matrices)
-  char* aux;            // transposed matrices, then derived fp32 vectors
+  char* aux;            // transposed matrices
+  float* fder;          // derived fp32 vectors
   float* grads;
-  int64_t n_trans;
   bool frozen;          // no parameter gradients (the frozen VAE decoder inside the diffusion loss): data gradients only
   float attn_dropout = 0.f;  // attention-probability dropout (train mode); layer l hashes with seed_hi + l
   uint32_t seed_lo = 0, seed_hi = 0;
@@ -250,7 +337,7 @@ struct Ctx {
   const float* P(int64_t off) const { return master + off; }       // fp32 vectors (biases, gammas)
   float* G(int64_t off) const { return grads + off; }
   const void* Wt(int64_t off) const { return aux + off * es; }
-  float* F(int64_t off) const { return reinterpret_cast<float*>(aux + ((n_trans + 63) / 64 * 64) * es) + off; }
+  float* F(int64_t off) const { return fder + off; }
 };
 
 // ------------------------------------------------------------------------------------------ weight gradient
@@ -845,30 +932,40 @@ struct VaePlan {
   float* red_scratch;
 };
 
-size_t max_wgrad_bytes(const DnVaeTrain* m, int B, int T) {
-  const int es = esize(m->cfg.dtype);
-  size_t mx = 0;
-  auto upd = [&](int cin, int cout, int taps, int max_shift) {
-    const size_t b = plan_wgrad(cin, cout, taps, max_shift, B, T, es).total();
-    mx = b > mx ? b : mx;
-  };
-  for (int n = 0; n < m->n_wave; ++n)
-    for (const WaveP* w : {&m->enc[n], &m->dec[n]}) {
-      upd(w->cin, w->cout, 3, 2);
-      upd(w->cout, w->cout, 3, 2 << (w->L - 1));
-      upd(w->cout, w->cout, w->L, 0);
-      const size_t grouped = (size_t)w->L * 2 * w->cout * 3 * padn(w->cout) * 4;  // the stack's blocks as groups of one launch, two slices of partial sums
-      mx = grouped > mx ? grouped : mx;
-    }
-  const TfP& t = m->tf;
+// Largest weight-gradient scratch (operand transposes + partial sums) among the contractions it is shown, at one batch shape.
+struct WgradMax {
+  int B, T, es;
+  size_t bytes = 0;
+  void raw(size_t b) { bytes = b > bytes ? b : bytes; }
+  void operator()(int cin, int cout, int taps, int max_shift) { raw(plan_wgrad(cin, cout, taps, max_shift, B, T, es).total()); }
+};
+
+void wave_wgrad_max(WgradMax& mx, const WaveP& w) {
+  mx(w.cin, w.cout, 3, 2);
+  mx(w.cout, w.cout, 3, 2 << (w.L - 1));
+  mx(w.cout, w.cout, w.L, 0);
+  mx.raw((size_t)w.L * 2 * w.cout * 3 * padn(w.cout) * 4);  // the stack's blocks as groups of one launch, two slices of partial sums
+}
+
+void tf_wgrad_max(WgradMax& mx, const TfP& t) {
   const int hd = t.heads * t.dim_head, ip = padk(t.inner);
-  upd(t.dim, 3 * hd, 1, 0); upd(hd, t.dim, 1, 0); upd(t.dim, 2 * ip, 1, 0); upd(t.inner, t.inner, 3, 2); upd(t.inner, t.dim, 1, 0);
-  upd(t.dim, t.dim, 1, 0); upd(t.dim, m->cfg.vocab, 1, 0);
-  return mx;
+  mx(t.dim, 3 * hd, 1, 0); mx(hd, t.dim, 1, 0); mx(t.dim, 2 * ip, 1, 0); mx(t.inner, t.inner, 3, 2); mx(t.inner, t.dim, 1, 0);
+  mx(t.dim, t.dim, 1, 0);
+}
+
+size_t max_wgrad_bytes(const DnVaeTrain* m, int B, int T) {
+  WgradMax mx{B, T, esize(m->dtype)};
+  for (int n = 0; n < m->n_wave; ++n) {
+    wave_wgrad_max(mx, m->enc[n]);
+    wave_wgrad_max(mx, m->dec[n]);
+  }
+  tf_wgrad_max(mx, m->tf);
+  mx(m->tf.dim, m->cfg.vocab, 1, 0);  // decoder_lm
+  return mx.bytes;
 }
 
 VaePlan plan_vae_train(const DnVaeTrain* m, int B, int T, Arena& ar, bool need_enc = true) {
-  const int es = esize(m->cfg.dtype), D = m->cfg.dim, Dp = padk(D), z = m->cfg.z, V = m->cfg.vocab;
+  const int es = esize(m->dtype), D = m->cfg.dim, Dp = padk(D), z = m->cfg.z, V = m->cfg.vocab;
   const size_t M = (size_t)B * T;
   VaePlan p;
   memset(&p, 0, sizeof(p));
@@ -913,13 +1010,28 @@ VaePlan plan_vae_train(const DnVaeTrain* m, int B, int T, Arena& ar, bool need_e
   return p;
 }
 
-Ctx make_ctx(const DnVaeTrain* m, int B, int T, const VaePlan& pl, hipStream_t s, bool frozen = false) {
+// The context of one forward / backward call over an engine's bound buffers and the scratch of its workspace plan (VaePlan / EpsPlan).
+template <typename Plan>
+Ctx make_ctx(const FlatParams& p, int B, int T, const Plan& pl, hipStream_t s, bool frozen = false) {
   Ctx c;
-  c.master = m->master; c.work = m->work; c.aux = m->aux; c.grads = m->grads; c.n_trans = m->n_trans; c.frozen = frozen;
-  c.dtype = m->cfg.dtype; c.es = esize(c.dtype); c.B = B; c.T = T; c.M = B * T; c.s = s;
+  c.master = p.master; c.work = p.work; c.aux = p.aux; c.fder = p.fderived(); c.grads = p.grads; c.frozen = frozen;
+  c.dtype = p.dtype; c.es = esize(c.dtype); c.B = B; c.T = T; c.M = B * T; c.s = s;
   c.wg_scratch = pl.wg_scratch; c.wg_scratch_bytes = pl.wg_scratch_bytes; c.red_scratch = pl.red_scratch;
   c.side = frozen ? nullptr : wg_side();
   return c;
+}
+
+// Lays `plan` out over the caller's workspace; `sizer` names the function that tells how large it has to be.
+template <typename PlanFn>
+int plan_workspace(void* ws, size_t ws_bytes, const char* who, const char* sizer, PlanFn plan) {
+  DN_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", who);
+  Arena ar{(char*)ws, 0, ws_bytes};
+  plan(ar);
+  if (ar.off > ws_bytes) {
+    dn_set_error("%s: workspace %zu < required %zu (%s)", who, ws_bytes, ar.off, sizer);
+    return DN_EWORKSPACE;
+  }
+  return DN_OK;
 }
 
 int check_batch(const DnVaeTrain* m, const DnVaeTrainBatch* b, void* ws, size_t ws_bytes, VaePlan* pl, const char* who) {
@@ -927,14 +1039,7 @@ int check_batch(const DnVaeTrain* m, const DnVaeTrainBatch* b, void* ws, size_t 
   DN_CHECK_ARG(m->master && m->work && m->aux && m->grads, "%s: dn_vae_train_bind has not been called", who);
   DN_CHECK_ARG(b->feat && b->units && b->lengths && b->noise && b->stats, "%s: null batch tensor", who);
   DN_CHECK_ARG(b->B > 0 && b->T > 2 && b->ntokens > 0, "%s: B=%d T=%d ntokens=%d", who, b->B, b->T, b->ntokens);
-  DN_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", who);
-  Arena ar{(char*)ws, 0, ws_bytes};
-  *pl = plan_vae_train(m, b->B, b->T, ar);
-  if (ar.off > ws_bytes) {
-    dn_set_error("%s: workspace %zu < required %zu (dn_vae_train_workspace_bytes)", who, ws_bytes, ar.off);
-    return DN_EWORKSPACE;
-  }
-  return DN_OK;
+  return plan_workspace(ws, ws_bytes, who, "dn_vae_train_workspace_bytes", [&](Arena& ar) { *pl = plan_vae_train(m, b->B, b->T, ar); });
 }
 
 // decode_feature (:1109-1116) from pl.z_act: decoder WaveNets -> transformer -> pl.rec (fp32) / pl.rec_act -> decoder_lm -> pl.logits
@@ -1001,6 +1106,7 @@ extern "C" int dn_vae_train_create(const DnVaeConfig* cfg, DnVaeTrain** out) {
   DN_CHECK_ARG(m != nullptr, "dn_vae_train_create: out of host memory");
   memset(m, 0, sizeof(*m));
   m->cfg = *cfg;
+  m->dtype = cfg->dtype;
   m->n_wave = cfg->n_mults;
   int64_t cur = 0, tcur = 0, fcur = 0;
   int width = cfg->dim;
@@ -1027,9 +1133,7 @@ extern "C" int dn_vae_train_create(const DnVaeConfig* cfg, DnVaeTrain** out) {
     dn_set_error("dn_vae_train_create: decoder width %d != dim %d", width, cfg->dim);
     return DN_EINVAL;
   }
-  m->tf.dim = cfg->dim; m->tf.depth = cfg->depth; m->tf.heads = cfg->heads; m->tf.dim_head = cfg->dim_head;
-  m->tf.inner = (int)((double)cfg->dim * 4 * 2 / 3);
-  m->tf.cond_col = -1;
+  tf_set_dims(m->tf, cfg->dim, cfg->depth, cfg->heads, cfg->dim_head, -1);
   layout_tf(m->tf, cur, tcur);
   const int64_t Dp = padk(cfg->dim), Vn = padn(cfg->vocab);
   m->lm_W = take(cur, Vn * Dp); m->lm_b = take(cur, Vn);
@@ -1043,9 +1147,7 @@ extern "C" void dn_vae_train_destroy(DnVaeTrain* m) { delete m; }
 
 extern "C" int64_t dn_vae_train_param_count(const DnVaeTrain* m) { return m ? m->n_params : 0; }
 
-extern "C" size_t dn_vae_train_aux_bytes(const DnVaeTrain* m) {
-  return m ? (size_t)r64(m->n_trans) * esize(m->cfg.dtype) + (size_t)m->n_fderived * 4 + 256 : 0;
-}
+extern "C" size_t dn_vae_train_aux_bytes(const DnVaeTrain* m) { return m ? m->aux_bytes() : 0; }
 
 // offsets (elements) of the packed tensors inside the flat buffers, in the order of diffnorm_amd/packing.py::pack_vae_train:
 // per WaveNet (encoders, then decoders) init_W, init_b, conv_W, conv_b, res_W, res_b, skip_W, skip_b[L], final_W, final_b;
@@ -1056,81 +1158,31 @@ extern "C" int dn_vae_train_offsets(const DnVaeTrain* m, int64_t* offsets, int32
   const int n = 2 * m->n_wave * 10 + 10 * m->tf.depth + 2 + 2;
   DN_CHECK_ARG(capacity >= n, "dn_vae_train_offsets: capacity %d < %d", capacity, n);
   int k = 0;
-  auto wave = [&](const WaveP& w) {
-    for (int64_t o : {w.init_W, w.init_b, w.conv_W, w.conv_b, w.res_W, w.res_b, w.skip_W, w.skip_b, w.final_W, w.final_b}) offsets[k++] = o;
-  };
-  for (int i = 0; i < m->n_wave; ++i) wave(m->enc[i]);
-  for (int i = 0; i < m->n_wave; ++i) wave(m->dec[i]);
-  const TfP& t = m->tf;
-  for (int l = 0; l < t.depth; ++l)
-    for (int64_t o : {t.qkv_W(l), t.out_W(l), t.ffin_W(l), t.ffin_b(l), t.ffconv_W(l), t.ffconv_b(l), t.ffout_W(l), t.ffout_b(l), t.g1(l),
-                      t.g2(l)})
-      offsets[k++] = o;
-  offsets[k++] = t.pred_gamma; offsets[k++] = t.pred_W;
-  offsets[k++] = m->lm_W; offsets[k++] = m->lm_b;
+  for (int i = 0; i < m->n_wave; ++i) push_wave_offsets(m->enc[i], offsets, k);
+  for (int i = 0; i < m->n_wave; ++i) push_wave_offsets(m->dec[i], offsets, k);
+  for (int l = 0; l < m->tf.depth; ++l) push_tf_layer_offsets(m->tf, l, offsets, k);
+  for (int64_t o : {m->tf.pred_gamma, m->tf.pred_W, m->lm_W, m->lm_b}) offsets[k++] = o;
   return n;
 }
 
 // Range of the flat gradient buffer that backward stage `stage` completes (stages as in dn_vae_train_backward).
 extern "C" int dn_vae_train_stage_range(const DnVaeTrain* m, int32_t stage, int64_t* offset, int64_t* count) {
-  DN_CHECK_ARG(m && offset && count, "dn_vae_train_stage_range: null argument");
-  const int depth = m->tf.depth;
-  DN_CHECK_ARG(stage >= 0 && stage <= depth + 2, "dn_vae_train_stage_range: stage %d", stage);
-  int64_t lo, hi;
-  if (stage == 0) {
-    lo = m->tf.pred_gamma; hi = m->n_params;
-  } else if (stage <= depth) {
-    lo = m->tf.layer0 + (int64_t)(depth - stage) * m->tf.layer_stride; hi = lo + m->tf.layer_stride;
-  } else if (stage == depth + 1) {
-    lo = m->dec[0].init_W; hi = m->tf.layer0;
-  } else {
-    lo = 0; hi = m->dec[0].init_W;
-  }
-  *offset = lo; *count = hi - lo;
-  return DN_OK;
+  DN_CHECK_ARG(m, "dn_vae_train_stage_range: null argument");
+  return stage_range(*m, m->tf, m->dec[0].init_W, "dn_vae_train_stage_range", stage, offset, count);
 }
 
 extern "C" int dn_vae_train_bind(DnVaeTrain* m, float* master, void* work, void* aux, float* grads) {
-  DN_CHECK_ARG(m && master && work && aux && grads, "dn_vae_train_bind: null argument");
-  for (const void* p : {(const void*)master, (const void*)work, (const void*)aux, (const void*)grads})
-    DN_CHECK_ARG(((uintptr_t)p & 255) == 0, "dn_vae_train_bind: buffers must be 256-byte aligned");
-  DN_CHECK_ARG(m->cfg.dtype == DN_BF16 || (const void*)work == (const void*)master, "dn_vae_train_bind: in f32 mode work must be master");
-  m->master = master; m->work = work; m->aux = (char*)aux; m->grads = grads;
-  return DN_OK;
+  DN_CHECK_ARG(m, "dn_vae_train_bind: null argument");
+  return bind_flat(*m, "dn_vae_train_bind", master, work, aux, grads);
 }
 
 // aux <- work: the transposed matrices of the data-gradient contractions and the summed skip biases.  Call after every update.
 extern "C" int dn_vae_train_refresh(DnVaeTrain* m, void* stream) {
   DN_CHECK_ARG(m && m->work && m->aux, "dn_vae_train_refresh: not bound");
-  const int dtype = m->cfg.dtype, es = esize(dtype);
-  hipStream_t s = (hipStream_t)stream;
-  // matrix [Np][Kp] (Np = padn(N)) -> [padn(Kp)][padk(N)]
-  auto tr_strided = [&](int64_t off, int64_t src_stride, int64_t toff, int count, int N, int Kp) -> int {
-    return dn_transpose_weights(static_cast<const char*>(m->work) + off * es, dtype, count, src_stride, padk(N), Kp, m->aux + toff * es,
-                                (int64_t)padn(Kp) * padk(N), padk(N), padn(Kp), s);
-  };
-  auto tr = [&](int64_t off, int64_t toff, int count, int N, int Kp) -> int { return tr_strided(off, (int64_t)padn(N) * Kp, toff, count, N, Kp); };
-  float* fder = reinterpret_cast<float*>(m->aux + r64(m->n_trans) * es);
-  for (int n = 0; n < 2 * m->n_wave; ++n) {
-    const WaveP& w = n < m->n_wave ? m->enc[n] : m->dec[n - m->n_wave];
-    const int cinp = padk(w.cin), cp = padk(w.cout);
-    DN_TRY(tr(w.init_W, w.t_init, 3, w.cout, cinp));
-    DN_TRY(tr(w.conv_W, w.t_conv, w.S * w.L * 3, w.cout, cp));
-    DN_TRY(tr(w.res_W, w.t_res, w.S * w.L, w.cout, cp));
-    DN_TRY(tr(w.skip_W, w.t_skip, w.L, w.cout, cp));
-    DN_TRY(tr(w.final_W, w.t_final, 1, w.cout, cp));
-    DN_TRY(dn_sum_groups(m->master + w.skip_b, cp, w.L, fder + w.skip_bsum, DN_F32, cp, s));
-  }
-  const TfP& t = m->tf;
-  const int Dp = padk(t.dim), hd = t.heads * t.dim_head, ip = padk(t.inner);
-  DN_TRY(tr_strided(t.qkv_W(0), t.layer_stride, t.t_qkv, t.depth, 3 * hd, Dp));
-  DN_TRY(tr_strided(t.out_W(0), t.layer_stride, t.t_out, t.depth, t.dim, hd));
-  DN_TRY(tr_strided(t.ffin_W(0), t.layer_stride, t.t_ffin, t.depth, 2 * ip, Dp));
-  for (int l = 0; l < t.depth; ++l)
-    DN_TRY(tr(t.ffconv_W(l), t.t_ffconv + (int64_t)l * 3 * padn(ip) * ip, 3, t.inner, ip));
-  DN_TRY(tr_strided(t.ffout_W(0), t.layer_stride, t.t_ffout, t.depth, t.dim, ip));
-  DN_TRY(tr(t.pred_W, t.t_pred, 1, t.dim, Dp));
-  return tr(m->lm_W, m->t_lm, 1, m->cfg.vocab, Dp);
+  const Transposer tr{*m, (hipStream_t)stream};
+  for (int n = 0; n < 2 * m->n_wave; ++n) DN_TRY(refresh_wave(tr, n < m->n_wave ? m->enc[n] : m->dec[n - m->n_wave]));
+  DN_TRY(refresh_tf(tr, m->tf));
+  return tr(m->lm_W, m->t_lm, 1, m->cfg.vocab, padk(m->cfg.dim));
 }
 
 extern "C" size_t dn_vae_train_workspace_bytes(const DnVaeTrain* m, int32_t B, int32_t T) {
@@ -1145,7 +1197,7 @@ extern "C" int dn_vae_train_forward(DnVaeTrain* m, const DnVaeTrainBatch* b, voi
   VaePlan pl;
   DN_TRY(check_batch(m, b, workspace, workspace_bytes, &pl, "dn_vae_train_forward"));
   hipStream_t s = (hipStream_t)stream;
-  Ctx c = make_ctx(m, b->B, b->T, pl, s);
+  Ctx c = make_ctx(*m, b->B, b->T, pl, s);
   c.attn_dropout = b->attn_dropout; c.seed_lo = b->dropout_seed_lo; c.seed_hi = b->dropout_seed_hi;
   const int dtype = c.dtype, M = c.M, T = c.T, D = m->cfg.dim, Dp = padk(D), z = m->cfg.z, zp = padk(z), V = m->cfg.vocab;
   DN_TRY(dn_convert_rows(b->feat, DN_F32, D, pl.feat_act, dtype, Dp, M, D, s));
@@ -1190,7 +1242,7 @@ extern "C" int dn_vae_train_backward(DnVaeTrain* m, const DnVaeTrainBatch* b, in
   VaePlan pl;
   DN_TRY(check_batch(m, b, workspace, workspace_bytes, &pl, "dn_vae_train_backward"));
   hipStream_t s = (hipStream_t)stream;
-  Ctx c = make_ctx(m, b->B, b->T, pl, s);
+  Ctx c = make_ctx(*m, b->B, b->T, pl, s);
   c.attn_dropout = b->attn_dropout; c.seed_lo = b->dropout_seed_lo; c.seed_hi = b->dropout_seed_hi;
   const int dtype = c.dtype, es = c.es, M = c.M, T = c.T, D = m->cfg.dim, Dp = padk(D), z = m->cfg.z, zp = padk(z), V = m->cfg.vocab;
   const int depth = m->tf.depth;
@@ -1329,7 +1381,7 @@ __global__ void eps_loss_kernel(const float* __restrict__ lsce_sums, const float
 
 }  // namespace dn
 
-struct DnEpsTrain {
+struct DnEpsTrain : FlatParams {
   DnEpsConfig cfg;
   int C, n_cond;
   int64_t w_freq, tc_W, tc_b, cond_W, cond_b, init_W, init_b, final_W, final_b;
@@ -1337,11 +1389,6 @@ struct DnEpsTrain {
   TfP tf;
   int64_t t_init, t_final;
   int64_t f_condT;  // fp32 transposed conditioning projection [padn(C)][n_cond], in the derived-fp32 region
-  int64_t n_params, n_trans, n_fderived;
-  float* master;
-  void* work;
-  char* aux;
-  float* grads;
   const float* pos_table;
 };
 
@@ -1364,23 +1411,20 @@ struct EpsPlan {
 };
 
 size_t eps_max_wgrad_bytes(const DnEpsTrain* m, int B, int T) {
-  const int es = esize(m->cfg.dtype);
-  size_t mx = 0;
-  auto upd = [&](int cin, int cout, int taps, int max_shift, int b, int t, int e) {
-    const size_t v = plan_wgrad(cin, cout, taps, max_shift, b, t, e).total();
-    mx = v > mx ? v : mx;
-  };
-  const int D = m->cfg.dim, hd = m->cfg.heads * m->cfg.dim_head, ip = padk(m->tf.inner);
-  upd(m->cfg.latent, D, 1, 0, B, T, es); upd(D, D, 3, 2, B, T, es); upd(D, D, 3, 2 << (m->wn.L - 1), B, T, es); upd(D, D, m->wn.L, 0, B, T, es);
-  upd(D, 3 * hd, 1, 0, B, T, es); upd(hd, D, 1, 0, B, T, es); upd(D, 2 * ip, 1, 0, B, T, es); upd(m->tf.inner, m->tf.inner, 3, 2, B, T, es);
-  upd(m->tf.inner, D, 1, 0, B, T, es); upd(D, D, 1, 0, B, T, es); upd(D, m->cfg.latent, 1, 0, B, T, es);
-  upd(m->C, m->n_cond, 1, 0, 1, B, 4);  // the conditioning projection: the batch is its "frame" axis, fp32
-  const size_t grouped = (size_t)m->wn.L * 2 * D * 3 * padn(D) * 4;  // the WaveNet stack's blocks as groups of one launch, two slices
-  return grouped > mx ? grouped : mx;
+  WgradMax mx{B, T, esize(m->dtype)};
+  const int D = m->cfg.dim;
+  mx(m->cfg.latent, D, 1, 0);  // init_conv
+  wave_wgrad_max(mx, m->wn);
+  tf_wgrad_max(mx, m->tf);
+  mx(D, m->cfg.latent, 1, 0);  // final_proj
+  WgradMax cond{1, B, 4};      // the conditioning projection: the batch is its "frame" axis, fp32
+  cond(m->C, m->n_cond, 1, 0);
+  mx.raw(cond.bytes);
+  return mx.bytes;
 }
 
 EpsPlan plan_eps_train(const DnEpsTrain* m, const DnVaeTrain* vae, int B, int T, Arena& ar) {
-  const int es = esize(m->cfg.dtype), D = m->cfg.dim, Dp = padk(D), zl = m->cfg.latent, zp = padk(zl);
+  const int es = esize(m->dtype), D = m->cfg.dim, Dp = padk(D), zl = m->cfg.latent, zp = padk(zl);
   const size_t M = (size_t)B * T;
   EpsPlan p;
   memset(&p, 0, sizeof(p));
@@ -1423,15 +1467,6 @@ EpsPlan plan_eps_train(const DnEpsTrain* m, const DnVaeTrain* vae, int B, int T,
   return p;
 }
 
-Ctx eps_ctx(const DnEpsTrain* m, int B, int T, const EpsPlan& pl, hipStream_t s) {
-  Ctx c;
-  c.master = m->master; c.work = m->work; c.aux = m->aux; c.grads = m->grads; c.n_trans = m->n_trans; c.frozen = false;
-  c.dtype = m->cfg.dtype; c.es = esize(c.dtype); c.B = B; c.T = T; c.M = B * T; c.s = s;
-  c.wg_scratch = pl.wg_scratch; c.wg_scratch_bytes = pl.wg_scratch_bytes; c.red_scratch = pl.red_scratch;
-  c.side = wg_side();
-  return c;
-}
-
 int eps_check(const DnEpsTrain* m, const DnVaeTrain* vae, const DnEpsTrainBatch* b, void* ws, size_t ws_bytes, EpsPlan* pl, const char* who) {
   DN_CHECK_ARG(m && b && ws, "%s: null argument", who);
   DN_CHECK_ARG(m->master && m->work && m->aux && m->grads && m->pos_table, "%s: dn_eps_train_bind has not been called", who);
@@ -1440,15 +1475,9 @@ int eps_check(const DnEpsTrain* m, const DnVaeTrain* vae, const DnEpsTrainBatch*
   DN_CHECK_ARG(b->B > 0 && b->T > 2 && b->T <= m->cfg.max_pos && b->timesteps > 1, "%s: B=%d T=%d", who, b->B, b->T);
   DN_CHECK_ARG(!b->multitask || (vae && vae->work && vae->aux && b->feat && b->units && b->n_units > 0 && b->n_frames > 0),
                "%s: the multitask loss needs the bound frozen VAE, feat and units", who);
-  DN_CHECK_ARG(!vae || (vae->cfg.z == m->cfg.latent && vae->cfg.dtype == m->cfg.dtype), "%s: VAE latent width / dtype do not match", who);
-  DN_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", who);
-  Arena ar{(char*)ws, 0, ws_bytes};
-  *pl = plan_eps_train(m, b->multitask ? vae : nullptr, b->B, b->T, ar);
-  if (ar.off > ws_bytes) {
-    dn_set_error("%s: workspace %zu < required %zu (dn_eps_train_workspace_bytes)", who, ws_bytes, ar.off);
-    return DN_EWORKSPACE;
-  }
-  return DN_OK;
+  DN_CHECK_ARG(!vae || (vae->cfg.z == m->cfg.latent && vae->dtype == m->dtype), "%s: VAE latent width / dtype do not match", who);
+  return plan_workspace(ws, ws_bytes, who, "dn_eps_train_workspace_bytes",
+                        [&](Arena& ar) { *pl = plan_eps_train(m, b->multitask ? vae : nullptr, b->B, b->T, ar); });
 }
 
 }  // namespace
@@ -1463,6 +1492,7 @@ extern "C" int dn_eps_train_create(const DnEpsConfig* cfg, DnEpsTrain** out) {
   DN_CHECK_ARG(m != nullptr, "dn_eps_train_create: out of host memory");
   memset(m, 0, sizeof(*m));
   m->cfg = *cfg;
+  m->dtype = cfg->dtype;
   const int64_t D = cfg->dim, Dp = padk(D), Dn = padn(D), zl = cfg->latent, zp = padk(zl);
   m->C = cfg->dim * cfg->cond_mult;
   m->n_cond = (cfg->wn_stacks * cfg->wn_layers + 2 * cfg->depth) * 2 * (int)Dp;
@@ -1473,9 +1503,7 @@ extern "C" int dn_eps_train_create(const DnEpsConfig* cfg, DnEpsTrain** out) {
   m->init_W = take(cur, Dn * zp); m->init_b = take(cur, Dp);
   m->wn.cin = m->wn.cout = cfg->dim; m->wn.S = cfg->wn_stacks; m->wn.L = cfg->wn_layers; m->wn.film_col = 0;
   layout_wave(m->wn, cur, tcur, fcur);
-  m->tf.dim = cfg->dim; m->tf.depth = cfg->depth; m->tf.heads = cfg->heads; m->tf.dim_head = cfg->dim_head;
-  m->tf.inner = (int)((double)cfg->dim * 4 * 2 / 3);
-  m->tf.cond_col = cfg->wn_stacks * cfg->wn_layers * 2 * (int)Dp;
+  tf_set_dims(m->tf, cfg->dim, cfg->depth, cfg->heads, cfg->dim_head, cfg->wn_stacks * cfg->wn_layers * 2 * (int)Dp);
   layout_tf(m->tf, cur, tcur);
   m->final_W = take(cur, (int64_t)padn(zl) * Dp); m->final_b = take(cur, zp);
   m->t_init = take(tcur, (int64_t)padn(zp) * Dp);
@@ -1488,9 +1516,7 @@ extern "C" int dn_eps_train_create(const DnEpsConfig* cfg, DnEpsTrain** out) {
 
 extern "C" void dn_eps_train_destroy(DnEpsTrain* m) { delete m; }
 extern "C" int64_t dn_eps_train_param_count(const DnEpsTrain* m) { return m ? m->n_params : 0; }
-extern "C" size_t dn_eps_train_aux_bytes(const DnEpsTrain* m) {
-  return m ? (size_t)r64(m->n_trans) * esize(m->cfg.dtype) + (size_t)m->n_fderived * 4 + 256 : 0;
-}
+extern "C" size_t dn_eps_train_aux_bytes(const DnEpsTrain* m) { return m ? m->aux_bytes() : 0; }
 
 // table order (diffnorm_amd/packing.py::eps_train_entries): w_freq, tc_W, tc_b, cond_W, cond_b, init_W, init_b, the WaveNet's 10
 // tensors, per layer qkv_W, out_W, ffin_W, ffin_b, ffconv_W, ffconv_b, ffout_W, ffout_b; pred_gamma, pred_W, final_W, final_b
@@ -1500,77 +1526,40 @@ extern "C" int dn_eps_train_offsets(const DnEpsTrain* m, int64_t* offsets, int32
   DN_CHECK_ARG(capacity >= n, "dn_eps_train_offsets: capacity %d < %d", capacity, n);
   int k = 0;
   for (int64_t o : {m->w_freq, m->tc_W, m->tc_b, m->cond_W, m->cond_b, m->init_W, m->init_b}) offsets[k++] = o;
-  const WaveP& w = m->wn;
-  for (int64_t o : {w.init_W, w.init_b, w.conv_W, w.conv_b, w.res_W, w.res_b, w.skip_W, w.skip_b, w.final_W, w.final_b}) offsets[k++] = o;
-  const TfP& t = m->tf;
-  for (int l = 0; l < t.depth; ++l)
-    for (int64_t o : {t.qkv_W(l), t.out_W(l), t.ffin_W(l), t.ffin_b(l), t.ffconv_W(l), t.ffconv_b(l), t.ffout_W(l), t.ffout_b(l)}) offsets[k++] = o;
-  for (int64_t o : {t.pred_gamma, t.pred_W, m->final_W, m->final_b}) offsets[k++] = o;
+  push_wave_offsets(m->wn, offsets, k);
+  for (int l = 0; l < m->tf.depth; ++l) push_tf_layer_offsets(m->tf, l, offsets, k);
+  for (int64_t o : {m->tf.pred_gamma, m->tf.pred_W, m->final_W, m->final_b}) offsets[k++] = o;
   return n;
 }
 
 // stages: 0 = losses + frozen VAE decoder + final_proj + to_pred; 1 .. depth = layers depth-1 .. 0; depth+1 = WaveNet + init_conv;
 // depth+2 = conditioning path (time MLP + FiLM / adaptive-norm projections)
 extern "C" int dn_eps_train_stage_range(const DnEpsTrain* m, int32_t stage, int64_t* offset, int64_t* count) {
-  DN_CHECK_ARG(m && offset && count, "dn_eps_train_stage_range: null argument");
-  const int depth = m->tf.depth;
-  DN_CHECK_ARG(stage >= 0 && stage <= depth + 2, "dn_eps_train_stage_range: stage %d", stage);
-  int64_t lo, hi;
-  if (stage == 0) {
-    lo = m->tf.pred_gamma; hi = m->n_params;
-  } else if (stage <= depth) {
-    lo = m->tf.layer0 + (int64_t)(depth - stage) * m->tf.layer_stride; hi = lo + m->tf.layer_stride;
-  } else if (stage == depth + 1) {
-    lo = m->init_W; hi = m->tf.layer0;
-  } else {
-    lo = 0; hi = m->init_W;
-  }
-  *offset = lo; *count = hi - lo;
-  return DN_OK;
+  DN_CHECK_ARG(m, "dn_eps_train_stage_range: null argument");
+  return stage_range(*m, m->tf, m->init_W, "dn_eps_train_stage_range", stage, offset, count);
 }
 
 extern "C" int dn_eps_train_bind(DnEpsTrain* m, float* master, void* work, void* aux, float* grads, const float* pos_table) {
-  DN_CHECK_ARG(m && master && work && aux && grads && pos_table, "dn_eps_train_bind: null argument");
-  for (const void* p : {(const void*)master, (const void*)work, (const void*)aux, (const void*)grads, (const void*)pos_table})
-    DN_CHECK_ARG(((uintptr_t)p & 255) == 0, "dn_eps_train_bind: buffers must be 256-byte aligned");
-  DN_CHECK_ARG(m->cfg.dtype == DN_BF16 || (const void*)work == (const void*)master, "dn_eps_train_bind: in f32 mode work must be master");
-  m->master = master; m->work = work; m->aux = (char*)aux; m->grads = grads; m->pos_table = pos_table;
+  DN_CHECK_ARG(m && pos_table, "dn_eps_train_bind: null argument");
+  DN_CHECK_ARG(((uintptr_t)pos_table & 255) == 0, "dn_eps_train_bind: buffers must be 256-byte aligned");
+  DN_TRY(bind_flat(*m, "dn_eps_train_bind", master, work, aux, grads));
+  m->pos_table = pos_table;
   return DN_OK;
 }
 
 extern "C" int dn_eps_train_refresh(DnEpsTrain* m, void* stream) {
   DN_CHECK_ARG(m && m->work && m->aux, "dn_eps_train_refresh: not bound");
-  const int dtype = m->cfg.dtype, es = esize(dtype);
-  hipStream_t s = (hipStream_t)stream;
-  auto tr_strided = [&](int64_t off, int64_t src_stride, int64_t toff, int count, int N, int Kp) -> int {
-    return dn_transpose_weights(static_cast<const char*>(m->work) + off * es, dtype, count, src_stride, padk(N), Kp, m->aux + toff * es,
-                                (int64_t)padn(Kp) * padk(N), padk(N), padn(Kp), s);
-  };
-  auto tr = [&](int64_t off, int64_t toff, int count, int N, int Kp) -> int { return tr_strided(off, (int64_t)padn(N) * Kp, toff, count, N, Kp); };
-  float* fder = reinterpret_cast<float*>(m->aux + r64(m->n_trans) * es);
-  const WaveP& w = m->wn;
-  const int D = m->cfg.dim, Dp = padk(D), zl = m->cfg.latent, zp = padk(zl);
-  DN_TRY(tr(m->init_W, m->t_init, 1, D, zp));
-  DN_TRY(tr(w.init_W, w.t_init, 3, D, Dp));
-  DN_TRY(tr(w.conv_W, w.t_conv, w.S * w.L * 3, D, Dp));
-  DN_TRY(tr(w.res_W, w.t_res, w.S * w.L, D, Dp));
-  DN_TRY(tr(w.skip_W, w.t_skip, w.L, D, Dp));
-  DN_TRY(tr(w.final_W, w.t_final, 1, D, Dp));
-  DN_TRY(dn_sum_groups(m->master + w.skip_b, Dp, w.L, fder + w.skip_bsum, DN_F32, Dp, s));
-  const TfP& t = m->tf;
-  const int hd = t.heads * t.dim_head, ip = padk(t.inner);
-  DN_TRY(tr_strided(t.qkv_W(0), t.layer_stride, t.t_qkv, t.depth, 3 * hd, Dp));
-  DN_TRY(tr_strided(t.out_W(0), t.layer_stride, t.t_out, t.depth, D, hd));
-  DN_TRY(tr_strided(t.ffin_W(0), t.layer_stride, t.t_ffin, t.depth, 2 * ip, Dp));
-  for (int l = 0; l < t.depth; ++l) DN_TRY(tr(t.ffconv_W(l), t.t_ffconv + (int64_t)l * 3 * padn(ip) * ip, 3, t.inner, ip));
-  DN_TRY(tr_strided(t.ffout_W(0), t.layer_stride, t.t_ffout, t.depth, D, ip));
-  DN_TRY(tr(t.pred_W, t.t_pred, 1, D, Dp));
+  const Transposer tr{*m, (hipStream_t)stream};
+  const int Dp = padk(m->cfg.dim), zl = m->cfg.latent;
+  DN_TRY(tr(m->init_W, m->t_init, 1, m->cfg.dim, padk(zl)));
+  DN_TRY(refresh_wave(tr, m->wn));
+  DN_TRY(refresh_tf(tr, m->tf));
   DN_TRY(tr(m->final_W, m->t_final, 1, zl, Dp));
   // the fp32 conditioning projection [n_cond][C] -> [padn(C)][n_cond], from the master buffer (option cond_stream = 0 only: by default
   // its data gradient streams the master matrix as it lies)
   if (cond_streamed()) return DN_OK;
-  return dn_transpose_weights(m->master + m->cond_W, DN_F32, 1, (int64_t)padn(m->n_cond) * m->C, m->n_cond, m->C, fder + m->f_condT,
-                              (int64_t)padn(m->C) * m->n_cond, m->n_cond, padn(m->C), s);
+  return dn_transpose_weights(m->master + m->cond_W, DN_F32, 1, (int64_t)padn(m->n_cond) * m->C, m->n_cond, m->C, m->fderived() + m->f_condT,
+                              (int64_t)padn(m->C) * m->n_cond, m->n_cond, padn(m->C), tr.s);
 }
 
 extern "C" size_t dn_eps_train_workspace_bytes(const DnEpsTrain* m, const DnVaeTrain* vae, int32_t B, int32_t T) {
@@ -1585,7 +1574,7 @@ extern "C" int dn_eps_train_forward(DnEpsTrain* m, DnVaeTrain* vae, const DnEpsT
   EpsPlan pl;
   DN_TRY(eps_check(m, vae, b, workspace, workspace_bytes, &pl, "dn_eps_train_forward"));
   hipStream_t s = (hipStream_t)stream;
-  Ctx c = eps_ctx(m, b->B, b->T, pl, s);
+  Ctx c = make_ctx(*m, b->B, b->T, pl, s);
   c.attn_dropout = b->attn_dropout; c.seed_lo = b->dropout_seed_lo; c.seed_hi = b->dropout_seed_hi;
   const int dtype = c.dtype, B = b->B, T = b->T, M = c.M, D = m->cfg.dim, Dp = padk(D), zl = m->cfg.latent, zp = padk(zl);
   const int ew = (int)std::min<int64_t>(((int64_t)M * zp + 255) / 256, 4096);
@@ -1627,7 +1616,7 @@ extern "C" int dn_eps_train_forward(DnEpsTrain* m, DnVaeTrain* vae, const DnEpsT
   DN_TRY(dn_colsum(pl.rows, 4, DN_F32, B, T, 4, pl.noise_b, 4, 1.0f, 0, pl.red_scratch, s));
   (void)hipMemsetAsync(pl.sums, 0, 64 * 4, s);
   if (b->multitask) {  // x1_hat through the frozen VAE decoder (:1574-1596)
-    const Ctx vc = make_ctx(vae, B, T, pl.vae, s, true);
+    const Ctx vc = make_ctx(*vae, B, T, pl.vae, s, true);
     const int V = vae->cfg.vocab, Dv = vae->cfg.dim;
     DN_TRY(vae_decoder_forward(vc, vae, pl.vae, b->lengths));
     const float g_ls = b->loss_scale / ((float)b->timesteps * (float)b->n_units);
@@ -1650,7 +1639,7 @@ extern "C" int dn_eps_train_backward(DnEpsTrain* m, DnVaeTrain* vae, const DnEps
   EpsPlan pl;
   DN_TRY(eps_check(m, vae, b, workspace, workspace_bytes, &pl, "dn_eps_train_backward"));
   hipStream_t s = (hipStream_t)stream;
-  Ctx c = eps_ctx(m, b->B, b->T, pl, s);
+  Ctx c = make_ctx(*m, b->B, b->T, pl, s);
   c.attn_dropout = b->attn_dropout; c.seed_lo = b->dropout_seed_lo; c.seed_hi = b->dropout_seed_hi;
   const int dtype = c.dtype, B = b->B, T = b->T, M = c.M, D = m->cfg.dim, Dp = padk(D), zl = m->cfg.latent, zp = padk(zl);
   const int depth = m->tf.depth;
@@ -1662,7 +1651,7 @@ extern "C" int dn_eps_train_backward(DnEpsTrain* m, DnVaeTrain* vae, const DnEps
       (void)hipMemsetAsync(pl.d_gb, 0, (size_t)B * m->n_cond * 4, s);
       const float* dx1 = nullptr;
       if (b->multitask) {  // d total / d x1_hat: the frozen decoder's data gradients (no parameter gradients)
-        const Ctx vc = make_ctx(vae, B, T, pl.vae, s, true);
+        const Ctx vc = make_ctx(*vae, B, T, pl.vae, s, true);
         const float g_mse = b->loss_scale * b->recon_weight * 2.0f / ((float)b->timesteps * (float)b->n_frames * (float)vae->cfg.dim);
         for (int vs = 0; vs <= vae->tf.depth + 1; ++vs) DN_TRY(vae_decoder_backward(vc, vae, pl.vae, b->feat, b->lengths, g_mse, vs));
         dx1 = pl.vae.dz;
@@ -1699,14 +1688,13 @@ extern "C" int dn_eps_train_backward(DnEpsTrain* m, DnVaeTrain* vae, const DnEps
         // d cond = d gb [B, n_cond] . W_c: B rows against a 57 k-deep contraction -- 16 output tiles on 256 CUs (measured 7.0 ms = 16 %
         // of a diffusion update when it ran un-split).  Split K over `ks` groups (a K-slice of the packed transpose: ldw = n_cond),
         // partial sums per group, then a fixed-order sum of the groups: every CU gets a slice and the 470 MB of weights stream once.
-        float* fder = reinterpret_cast<float*>(m->aux + r64(m->n_trans) * c.es);
         int ks = 1;
         for (int cand = 32; cand >= 2; --cand)
           if (m->n_cond % (cand * 32) == 0 && (size_t)cand * B * m->C * 4 <= pl.d_cond_parts_bytes) { ks = cand; break; }
         DnGemmParams p = gemm_base(DN_F32, B, m->C, m->n_cond / ks, 1);
         p.groups = ks;
         p.terms[0].A = pl.d_gb; p.terms[0].lda = m->n_cond; p.terms[0].a_gstride = m->n_cond / ks;
-        p.terms[0].W = fder + m->f_condT; p.terms[0].ldw = m->n_cond; p.terms[0].w_gstride = m->n_cond / ks;
+        p.terms[0].W = m->fderived() + m->f_condT; p.terms[0].ldw = m->n_cond; p.terms[0].w_gstride = m->n_cond / ks;
         p.out = ks > 1 ? pl.d_cond_parts : pl.d_cond; p.ldo = m->C; p.out_dtype = DN_F32; p.out_gstride = (int64_t)B * m->C;
         DN_TRY(dn_conv_gemm(&p, s));
         if (ks > 1) DN_TRY(dn_sum_groups(pl.d_cond_parts, (int64_t)B * m->C, ks, pl.d_cond, DN_F32, (int64_t)B * m->C, s));

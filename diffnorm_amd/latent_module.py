@@ -79,6 +79,59 @@ class _ParamTree(nn.Module):
     def _state_key(self):
         return tuple((p.data_ptr(), p._version) for p in self.parameters())
 
+    # ---- training: the flat packed master buffer of a HIP training engine (diffnorm_amd/training.py) becomes THE
+    # parameter; state_dict() / load_state_dict() keep speaking the reference's key layout
+    _train_engine = None
+    _extra_state_keys = ()  # non-parameter keys the reference's state dict carries (buffers that the engines rebuild themselves)
+
+    def _adopt_flat(self, eng):
+        """The per-tensor parameters (and buffers) give way to one `flat_params` Parameter that aliases eng.master, with `.grad`
+        aliasing eng.grads."""
+        for name in list(self._modules):
+            del self._modules[name]
+        self._buffers.clear()
+        self.flat_params = nn.Parameter(eng.master)
+        self.flat_params.grad = eng.grads
+        self._train_engine = eng
+        self._engine = None
+
+    def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
+        if self._train_engine is None:
+            return super().state_dict(*args, destination=destination, prefix=prefix, keep_vars=keep_vars)
+        from collections import OrderedDict
+
+        out = OrderedDict() if destination is None else destination
+        for k, v in self._train_engine.state_dict().items():
+            out[prefix + k] = v
+        for k in self._extra_state_keys:
+            out[prefix + k] = torch.zeros(1)
+        return out
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        if self._train_engine is None:
+            return super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+        want = set(self._train_engine.state_dict())
+        got = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix) and not k.endswith(self._extra_state_keys)}
+        missing_keys += [prefix + k for k in want - set(got)]
+        unexpected_keys += [prefix + k for k in set(got) - want]
+        if not (want - set(got)):
+            self._train_engine.load_state_dict({k: got[k] for k in want})
+
+    def engine(self):
+        """The inference engine over the current parameters (`_build_engine(sd)`: the subclass's engine class), rebuilt when they
+        have changed: with a training engine, from its master buffer once an update has happened."""
+        if self._train_engine is not None:
+            key = ("train", self._train_engine.update_count)
+            if self._engine is None or self._engine_key != key:
+                self._engine = self._build_engine(self._train_engine.state_dict())
+                self._engine_key = key
+            return self._engine
+        key = self._state_key()
+        if self._engine is None or self._engine_key != key:
+            self._engine = self._build_engine({k: v.detach().cpu() for k, v in self.state_dict().items()})
+            self._engine_key = key
+        return self._engine
+
     @property
     def device(self):
         return next(self.parameters()).device
@@ -108,53 +161,11 @@ class Model(_ParamTree):
         if self.condition_on_prompt:
             self._attach("perceiver_resampler.embed_positions._float_tensor", torch.zeros(1), buffer=True)  # (:428-435)
 
-    # ---- training: set by LatentDiscreteModel.enable_training -- the flat master buffer of the diffusion
-    # training engine becomes this module's only parameter; state_dict() keeps the reference's keys
-    _train_engine = None
+    _extra_state_keys = ("pos_embed._float_tensor",)
 
-    def _adopt_flat(self, eng):
-        for name in list(self._modules):
-            del self._modules[name]
-        self._buffers.clear()
-        self.flat_params = nn.Parameter(eng.master)
-        self.flat_params.grad = eng.grads
-        self._train_engine = eng
-        self._engine = None
-
-    def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
-        if self._train_engine is None:
-            return super().state_dict(*args, destination=destination, prefix=prefix, keep_vars=keep_vars)
-        from collections import OrderedDict
-
-        out = OrderedDict() if destination is None else destination
-        for k, v in self._train_engine.state_dict().items():
-            out[prefix + k] = v
-        out[prefix + "pos_embed._float_tensor"] = torch.zeros(1)
-        return out
-
-    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
-        if self._train_engine is None:
-            return super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
-        want = set(self._train_engine.state_dict())
-        got = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix) and not k.endswith("pos_embed._float_tensor")}
-        missing_keys += [prefix + k for k in want - set(got)]
-        unexpected_keys += [prefix + k for k in set(got) - want]
-        if not (want - set(got)):
-            self._train_engine.load_state_dict({k: got[k] for k in want})
-
-    def engine(self) -> engine.EpsEngine:
-        if self._train_engine is not None:
-            key = ("train", self._train_engine.update_count)
-            if self._engine is None or self._engine_key != key:
-                self._engine = engine.EpsEngine(self._train_engine.state_dict(), self.cfg, dtype=self.arith, device=self.device)
-                self._engine_key = key
-            return self._engine
-        key = self._state_key()
-        if self._engine is None or self._engine_key != key:
-            sd = {k: v.detach().cpu() for k, v in self.state_dict().items() if not k.endswith("._float_tensor")}
-            self._engine = engine.EpsEngine(sd, self.cfg, dtype=self.arith, device=self.device)
-            self._engine_key = key
-        return self._engine
+    def _build_engine(self, sd) -> engine.EpsEngine:
+        sd = {k: v for k, v in sd.items() if not k.endswith("._float_tensor")}
+        return engine.EpsEngine(sd, self.cfg, dtype=self.arith, device=self.device)
 
     def forward(self, x, times, prompt=None, prompt_mask=None, input_mask=None, cond=None, cond_drop_prob=None, drop_mask=None):
         """x [B,T,latent], times [B] (raw integer steps), input_mask [B,T] bool -> eps_hat [B,T,latent].  With
@@ -334,7 +345,6 @@ class SpeechVAEEncoderDecoder(_ParamTree):
         super().__init__()
         self.dim, self.latent_dim = dim, latent_dim
         self.arith = dtype
-        self._train_engine = None
         self.train_on_move = False  # the plugin's build_model sets it for a training run: see _apply
         self.attn_dropout = 0.1  # Attention(dropout=0.1) of the decoder transformer (:668); active in train() mode with the training engine
         self._adopt(synthetic.random_vae_state_dict(dim, latent_dim, seed=seed))
@@ -375,48 +385,11 @@ class SpeechVAEEncoderDecoder(_ParamTree):
         sd = {k: v.detach().cpu() for k, v in self.state_dict().items()}
         dev = self.device
         eng = training.VaeTrainEngine(sd, dim=self.dim, latent_dim=self.latent_dim, dtype=self.arith, device=dev)
-        for name in list(self._modules):
-            del self._modules[name]
-        self.flat_params = nn.Parameter(eng.master)
-        self.flat_params.grad = eng.grads
-        self._train_engine = eng
-        self._engine = None
+        self._adopt_flat(eng)
         return eng
 
-    def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
-        if self._train_engine is None:
-            return super().state_dict(*args, destination=destination, prefix=prefix, keep_vars=keep_vars)
-        from collections import OrderedDict
-
-        out = OrderedDict() if destination is None else destination
-        for k, v in self._train_engine.state_dict().items():
-            out[prefix + k] = v
-        return out
-
-    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
-        if self._train_engine is None:
-            return super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
-        want = set(self._train_engine.state_dict())
-        got = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
-        missing_keys += [prefix + k for k in want - set(got)]
-        unexpected_keys += [prefix + k for k in set(got) - want]
-        if not (want - set(got)):
-            self._train_engine.load_state_dict({k: got[k] for k in want})
-
-    def engine(self) -> engine.VaeEngine:
-        if self._train_engine is not None:  # inference engine rebuilt from the master buffer when an update has happened
-            key = ("train", self._train_engine.update_count)
-            if self._engine is None or self._engine_key != key:
-                self._engine = engine.VaeEngine(self._train_engine.state_dict(), dim=self.dim, latent_dim=self.latent_dim,
-                                                dtype=self.arith, device=self.device)
-                self._engine_key = key
-            return self._engine
-        key = self._state_key()
-        if self._engine is None or self._engine_key != key:
-            sd = {k: v.detach().cpu() for k, v in self.state_dict().items()}
-            self._engine = engine.VaeEngine(sd, dim=self.dim, latent_dim=self.latent_dim, dtype=self.arith, device=self.device)
-            self._engine_key = key
-        return self._engine
+    def _build_engine(self, sd) -> engine.VaeEngine:
+        return engine.VaeEngine(sd, dim=self.dim, latent_dim=self.latent_dim, dtype=self.arith, device=self.device)
 
     def _posterior_noise(self, B, T, noise):
         e = self.engine()

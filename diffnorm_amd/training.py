@@ -50,7 +50,109 @@ def _dropout_fields(engine):
     return p, mixed & 0xFFFFFFFF, (mixed >> 32) & 0xFFFFFFFF, 0
 
 
-class VaeTrainEngine:
+class _FlatEngine:
+    """What the two training engines share: the handle of the C-ABI engine `<prefix>create` makes, its flat master / work / aux /
+    gradient buffers, the state-dict conversions over its entry table, refresh, the backward stages' gradient ranges and the
+    workspace.  A subclass builds its config, calls `_open`, binds the buffers and supplies `forward` / `backward`."""
+
+    def _open(self, prefix: str, cfg_struct, entries):
+        """Creates the engine `prefix` (dn_vae_train_ / dn_eps_train_) names, reads its layout and allocates the flat buffers."""
+        self._prefix, self.entries = prefix, entries
+        self.handle = C.c_void_p()
+        _lib.check(self._fn("create")(C.byref(cfg_struct), C.byref(self.handle)), prefix + "create")
+        self.n_params = int(self._fn("param_count")(self.handle))
+        offs = (C.c_int64 * len(entries))()
+        n = _lib.check(self._fn("offsets")(self.handle, offs, len(entries)), prefix + "offsets")
+        assert n == len(entries), (n, len(entries))
+        self.offsets = list(offs)
+        self._alloc(int(self._fn("aux_bytes")(self.handle)))
+        self.update_count = 0      # refreshes so far: the cache key of the module layer's inference engine
+        self.work_current = False  # set by refresh, cleared by the autograd bridge's backward (latent_module._prepare_step)
+        self.attn_dropout, self.dropout_seed, self._dropout_calls = 0.0, 0, 0  # see _dropout_fields
+        self._ws: Optional[torch.Tensor] = None
+        self._batch = None
+        self._keep = None
+
+    def _fn(self, name: str):
+        return getattr(self.lib, self._prefix + name)
+
+    def __del__(self):
+        if getattr(self, "handle", None) and self.handle.value:
+            self._fn("destroy")(self.handle)
+            self.handle = None
+
+    def _alloc(self, aux_bytes: int):
+        with torch.cuda.device(self.device):
+            self._own = []
+            raw, view = _aligned_empty(self.n_params * 4, self.device)
+            self._own.append(raw)
+            self.master = view.view(torch.float32)
+            raw, view = _aligned_empty(self.n_params * 4, self.device)
+            self._own.append(raw)
+            self.grads = view.view(torch.float32)
+            if self.dtype == _lib.DN_BF16:
+                raw, view = _aligned_empty(self.n_params * 2, self.device)
+                self._own.append(raw)
+                self.work = view.view(torch.bfloat16)
+            else:
+                self.work = self.master
+            raw, self.aux = _aligned_empty(aux_bytes, self.device)
+            self._own.append(raw)
+
+    # ---- parameters ----------------------------------------------------------------------------------------------------
+    def load_state_dict(self, sd: Dict[str, torch.Tensor]):
+        """Reference-layout state dict (SURVEY 8b, keys without the `encoder.` prefix) -> the flat master buffer."""
+        flat = packing.pack_flat(sd, self.entries, self.offsets, self.n_params)
+        self.master.copy_(flat.to(self.device))
+        self.sync_work()
+
+    def sync_work(self):
+        """work / aux <- master (after loading or an external update of the master buffer)."""
+        if self.work is not self.master:
+            self.work.copy_(self.master)  # fp32 -> bf16, round to nearest even (the same rounding dn_adam_step applies)
+        self.refresh()
+
+    def refresh(self):
+        """aux <- work: call after every optimizer step (dn_adam_step has already written the bf16 work copy)."""
+        self.update_count += 1
+        with torch.cuda.device(self.device):
+            _lib.check(self._fn("refresh")(self.handle, _lib.current_stream()), self._prefix + "refresh")
+        self.work_current = True
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        return packing.unpack_flat(self.master, self.entries, self.offsets)
+
+    def grad_dict(self) -> Dict[str, torch.Tensor]:
+        """Gradients under the reference's parameter names and shapes."""
+        return packing.unpack_flat(self.grads, self.entries, self.offsets)
+
+    def zero_grad(self):
+        self.grads.zero_()
+
+    @property
+    def n_stages(self) -> int:
+        return self.depth + 3
+
+    def stage_ranges(self) -> List[Tuple[int, int]]:
+        """(offset, count) of the gradient range each backward stage completes, stage 0 first."""
+        out = []
+        off, cnt = C.c_int64(), C.c_int64()
+        for st in range(self.n_stages):
+            _lib.check(self._fn("stage_range")(self.handle, st, C.byref(off), C.byref(cnt)), self._prefix + "stage_range")
+            out.append((off.value, cnt.value))
+        return out
+
+    def _ws_ptr(self, need: int):
+        """(256-byte aligned address, bytes behind it) of the workspace, grown to `need` bytes."""
+        if self._ws is None or self._ws.numel() < need + 256:
+            self._ws = None
+            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+        p = self._ws.data_ptr()
+        a = (p + 255) & ~255
+        return a, self._ws.numel() - (a - p)
+
+
+class VaeTrainEngine(_FlatEngine):
     """SpeechVAEEncoderDecoder training on the GPU (reference latent_module.py:1118-1142 + speech_vae_decoder_loss.py:45-95)."""
 
     LOSS_WEIGHTS = (0.1, 10.0, 1e-4)  # LS-CE, MSE, KL (speech_vae_decoder_loss.py:80-83)
@@ -68,95 +170,12 @@ class VaeTrainEngine:
         self.dtype = _training_dtype(dtype)
         mults = (C.c_int32 * 4)(*(self.mults + [0] * (4 - len(self.mults))))
         cfg = _lib.VaeConfig(dim, self.z, depth, heads, dim_head, stacks, layers, vocab, len(self.mults), mults, self.dtype)
-        self.handle = C.c_void_p()
-        _lib.check(self.lib.dn_vae_train_create(C.byref(cfg), C.byref(self.handle)), "dn_vae_train_create")
-        self.n_params = int(self.lib.dn_vae_train_param_count(self.handle))
-        self.entries = packing.vae_train_entries(dim, self.mults, depth, heads, dim_head, stacks, layers, vocab)
-        offs = (C.c_int64 * len(self.entries))()
-        n = _lib.check(self.lib.dn_vae_train_offsets(self.handle, offs, len(self.entries)), "dn_vae_train_offsets")
-        assert n == len(self.entries), (n, len(self.entries))
-        self.offsets = list(offs)
-        with torch.cuda.device(self.device):
-            self._own = []
-            raw, view = _aligned_empty(self.n_params * 4, self.device)
-            self._own.append(raw)
-            self.master = view.view(torch.float32)
-            raw, view = _aligned_empty(self.n_params * 4, self.device)
-            self._own.append(raw)
-            self.grads = view.view(torch.float32)
-            if self.dtype == _lib.DN_BF16:
-                raw, view = _aligned_empty(self.n_params * 2, self.device)
-                self._own.append(raw)
-                self.work = view.view(torch.bfloat16)
-            else:
-                self.work = self.master
-            raw, self.aux = _aligned_empty(int(self.lib.dn_vae_train_aux_bytes(self.handle)), self.device)
-            self._own.append(raw)
+        self._open("dn_vae_train_", cfg, packing.vae_train_entries(dim, self.mults, depth, heads, dim_head, stacks, layers, vocab))
         _lib.check(self.lib.dn_vae_train_bind(self.handle, self.master.data_ptr(), self.work.data_ptr(), self.aux.data_ptr(),
                                               self.grads.data_ptr()), "dn_vae_train_bind")
-        self._ws: Optional[torch.Tensor] = None
-        self._batch = None
-        self._keep = None
         self.load_state_dict(state_dict)
 
-    def __del__(self):
-        if getattr(self, "handle", None) and self.handle.value:
-            self.lib.dn_vae_train_destroy(self.handle)
-            self.handle = None
-
-    # ---- parameters ----------------------------------------------------------------------------------------------------
-    def load_state_dict(self, sd: Dict[str, torch.Tensor]):
-        """Reference-layout state dict (SURVEY 8b, keys without the `encoder.` prefix) -> the flat master buffer."""
-        flat = packing.pack_flat(sd, self.entries, self.offsets, self.n_params)
-        self.master.copy_(flat.to(self.device))
-        self.sync_work()
-
-    def sync_work(self):
-        """work / aux <- master (after loading or an external update of the master buffer)."""
-        if self.work is not self.master:
-            self.work.copy_(self.master)  # fp32 -> bf16, round to nearest even (the same rounding dn_adam_step applies)
-        self.refresh()
-
-    def refresh(self):
-        """aux <- work: call after every optimizer step (dn_adam_step has already written the bf16 work copy)."""
-        self.update_count = getattr(self, "update_count", 0) + 1
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.dn_vae_train_refresh(self.handle, _lib.current_stream()), "dn_vae_train_refresh")
-        self.work_current = True  # (latent_module._prepare_step: cleared by the autograd bridge's backward)
-
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        return packing.unpack_flat(self.master, self.entries, self.offsets)
-
-    def grad_dict(self) -> Dict[str, torch.Tensor]:
-        """Gradients under the reference's parameter names and shapes."""
-        return packing.unpack_flat(self.grads, self.entries, self.offsets)
-
-    def zero_grad(self):
-        self.grads.zero_()
-
-    def stage_ranges(self) -> List[Tuple[int, int]]:
-        """(offset, count) of the gradient range each backward stage completes, stage 0 first."""
-        out = []
-        off, cnt = C.c_int64(), C.c_int64()
-        for st in range(self.depth + 3):
-            _lib.check(self.lib.dn_vae_train_stage_range(self.handle, st, C.byref(off), C.byref(cnt)), "dn_vae_train_stage_range")
-            out.append((off.value, cnt.value))
-        return out
-
-    @property
-    def n_stages(self) -> int:
-        return self.depth + 3
-
     # ---- one step ------------------------------------------------------------------------------------------------------
-    def _workspace(self, B: int, T: int):
-        need = int(self.lib.dn_vae_train_workspace_bytes(self.handle, B, T))
-        if self._ws is None or self._ws.numel() < need + 256:
-            self._ws = None
-            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-        p = self._ws.data_ptr()
-        a = (p + 255) & ~255
-        return a, self._ws.numel() - (a - p)
-
     def forward(self, feat: torch.Tensor, units: torch.Tensor, lengths: torch.Tensor, noise: Optional[torch.Tensor] = None,
                 ntokens: Optional[int] = None, weights: Sequence[float] = LOSS_WEIGHTS, label_smoothing: float = 0.1,
                 loss_scale: float = 1.0, want_logits: bool = False, want_recon: bool = False):
@@ -184,7 +203,7 @@ class VaeTrainEngine:
                                float(weights[0]), float(weights[1]), float(weights[2]), float(label_smoothing), float(loss_scale),
                                stats.data_ptr(), _lib.ptr(logits), _lib.ptr(recon), None, *_dropout_fields(self))
         self._batch, self._keep = b, (feat, units, lengths, noise, stats, logits, recon)
-        wp, wn = self._workspace(B, T)
+        wp, wn = self._ws_ptr(int(self.lib.dn_vae_train_workspace_bytes(self.handle, B, T)))
         with torch.cuda.device(dev):
             _lib.check(self.lib.dn_vae_train_forward(self.handle, C.byref(b), wp, wn, _lib.current_stream()), "dn_vae_train_forward")
         return (stats, logits, recon) if (want_logits or want_recon) else stats
@@ -202,59 +221,10 @@ class VaeTrainEngine:
             self._batch.w_mse, self._batch.w_kl = float(d_mse), float(d_kl)
         last_stage = self.n_stages - 1 if last_stage is None else last_stage
         B, T = self._batch.B, self._batch.T
-        wp, wn = self._workspace(B, T)
+        wp, wn = self._ws_ptr(int(self.lib.dn_vae_train_workspace_bytes(self.handle, B, T)))
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dn_vae_train_backward(self.handle, C.byref(self._batch), first_stage, last_stage, wp, wn,
                                                       _lib.current_stream()), "dn_vae_train_backward")
-
-
-class _FlatEngine:
-    """Flat master / work / aux / gradient buffers of a training engine and the state-dict conversions over its entry table."""
-
-    def _alloc(self, aux_bytes: int):
-        with torch.cuda.device(self.device):
-            self._own = []
-            raw, view = _aligned_empty(self.n_params * 4, self.device)
-            self._own.append(raw)
-            self.master = view.view(torch.float32)
-            raw, view = _aligned_empty(self.n_params * 4, self.device)
-            self._own.append(raw)
-            self.grads = view.view(torch.float32)
-            if self.dtype == _lib.DN_BF16:
-                raw, view = _aligned_empty(self.n_params * 2, self.device)
-                self._own.append(raw)
-                self.work = view.view(torch.bfloat16)
-            else:
-                self.work = self.master
-            raw, self.aux = _aligned_empty(aux_bytes, self.device)
-            self._own.append(raw)
-
-    def load_state_dict(self, sd: Dict[str, torch.Tensor]):
-        flat = packing.pack_flat(sd, self.entries, self.offsets, self.n_params)
-        self.master.copy_(flat.to(self.device))
-        self.sync_work()
-
-    def sync_work(self):
-        if self.work is not self.master:
-            self.work.copy_(self.master)
-        self.refresh()
-
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        return packing.unpack_flat(self.master, self.entries, self.offsets)
-
-    def grad_dict(self) -> Dict[str, torch.Tensor]:
-        return packing.unpack_flat(self.grads, self.entries, self.offsets)
-
-    def zero_grad(self):
-        self.grads.zero_()
-
-    def _ws_ptr(self, need: int):
-        if self._ws is None or self._ws.numel() < need + 256:
-            self._ws = None
-            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-        p = self._ws.data_ptr()
-        a = (p + 255) & ~255
-        return a, self._ws.numel() - (a - p)
 
 
 class EpsTrainEngine(_FlatEngine):
@@ -273,15 +243,7 @@ class EpsTrainEngine(_FlatEngine):
         self.depth = cfg.depth
         c = _lib.EpsConfig(cfg.dim, cfg.latent_dim, cfg.depth, cfg.heads, cfg.dim_head, cfg.wavenet_layers, cfg.wavenet_stacks,
                            cfg.dim_cond_mult, self.dtype, max_pos)
-        self.handle = C.c_void_p()
-        _lib.check(self.lib.dn_eps_train_create(C.byref(c), C.byref(self.handle)), "dn_eps_train_create")
-        self.n_params = int(self.lib.dn_eps_train_param_count(self.handle))
-        self.entries = packing.eps_train_entries(cfg)
-        offs = (C.c_int64 * len(self.entries))()
-        n = _lib.check(self.lib.dn_eps_train_offsets(self.handle, offs, len(self.entries)), "dn_eps_train_offsets")
-        assert n == len(self.entries), (n, len(self.entries))
-        self.offsets = list(offs)
-        self._alloc(int(self.lib.dn_eps_train_aux_bytes(self.handle)))
+        self._open("dn_eps_train_", c, packing.eps_train_entries(cfg))
         raw, view = _aligned_empty((max_pos + 1) * packing.padk(cfg.dim) * 4, self.device)
         self._own.append(raw)
         self.pos_table = view.view(torch.float32)
@@ -292,32 +254,7 @@ class EpsTrainEngine(_FlatEngine):
         self._sa = self.sched.f32("sqrt_alphas_cumprod", self.device)
         self._s1 = self.sched.f32("sqrt_one_minus_alphas_cumprod", self.device)
         self._beta0 = float(self.sched.f32("betas")[0])
-        self._ws = None
-        self._batch = None
         self.load_state_dict(state_dict)
-
-    def __del__(self):
-        if getattr(self, "handle", None) and self.handle.value:
-            self.lib.dn_eps_train_destroy(self.handle)
-            self.handle = None
-
-    def refresh(self):
-        self.update_count = getattr(self, "update_count", 0) + 1
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.dn_eps_train_refresh(self.handle, _lib.current_stream()), "dn_eps_train_refresh")
-        self.work_current = True
-
-    @property
-    def n_stages(self) -> int:
-        return self.depth + 3
-
-    def stage_ranges(self) -> List[Tuple[int, int]]:
-        out = []
-        off, cnt = C.c_int64(), C.c_int64()
-        for st in range(self.n_stages):
-            _lib.check(self.lib.dn_eps_train_stage_range(self.handle, st, C.byref(off), C.byref(cnt)), "dn_eps_train_stage_range")
-            out.append((off.value, cnt.value))
-        return out
 
     def _vae_handle(self):
         return self.vae.handle if (self.vae is not None and self.multitask) else None
