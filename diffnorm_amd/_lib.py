@@ -190,6 +190,8 @@ SYMBOLS = {
     "dn_rows_times_weight_scratch_bytes": (_sz, [_i32, _i32, _i32]),
     "dn_rows_times_weight": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "dn_transpose_weights": (C.c_int, [_vp, _i32, _i32, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp]),
+    "dn_split_rows": (C.c_int, [_vp, _i64, _vp, _i32, _vp]),
+    "dn_transpose_slices": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "dn_wgrad_reduce": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "dn_conv_weight_grad_tn": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "dn_add_broadcast": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),

@@ -562,7 +562,12 @@ extern "C" int dn_attention_backward(const DnAttnBwdParams* pp, void* stream) {
   const DnAttnBwdParams& p = *pp;
   DN_CHECK_ARG(p.q && p.k && p.v && p.out && p.dout && p.dq && p.dk && p.dv && p.lse && p.delta, "dn_attention_backward: null tensor");
   DN_CHECK_ARG(p.B > 0 && p.T > 0 && p.heads > 0 && p.dim_head > 0 && p.dim_head % 4 == 0, "dn_attention_backward: bad shape");
-  DN_CHECK_ARG(p.dtype == DN_F32 || p.dtype == DN_BF16, "dn_attention_backward: bad dtype");
+  // DN_BF16X3 (the split-operand training engine): q / k / v / O / dO plain fp32 and the exact-fp32 kernels; dq / dk / dv, operands of
+  // the q / kv contractions, are stored as split rows
+  DN_CHECK_ARG(p.dtype == DN_F32 || p.dtype == DN_BF16 || p.dtype == DN_BF16X3, "dn_attention_backward: bad dtype");
+  if (p.dtype == DN_BF16X3)
+    DN_CHECK_ARG(p.lddq % 32 == 0 && p.lddk % 32 == 0 && p.lddv % 32 == 0 && ((uintptr_t)p.dq & 127) == 0,
+                 "dn_attention_backward: split-row dq / dk / dv need row strides that are multiples of 32 and 128-byte aligned bases");
   DN_CHECK_ARG(p.dropout_p >= 0.f && p.dropout_p < 1.f, "dn_attention_backward: dropout_p %g", (double)p.dropout_p);
   const int es = p.dtype == DN_BF16 ? 2 : 4;
   DN_CHECK_ARG((p.dim_head * es) % 16 == 0, "dn_attention_backward: dim_head*elem must be a multiple of 16 bytes (dim_head=%d)", p.dim_head);
@@ -577,7 +582,7 @@ extern "C" int dn_attention_backward(const DnAttnBwdParams* pp, void* stream) {
     while (G < 64 && G * 8 < p.dim_head) G *= 2;  // lanes per (row, head)
     const int64_t per_block = 4 * (64 / G);
     hipLaunchKernelGGL(dn::attn_delta_kernel, dim3((unsigned)((rows + per_block - 1) / per_block)), dim3(256), 0, s, p.out, p.ldo, p.dout, p.lddo,
-                       p.dtype, p.B, p.T, p.heads, p.dim_head, G, p.delta);
+                       p.dtype == DN_BF16X3 ? DN_F32 : p.dtype, p.B, p.T, p.heads, p.dim_head, G, p.delta);
   }
   dn::AttnBwdArgs a;
   a.q = p.q; a.k = p.k; a.v = p.v; a.dout = p.dout; a.dq = p.dq; a.dk = p.dk; a.dv = p.dv;

@@ -110,6 +110,15 @@ __device__ __forceinline__ void store4_split(void* base, int64_t off, float a, f
   *reinterpret_cast<uint2*>(p) = make_uint2(h0, h1);
   *reinterpret_cast<uint2*>(p + 64) = make_uint2(l0, l1);
 }
+// the same for a packed WEIGHT (W operand): [lo | hi] halves
+__device__ __forceinline__ void store4_split_w(void* base, int64_t off, float a, float b, float c, float d) {
+  uint32_t h0, l0, h1, l1;
+  split_pair(a, b, h0, l0);
+  split_pair(c, d, h1, l1);
+  char* p = reinterpret_cast<char*>(base) + split_byte(off);
+  *reinterpret_cast<uint2*>(p) = make_uint2(l0, l1);
+  *reinterpret_cast<uint2*>(p + 64) = make_uint2(h0, h1);
+}
 __device__ __forceinline__ void store1_split(void* base, int64_t off, float v) {
   uint32_t h, l;
   split_pair(v, 0.f, h, l);
@@ -138,6 +147,12 @@ __device__ __forceinline__ void store4(void* base, int64_t elem_off, int out_dty
 }
 
 __device__ __forceinline__ float4 load4(const void* base, int64_t elem_off, int dtype) {
+  if (dtype == DN_BF16X3) {  // split rows [hi | lo]: two 8-byte loads, x = hi + lo (exact in fp32)
+    const char* p = reinterpret_cast<const char*>(base) + split_byte(elem_off);
+    const uint2 h = *reinterpret_cast<const uint2*>(p), l = *reinterpret_cast<const uint2*>(p + 64);
+    return make_float4(__uint_as_float(h.x << 16) + __uint_as_float(l.x << 16), __uint_as_float(h.x & 0xffff0000u) + __uint_as_float(l.x & 0xffff0000u),
+                       __uint_as_float(h.y << 16) + __uint_as_float(l.y << 16), __uint_as_float(h.y & 0xffff0000u) + __uint_as_float(l.y & 0xffff0000u));
+  }
   if (dtype == DN_BF16) {
     uint2 v = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(base) + elem_off);
     return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16),

@@ -7,7 +7,8 @@
 //
 // Parameters live in the PACKED layout the contractions consume (engine.h; rows padded to 128, K to 64, the GEGLU projection
 // interleaved, conv taps as separate matrices): `master` (fp32) is what the optimizer updates, `work` the same buffer in the
-// arithmetic dtype (bf16: written by dn_adam_step's bf16 copy; f32: == master), `aux` holds what dn_vae_train_refresh derives
+// arithmetic dtype (bf16: written by dn_adam_step's bf16 copy; f32: == master; bf16x3 -- VAE only --: the split-row image of master,
+// [lo | hi] per 32 elements, written by dn_vae_train_refresh), `aux` holds what dn_vae_train_refresh derives
 // after every update (the transposed matrices of the data-gradient contractions, the summed skip biases).  Every contraction,
 // forward and backward, is dn_conv_gemm:
 //   data gradient    dX[t] = sum_j dY[t + shift_j] W_j            negative shifts, transposed weights
@@ -33,10 +34,14 @@ namespace dn {
 // through LDS with 16-byte global accesses on both sides: loads run along the channels of one frame, stores along the frames
 // of one channel (a 64-frame tile never straddles a K-slice: chunk % 64 == 0).  src rows are 16-byte aligned with ld a
 // multiple of the access width and >= C rounded up to it (activation buffers: ld = padk(C)).
-template <typename T>
+// SPLIT (T = float, DN_BF16X3): src is split rows [hi | lo] (ld a multiple of 32) and dst receives split rows in the order of its role
+// in the contraction -- weight_order 0: [hi | lo] (dY^T, the A operand), 1: [lo | hi] (X^T, the W operand); values pass through fp32,
+// so dst = split(transpose(hi + lo)).
+template <typename T, bool SPLIT = false>
 __global__ __launch_bounds__(256) void transpose_slices_kernel(const T* __restrict__ src, int ld, int B, int Tn, int C, int front, int Tp,
                                                                int64_t cols_total, T* __restrict__ dst, int rows, int rows_total, int row0,
-                                                               int chunk) {
+                                                               int chunk, int weight_order = 0) {
+  static_assert(!SPLIT || sizeof(T) == 4, "split rows pass through fp32");
   constexpr int V = 16 / (int)sizeof(T);   // elements per 16-byte access
   constexpr int LDT = 64 + V;              // LDS row: 64 frames + one access of padding (rows stay 16-byte aligned)
   constexpr int CPR = 64 / V;              // 16-byte pieces per 64-element row
@@ -56,7 +61,12 @@ __global__ __launch_bounds__(256) void transpose_slices_kernel(const T* __restri
       const int b = (int)(j / Tp), t = (int)(j - (int64_t)b * Tp) - front;
       const int c = c0 + q * V;
       if (t >= 0 && t < Tn && c < C) {
-        v.u = *reinterpret_cast<const uint4*>(src + ((int64_t)b * Tn + t) * ld + c);
+        if constexpr (SPLIT) {
+          const float4 f = load4(src, ((int64_t)b * Tn + t) * ld + c, DN_BF16X3);
+          v.u = make_uint4(__float_as_uint(f.x), __float_as_uint(f.y), __float_as_uint(f.z), __float_as_uint(f.w));
+        } else {
+          v.u = *reinterpret_cast<const uint4*>(src + ((int64_t)b * Tn + t) * ld + c);
+        }
 #pragma unroll
         for (int e = 0; e < V; ++e)
           if (c + e >= C) v.e[e] = T(0);
@@ -70,8 +80,16 @@ __global__ __launch_bounds__(256) void transpose_slices_kernel(const T* __restri
     const int r = i / CPR, q = i - r * CPR;
     const int c = c0 + r;
     const int64_t j = j0 + q * V;
-    if (c < rows && j < cols_total)
-      *reinterpret_cast<uint4*>(dst + ((j / chunk) * rows_total + row0 + c) * chunk + j % chunk) = *reinterpret_cast<const uint4*>(&tile[r][swz(r, q * V)]);
+    if (c < rows && j < cols_total) {
+      const int64_t o = ((j / chunk) * rows_total + row0 + c) * chunk + j % chunk;
+      if constexpr (SPLIT) {
+        const float* e = reinterpret_cast<const float*>(&tile[r][swz(r, q * V)]);
+        if (weight_order) store4_split_w(dst, o, e[0], e[1], e[2], e[3]);
+        else store4_split(dst, o, e[0], e[1], e[2], e[3]);
+      } else {
+        *reinterpret_cast<uint4*>(dst + o) = *reinterpret_cast<const uint4*>(&tile[r][swz(r, q * V)]);
+      }
+    }
   }
 }
 
@@ -227,7 +245,8 @@ int bind_flat(FlatParams& p, const char* who, float* master, void* work, void* a
   DN_CHECK_ARG(master && work && aux && grads, "%s: null argument", who);
   for (const void* q : {(const void*)master, (const void*)work, (const void*)aux, (const void*)grads})
     DN_CHECK_ARG(((uintptr_t)q & 255) == 0, "%s: buffers must be 256-byte aligned", who);
-  DN_CHECK_ARG(p.dtype == DN_BF16 || (const void*)work == (const void*)master, "%s: in f32 mode work must be master", who);
+  DN_CHECK_ARG(p.dtype != DN_F32 || (const void*)work == (const void*)master, "%s: in f32 mode work must be master", who);
+  DN_CHECK_ARG(p.dtype != DN_BF16X3 || (const void*)work != (const void*)master, "%s: in bf16x3 mode work is the split image of master, not master", who);
   p.master = master; p.work = work; p.aux = (char*)aux; p.grads = grads;
   return DN_OK;
 }
@@ -381,12 +400,12 @@ struct WgTap { const void* x; int ldx; int shift; };
 inline bool cond_streamed() { return option_or(OPT_COND_STREAM, 1) != 0; }
 
 
-template <typename T>
+template <typename T, bool SPLIT = false>
 void launch_transpose_slices(const void* src, int ld, int B, int Tn, int C, int front, const WgPlan& pl, void* dst, int rows, int rows_total,
-                             int row0, hipStream_t s) {
+                             int row0, hipStream_t s, int weight_order = 0) {
   dim3 grid((unsigned)((pl.cols_total + 63) / 64), (unsigned)((rows + 63) / 64));
-  hipLaunchKernelGGL((dn::transpose_slices_kernel<T>), grid, dim3(256), 0, s, static_cast<const T*>(src), ld, B, Tn, C, front, pl.Tp,
-                     pl.cols_total, static_cast<T*>(dst), rows, rows_total, row0, pl.chunk);
+  hipLaunchKernelGGL((dn::transpose_slices_kernel<T, SPLIT>), grid, dim3(256), 0, s, static_cast<const T*>(src), ld, B, Tn, C, front, pl.Tp,
+                     pl.cols_total, static_cast<T*>(dst), rows, rows_total, row0, pl.chunk, weight_order);
 }
 
 // main stream: wait for weight gradient `handle` (weight_grad's `overlap` result; < 0: it ran on the main stream)
@@ -453,7 +472,11 @@ int weight_grad(const Ctx& c0, const WgTap* taps, int n_taps, int cin, const voi
   void* dyT = base;
   void* xT = base + pl.b_dyT;
   float* part = reinterpret_cast<float*>(base + pl.b_dyT + pl.b_xT);
-  if (c.es == 2) {
+  if (c.dtype == DN_BF16X3) {  // dY^T is the A operand ([hi | lo]), X^T the W operand ([lo | hi])
+    launch_transpose_slices<float, true>(dy, lddy, c.B, c.T, cout, 0, pl, dyT, cout, cout, 0, c.s, 0);
+    for (int j = 0; j < n_taps; ++j)
+      launch_transpose_slices<float, true>(taps[j].x, taps[j].ldx, c.B, c.T, cin, taps[j].shift, pl, xT, pl.rows_w, pl.N, j * pl.rows_w, c.s, 1);
+  } else if (c.es == 2) {
     launch_transpose_slices<uint16_t>(dy, lddy, c.B, c.T, cout, 0, pl, dyT, cout, cout, 0, c.s);
     for (int j = 0; j < n_taps; ++j)
       launch_transpose_slices<uint16_t>(taps[j].x, taps[j].ldx, c.B, c.T, cin, taps[j].shift, pl, xT, pl.rows_w, pl.N, j * pl.rows_w, c.s);
@@ -680,6 +703,7 @@ int wave_backward(const Ctx& c, const WaveP& w, const void* in, const WaveSave& 
 // ------------------------------------------------------------------------------------------ transformer (learned-gamma norms)
 struct TfSave {  // per layer l: x [depth+1][M][Dp] fp32, xmid [depth][M][Dp] fp32, and the operand copies
   float *x, *xmid, *lse;
+  float* ao32;  // split operands only: the attention output in fp32 [depth][M][hd] (what the backward reads; `ao` is its split copy)
   void *xn1, *qkv, *ao, *xn2, *pre, *gg, *fc, *xnp;
 };
 struct TfTmp {
@@ -688,7 +712,7 @@ struct TfTmp {
   float* delta;
 };
 
-TfSave plan_tf_save(const TfP& w, int B, int T, int es, Arena& ar) {
+TfSave plan_tf_save(const TfP& w, int B, int T, int es, Arena& ar, bool split = false) {
   const size_t M = (size_t)B * T, Dp = padk(w.dim), hd = w.heads * w.dim_head, ip = padk(w.inner), d = w.depth;
   TfSave s;
   s.x = (float*)ar.take((d + 1) * M * Dp * 4);
@@ -697,6 +721,7 @@ TfSave plan_tf_save(const TfP& w, int B, int T, int es, Arena& ar) {
   s.xn1 = ar.take(d * M * Dp * es); s.qkv = ar.take(d * M * 3 * hd * es); s.ao = ar.take(d * M * hd * es);
   s.xn2 = ar.take(d * M * Dp * es); s.pre = ar.take(d * M * 2 * ip * es); s.gg = ar.take(d * M * ip * es);
   s.fc = ar.take(d * M * ip * es); s.xnp = ar.take(M * Dp * es);
+  s.ao32 = split ? (float*)ar.take(d * M * hd * 4) : nullptr;
   return s;
 }
 
@@ -736,18 +761,23 @@ int tf_forward(const Ctx& c, const TfP& w, const int32_t* lengths, const TfSave&
       DnGemmParams p = gemm_base(dtype, M, 3 * hd, Dp, T);
       p.terms[0].A = xn1; p.terms[0].lda = Dp; p.terms[0].W = c.W(w.qkv_W(l));
       p.out = qkv; p.ldo = 3 * hd;
+      if (dtype == DN_BF16X3) p.out_dtype = DN_F32;  // q / k / v are read by the attention kernels, not staged: plain fp32
       DN_TRY(dn_conv_gemm(&p, c.s));
     }
     {
       DnAttnParams a;
       memset(&a, 0, sizeof(a));
-      a.q = qkv; a.k = eoff(qkv, hd, es); a.v = eoff(qkv, 2 * hd, es); a.out = ao;
+      // split operands: the exact-fp32 attention (q / k / v fp32) writes O in fp32 for the backward, then one conversion makes the
+      // to_out operand
+      float* ao32 = sv.ao32 ? sv.ao32 + (size_t)l * M * hd : nullptr;
+      a.q = qkv; a.k = eoff(qkv, hd, es); a.v = eoff(qkv, 2 * hd, es); a.out = ao32 ? (void*)ao32 : ao;
       a.ldq = a.ldk = a.ldv = 3 * hd; a.ldo = hd;
-      a.B = B; a.T = T; a.heads = w.heads; a.dim_head = w.dim_head; a.dtype = dtype; a.lengths = lengths;
+      a.B = B; a.T = T; a.heads = w.heads; a.dim_head = w.dim_head; a.dtype = ao32 ? DN_F32 : dtype; a.lengths = lengths;
       a.scale = 1.0f / sqrtf((float)w.dim_head);
       a.lse = sv.lse + (size_t)l * B * w.heads * T;
       a.dropout_p = c.attn_dropout; a.seed_lo = c.seed_lo; a.seed_hi = c.seed_hi + (uint32_t)l;
       DN_TRY(dn_attention(&a, c.s));
+      if (ao32) DN_TRY(dn_convert_rows(ao32, DN_F32, hd, ao, dtype, hd, M, hd, c.s));
     }
     {  // to_out + residual (:932,692)
       DnGemmParams p = gemm_base(dtype, M, Dp, hd, T);
@@ -756,13 +786,13 @@ int tf_forward(const Ctx& c, const TfP& w, const int32_t* lengths, const TfSave&
       DN_TRY(dn_conv_gemm(&p, c.s));
     }
     DN_TRY(dn_rmsnorm(xmid, Dp, xn2, Dp, dtype, M, D, T, ada ? nullptr : c.P(w.g2(l)), gb2, gb_ld, Dp, c.s));
-    if (option_or(OPT_FUSED_GEGLU, 1) != 0) {  // Linear(D -> 2*inner) + GEGLU in the contraction's epilogue as inference runs it (:899,881-884),
+    if (option_or(OPT_FUSED_GEGLU, 1) != 0 && dtype != DN_BF16X3) {  // Linear(D -> 2*inner) + GEGLU in the contraction's epilogue as inference runs it (:899,881-884),
       DnGemmParams p = gemm_base(dtype, M, ip, Dp, T);  // which also keeps the pre-activation (packed [8 value ; 8 gate] columns) for the backward
       p.terms[0].A = xn2; p.terms[0].lda = Dp; p.terms[0].W = c.W(w.ffin_W(l));
       p.bias = c.P(w.ffin_b(l)); p.epilogue = DN_EPI_GEGLU; p.out = gg; p.ldo = ip;
       p.pre_out = pre; p.pre_ld = 2 * ip;
       DN_TRY(dn_conv_gemm(&p, c.s));
-    } else {  // option fused_geglu = 0: the projection, then a pass over its output (A/B timing)
+    } else {  // option fused_geglu = 0 (A/B timing) and split operands (no kept pre-activation): the projection, then a pass over its output
       DnGemmParams p = gemm_base(dtype, M, 2 * ip, Dp, T);
       p.terms[0].A = xn2; p.terms[0].lda = Dp; p.terms[0].W = c.W(w.ffin_W(l));
       p.bias = c.P(w.ffin_b(l)); p.out = pre; p.ldo = 2 * ip;
@@ -881,12 +911,14 @@ int tf_backward_layer(const Ctx& c, const TfP& w, int l, const int32_t* lengths,
   {  // to_out (:932)
     WgTap tap{ao, hd, 0};
     DN_TRY(weight_grad(c, &tap, 1, hd, tb.dx_act, Dp, D, c.G(w.out_W(l)), 0, &h_out));
-    DN_TRY(linear_dgrad(c, tb.dx_act, Dp, Dp, eoff(c.Wt(w.t_out), (size_t)l * padn(hd) * Dp, es), tb.d_ao, hd, dtype));
+    // split operands: dO reaches the attention backward as plain fp32, like q / k / v
+    DN_TRY(linear_dgrad(c, tb.dx_act, Dp, Dp, eoff(c.Wt(w.t_out), (size_t)l * padn(hd) * Dp, es), tb.d_ao, hd, dtype == DN_BF16X3 ? DN_F32 : dtype));
   }
   {  // Attend (:299-343)
     DnAttnBwdParams a;
     memset(&a, 0, sizeof(a));
-    a.q = qkv; a.k = eoff(qkv, hd, es); a.v = eoff(qkv, 2 * hd, es); a.out = ao; a.dout = tb.d_ao;
+    a.q = qkv; a.k = eoff(qkv, hd, es); a.v = eoff(qkv, 2 * hd, es); a.out = sv.ao32 ? (const void*)(sv.ao32 + (size_t)l * M * hd) : ao;
+    a.dout = tb.d_ao;
     a.dq = tb.d_qkv; a.dk = eoff(tb.d_qkv, hd, es); a.dv = eoff(tb.d_qkv, 2 * hd, es);
     a.ldq = a.ldk = a.ldv = 3 * hd; a.ldo = hd; a.lddo = hd; a.lddq = a.lddk = a.lddv = 3 * hd;
     a.B = B; a.T = T; a.heads = w.heads; a.dim_head = w.dim_head; a.dtype = dtype; a.lengths = lengths;
@@ -985,7 +1017,7 @@ VaePlan plan_vae_train(const DnVaeTrain* m, int B, int T, Arena& ar, bool need_e
   p.z = (float*)ar.take(M * padk(z) * 4);
   p.z_act = ar.take(M * padk(z) * es);
   p.kl_rows = (float*)ar.take(M * 4);
-  p.tf = plan_tf_save(m->tf, B, T, es, ar);
+  p.tf = plan_tf_save(m->tf, B, T, es, ar, m->dtype == DN_BF16X3);
   p.rec = (float*)ar.take(M * Dp * 4);
   p.rec_act = ar.take(M * Dp * es);
   p.logits = (float*)ar.take(M * V * 4);
@@ -1098,7 +1130,7 @@ int vae_decoder_backward(const Ctx& c, const DnVaeTrain* m, const VaePlan& pl, c
 extern "C" int dn_vae_train_create(const DnVaeConfig* cfg, DnVaeTrain** out) {
   DN_CHECK_ARG(cfg && out, "dn_vae_train_create: null argument");
   DN_CHECK_ARG(cfg->n_mults >= 1 && cfg->n_mults <= 4, "dn_vae_train_create: n_mults=%d", cfg->n_mults);
-  DN_CHECK_ARG(cfg->dtype == DN_F32 || cfg->dtype == DN_BF16, "dn_vae_train_create: bad dtype");
+  DN_CHECK_ARG(cfg->dtype == DN_F32 || cfg->dtype == DN_BF16 || cfg->dtype == DN_BF16X3, "dn_vae_train_create: bad dtype");
   DN_CHECK_ARG(cfg->dim % 8 == 0 && (cfg->heads * cfg->dim_head) % 64 == 0 && cfg->z % 4 == 0 && cfg->vocab % 4 == 0 && cfg->vocab <= 1024,
                "dn_vae_train_create: dim %% 8, heads*dim_head %% 64, z %% 4, vocab %% 4 (<= 1024) required");
   DN_CHECK_ARG(cfg->layers >= 1 && cfg->layers <= DN_MAX_TERMS && cfg->stacks >= 1, "dn_vae_train_create: stacks/layers");
@@ -1145,6 +1177,29 @@ extern "C" int dn_vae_train_create(const DnVaeConfig* cfg, DnVaeTrain** out) {
 
 extern "C" void dn_vae_train_destroy(DnVaeTrain* m) { delete m; }
 
+// The weight gradient's operand transpose on its own (tests): rows [row0, row0 + rows) of the K-sliced channels-major copy.
+extern "C" int dn_transpose_slices(const void* src, int32_t dtype, int32_t ld, int32_t B, int32_t T, int32_t C, int32_t front, int32_t Tp,
+                                   int64_t cols_total, int32_t chunk, void* dst, int32_t rows, int32_t rows_total, int32_t row0,
+                                   int32_t weight_order, void* stream) {
+  DN_CHECK_ARG(src && dst && B > 0 && T > 0 && C > 0 && ld >= C && front >= 0 && Tp >= T + front && rows >= C && row0 >= 0 &&
+                   row0 + rows <= rows_total && chunk > 0 && chunk % 64 == 0 && cols_total >= (int64_t)B * Tp && cols_total % chunk == 0,
+               "dn_transpose_slices: B=%d T=%d C=%d ld=%d front=%d Tp=%d rows=%d row0=%d rows_total=%d chunk=%d", B, T, C, ld, front, Tp, rows,
+               row0, rows_total, chunk);
+  DN_CHECK_ARG(dtype == DN_F32 || dtype == DN_BF16 || dtype == DN_BF16X3, "dn_transpose_slices: bad dtype %d", dtype);
+  DN_CHECK_ARG(ld % (dtype == DN_BF16X3 ? 32 : (dtype == DN_BF16 ? 8 : 4)) == 0 && ((uintptr_t)src & 15) == 0 &&
+                   ((uintptr_t)dst & (dtype == DN_BF16X3 ? 127 : 15)) == 0,
+               "dn_transpose_slices: ld=%d / alignment", ld);
+  WgPlan pl;
+  memset(&pl, 0, sizeof(pl));
+  pl.Tp = Tp; pl.cols_total = cols_total; pl.chunk = chunk;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == DN_BF16X3) launch_transpose_slices<float, true>(src, ld, B, T, C, front, pl, dst, rows, rows_total, row0, s, weight_order);
+  else if (dtype == DN_BF16) launch_transpose_slices<uint16_t>(src, ld, B, T, C, front, pl, dst, rows, rows_total, row0, s);
+  else launch_transpose_slices<float>(src, ld, B, T, C, front, pl, dst, rows, rows_total, row0, s);
+  DN_CHECK_LAUNCH("dn_transpose_slices");
+  return DN_OK;
+}
+
 extern "C" int64_t dn_vae_train_param_count(const DnVaeTrain* m) { return m ? m->n_params : 0; }
 
 extern "C" size_t dn_vae_train_aux_bytes(const DnVaeTrain* m) { return m ? m->aux_bytes() : 0; }
@@ -1177,8 +1232,11 @@ extern "C" int dn_vae_train_bind(DnVaeTrain* m, float* master, void* work, void*
 }
 
 // aux <- work: the transposed matrices of the data-gradient contractions and the summed skip biases.  Call after every update.
+// bf16x3: the split work copy is made here from master first.
 extern "C" int dn_vae_train_refresh(DnVaeTrain* m, void* stream) {
   DN_CHECK_ARG(m && m->work && m->aux, "dn_vae_train_refresh: not bound");
+  // split operands: work <- split(master) first (after dn_adam_step and after any external update of master alike)
+  if (m->dtype == DN_BF16X3) DN_TRY(dn_split_rows(m->master, m->n_params, m->work, 1, stream));
   const Transposer tr{*m, (hipStream_t)stream};
   for (int n = 0; n < 2 * m->n_wave; ++n) DN_TRY(refresh_wave(tr, n < m->n_wave ? m->enc[n] : m->dec[n - m->n_wave]));
   DN_TRY(refresh_tf(tr, m->tf));
@@ -1484,7 +1542,8 @@ int eps_check(const DnEpsTrain* m, const DnVaeTrain* vae, const DnEpsTrainBatch*
 
 extern "C" int dn_eps_train_create(const DnEpsConfig* cfg, DnEpsTrain** out) {
   DN_CHECK_ARG(cfg && out, "dn_eps_train_create: null argument");
-  DN_CHECK_ARG(cfg->dtype == DN_F32 || cfg->dtype == DN_BF16, "dn_eps_train_create: bad dtype");
+  DN_CHECK_ARG(cfg->dtype == DN_F32 || cfg->dtype == DN_BF16,
+               "dn_eps_train_create: dtype %d: the diffusion training engine runs f32 or bf16 (bf16x3 training is the VAE's only)", cfg->dtype);
   DN_CHECK_ARG(cfg->dim % 8 == 0 && (cfg->heads * cfg->dim_head) % 64 == 0 && cfg->latent % 4 == 0 && (cfg->dim * cfg->cond_mult) % 64 == 0,
                "dn_eps_train_create: dim %% 8, heads*dim_head %% 64, latent %% 4, dim*cond_mult %% 64 required");
   DN_CHECK_ARG(cfg->wn_layers >= 1 && cfg->wn_layers <= DN_MAX_TERMS && cfg->wn_stacks >= 1, "dn_eps_train_create: wavenet stacks/layers");

@@ -323,6 +323,8 @@ __global__ __launch_bounds__(256) void posterior_bwd_kernel(const float* __restr
     }
     if (act_dtype == DN_BF16)
       reinterpret_cast<uint16_t*>(dparams)[i] = (uint16_t)(pack_bf16x2(v, 0.f) & 0xffff);
+    else if (act_dtype == DN_BF16X3)
+      store1_split(dparams, i, v);
     else
       reinterpret_cast<float*>(dparams)[i] = v;
   }
@@ -388,6 +390,8 @@ __global__ __launch_bounds__(256) void lsce_kernel(const float* __restrict__ log
     }
     if (act_dtype == DN_BF16)
       reinterpret_cast<uint16_t*>(dlogits)[(int64_t)m * ldd + c] = (uint16_t)(pack_bf16x2(g, 0.f) & 0xffff);
+    else if (act_dtype == DN_BF16X3)
+      store1_split(dlogits, (int64_t)m * ldd + c, g);
     else
       reinterpret_cast<float*>(dlogits)[(int64_t)m * ldd + c] = g;
   }
@@ -546,6 +550,39 @@ __global__ __launch_bounds__(256) void transpose_mat_kernel(const T* __restrict_
   for (int i = ty; i < 64; i += 4) {
     const int c = c0 + i, r = r0 + tx;
     if (c < Cp && r < Rp) d[(int64_t)c * Rp + r] = tile[tx][i];
+  }
+}
+
+// The same for split-row weights (DN_BF16X3, [lo | hi] on both sides): dst = split(transpose(hi + lo)) -- every element is re-split
+// from its fp32 value, so the copy is exactly what splitting the transposed fp32 matrix gives.  Rows of 32-element groups: Cc, Rp and
+// both strides are multiples of 32.
+__global__ __launch_bounds__(256) void transpose_mat_split_kernel(const void* __restrict__ src, int64_t src_stride, int R, int Cc,
+                                                                  void* __restrict__ dst, int64_t dst_stride, int Rp, int Cp) {
+  __shared__ float tile[64][65];
+  const int64_t s0 = (int64_t)blockIdx.z * src_stride, d0 = (int64_t)blockIdx.z * dst_stride;
+  const int c0 = blockIdx.x * 64, r0 = blockIdx.y * 64;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  for (int i = ty; i < 64; i += 4) {
+    const int r = r0 + i, c = c0 + tx;
+    tile[i][tx] = (r < R && c < Cc) ? load1_split(src, s0 + (int64_t)r * Cc + c) : 0.f;
+  }
+  __syncthreads();
+  // four consecutive r per thread: one split store of 4 elements (Rp % 32 == 0, so they stay in one 32-element group)
+  for (int i = threadIdx.x; i < 64 * 16; i += 256) {
+    const int ci = i >> 4, rq = (i & 15) * 4;
+    const int c = c0 + ci, r = r0 + rq;
+    if (c < Cp && r < Rp) store4_split_w(dst, d0 + (int64_t)c * Rp + r, tile[rq][ci], tile[rq + 1][ci], tile[rq + 2][ci], tile[rq + 3][ci]);
+  }
+}
+
+// work <- master in split rows: dst = split(src) over n elements (n % 4 == 0), in the order of a weight ([lo | hi]) or of an
+// activation ([hi | lo])
+__global__ __launch_bounds__(256) void split_rows_kernel(const float* __restrict__ src, int64_t n, void* __restrict__ dst, int weight_order) {
+  const int64_t n4 = n >> 2;
+  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    const float4 v = *reinterpret_cast<const float4*>(src + 4 * i);
+    if (weight_order) store4_split_w(dst, 4 * i, v.x, v.y, v.z, v.w);
+    else store4_split(dst, 4 * i, v.x, v.y, v.z, v.w);
   }
 }
 
@@ -871,13 +908,25 @@ extern "C" int dn_transpose_weights(const void* src, int32_t dtype, int32_t coun
                    dst_stride >= (int64_t)Rp * Cp,
                "dn_transpose_weights: bad args");
   dim3 grid((Cp + 63) / 64, (Rp + 63) / 64, count);
-  if (dtype == DN_BF16)
+  if (dtype == DN_BF16X3) {
+    DN_CHECK_ARG(Cc % 32 == 0 && Rp % 32 == 0 && src_stride % 32 == 0 && dst_stride % 32 == 0 && ((uintptr_t)src & 127) == 0 && ((uintptr_t)dst & 127) == 0,
+                 "dn_transpose_weights: split rows need Cc, Rp and the strides multiples of 32 and 128-byte aligned bases");
+    hipLaunchKernelGGL(transpose_mat_split_kernel, grid, dim3(256), 0, S_(stream), src, src_stride, R, Cc, dst, dst_stride, Rp, Cp);
+  } else if (dtype == DN_BF16)
     hipLaunchKernelGGL(transpose_mat_kernel<uint16_t>, grid, dim3(256), 0, S_(stream), (const uint16_t*)src, src_stride, R, Cc,
                        (uint16_t*)dst, dst_stride, Rp, Cp);
   else
     hipLaunchKernelGGL(transpose_mat_kernel<float>, grid, dim3(256), 0, S_(stream), (const float*)src, src_stride, R, Cc, (float*)dst,
                        dst_stride, Rp, Cp);
   DN_CHECK_LAUNCH("dn_transpose_weights");
+  return DN_OK;
+}
+
+extern "C" int dn_split_rows(const float* src, int64_t n, void* dst, int32_t weight_order, void* stream) {
+  DN_CHECK_ARG(src && dst && n > 0 && n % 32 == 0, "dn_split_rows: n=%lld must be a positive multiple of 32", (long long)n);
+  DN_CHECK_ARG(((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 127) == 0, "dn_split_rows: src 16-byte, dst 128-byte aligned");
+  hipLaunchKernelGGL(split_rows_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, S_(stream), src, n, dst, weight_order);
+  DN_CHECK_LAUNCH("dn_split_rows");
   return DN_OK;
 }
 

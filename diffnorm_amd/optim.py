@@ -102,7 +102,7 @@ class FlatOptimizer:
     def __init__(self, engine, lr: float = 5e-4, betas=(0.9, 0.98), eps: float = 1e-8, weight_decay: float = 0.0):
         self.engine = engine
         self.adam = Adam(engine.master, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, clip_norm=0.0,
-                         bf16_copy=engine.work if engine.work is not engine.master else None)
+                         bf16_copy=getattr(engine, "adam_copy", engine.work if engine.work is not engine.master else None))
         self._scale, self._scale_dev, self._max_norm = 1.0, None, 0.0
 
     def backward(self, loss):

@@ -20,13 +20,17 @@ from .profiling import profile_range
 from .engine import _dtype_code, _require_cuda
 
 
-def _training_dtype(dtype) -> int:
-    """The training engines run exact fp32 (the reference's own training arithmetic: parity at 1e-3) or bf16 (the fast mode);
-    f16 and bf16x3 are arithmetic modes of the inference / sampling engines."""
+def _training_dtype(dtype, split_ok: bool = False) -> int:
+    """The training engines run exact fp32 (the reference's own training arithmetic: parity at 1e-3) or bf16 (the fast mode); the
+    VAE's also runs bf16x3 (split operands: fp32-class results at the bf16 matrix pipe, `split_ok`).  f16 is an arithmetic mode of
+    the inference / sampling engines only."""
     code = _dtype_code(dtype)
-    if code not in (_lib.DN_F32, _lib.DN_BF16):
-        raise ValueError(f"training engines run dtype 'f32' or 'bf16'; {dtype!r} is an inference-only arithmetic mode "
-                         "(build the model with --hip-dtype bf16 / f32 for a training run)")
+    if code == _lib.DN_BF16X3 and not split_ok:
+        raise ValueError(f"{dtype!r}: the VAE training engine is the one bf16x3 training engine; the diffusion training engine runs "
+                         "'f32' or 'bf16' (build the model with --hip-dtype bf16 / f32 for a diffusion training run)")
+    if code not in (_lib.DN_F32, _lib.DN_BF16, _lib.DN_BF16X3):
+        raise ValueError(f"training engines run dtype 'f32', 'bf16' or (the VAE) 'bf16x3'; {dtype!r} is an inference-only arithmetic mode "
+                         "(build the model with --hip-dtype bf16 / bf16x3 / f32 for a training run)")
     return code
 
 
@@ -94,6 +98,10 @@ class _FlatEngine:
                 raw, view = _aligned_empty(self.n_params * 2, self.device)
                 self._own.append(raw)
                 self.work = view.view(torch.bfloat16)
+            elif self.dtype == _lib.DN_BF16X3:  # the split-row image of master (packing.split_rows, weight order): 2 bf16 per element
+                raw, view = _aligned_empty(self.n_params * 4, self.device)
+                self._own.append(raw)
+                self.work = view.view(torch.bfloat16)
             else:
                 self.work = self.master
             raw, self.aux = _aligned_empty(aux_bytes, self.device)
@@ -108,12 +116,19 @@ class _FlatEngine:
 
     def sync_work(self):
         """work / aux <- master (after loading or an external update of the master buffer)."""
-        if self.work is not self.master:
+        if self.dtype == _lib.DN_BF16:
             self.work.copy_(self.master)  # fp32 -> bf16, round to nearest even (the same rounding dn_adam_step applies)
-        self.refresh()
+        self.refresh()  # (bf16x3: refresh itself splits master into the work copy on the device)
+
+    @property
+    def adam_copy(self) -> Optional[torch.Tensor]:
+        """The buffer dn_adam_step refreshes beside master: the bf16 work copy (bf16 mode); None in f32 (work is master) and in bf16x3
+        (refresh splits master into work)."""
+        return self.work if self.dtype == _lib.DN_BF16 else None
 
     def refresh(self):
-        """aux <- work: call after every optimizer step (dn_adam_step has already written the bf16 work copy)."""
+        """aux <- work: call after every optimizer step (dn_adam_step has already written the bf16 work copy; bf16x3: the split work
+        copy is made from master first)."""
         self.update_count += 1
         with torch.cuda.device(self.device):
             _lib.check(self._fn("refresh")(self.handle, _lib.current_stream()), self._prefix + "refresh")
@@ -167,7 +182,7 @@ class VaeTrainEngine(_FlatEngine):
         for m in self.mults:
             z //= m
         self.z = z // 2
-        self.dtype = _training_dtype(dtype)
+        self.dtype = _training_dtype(dtype, split_ok=True)
         mults = (C.c_int32 * 4)(*(self.mults + [0] * (4 - len(self.mults))))
         cfg = _lib.VaeConfig(dim, self.z, depth, heads, dim_head, stacks, layers, vocab, len(self.mults), mults, self.dtype)
         self._open("dn_vae_train_", cfg, packing.vae_train_entries(dim, self.mults, depth, heads, dim_head, stacks, layers, vocab))
@@ -402,7 +417,7 @@ class VaeTrainer:
         # `adam`: anything with set_lr / step(grads, grad_scale, grad_scale_dev) -- the CPU tests of the exchange logic pass a recorder
         self.adam = adam if adam is not None else optim.Adam(
             engine.master, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, clip_norm=clip_norm,
-            bf16_copy=engine.work if engine.work is not engine.master else None)
+            bf16_copy=engine.adam_copy)
         self.schedule = optim.InverseSquareRootSchedule(lr, warmup_updates, warmup_init_lr)
         self.reducer = GradientReducer(engine.grads, engine.stage_ranges(), group=group, bucket_mb=bucket_mb)
         self.group = group

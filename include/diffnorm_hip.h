@@ -20,7 +20,9 @@
  *     (hi = bf16(x), lo = bf16(x - hi): 16 mantissa bits) and a product runs as three bf16 MFMAs into one fp32
  *     accumulator, a_hi b_hi + a_lo b_hi + a_hi b_lo (the dropped a_lo b_lo term is 2^-18 relative), i.e. fp32-class
  *     results (1e-3 budget of north_star's fp32 column) at a third of the bf16 MFMA rate instead of a sixteenth.
- *     Everything that is not a contraction operand is fp32 exactly as in DN_F32 mode.
+ *     Everything that is not a contraction operand is fp32 exactly as in DN_F32 mode.  Inference / sampling engines and the VAE
+ *     training engine (dn_vae_train_*: work = the split image of master, made by dn_vae_train_refresh); the diffusion training
+ *     engine runs DN_F32 / DN_BF16.
  *     DN_F16 = IEEE-half MFMA operands (v_mfma_f32_16x16x32_f16: the bf16 issue rate on gfx950) with fp32 accumulation --
  *     DN_BF16 with three more significand bits: the same 2-byte layouts, tiles and schedules, every tensor DN_BF16 stores as
  *     bf16 is stored as half, everything DN_BF16 keeps fp32 stays fp32.  The format ends at 65504: a value beyond it saturates
@@ -457,9 +459,23 @@ int dn_rows_times_weight(const float* X, int32_t ldx, int32_t B, const float* W,
                          float* scratch, void* stream);
 
 /* Batched padded transpose of packed weights, the W operand of the data-gradient contraction: dst[n] [Cp][Rp] = (the first
- * R rows of src[n], [R][Cc])^T, zeros beyond; matrices src_stride / dst_stride elements apart.                           */
+ * R rows of src[n], [R][Cc])^T, zeros beyond; matrices src_stride / dst_stride elements apart.  DN_BF16X3: both sides are
+ * weight-order split rows ([lo | hi]), dst = split(transpose(hi + lo)); Cc, Rp and the strides multiples of 32.            */
 int dn_transpose_weights(const void* src, int32_t dtype, int32_t count, int64_t src_stride, int32_t R, int32_t Cc, void* dst,
                          int64_t dst_stride, int32_t Rp, int32_t Cp, void* stream);
+
+/* fp32 [n] -> DN_BF16X3 split rows (n a multiple of 32; dst 128-byte aligned): weight_order != 0 stores [lo | hi] (packed
+ * weights), 0 stores [hi | lo] (activations).  The split-operand training engine's work copy of its master parameters, the
+ * operand type of the contractions that replace torch's fp32 autograd of nn.Linear / CausalConv1d (latent_module.py:476-488). */
+int dn_split_rows(const float* src, int64_t n, void* dst, int32_t weight_order, void* stream);
+
+/* The operand transpose of the training engines' weight gradient (autograd of CausalConv1d / nn.Linear, latent_module.py:476-485):
+ * dst[j / chunk][row0 + c][j % chunk] = src[b * T + t, c] with j = b * Tp + front + t, zero for pad frames, channels >= C and the tail
+ * columns [B * Tp, cols_total).  dtype DN_F32 / DN_BF16 / DN_BF16X3 (src split rows [hi | lo]; dst split rows in the order of its role:
+ * weight_order 0 = [hi | lo], the A operand dY^T, 1 = [lo | hi], the W operand X^T).  chunk a multiple of 64 dividing cols_total.  */
+int dn_transpose_slices(const void* src, int32_t dtype, int32_t ld, int32_t B, int32_t T, int32_t C, int32_t front, int32_t Tp,
+                        int64_t cols_total, int32_t chunk, void* dst, int32_t rows, int32_t rows_total, int32_t row0, int32_t weight_order,
+                        void* stream);
 
 /* Last step of a weight gradient: grad[tap][n][k] += sum_s part[s][n][tap * rows_w + k] for n < cout, k < Kp; part is the fp32
  * split-K output [slices][cout][n_total] of the contraction over frames, grad the packed fp32 layout [n_taps][Np][Kp].    */
