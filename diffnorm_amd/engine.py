@@ -109,7 +109,7 @@ class EpsEngine(_Engine):
 
     def cond_time_table(self, t0: int, n_t: int) -> torch.Tensor:
         """The time half of the conditioning rows of timesteps t0 .. t0 + n_t - 1 (dn_eps_cond_time_table): fp32 [n_t, n_cond]."""
-        n_cond = (self.cfg.wavenet_stacks * self.cfg.wavenet_layers + 3 * self.cfg.depth) * 2 * packing.padk(self.cfg.dim)
+        n_cond = len(packing.eps_cond_modules(self.cfg)) * 2 * packing.padk(self.cfg.dim)
         table = torch.empty(n_t, n_cond, dtype=torch.float32, device=self.device)
         ws = torch.empty(int(self.lib.dn_eps_cond_time_table_workspace_bytes(self.handle, n_t)) + 256, dtype=torch.uint8, device=self.device)
         wp, wn = self._aligned(ws)

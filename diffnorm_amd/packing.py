@@ -1,17 +1,26 @@
-"""State-dict -> packed device tensors for libdiffnorm_hip.so.
+"""State-dict -> packed tensors for libdiffnorm_hip.so: ONE table of packed tensors behind inference and training.
 
-Input: tensors in the reference's state-dict layout (conv weights [Cout,Cin,k], linear
-weights [out,in]).  Output: the ordered tensor tables `dn_eps_create` / `dn_vae_create` expect
-(diffnorm_amd/csrc/engine.h documents each entry).  Packing rules:
+Input: tensors in the reference's state-dict layout (conv weights [Cout,Cin,k], linear weights [out,in]).  Each
+network piece (`_wavenet_entries`, `_tf_layer_entries`, the models' own tensors in `_eps_entries` / `_vae_entries`) is a table of
+`_Entry` rows: name, packed fp32 shape, how to build the packed fp32 tensor from a state dict, how to write it back.  Two walks
+over the tables:
 
-* every weight becomes [rows padded to 128][K padded to 64] with K contiguous, in the arithmetic
-  dtype (bf16, fp32, or DN_BF16X3 split rows: hi / lo bf16 halves per 32 elements, `split_rows`); pads are zeros, so padded channels stay exactly zero through the network;
-* a k-tap causal conv becomes k matrices, tap j multiplying the frame t-(k-1-j)*dilation;
-* Linear(D, 2*inner) of the GEGLU is interleaved per 16-row MFMA tile = [8 value rows ; 8 gate rows of the same output
-  columns], so every tile is self-contained and one wave holds value and gate of a column (epilogue DN_EPI_GEGLU);
-* the 2*S*L FiLM and 2*depth adaptive-RMSNorm projections are stacked into one [n_cond, C] matrix,
-  each as [gamma(Dp) ; beta(Dp)];
-* biases, norm gammas, the Fourier frequencies and the sinusoidal table stay fp32.
+* training (`*_train_entries`, `pack_flat` / `unpack_flat`): the flat fp32 master / gradient buffers of csrc/train_engine.hip hold
+  the entries one after the other, the transformer's layer by layer;
+* inference (`pack_eps` / `pack_vae`: the ordered lists `dn_eps_create` / `dn_vae_create` expect, documented in csrc/engine.h):
+  the same entries, weights converted to the arithmetic dtype, the transformer's stacked per tensor, plus the few tensors derived
+  for inference only (summed skip bias, K-blocked copies, placeholders, the sinusoidal table).
+
+Packing rules:
+
+* every weight becomes [rows padded to 128][K padded to 64] with K contiguous; pads are zeros, so padded channels stay exactly zero
+  through the network.  Arithmetic dtypes (`_arith`): bf16, f16, fp32, or DN_BF16X3 split rows (`split_rows`);
+* a k-tap causal conv becomes k matrices, tap j multiplying the frame t-(k-1-j)*dilation (`_conv`);
+* Linear(D, 2*inner) of the GEGLU is interleaved per 16-row MFMA tile = [8 value rows ; 8 gate rows of the same output columns], so
+  every tile is self-contained and one wave holds value and gate of a column (epilogue DN_EPI_GEGLU; `_geglu_pack` / `_geglu_unpack`);
+* the 2*S*L FiLM and 2 (3 with a prompt branch) * depth adaptive-RMSNorm projections (`eps_cond_modules`) are stacked into one
+  [n_cond, C] matrix, each as [gamma(Dp) ; beta(Dp)] (`_cond_stack` / `_cond_unstack`);
+* biases, norm gammas, the conditioning path, the Fourier frequencies and the sinusoidal table stay fp32.
 """
 import math
 from typing import Dict, List
@@ -103,31 +112,6 @@ def sinusoidal_table(num: int, dim: int, ld: int) -> torch.Tensor:
     return tab
 
 
-def pack_wavenet(sd: SD, prefix: str, cin: int, cout: int, stacks: int, layers: int, dtype: int) -> List[torch.Tensor]:
-    cp = padk(cout)
-    g = lambda k: sd[prefix + k]
-    conv_W, conv_b, res_W, res_b = [], [], [], []
-    for s in range(stacks):
-        for i in range(layers):
-            p = f"stacks.{s}.blocks.{i}."
-            conv_W.append(_conv(g(p + "conv.weight"), dtype))
-            conv_b.append(_vec(g(p + "conv.bias"), cp))
-            res_W.append(_mat(g(p + "res_conv.weight")[:, :, 0], dtype))
-            res_b.append(_vec(g(p + "res_conv.bias"), cp))
-    last = f"stacks.{stacks - 1}.blocks."
-    skip_W = torch.stack([_mat(g(f"{last}{i}.skip_conv.weight")[:, :, 0], dtype) for i in range(layers)])
-    skip_b = _vec(sum(g(f"{last}{i}.skip_conv.bias").float() for i in range(layers)), cp)
-    return [
-        _conv(g("init_conv.weight"), dtype), _vec(g("init_conv.bias"), cp),
-        torch.stack(conv_W), torch.stack(conv_b), torch.stack(res_W), torch.stack(res_b),
-        skip_W, skip_b,
-        _mat(g("final_conv.weight")[:, :, 0], dtype), _vec(g("final_conv.bias"), cp),
-        # conv_W and res_W once more, K-blocked, for the 256 x 256 tile (bf16 only; placeholders in f32 mode)
-        kblock(torch.stack(conv_W)) if _is16(dtype) else torch.zeros(4),
-        kblock(torch.stack(res_W)) if _is16(dtype) else torch.zeros(4),
-    ]
-
-
 def _geglu_rows(inner: int) -> torch.Tensor:
     """Source row in Linear(D,2*inner).weight for every packed row (or -1 for a zero row)."""
     ip = padk(inner)
@@ -138,159 +122,6 @@ def _geglu_rows(inner: int) -> torch.Tensor:
     is_gate = (p % 16) >= 8
     src = torch.where(is_gate, col + inner, col)
     return torch.where(col < inner, src, torch.full_like(src, -1))
-
-
-def pack_transformer(sd: SD, prefix: str, dim: int, depth: int, heads: int, dim_head: int, dtype: int,
-                     conditioned: bool) -> List[torch.Tensor]:
-    inner = int(dim * 4 * 2 / 3)
-    ip, Dp, hd = padk(inner), padk(dim), heads * dim_head
-    rows = _geglu_rows(inner)
-    keep = rows >= 0
-    g = lambda k: sd[prefix + k]
-    qkv, out, ffin, ffin_b, ffc, ffc_b, ffo, ffo_b, g1, g2 = ([] for _ in range(10))
-    for l in range(depth):
-        p = f"layers.{l}."
-        qkv.append(_mat(torch.cat([g(p + "1.to_q.weight"), g(p + "1.to_kv.weight")], dim=0), dtype))
-        out.append(_mat(g(p + "1.to_out.weight"), dtype))
-        w, b = g(p + "5.0.weight").float(), g(p + "5.0.bias").float()
-        wp = torch.zeros(2 * ip, Dp)
-        bp = torch.zeros(2 * ip)
-        wp[keep, :dim] = w[rows[keep]]
-        bp[keep] = b[rows[keep]]
-        ffin.append(_arith(wp, dtype))
-        ffin_b.append(bp)
-        ffc.append(_conv(g(p + "5.2.1.weight"), dtype))
-        ffc_b.append(_vec(g(p + "5.2.1.bias"), ip))
-        ffo.append(_mat(g(p + "5.3.weight"), dtype))
-        ffo_b.append(_vec(g(p + "5.3.bias"), Dp))
-        if not conditioned:
-            g1.append(g(p + "0.gamma").float())
-            g2.append(g(p + "4.gamma").float())
-    dummy = torch.zeros(4, dtype=torch.float32)
-    return [
-        torch.stack(qkv), torch.stack(out), torch.stack(ffin), torch.stack(ffin_b), torch.stack(ffc),
-        torch.stack(ffc_b), torch.stack(ffo), torch.stack(ffo_b),
-        torch.stack(g1) if g1 else dummy, torch.stack(g2) if g2 else dummy.clone(),
-        g("to_pred.0.gamma").float().clone(), _mat(g("to_pred.1.weight"), dtype),
-        # the FFN conv weights once more, K-blocked, for the 256 x 352 tile (bf16 only; a placeholder in f32 mode)
-        kblock(torch.stack(ffc)) if _is16(dtype) else dummy.clone(),
-        # the GEGLU projection's packed weights K-blocked (its activations arrive K-blocked from the split norm's producer)
-        kblock(torch.stack(ffin)) if _is16(dtype) else dummy.clone(),
-        # and the q/kv projection's (layers >= 1 read the attention norm's output K-blocked from the previous layer's last contraction)
-        kblock(torch.stack(qkv)) if _is16(dtype) else dummy.clone(),
-    ]
-
-
-def pack_eps(sd: SD, cfg, dtype: int, max_pos: int = 2048) -> List[torch.Tensor]:
-    """cfg: object with dim, latent_dim, depth, heads, dim_head, wavenet_layers, wavenet_stacks, dim_cond_mult [, dim_prompt,
-    num_latents_m, resampler_depth: the conditional variant, whose extra tensors (csrc/engine.h kEpsCondTensors) follow the table]."""
-    D, Dp = cfg.dim, padk(cfg.dim)
-    C = D * cfg.dim_cond_mult
-    cond = getattr(cfg, "dim_prompt", 0) > 0
-    C2 = 2 * C if cond else C  # [time cond | pooled-prompt cond] (reference latent_module.py:784, 852)
-    cond_rows, cond_b = [], []
-
-    def add_cond(wname, bname):
-        w, b = sd[wname].float(), sd[bname].float()  # [2D, C2]: [gamma ; beta]
-        blk = torch.zeros(2 * Dp, C2)
-        bb = torch.zeros(2 * Dp)
-        blk[:D], blk[Dp:Dp + D] = w[:D], w[D:]
-        bb[:D], bb[Dp:Dp + D] = b[:D], b[D:]
-        cond_rows.append(blk)
-        cond_b.append(bb)
-
-    for s in range(cfg.wavenet_stacks):
-        for i in range(cfg.wavenet_layers):
-            p = f"wavenet.stacks.{s}.blocks.{i}.to_time_cond."
-            add_cond(p + "weight", p + "bias")
-    for l in range(cfg.depth):
-        for j in ((0, 2, 4) if cond else (0, 4)):  # attention norm, [cross-attention norm,] feed-forward norm
-            p = f"transformer.layers.{l}.{j}.to_gamma_beta."
-            add_cond(p + "weight", p + "bias")
-    cond_W = _mat(torch.cat(cond_rows, dim=0), _lib.DN_F32)  # conditioning stays fp32 in every mode
-    tensors = [
-        sd["to_time_cond.0.weights"].float().clone(),
-        sd["to_time_cond.1.weight"].float().contiguous().clone(),
-        sd["to_time_cond.1.bias"].float().clone(),
-        cond_W, torch.cat(cond_b),
-        _mat(sd["init_conv.weight"][:, :, 0], dtype), _vec(sd["init_conv.bias"], Dp),
-    ]
-    wsd = {k[len("wavenet."):]: v for k, v in sd.items() if k.startswith("wavenet.")}
-    tensors += pack_wavenet(wsd, "", D, D, cfg.wavenet_stacks, cfg.wavenet_layers, dtype)
-    tsd = {k[len("transformer."):]: v for k, v in sd.items() if k.startswith("transformer.")}
-    tensors += pack_transformer(tsd, "", D, cfg.depth, cfg.heads, cfg.dim_head, dtype, conditioned=True)
-    tensors += [
-        _mat(sd["final_proj.weight"], dtype), _vec(sd["final_proj.bias"], padk(cfg.latent_dim)),
-        sinusoidal_table(max_pos + 1, D, Dp),
-    ]
-    if cond:
-        tensors += pack_eps_cond(sd, cfg, dtype)
-    return tensors
-
-
-def pack_eps_cond(sd: SD, cfg, dtype: int) -> List[torch.Tensor]:
-    """Extra tensors of the conditional variant in csrc/engine.h's kEpsCondTensors order (reference latent_module.py:416-471,
-    752-773): prompt-condition MLP and null condition (fp32), null prompt tokens, the PerceiverResampler (latents with their
-    sinusoidal positions 1..m folded in: a constant), and the transformer layers' cross-attention projections."""
-    D, Dp, Dn = cfg.dim, padk(cfg.dim), padn(cfg.dim)
-    C, P, m, R = D * cfg.dim_cond_mult, cfg.dim_prompt, cfg.num_latents_m, cfg.resampler_depth
-    inner = int(D * 4 * 2 / 3)
-    ip, hd = padk(inner), cfg.heads * cfg.dim_head
-    rows = _geglu_rows(inner)
-    keep = rows >= 0
-    r = "perceiver_resampler."
-    pad_rows = lambda t: torch.cat([t, torch.zeros(t.shape[0], Dp - t.shape[1])], dim=1)
-    lat_pos = pad_rows(sd[r + "latents"].float() + sinusoidal_table(m + 1, D, D)[1:m + 1])
-    rq, rkv, rout, rffin, rffin_b, rffout, rffout_b = ([] for _ in range(7))
-    for l in range(R):
-        a = f"{r}layers.{l}.0."
-        f = f"{r}layers.{l}.1."
-        rq.append(_mat(sd[a + "to_q.weight"], dtype))
-        rkv.append(_mat(sd[a + "to_kv.weight"], dtype))
-        rout.append(_mat(sd[a + "to_out.weight"], dtype))
-        w, b = sd[f + "0.weight"].float(), sd[f + "0.bias"].float()
-        wp, bp = torch.zeros(2 * ip, Dp), torch.zeros(2 * ip)
-        wp[keep, :D], bp[keep] = w[rows[keep]], b[rows[keep]]
-        rffin.append(_arith(wp, dtype))
-        rffin_b.append(bp)
-        rffout.append(_mat(sd[f + "2.weight"], dtype))
-        rffout_b.append(_vec(sd[f + "2.bias"], Dp))
-    t = "transformer.layers."
-    return [
-        _mat(sd["to_prompt_cond.1.weight"], _lib.DN_F32), sd["to_prompt_cond.1.bias"].float().clone(), sd["null_prompt_cond"].float().clone(),
-        _arith(pad_rows(sd["null_prompt_tokens"].float()), dtype, weight=False),
-        _mat(sd[r + "proj_context.weight"], dtype), _vec(sd[r + "proj_context.bias"], Dp), lat_pos,
-        torch.stack(rq), torch.stack(rkv), torch.stack(rout), torch.stack(rffin), torch.stack(rffin_b), torch.stack(rffout),
-        torch.stack(rffout_b), sd[r + "norm.gamma"].float().clone(),
-        torch.stack([_mat(sd[f"{t}{l}.3.to_q.weight"], dtype) for l in range(cfg.depth)]),
-        torch.stack([_mat(sd[f"{t}{l}.3.to_kv.weight"], dtype) for l in range(cfg.depth)]),
-        torch.stack([_mat(sd[f"{t}{l}.3.to_out.weight"], dtype) for l in range(cfg.depth)]),
-    ]
-
-
-def vae_mults(latent_flag: int) -> List[int]:
-    """chan_mults of SpeechVAEEncoderDecoder (reference latent_module.py:1044-1051)."""
-    return {16: [4, 3, 2], 32: [4, 3], 128: [3]}[latent_flag]
-
-
-def pack_vae(sd: SD, dim: int, mults: List[int], depth: int, heads: int, dim_head: int, stacks: int, layers: int,
-             vocab: int, dtype: int) -> List[torch.Tensor]:
-    tensors: List[torch.Tensor] = []
-    cur = dim
-    for n, m in enumerate(mults):
-        tensors += pack_wavenet(sd, f"encoder_wave.{n}.", cur, cur // m, stacks, layers, dtype)
-        cur //= m
-    first = True
-    for n, m in enumerate(reversed(mults)):
-        tgt = cur * m
-        cin = cur // 2 if first else cur
-        first = False
-        tensors += pack_wavenet(sd, f"decoder_wave.{n}.", cin, tgt, stacks, layers, dtype)
-        cur = tgt
-    tsd = {k[len("decoder_tf."):]: v for k, v in sd.items() if k.startswith("decoder_tf.")}
-    tensors += pack_transformer(tsd, "", dim, depth, heads, dim_head, dtype, conditioned=False)
-    tensors += [_mat(sd["decoder_lm.weight"], dtype), _vec(sd["decoder_lm.bias"], padn(vocab))]
-    return tensors
 
 
 def kblock(t: torch.Tensor) -> torch.Tensor:
@@ -307,143 +138,222 @@ def unkblock(t: torch.Tensor) -> torch.Tensor:
     return t.transpose(-3, -2).reshape(*lead, rows, kb * 32).contiguous()
 
 
-# ------------------------------------------------------------------------------------------ training layout
-# The flat fp32 parameter / gradient buffers of the training engine (csrc/train_engine.hip) hold the same packed tensors as
-# above (fp32; no K-blocked copies; the L skip-conv biases separately; the transformer's tensors layer-major).  An entry
-# knows how to build its packed tensor from a state dict in the reference layout and how to write it back -- the latter is
-# what turns the flat gradient buffer into per-parameter gradients under the reference's names, and the flat master buffer
-# into a checkpoint the reference can load.
+# ------------------------------------------------------------------------------------------ layout rules, each beside its inverse
+def _geglu_pack(w: torch.Tensor, inner: int, cols: int = None) -> torch.Tensor:
+    """Linear(D, 2*inner) weight [2*inner, D] -> [2*padk(inner), cols], or its bias [2*inner] -> [2*padk(inner)], rows as _geglu_rows says."""
+    rows = _geglu_rows(inner)
+    keep = rows >= 0
+    w2 = w.float().reshape(2 * inner, -1)
+    out = torch.zeros(len(rows), cols or 1)
+    out[keep, :w2.shape[1]] = w2[rows[keep]]
+    return out if w.dim() == 2 else out[:, 0].contiguous()
+
+
+def _geglu_unpack(p: torch.Tensor, inner: int, cols: int = None) -> torch.Tensor:
+    """Inverse of _geglu_pack: the packed matrix -> [2*inner, cols], the packed bias -> [2*inner]."""
+    rows = _geglu_rows(inner)
+    keep = rows >= 0
+    w = torch.zeros(2 * inner, cols or 1)
+    w[rows[keep]] = p.reshape(len(rows), -1)[keep, :w.shape[1]]
+    return w if p.dim() == 2 else w[:, 0].contiguous()
+
+
+def _cond_stack(sd: SD, mods: List[str], leaf: str, D: int, Dp: int, rows: int = None) -> torch.Tensor:
+    """The `leaf` ("weight" [2D, cols] / "bias" [2D], each [gamma ; beta]) of the conditioning projections `mods`, stacked as one
+    [gamma (Dp) ; beta (Dp)] block per module: [rows or len(mods) * 2 Dp (, cols)]."""
+    tail = sd[mods[0] + leaf].shape[1:]
+    out = torch.zeros(rows or len(mods) * 2 * Dp, *tail)
+    for m, blk in zip(mods, out[: len(mods) * 2 * Dp].view(len(mods), 2, Dp, *tail)):
+        blk[:, :D] = sd[m + leaf].float().reshape(2, D, *tail)
+    return out
+
+
+def _cond_unstack(p: torch.Tensor, sd: SD, mods: List[str], leaf: str, D: int, Dp: int):
+    """Inverse of _cond_stack: every module's [2D (, cols)] back under its key."""
+    for m, blk in zip(mods, p[: len(mods) * 2 * Dp].view(len(mods), 2, Dp, *p.shape[1:])):
+        sd[m + leaf] = blk[:, :D].reshape(2 * D, *p.shape[1:]).clone()
+
+
+def eps_cond_modules(cfg) -> List[str]:
+    """Key prefixes of the eps model's conditioning projections in the order of the stacked conditioning matrix: the FiLM of every
+    WaveNet block, then per transformer layer the attention norm, [the cross-attention norm of the prompt-conditioned model,] the
+    feed-forward norm.  A conditioning row has 2 * padk(dim) columns for each."""
+    norms = (0, 2, 4) if getattr(cfg, "dim_prompt", 0) > 0 else (0, 4)
+    return ([f"wavenet.stacks.{s}.blocks.{i}.to_time_cond." for s in range(cfg.wavenet_stacks) for i in range(cfg.wavenet_layers)]
+            + [f"transformer.layers.{l}.{j}.to_gamma_beta." for l in range(cfg.depth) for j in norms])
+
+
+def vae_mults(latent_flag: int) -> List[int]:
+    """chan_mults of SpeechVAEEncoderDecoder (reference latent_module.py:1044-1051)."""
+    return {16: [4, 3, 2], 32: [4, 3], 128: [3]}[latent_flag]
+
+
+def vae_chain(dim: int, mults: List[int]):
+    """(key prefix, cin, cout) of the VAE's cascaded WaveNets (reference latent_module.py:1053-1081): the encoder divides the width by
+    every chan_mult, the decoder multiplies it back; its first WaveNet reads the posterior sample, half the encoder's [mean ; logvar]."""
+    cur = dim
+    for n, m in enumerate(mults):
+        yield f"encoder_wave.{n}.", cur, cur // m
+        cur //= m
+    cin = cur // 2
+    for n, m in enumerate(reversed(mults)):
+        cur *= m
+        yield f"decoder_wave.{n}.", cin, cur
+        cin = cur
+
+
+# ------------------------------------------------------------------------------------------ the table of packed tensors
 class _Entry:
-    def __init__(self, name, shape, pack, unpack):
-        self.name, self.shape, self.pack, self.unpack = name, tuple(shape), pack, unpack
+    """One packed tensor: `pack(sd)` builds it in fp32, of `shape`, from a state dict in the reference layout; `unpack(p, sd)` writes
+    it (or its gradient) back under the reference's keys and shapes.  `arith`: "weight" = a contraction's weight, which the inference
+    lists hold in the arithmetic dtype; "act" = activation rows in it; None = fp32 in every mode (biases, gammas, conditioning).
+    `unpack` is None where nothing is trained: the prompt tokens and `lat_pos` (positions folded into the latents: no inverse)."""
+
+    def __init__(self, name, shape, pack, unpack=None, arith=None):
+        self.name, self.shape, self.pack, self.unpack, self.arith = name, tuple(shape), pack, unpack, arith
 
 
-def _unmat(p: torch.Tensor, n: int, k: int) -> torch.Tensor:
-    return p[:n, :k].clone()
+def _set(key: str, fn):
+    return lambda p, sd: sd.__setitem__(key, fn(p))
+
+
+def _raw(name, key, shape) -> _Entry:
+    return _Entry(name, shape, lambda sd: sd[key].float().clone(), _set(key, torch.clone))
+
+
+def _bias(name, key, n, n_pad) -> _Entry:
+    return _Entry(name, (n_pad,), lambda sd: _vec(sd[key], n_pad), _set(key, lambda p: p[:n].clone()))
+
+
+def _lin(name, key, n, k, k1=False, arith="weight") -> _Entry:
+    """Linear weight [n, k], or (k1) the [n, k, 1] of a 1 x 1 conv."""
+    return _Entry(name, (padn(n), padk(k)), lambda sd: _mat(sd[key][:, :, 0] if k1 else sd[key], _lib.DN_F32),
+                  _set(key, lambda p: p[:n, :k].clone().unsqueeze(-1) if k1 else p[:n, :k].clone()), arith)
+
+
+def _conv3(name, key, n, k) -> _Entry:
+    return _Entry(name, (3, padn(n), padk(k)), lambda sd: _conv(sd[key], _lib.DN_F32),
+                  _set(key, lambda p: p[:, :n, :k].permute(1, 2, 0).contiguous()), "weight")
+
+
+def _stacked(name, ents: List[_Entry]) -> _Entry:
+    """Entries of one shape as one [len(ents), ...] entry: one tensor of every block of a WaveNet."""
+    return _Entry(name, (len(ents),) + ents[0].shape, lambda sd: torch.stack([e.pack(sd) for e in ents]),
+                  lambda p, sd: [e.unpack(p[n], sd) for n, e in enumerate(ents)], ents[0].arith)
+
+
+def _attn_entries(name, key, dim, hd, fused) -> List[_Entry]:
+    """Projections of the attention block under `key`: [q, kv, out], or [qkv, out] where q and kv read the same rows (self-attention)."""
+    q, kv, out = (_lin(f"{name}{n}_W", f"{key}to_{n}.weight", r, c) for n, r, c in (("q", hd, dim), ("kv", 2 * hd, dim), ("out", dim, hd)))
+    if not fused:
+        return [q, kv, out]
+    qkv = _Entry(name + "qkv_W", (padn(3 * hd), padk(dim)), lambda sd: _mat(torch.cat([q.pack(sd)[:hd], kv.pack(sd)[: 2 * hd]]), _lib.DN_F32),
+                 lambda p, sd: (q.unpack(p[:hd], sd), kv.unpack(p[hd:], sd)), "weight")
+    return [qkv, out]
+
+
+def _geglu_entries(name, key, dim, inner) -> List[_Entry]:
+    return [_Entry(name + "_W", (2 * padk(inner), padk(dim)), lambda sd: _geglu_pack(sd[key + "weight"], inner, padk(dim)),
+                   _set(key + "weight", lambda p: _geglu_unpack(p, inner, dim)), "weight"),
+            _Entry(name + "_b", (2 * padk(inner),), lambda sd: _geglu_pack(sd[key + "bias"], inner), _set(key + "bias", lambda p: _geglu_unpack(p, inner)))]
 
 
 def _wavenet_entries(prefix: str, cin: int, cout: int, S: int, L: int) -> List[_Entry]:
-    cinp, cp, cn = padk(cin), padk(cout), padn(cout)
-    f32 = _lib.DN_F32
-    blocks = [(s, i) for s in range(S) for i in range(L)]
-    bk = lambda s, i: f"{prefix}stacks.{s}.blocks.{i}."
-    last = lambda i: f"{prefix}stacks.{S - 1}.blocks.{i}.skip_conv."
-
-    def conv_unpack(p, sd, key, c_in):  # [k, cn, Kp] -> [cout, cin, k]
-        sd[key] = p[:, :cout, :c_in].permute(1, 2, 0).contiguous()
-
-    def stack_unpack(p, sd, fmt, fn):
-        for n, (s, i) in enumerate(blocks):
-            fn(p[n], sd, fmt(s, i))
-
+    cp = padk(cout)
+    blocks = [f"{prefix}stacks.{s}.blocks.{i}." for s in range(S) for i in range(L)]
     return [
-        _Entry(prefix + "init_W", (3, cn, cinp), lambda sd: _conv(sd[prefix + "init_conv.weight"], f32),
-               lambda p, sd: conv_unpack(p, sd, prefix + "init_conv.weight", cin)),
-        _Entry(prefix + "init_b", (cp,), lambda sd: _vec(sd[prefix + "init_conv.bias"], cp),
-               lambda p, sd: sd.__setitem__(prefix + "init_conv.bias", p[:cout].clone())),
-        _Entry(prefix + "conv_W", (S * L, 3, cn, cp), lambda sd: torch.stack([_conv(sd[bk(s, i) + "conv.weight"], f32) for s, i in blocks]),
-               lambda p, sd: stack_unpack(p, sd, lambda s, i: bk(s, i) + "conv.weight", lambda q, d, k: conv_unpack(q, d, k, cout))),
-        _Entry(prefix + "conv_b", (S * L, cp), lambda sd: torch.stack([_vec(sd[bk(s, i) + "conv.bias"], cp) for s, i in blocks]),
-               lambda p, sd: stack_unpack(p, sd, lambda s, i: bk(s, i) + "conv.bias", lambda q, d, k: d.__setitem__(k, q[:cout].clone()))),
-        _Entry(prefix + "res_W", (S * L, cn, cp), lambda sd: torch.stack([_mat(sd[bk(s, i) + "res_conv.weight"][:, :, 0], f32) for s, i in blocks]),
-               lambda p, sd: stack_unpack(p, sd, lambda s, i: bk(s, i) + "res_conv.weight",
-                                          lambda q, d, k: d.__setitem__(k, _unmat(q, cout, cout).unsqueeze(-1)))),
-        _Entry(prefix + "res_b", (S * L, cp), lambda sd: torch.stack([_vec(sd[bk(s, i) + "res_conv.bias"], cp) for s, i in blocks]),
-               lambda p, sd: stack_unpack(p, sd, lambda s, i: bk(s, i) + "res_conv.bias", lambda q, d, k: d.__setitem__(k, q[:cout].clone()))),
-        _Entry(prefix + "skip_W", (L, cn, cp), lambda sd: torch.stack([_mat(sd[last(i) + "weight"][:, :, 0], f32) for i in range(L)]),
-               lambda p, sd: [sd.__setitem__(last(i) + "weight", _unmat(p[i], cout, cout).unsqueeze(-1)) for i in range(L)]),
-        _Entry(prefix + "skip_b", (L, cp), lambda sd: torch.stack([_vec(sd[last(i) + "bias"], cp) for i in range(L)]),
-               lambda p, sd: [sd.__setitem__(last(i) + "bias", p[i, :cout].clone()) for i in range(L)]),
-        _Entry(prefix + "final_W", (cn, cp), lambda sd: _mat(sd[prefix + "final_conv.weight"][:, :, 0], f32),
-               lambda p, sd: sd.__setitem__(prefix + "final_conv.weight", _unmat(p, cout, cout).unsqueeze(-1))),
-        _Entry(prefix + "final_b", (cp,), lambda sd: _vec(sd[prefix + "final_conv.bias"], cp),
-               lambda p, sd: sd.__setitem__(prefix + "final_conv.bias", p[:cout].clone())),
+        _conv3(prefix + "init_W", prefix + "init_conv.weight", cout, cin), _bias(prefix + "init_b", prefix + "init_conv.bias", cout, cp),
+        _stacked(prefix + "conv_W", [_conv3("", b + "conv.weight", cout, cout) for b in blocks]),
+        _stacked(prefix + "conv_b", [_bias("", b + "conv.bias", cout, cp) for b in blocks]),
+        _stacked(prefix + "res_W", [_lin("", b + "res_conv.weight", cout, cout, k1=True) for b in blocks]),
+        _stacked(prefix + "res_b", [_bias("", b + "res_conv.bias", cout, cp) for b in blocks]),
+        # only the last stack's blocks feed the skip sum
+        _stacked(prefix + "skip_W", [_lin("", b + "skip_conv.weight", cout, cout, k1=True) for b in blocks[-L:]]),
+        _stacked(prefix + "skip_b", [_bias("", b + "skip_conv.bias", cout, cp) for b in blocks[-L:]]),
+        _lin(prefix + "final_W", prefix + "final_conv.weight", cout, cout, k1=True), _bias(prefix + "final_b", prefix + "final_conv.bias", cout, cp),
     ]
 
 
-def _tf_layer_entries(prefix: str, l: int, dim: int, heads: int, dim_head: int) -> List[_Entry]:
+def _tf_layer_entries(prefix: str, l: int, dim: int, heads: int, dim_head: int, gammas: bool = True) -> List[_Entry]:
+    """One transformer layer.  gammas: its two RMSNorms' learned gammas (the VAE's decoder); the eps model's norms are adaptive, their
+    scale and shift are rows of the conditioning stack.  (The prompt-conditioned model's cross-attention block: _eps_prompt_entries.)"""
     inner = int(dim * 4 * 2 / 3)
-    ip, Dp, Dn, hd, in_n = padk(inner), padk(dim), padn(dim), heads * dim_head, padn(inner)
-    f32 = _lib.DN_F32
     p_ = f"{prefix}layers.{l}."
-    rows = _geglu_rows(inner)
-    keep = rows >= 0
-
-    def ffin_pack(sd):
-        w = sd[p_ + "5.0.weight"].float()
-        out = torch.zeros(2 * ip, Dp)
-        out[keep, :dim] = w[rows[keep]]
-        return out
-
-    def ffin_unpack(p, sd):
-        w = torch.zeros(2 * inner, dim)
-        w[rows[keep]] = p[keep, :dim]
-        sd[p_ + "5.0.weight"] = w
-
-    def ffin_b_pack(sd):
-        out = torch.zeros(2 * ip)
-        out[keep] = sd[p_ + "5.0.bias"].float()[rows[keep]]
-        return out
-
-    def ffin_b_unpack(p, sd):
-        b = torch.zeros(2 * inner)
-        b[rows[keep]] = p[keep]
-        sd[p_ + "5.0.bias"] = b
-
-    def qkv_unpack(p, sd):
-        sd[p_ + "1.to_q.weight"] = p[:hd, :dim].clone()
-        sd[p_ + "1.to_kv.weight"] = p[hd:3 * hd, :dim].clone()
-
-    return [
-        _Entry(p_ + "qkv_W", (padn(3 * hd), Dp), lambda sd: _mat(torch.cat([sd[p_ + "1.to_q.weight"], sd[p_ + "1.to_kv.weight"]], dim=0), f32),
-               qkv_unpack),
-        _Entry(p_ + "out_W", (Dn, hd), lambda sd: _mat(sd[p_ + "1.to_out.weight"], f32),
-               lambda p, sd: sd.__setitem__(p_ + "1.to_out.weight", _unmat(p, dim, hd))),
-        _Entry(p_ + "ffin_W", (2 * ip, Dp), ffin_pack, ffin_unpack),
-        _Entry(p_ + "ffin_b", (2 * ip,), ffin_b_pack, ffin_b_unpack),
-        _Entry(p_ + "ffconv_W", (3, in_n, ip), lambda sd: _conv(sd[p_ + "5.2.1.weight"], f32),
-               lambda p, sd: sd.__setitem__(p_ + "5.2.1.weight", p[:, :inner, :inner].permute(1, 2, 0).contiguous())),
-        _Entry(p_ + "ffconv_b", (ip,), lambda sd: _vec(sd[p_ + "5.2.1.bias"], ip),
-               lambda p, sd: sd.__setitem__(p_ + "5.2.1.bias", p[:inner].clone())),
-        _Entry(p_ + "ffout_W", (Dn, ip), lambda sd: _mat(sd[p_ + "5.3.weight"], f32),
-               lambda p, sd: sd.__setitem__(p_ + "5.3.weight", _unmat(p, dim, inner))),
-        _Entry(p_ + "ffout_b", (Dp,), lambda sd: _vec(sd[p_ + "5.3.bias"], Dp),
-               lambda p, sd: sd.__setitem__(p_ + "5.3.bias", p[:dim].clone())),
-        _Entry(p_ + "g1", (dim,), lambda sd: sd[p_ + "0.gamma"].float().clone(), lambda p, sd: sd.__setitem__(p_ + "0.gamma", p.clone())),
-        _Entry(p_ + "g2", (dim,), lambda sd: sd[p_ + "4.gamma"].float().clone(), lambda p, sd: sd.__setitem__(p_ + "4.gamma", p.clone())),
+    ents = _attn_entries(p_, p_ + "1.", dim, heads * dim_head, fused=True) + _geglu_entries(p_ + "ffin", p_ + "5.0.", dim, inner) + [
+        _conv3(p_ + "ffconv_W", p_ + "5.2.1.weight", inner, inner), _bias(p_ + "ffconv_b", p_ + "5.2.1.bias", inner, padk(inner)),
+        _lin(p_ + "ffout_W", p_ + "5.3.weight", dim, inner), _bias(p_ + "ffout_b", p_ + "5.3.bias", dim, padk(dim)),
     ]
+    if gammas:
+        ents += [_raw(p_ + "g1", p_ + "0.gamma", (dim,)), _raw(p_ + "g2", p_ + "4.gamma", (dim,))]
+    return ents
 
 
+def _tf_entries(name: str, prefix: str, dim: int, depth: int, heads: int, dim_head: int, gammas: bool):
+    """A transformer as (per-layer tables, [final norm's gamma, to_pred])."""
+    return ([_tf_layer_entries(prefix, l, dim, heads, dim_head, gammas) for l in range(depth)],
+            [_raw(name + "pred_gamma", prefix + "to_pred.0.gamma", (dim,)), _lin(name + "pred_W", prefix + "to_pred.1.weight", dim, dim)])
+
+
+def _eps_entries(cfg):
+    """The eps model as (head, WaveNet, transformer layers, to_pred, tail).  head = the conditioning path first: to_time_cond, then
+    the conditioning projections (eps_cond_modules) stacked as [gamma (Dp) ; beta (Dp)] rows over C (2C: [time | pooled prompt]
+    with a prompt branch, reference latent_module.py:784, 852) columns."""
+    D, Dp, zl, C = cfg.dim, padk(cfg.dim), cfg.latent_dim, cfg.dim * cfg.dim_cond_mult
+    mods = eps_cond_modules(cfg)
+    n_cond, C2 = len(mods) * 2 * Dp, 2 * C if getattr(cfg, "dim_prompt", 0) > 0 else C
+    head = [
+        _raw("w_freq", "to_time_cond.0.weights", (D // 2,)), _raw("tc_W", "to_time_cond.1.weight", (C, D + 1)), _raw("tc_b", "to_time_cond.1.bias", (C,)),
+        _Entry("cond_W", (padn(n_cond), C2), lambda sd: _cond_stack(sd, mods, "weight", D, Dp, padn(n_cond)),
+               lambda p, sd: _cond_unstack(p, sd, mods, "weight", D, Dp)),
+        _Entry("cond_b", (n_cond,), lambda sd: _cond_stack(sd, mods, "bias", D, Dp), lambda p, sd: _cond_unstack(p, sd, mods, "bias", D, Dp)),
+        _lin("init_W", "init_conv.weight", D, zl, k1=True), _bias("init_b", "init_conv.bias", D, Dp),
+    ]
+    tail = [_lin("final_W", "final_proj.weight", zl, D), _bias("final_b", "final_proj.bias", zl, padk(zl))]
+    return (head, _wavenet_entries("wavenet.", D, D, cfg.wavenet_stacks, cfg.wavenet_layers),
+            *_tf_entries("", "transformer.", D, cfg.depth, cfg.heads, cfg.dim_head, gammas=False), tail)
+
+
+def _eps_prompt_entries(cfg):
+    """The prompt branch (reference latent_module.py:416-471, 752-773) as (head, resampler layers, resampler norm, cross-attention
+    layers).  head = prompt-condition MLP and null condition (fp32), null prompt tokens, the PerceiverResampler's input projection and
+    its latents with their sinusoidal positions 1..m folded in (a constant); then the resampler's layers and, per transformer layer,
+    the cross-attention projections."""
+    D, Dp, C, P, m = cfg.dim, padk(cfg.dim), cfg.dim * cfg.dim_cond_mult, cfg.dim_prompt, cfg.num_latents_m
+    inner, hd, r = int(D * 4 * 2 / 3), cfg.heads * cfg.dim_head, "perceiver_resampler."
+    resampler = [_attn_entries("", f"{r}layers.{l}.0.", D, hd, fused=False) + _geglu_entries("", f"{r}layers.{l}.1.0.", D, inner)
+                 + [_lin("", f"{r}layers.{l}.1.2.weight", D, inner), _bias("", f"{r}layers.{l}.1.2.bias", D, Dp)] for l in range(cfg.resampler_depth)]
+    cross = [_attn_entries("", f"transformer.layers.{l}.3.", D, hd, fused=False) for l in range(cfg.depth)]
+    head = [
+        _lin("tpc_W", "to_prompt_cond.1.weight", C, P, arith=None), _raw("tpc_b", "to_prompt_cond.1.bias", (C,)), _raw("null_pc", "null_prompt_cond", (C,)),
+        _Entry("null_tok", (m, Dp), lambda sd: _mat(sd["null_prompt_tokens"], _lib.DN_F32, rows=m), arith="act"),
+        _lin("proj_W", r + "proj_context.weight", D, P), _bias("proj_b", r + "proj_context.bias", D, Dp),
+        _Entry("lat_pos", (m, Dp), lambda sd: _mat(sd[r + "latents"].float() + sinusoidal_table(m + 1, D, D)[1: m + 1], _lib.DN_F32, rows=m)),
+    ]
+    return head, resampler, [_raw("rnorm_g", r + "norm.gamma", (D,))], cross
+
+
+def _vae_entries(dim: int, mults: List[int], depth: int, heads: int, dim_head: int, stacks: int, layers: int, vocab: int):
+    """The VAE as (its WaveNets' tables, transformer layers, to_pred, tail)."""
+    tail = [_lin("decoder_lm.W", "decoder_lm.weight", vocab, dim), _bias("decoder_lm.b", "decoder_lm.bias", vocab, padn(vocab))]
+    return ([_wavenet_entries(prefix, cin, cout, stacks, layers) for prefix, cin, cout in vae_chain(dim, mults)],
+            *_tf_entries("decoder_tf.", "decoder_tf.", dim, depth, heads, dim_head, gammas=True), tail)
+
+
+# ------------------------------------------------------------------------------------------ training: the flat buffers (SURVEY 8 f2)
+# The flat fp32 parameter / gradient buffers of the training engines (csrc/train_engine.hip) hold the table's packed tensors one
+# after the other, the transformer's layer by layer.  `unpack` is what turns the flat gradient buffer into per-parameter gradients
+# under the reference's names, and the flat master buffer into a checkpoint the reference can load.
 def vae_train_entries(dim: int, mults: List[int], depth: int, heads: int, dim_head: int, stacks: int, layers: int,
                       vocab: int) -> List[_Entry]:
     """Table of the VAE training engine's packed tensors, in the order of dn_vae_train_offsets."""
-    f32 = _lib.DN_F32
-    Dp, Dn, Vn = padk(dim), padn(dim), padn(vocab)
-    ents: List[_Entry] = []
-    cur = dim
-    for n, m in enumerate(mults):
-        ents += _wavenet_entries(f"encoder_wave.{n}.", cur, cur // m, stacks, layers)
-        cur //= m
-    first = True
-    for n, m in enumerate(reversed(mults)):
-        tgt = cur * m
-        cin = cur // 2 if first else cur
-        first = False
-        ents += _wavenet_entries(f"decoder_wave.{n}.", cin, tgt, stacks, layers)
-        cur = tgt
-    for l in range(depth):
-        ents += _tf_layer_entries("decoder_tf.", l, dim, heads, dim_head)
-    ents += [
-        _Entry("decoder_tf.pred_gamma", (dim,), lambda sd: sd["decoder_tf.to_pred.0.gamma"].float().clone(),
-               lambda p, sd: sd.__setitem__("decoder_tf.to_pred.0.gamma", p.clone())),
-        _Entry("decoder_tf.pred_W", (Dn, Dp), lambda sd: _mat(sd["decoder_tf.to_pred.1.weight"], f32),
-               lambda p, sd: sd.__setitem__("decoder_tf.to_pred.1.weight", _unmat(p, dim, dim))),
-        _Entry("decoder_lm.W", (Vn, Dp), lambda sd: _mat(sd["decoder_lm.weight"], f32),
-               lambda p, sd: sd.__setitem__("decoder_lm.weight", _unmat(p, vocab, dim))),
-        _Entry("decoder_lm.b", (Vn,), lambda sd: _vec(sd["decoder_lm.bias"], Vn),
-               lambda p, sd: sd.__setitem__("decoder_lm.bias", p[:vocab].clone())),
-    ]
-    return ents
+    waves, tf_layers, pred, tail = _vae_entries(dim, mults, depth, heads, dim_head, stacks, layers, vocab)
+    return sum(waves + tf_layers, []) + pred + tail
+
+
+def eps_train_entries(cfg) -> List[_Entry]:
+    """Table of the diffusion training engine's packed tensors, in the order of dn_eps_train_offsets."""
+    head, wave, tf_layers, pred, tail = _eps_entries(cfg)
+    return head + wave + sum(tf_layers, []) + pred + tail
 
 
 def pack_flat(sd: SD, entries: List[_Entry], offsets: List[int], total: int) -> torch.Tensor:
@@ -461,69 +371,67 @@ def unpack_flat(flat: torch.Tensor, entries: List[_Entry], offsets: List[int]) -
     flat = flat.detach().float().cpu()
     sd: SD = {}
     for e, off in zip(entries, offsets):
-        n = 1
-        for s in e.shape:
-            n *= s
-        e.unpack(flat[off: off + n].view(e.shape), sd)
+        e.unpack(flat[off: off + math.prod(e.shape)].view(e.shape), sd)
     return sd
 
 
-def eps_train_entries(cfg) -> List[_Entry]:
-    """Table of the diffusion training engine's packed tensors, in the order of dn_eps_train_offsets (fp32; the conditioning
-    path first: to_time_cond, then the 2 S L FiLM and 2 depth adaptive-norm projections stacked as [gamma (Dp) ; beta (Dp)] rows)."""
-    f32 = _lib.DN_F32
-    D, Dp, Dn, zl = cfg.dim, padk(cfg.dim), padn(cfg.dim), cfg.latent_dim
-    zp, C = padk(zl), cfg.dim * cfg.dim_cond_mult
-    mods = [f"wavenet.stacks.{s}.blocks.{i}.to_time_cond." for s in range(cfg.wavenet_stacks) for i in range(cfg.wavenet_layers)]
-    mods += [f"transformer.layers.{l}.{j}.to_gamma_beta." for l in range(cfg.depth) for j in (0, 4)]
-    n_cond = len(mods) * 2 * Dp
+# ------------------------------------------------------------------------------------------ inference: the ordered lists (csrc/engine.h)
+# Each list walks the same tables: the packed fp32 tensor in the arithmetic dtype (_pack), a layered piece's stacked per tensor
+# (_per_tensor), plus the tensors derived for inference only, which each function below names where it returns.
+def _pack(ents: List[_Entry], sd: SD, dtype: int) -> List[torch.Tensor]:
+    return [_arith(e.pack(sd), dtype, weight=e.arith == "weight") if e.arith else e.pack(sd) for e in ents]
 
-    def cond_pack(sd):
-        out = torch.zeros(padn(n_cond), C)
-        for n, key in enumerate(mods):
-            w = sd[key + "weight"].float()  # [2D, C]: [gamma ; beta]
-            out[n * 2 * Dp: n * 2 * Dp + D] = w[:D]
-            out[n * 2 * Dp + Dp: n * 2 * Dp + Dp + D] = w[D:]
-        return out
 
-    def cond_unpack(p, sd):
-        for n, key in enumerate(mods):
-            sd[key + "weight"] = torch.cat([p[n * 2 * Dp: n * 2 * Dp + D], p[n * 2 * Dp + Dp: n * 2 * Dp + Dp + D]], dim=0).clone()
+def _per_tensor(layers: List[List[_Entry]], sd: SD, dtype: int) -> List[torch.Tensor]:
+    """Per-layer tables (the flat buffers are layer-major) -> every tensor stacked over the layers (the inference lists' order)."""
+    return [torch.stack(_pack(col, sd, dtype)) for col in zip(*layers)]
 
-    def condb_pack(sd):
-        out = torch.zeros(n_cond)
-        for n, key in enumerate(mods):
-            b = sd[key + "bias"].float()
-            out[n * 2 * Dp: n * 2 * Dp + D] = b[:D]
-            out[n * 2 * Dp + Dp: n * 2 * Dp + Dp + D] = b[D:]
-        return out
 
-    def condb_unpack(p, sd):
-        for n, key in enumerate(mods):
-            sd[key + "bias"] = torch.cat([p[n * 2 * Dp: n * 2 * Dp + D], p[n * 2 * Dp + Dp: n * 2 * Dp + Dp + D]]).clone()
+def _kb(w: torch.Tensor, dtype: int) -> torch.Tensor:
+    """The K-blocked copy of a stacked weight that the 2-byte modes' large tiles read; a placeholder in the other modes."""
+    return kblock(w) if _is16(dtype) else torch.zeros(4)
 
-    ents = [
-        _Entry("w_freq", (D // 2,), lambda sd: sd["to_time_cond.0.weights"].float().clone(),
-               lambda p, sd: sd.__setitem__("to_time_cond.0.weights", p.clone())),
-        _Entry("tc_W", (C, D + 1), lambda sd: sd["to_time_cond.1.weight"].float().clone(),
-               lambda p, sd: sd.__setitem__("to_time_cond.1.weight", p.clone())),
-        _Entry("tc_b", (C,), lambda sd: sd["to_time_cond.1.bias"].float().clone(), lambda p, sd: sd.__setitem__("to_time_cond.1.bias", p.clone())),
-        _Entry("cond_W", (padn(n_cond), C), cond_pack, cond_unpack),
-        _Entry("cond_b", (n_cond,), condb_pack, condb_unpack),
-        _Entry("init_W", (Dn, zp), lambda sd: _mat(sd["init_conv.weight"][:, :, 0], f32),
-               lambda p, sd: sd.__setitem__("init_conv.weight", _unmat(p, D, zl).unsqueeze(-1))),
-        _Entry("init_b", (Dp,), lambda sd: _vec(sd["init_conv.bias"], Dp), lambda p, sd: sd.__setitem__("init_conv.bias", p[:D].clone())),
-    ]
-    ents += _wavenet_entries("wavenet.", D, D, cfg.wavenet_stacks, cfg.wavenet_layers)
-    for l in range(cfg.depth):
-        ents += _tf_layer_entries("transformer.", l, D, cfg.heads, cfg.dim_head)[:8]  # no learned gammas in conditional norms
-    ents += [
-        _Entry("pred_gamma", (D,), lambda sd: sd["transformer.to_pred.0.gamma"].float().clone(),
-               lambda p, sd: sd.__setitem__("transformer.to_pred.0.gamma", p.clone())),
-        _Entry("pred_W", (Dn, Dp), lambda sd: _mat(sd["transformer.to_pred.1.weight"], f32),
-               lambda p, sd: sd.__setitem__("transformer.to_pred.1.weight", _unmat(p, D, D))),
-        _Entry("final_W", (padn(zl), Dp), lambda sd: _mat(sd["final_proj.weight"], f32),
-               lambda p, sd: sd.__setitem__("final_proj.weight", _unmat(p, zl, D))),
-        _Entry("final_b", (zp,), lambda sd: _vec(sd["final_proj.bias"], zp), lambda p, sd: sd.__setitem__("final_proj.bias", p[:zl].clone())),
-    ]
-    return ents
+
+def _wavenet_tensors(ents: List[_Entry], sd: SD, dtype: int) -> List[torch.Tensor]:
+    init_W, init_b, conv_W, conv_b, res_W, res_b, skip_W, skip_b, final_W, final_b = _pack(ents, sd, dtype)
+    # derived: one bias for the summed skip path; conv_W and res_W K-blocked for the 256 x 256 tile
+    return [init_W, init_b, conv_W, conv_b, res_W, res_b, skip_W, sum(skip_b), final_W, final_b, _kb(conv_W, dtype), _kb(res_W, dtype)]
+
+
+def _tf_tensors(tf_layers: List[List[_Entry]], pred: List[_Entry], sd: SD, dtype: int) -> List[torch.Tensor]:
+    qkv, out, ffin, ffin_b, ffc, ffc_b, ffo, ffo_b, *gammas = _per_tensor(tf_layers, sd, dtype)
+    # derived: placeholders for the gammas adaptive norms do not have; K-blocked copies of the FFN conv's weights (256 x 352 tile),
+    # the GEGLU projection's (its activations arrive K-blocked from the split norm's producer) and the q/kv projection's (layers
+    # >= 1 read the attention norm's output K-blocked from the previous layer's last contraction)
+    g1, g2 = gammas or (torch.zeros(4), torch.zeros(4))
+    return [qkv, out, ffin, ffin_b, ffc, ffc_b, ffo, ffo_b, g1, g2, *_pack(pred, sd, dtype), _kb(ffc, dtype), _kb(ffin, dtype), _kb(qkv, dtype)]
+
+
+def pack_wavenet(sd: SD, prefix: str, cin: int, cout: int, stacks: int, layers: int, dtype: int) -> List[torch.Tensor]:
+    return _wavenet_tensors(_wavenet_entries(prefix, cin, cout, stacks, layers), sd, dtype)
+
+
+def pack_transformer(sd: SD, prefix: str, dim: int, depth: int, heads: int, dim_head: int, dtype: int,
+                     conditioned: bool) -> List[torch.Tensor]:
+    return _tf_tensors(*_tf_entries("", prefix, dim, depth, heads, dim_head, gammas=not conditioned), sd, dtype)
+
+
+def pack_eps(sd: SD, cfg, dtype: int, max_pos: int = 2048) -> List[torch.Tensor]:
+    """cfg: object with dim, latent_dim, depth, heads, dim_head, wavenet_layers, wavenet_stacks, dim_cond_mult [, dim_prompt,
+    num_latents_m, resampler_depth: the conditional variant, whose extra tensors (csrc/engine.h kEpsCondTensors) follow the table]."""
+    head, wave, tf_layers, pred, tail = _eps_entries(cfg)
+    tensors = _pack(head, sd, dtype) + _wavenet_tensors(wave, sd, dtype) + _tf_tensors(tf_layers, pred, sd, dtype) + _pack(tail, sd, dtype)
+    tensors.append(sinusoidal_table(max_pos + 1, cfg.dim, padk(cfg.dim)))  # derived: the frames' positions
+    return tensors + (pack_eps_cond(sd, cfg, dtype) if getattr(cfg, "dim_prompt", 0) > 0 else [])
+
+
+def pack_eps_cond(sd: SD, cfg, dtype: int) -> List[torch.Tensor]:
+    """The conditional variant's extra tensors, in csrc/engine.h's kEpsCondTensors order."""
+    head, resampler, norm, cross = _eps_prompt_entries(cfg)
+    return _pack(head, sd, dtype) + _per_tensor(resampler, sd, dtype) + _pack(norm, sd, dtype) + _per_tensor(cross, sd, dtype)
+
+
+def pack_vae(sd: SD, dim: int, mults: List[int], depth: int, heads: int, dim_head: int, stacks: int, layers: int,
+             vocab: int, dtype: int) -> List[torch.Tensor]:
+    waves, tf_layers, pred, tail = _vae_entries(dim, mults, depth, heads, dim_head, stacks, layers, vocab)
+    return sum((_wavenet_tensors(w, sd, dtype) for w in waves), []) + _tf_tensors(tf_layers, pred, sd, dtype) + _pack(tail, sd, dtype)

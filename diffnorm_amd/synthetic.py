@@ -87,7 +87,7 @@ def random_eps_state_dict(cfg, seed: int = 0) -> Dict[str, torch.Tensor]:
 
 def random_vae_state_dict(dim=768, latent_dim=128, depth=6, heads=8, dim_head=96, stacks=2, layers=3, vocab=1004,
                           seed: int = 1) -> Dict[str, torch.Tensor]:
-    from .packing import vae_mults
+    from .packing import vae_chain, vae_mults
 
     it = _Init(seed)
 
@@ -102,17 +102,8 @@ def random_vae_state_dict(dim=768, latent_dim=128, depth=6, heads=8, dim_head=96
                     it.lin(p + "skip_conv", cout, cout, k=1)
         it.lin(prefix + "final_conv", cout, cout, k=1)
 
-    mults = vae_mults(latent_dim)
-    cur = dim
-    for n, m in enumerate(mults):
-        wave(f"encoder_wave.{n}.", cur, cur // m)
-        cur //= m
-    first = True
-    for n, m in enumerate(reversed(mults)):
-        tgt = cur * m
-        wave(f"decoder_wave.{n}.", cur // 2 if first else cur, tgt)
-        first = False
-        cur = tgt
+    for prefix, cin, cout in vae_chain(dim, vae_mults(latent_dim)):
+        wave(prefix, cin, cout)
     inner, hd = int(dim * 4 * 2 / 3), heads * dim_head
     for l in range(depth):
         p = f"decoder_tf.layers.{l}."
