@@ -117,7 +117,10 @@ __global__ __launch_bounds__(128 / (16 * QT) * 64, QT == 1 ? (DHP <= 64 ? 4 : 2)
     sc = 0.f;
   }
 
-  // attention dropout (training): thr = p * 2^32, kept probabilities scaled by 1 / (1 - p); the per-lane query rows' hashes are hoisted
+  // attention dropout (training): thr = p * 2^32; the per-lane query rows' hashes are hoisted.  The 1 / (1 - p) of the kept probabilities
+  // is applied once to the fp32 output accumulator at the end, not to P: the P that enters the PV product is then the same rounded P
+  // as in the denominator and as dn_attention_backward recomputes (which scales dP by the fp32 1 / (1 - p)); scaling before the
+  // 2-byte pack made a one-key sequence's O = bf16(bf16(1 / (1 - p)) v), two roundings that the backward's delta could not cancel
   uint32_t drop_thr = 0, drop_row[QT];
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) drop_row[qt] = 0;
@@ -130,7 +133,7 @@ __global__ __launch_bounds__(128 / (16 * QT) * 64, QT == 1 ? (DHP <= 64 ? 4 : 2)
       drop_row[qt] = dn_drop_row((uint32_t)(((int64_t)b * p.heads + h) * T + (q0 + qt * 16 + fr)), p.seed_lo);
   }
   auto dropped = [&](float pv, int qt, int key) -> float {
-    if constexpr (DROP) return dn_drop_keep(drop_row[qt], (uint32_t)key, p.seed_hi, drop_thr) ? pv * drop_inv : 0.f;
+    if constexpr (DROP) return dn_drop_keep(drop_row[qt], (uint32_t)key, p.seed_hi, drop_thr) ? pv : 0.f;
     return pv;
   };
 
@@ -332,7 +335,7 @@ __global__ __launch_bounds__(128 / (16 * QT) * 64, QT == 1 ? (DHP <= 64 ? 4 : 2)
   for (int qt = 0; qt < QT; ++qt) {
     const int q = q0 + qt * 16 + fr;
     if (q >= T) continue;
-    const float inv = 1.0f / (ES == 2 ? acc_l[qt][0] : l_run[qt]);
+    const float inv = (DROP ? drop_inv : 1.0f) / (ES == 2 ? acc_l[qt][0] : l_run[qt]);
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
       const int d = dt * 16 + fg * 4;
@@ -433,7 +436,7 @@ __global__ __launch_bounds__(128 / (16 * QT) * 64, QT == 1 ? 4 : 2) void attn_x3
       drop_row[qt] = dn_drop_row((uint32_t)(((int64_t)b * p.heads + h) * T + (q0 + qt * 16 + fr)), p.seed_lo);
   }
   auto dropped = [&](float pv, int qt, int key) -> float {
-    if constexpr (DROP) return dn_drop_keep(drop_row[qt], (uint32_t)key, p.seed_hi, drop_thr) ? pv * drop_inv : 0.f;
+    if constexpr (DROP) return dn_drop_keep(drop_row[qt], (uint32_t)key, p.seed_hi, drop_thr) ? pv : 0.f;
     return pv;
   };
 
@@ -609,7 +612,7 @@ __global__ __launch_bounds__(128 / (16 * QT) * 64, QT == 1 ? 4 : 2) void attn_x3
   for (int qt = 0; qt < QT; ++qt) {
     const int q = q0 + qt * 16 + fr;
     if (q >= T) continue;
-    const float inv = 1.0f / l_run[qt];
+    const float inv = (DROP ? drop_inv : 1.0f) / l_run[qt];
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
       const int d = dt * 16 + fg * 4;

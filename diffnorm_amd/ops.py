@@ -113,15 +113,25 @@ def conv_gemm(terms: Sequence[Tuple[torch.Tensor, torch.Tensor, int]], out: torc
     return out
 
 
-def attention(q, k, v, out, B, T, heads, dim_head, lengths: Optional[torch.Tensor], ldq=None, ldk=None, ldv=None):
-    lib = _lib.load()
+def _attn_params(q, k, v, out, B, T, heads, dim_head, lengths, ldq, ldk, ldv, Tk, ldo, dtype):
+    """DnAttnParams of one call.  Tk: keys per sequence of a cross-attention (0 = T); ldo: row stride of `out` in elements (default:
+    its width); dtype: the arithmetic mode when it is not the tensors' own -- DN_BF16X3 takes fp32 q / k / v and writes `out`, a bf16
+    tensor of twice ldo entries per row, as split rows."""
     a = _lib.AttnParams()
     a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
-    a.ldq, a.ldk, a.ldv, a.ldo = ldq or q.shape[-1], ldk or k.shape[-1], ldv or v.shape[-1], out.shape[-1]
-    a.B, a.T, a.heads, a.dim_head = B, T, heads, dim_head
-    a.dtype = _code(q)
+    a.dtype = _code(q) if dtype is None else dtype
+    sw = 2 if (a.dtype == _lib.DN_BF16X3 and out.dtype == torch.bfloat16) else 1
+    a.ldq, a.ldk, a.ldv, a.ldo = ldq or q.shape[-1], ldk or k.shape[-1], ldv or v.shape[-1], ldo or out.shape[-1] // sw
+    a.B, a.T, a.Tk, a.heads, a.dim_head = B, T, Tk, heads, dim_head
     a.lengths = _lib.ptr(lengths)
     a.scale = dim_head ** -0.5
+    return a
+
+
+def attention(q, k, v, out, B, T, heads, dim_head, lengths: Optional[torch.Tensor], ldq=None, ldk=None, ldv=None, Tk=0, ldo=None,
+              dtype=None):
+    lib = _lib.load()
+    a = _attn_params(q, k, v, out, B, T, heads, dim_head, lengths, ldq, ldk, ldv, Tk, ldo, dtype)
     _lib.check(lib.dn_attention(C.byref(a), _stream()), "dn_attention")
     return out
 
@@ -270,46 +280,51 @@ def _scratch(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=device)
 
 
-def attention_fwd_lse(q, k, v, out, B, T, heads, dim_head, lengths, ldq=None, ldk=None, ldv=None, dropout_p=0.0, seed=0):
-    """dn_attention that also keeps the per-query log-sum-exp [B, heads, T] for `attention_backward`.  dropout_p > 0: train-mode
-    dropout on the probabilities with the counter-hash mask of `seed` (64 bits)."""
+def attention_fwd_lse(q, k, v, out, B, T, heads, dim_head, lengths, ldq=None, ldk=None, ldv=None, dropout_p=0.0, seed=0, Tk=0, ldo=None,
+                      dtype=None, lse=None):
+    """dn_attention that also keeps the per-query log-sum-exp [B, heads, T] for `attention_backward` (written to `lse` when the caller
+    brings the buffer).  dropout_p > 0: train-mode dropout on the probabilities with the counter-hash mask of `seed` (64 bits).
+    Tk / ldo / dtype: see `attention`."""
     lib = _lib.load()
-    lse = torch.empty(B, heads, T, dtype=torch.float32, device=q.device)
-    a = _lib.AttnParams()
-    a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
-    a.ldq, a.ldk, a.ldv, a.ldo = ldq or q.shape[-1], ldk or k.shape[-1], ldv or v.shape[-1], out.shape[-1]
-    a.B, a.T, a.heads, a.dim_head = B, T, heads, dim_head
-    a.dtype = _code(q)
-    a.lengths = _lib.ptr(lengths)
-    a.scale = dim_head ** -0.5
+    lse = torch.empty(B, heads, T, dtype=torch.float32, device=q.device) if lse is None else lse
+    a = _attn_params(q, k, v, out, B, T, heads, dim_head, lengths, ldq, ldk, ldv, Tk, ldo, dtype)
     a.lse = lse.data_ptr()
     a.dropout_p, a.seed_lo, a.seed_hi = float(dropout_p), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
     _lib.check(lib.dn_attention(C.byref(a), _stream()), "dn_attention")
     return out, lse
 
 
-def attention_backward(q, k, v, out, dout, lse, B, T, heads, dim_head, lengths, ld_qkv=None, dropout_p=0.0, seed=0):
-    """-> (dq, dk, dv) as three column blocks of one [B*T, 3*heads*dim_head] tensor (reference :299-343 differentiated)."""
+def attention_backward(q, k, v, out, dout, lse, B, T, heads, dim_head, lengths, ld_qkv=None, dropout_p=0.0, seed=0, ldq=None, ldk=None,
+                       ldv=None, ldo=None, lddo=None, dtype=None, dq=None, dk=None, dv=None, lddq=None, lddk=None, lddv=None,
+                       delta=None):
+    """-> (dq, dk, dv) as three column blocks of one [B*T, 3*heads*dim_head] tensor (reference :299-343 differentiated).
+    ld_qkv: one row stride for q, k and v; ldq / ldk / ldv / ldo / lddo: each tensor's own (default: its width).  dq / dk / dv: the
+    caller's gradient tensors with row strides lddq / lddk / lddv (all three or none); delta: the caller's [B, heads, T] scratch.
+    dtype = DN_BF16X3: fp32 operands, dq / dk / dv (bf16, twice the stride in entries per row) written as split rows."""
     lib = _lib.load()
     hd = heads * dim_head
-    dqkv = torch.empty(B * T, 3 * hd, dtype=q.dtype, device=q.device)
-    delta = torch.empty(B, heads, T, dtype=torch.float32, device=q.device)
     a = _lib.AttnBwdParams()
+    a.dtype = _code(q) if dtype is None else dtype
+    if dq is None:
+        if dk is not None or dv is not None or a.dtype == _lib.DN_BF16X3:
+            raise ValueError("attention_backward: pass dq, dk and dv together (DN_BF16X3 always takes the caller's split-row tensors)")
+        dqkv = torch.empty(B * T, 3 * hd, dtype=q.dtype, device=q.device)
+        dq, dk, dv = dqkv[:, :hd], dqkv[:, hd:2 * hd], dqkv[:, 2 * hd:]
+        lddq = lddk = lddv = 3 * hd
+    delta = torch.empty(B, heads, T, dtype=torch.float32, device=q.device) if delta is None else delta
     a.q, a.k, a.v, a.out, a.dout = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr()
-    es = dqkv.element_size()
-    a.dq, a.dk, a.dv = dqkv.data_ptr(), dqkv.data_ptr() + hd * es, dqkv.data_ptr() + 2 * hd * es
-    ld = ld_qkv or q.shape[-1]
-    a.ldq = a.ldk = a.ldv = ld
-    a.ldo, a.lddo = out.shape[-1], dout.shape[-1]
-    a.lddq = a.lddk = a.lddv = 3 * hd
+    a.dq, a.dk, a.dv = dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
+    a.ldq, a.ldk, a.ldv = ldq or ld_qkv or q.shape[-1], ldk or ld_qkv or k.shape[-1], ldv or ld_qkv or v.shape[-1]
+    a.ldo, a.lddo = ldo or out.shape[-1], lddo or dout.shape[-1]
+    sw = 2 if a.dtype == _lib.DN_BF16X3 else 1
+    a.lddq, a.lddk, a.lddv = lddq or dq.shape[-1] // sw, lddk or dk.shape[-1] // sw, lddv or dv.shape[-1] // sw
     a.B, a.T, a.heads, a.dim_head = B, T, heads, dim_head
-    a.dtype = _code(q)
     a.lengths = _lib.ptr(lengths)
     a.scale = dim_head ** -0.5
     a.lse, a.delta = lse.data_ptr(), delta.data_ptr()
     a.dropout_p, a.seed_lo, a.seed_hi = float(dropout_p), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
     _lib.check(lib.dn_attention_backward(C.byref(a), _stream()), "dn_attention_backward")
-    return dqkv[:, :hd], dqkv[:, hd:2 * hd], dqkv[:, 2 * hd:]
+    return dq, dk, dv
 
 
 def gate_forward(h, res, T, gamma_beta=None, gb_half=0):

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import diffnorm_oracle as O
+from attention_ref import attention_ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -202,11 +203,7 @@ def test_attention_f16(ops, dh, heads, B, T):
     lens = torch.tensor(([T, T // 3, 0] * 2)[:B], dtype=torch.int32)
     out = torch.empty(B * T, hd, device=DEV, dtype=torch.float16)
     ops_.attention(act(q.view(-1, hd)), act(k.view(-1, hd)), act(v.view(-1, hd)), out, B, T, heads, dh, lens.to(DEV))
-    qr, kr, vr = (f16r(z).view(B, T, heads, dh).transpose(1, 2) for z in (q, k, v))
-    sim = qr @ kr.transpose(-1, -2) * dh ** -0.5
-    mask = O.lengths_to_mask(lens.long(), T)
-    sim = sim.masked_fill(~mask.view(B, 1, 1, T), -torch.finfo(sim.dtype).max)
-    want = (sim.softmax(-1) @ vr).transpose(1, 2).reshape(B, T, hd)
+    want, _ = attention_ref(f16r(q), f16r(k), f16r(v), heads, lens.long())
     assert maxerr(out.float().cpu().view(B, T, hd), want) < 3e-3  # P and the output rounded to half (bf16 kernel: 2e-2)
 
 
@@ -229,15 +226,9 @@ def test_attention_on_eight_waves_is_bit_identical(ops, hip_option, half, dh, he
     for on in (0, 1):
         hip_option("attn_waves8", on)
         out = torch.full((B * T, 2 * hd if half == "x3" else hd), float("nan"), device=DEV, dtype=torch.bfloat16 if half == "x3" else tdt)  # (x3: split rows)
-        p = _lib.AttnParams()
         qa, ka, va = (z.view(-1, hd).to(DEV, tdt).contiguous() for z in (q, k, v))
-        p.q, p.k, p.v, p.out = qa.data_ptr(), ka.data_ptr(), va.data_ptr(), out.data_ptr()
-        p.ldq = p.ldk = p.ldv = p.ldo = hd
-        p.B, p.T, p.Tk, p.heads, p.dim_head = B, T, Tk, heads, dh
-        p.dtype = {"f16": _lib.DN_F16, "bf16": _lib.DN_BF16, "x3": _lib.DN_BF16X3}[half]
-        p.lengths = lens.data_ptr() if lens is not None else None
-        p.scale = dh ** -0.5
-        _lib.check(_lib.load().dn_attention(C.byref(p), ops_._stream()), "dn_attention")
+        ops_.attention(qa, ka, va, out, B, T, heads, dh, lens, Tk=Tk, ldo=hd,
+                       dtype={"f16": _lib.DN_F16, "bf16": _lib.DN_BF16, "x3": _lib.DN_BF16X3}[half])
         torch.cuda.synchronize()
         outs.append(out.cpu())
     assert torch.isfinite(outs[1].float()).all()

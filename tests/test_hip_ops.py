@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import diffnorm_oracle as O
+from attention_ref import attention_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -680,20 +681,13 @@ def test_attention(ops, dtype, heads, dh, B, T, lens):
     hd = heads * dh
     q, k, v = seeded((B, T, hd), 1), seeded((B, T, hd), 2), seeded((B, T, hd), 3)
     lens_t = torch.tensor(lens)
-    mask = O.lengths_to_mask(lens_t, T)
     rnd = bf16r if dtype == "bf16" else (lambda z: z)
-
-    def ref(q, k, v):
-        qh, kh, vh = (z.view(B, T, heads, dh).transpose(1, 2) for z in (q, k, v))
-        sim = torch.matmul(qh, kh.transpose(-1, -2)) * dh ** -0.5
-        sim = sim.masked_fill(~mask.view(B, 1, 1, T), -torch.finfo(sim.dtype).max)
-        return torch.matmul(sim.softmax(-1), vh).transpose(1, 2).reshape(B, T, hd)
 
     qkv = act(torch.cat([q, k, v], dim=-1).view(B * T, 3 * hd), dtype)
     out = torch.empty(B * T, hd, device=DEV, dtype=qkv.dtype)
     ops_.attention(qkv, qkv[:, hd:], qkv[:, 2 * hd:], out, B, T, heads, dh, lens_t.to(DEV).int(), ldq=3 * hd, ldk=3 * hd, ldv=3 * hd)
     got = out.float().cpu().view(B, T, hd)
-    want = ref(rnd(q), rnd(k), rnd(v))
+    want, _ = attention_ref(rnd(q), rnd(k), rnd(v), heads, lens_t)
     # bf16: P is rounded to bf16 before PV and the output is stored bf16
     assert maxerr(got, want) < (2e-2 if dtype == "bf16" else 2e-5)
 

@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as F
 
 import diffnorm_oracle as O
+from attention_ref import attention_ref
 from dropout_mask import dropout_keep_mask
 
 pytestmark = pytest.mark.gpu
@@ -44,18 +45,6 @@ def ops():
     return ops, packing, _lib
 
 
-def ref_attention(q, k, v, lens, heads):
-    """Attend.forward non-flash (latent_module.py:299-343) in float64, [B,T,h*d] layout."""
-    B, T, hd = q.shape
-    d = hd // heads
-    split = lambda t: t.view(B, T, heads, d).transpose(1, 2)
-    sim = torch.einsum("bhid,bhjd->bhij", split(q), split(k)) * d ** -0.5
-    mask = O.lengths_to_mask(lens, T)
-    sim = sim.masked_fill(~mask.view(B, 1, 1, T), -torch.finfo(sim.dtype).max)
-    out = torch.einsum("bhij,bhjd->bhid", sim.softmax(dim=-1), split(v))
-    return out.transpose(1, 2).reshape(B, T, hd)
-
-
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 @pytest.mark.parametrize("heads,dh,B,T,lens", [(4, 16, 3, 40, [40, 23, 1]), (2, 64, 2, 150, [150, 77]), (8, 96, 2, 200, [130, 200]),
                                                (2, 64, 1, 300, [257]), (2, 32, 2, 64, [64, 0])])
@@ -66,7 +55,7 @@ def test_attention_backward(ops, dtype, heads, dh, B, T, lens):
     q, k, v, do = (rnd(seeded((B, T, hd), 50 + i)) for i in range(4))
     lens_t = torch.tensor(lens)
     qd, kd, vd = (t.double().requires_grad_(True) for t in (q, k, v))
-    want_o = ref_attention(qd, kd, vd, lens_t, heads)
+    want_o, _ = attention_ref(qd, kd, vd, heads, lens_t)
     want_o.backward(do.double())
     qkv = act(torch.cat([q, k, v], dim=-1).view(B * T, 3 * hd), dtype)
     out = torch.empty(B * T, hd, dtype=qkv.dtype, device=DEV)
