@@ -35,13 +35,14 @@ const OptDef kOpts[dn::OPT_COUNT] = {
     {"wgrad_groups", "DN_WGRAD_GROUPS", nullptr},          // 0: one weight-gradient launch per WaveNet block
     {"qkv_192", "DN_QKV_192", nullptr},                    // 1: the q/kv projection (N = 1536 = 8 x 192) on the 256 x 192 tile (A/B timing)
     {"mid2", "DN_MID2", nullptr},                          // bit 0 / bit 1: the q/kv / GEGLU projection on the 256 x 128 two-workgroups-per-CU tile
-    {"wgrad_stages", "DN_WGRAD_STAGES", nullptr},          // 5: the weight-gradient kernel on a 160 KiB ring of five stages (default 4 stages = 128 KiB)
+    {"wgrad_stages", "DN_WGRAD_STAGES", nullptr},          // 5: the weight-gradient kernel on a 160 KiB ring of five stages (default 4 stages = 128 KiB); 2: the split-operand one on two stages (default 3 = 144 KiB)
     {"tile_192", "DN_TILE_192", nullptr},                  // 0: never choose the 256 x 192 tile by score (default: where a lone launch fills the chip better on it)
     {"fused_geglu", "DN_FUSED_GEGLU", nullptr},            // 0: training forward runs the GEGLU as a pass over the projection's output (default: in its epilogue)
     {"attn_waves8", "DN_ATTN_WAVES8", nullptr},            // 0: attention (2-byte modes) on four waves of 32 queries per workgroup (default: eight waves of 16)
     {"cond_stream", "DN_COND_STREAM", nullptr},            // 0: training: the data gradient of the conditioning projection from a transposed copy (default: the master matrix streamed as it lies)
     {"wgrad_k192", "DN_WGRAD_K192", nullptr},              // 1: the weight-gradient kernel on 192 k-columns per tile where that fills the chip better (default off: faster alone, slower beside the data-gradient chain)
     {"wgrad_prio", "DN_WGRAD_PRIO", nullptr},              // 1: the weight-gradient stream at the lowest priority (read when the stream is created; measured level, default off)
+    {"wgrad_tn_x3", "DN_WGRAD_TN_X3", nullptr},            // split-operand (bf16x3) weight gradients: 0 from transposed copies (default 1: straight from the row-major split rows) ("wgrad_tn" covers the 2-byte modes only)
 };
 std::atomic<int> g_opt[dn::OPT_COUNT];
 std::atomic<int> g_opt_gen{0};

@@ -441,7 +441,9 @@ int weight_grad(const Ctx& c0, const WgTap* taps, int n_taps, int cin, const voi
   // bf16: straight from the row-major operands (wgrad_tn.hip: transposing LDS reads, no channel-major copies).  Slices of the
   // frames until about 160 tile-slices (at least 256 frames each), partial sums in the scratch the transposed copies would use;
   // a contraction that has its tiles anyway accumulates straight into the gradient.  DN_WGRAD_TN=0: the transposed-copies form.
-  const bool use_tn = c.es == 2 && option_or(OPT_WGRAD_TN, 1) != 0;
+  // bf16x3: the same on split rows (wgrad_tn_x3_kernel), option wgrad_tn_x3; its other arm is the transposed-copies form below.
+  const bool tn_x3 = c.dtype == DN_BF16X3 && option_or(OPT_WGRAD_TN_X3, WGRAD_TN_X3_DEFAULT) != 0;
+  const bool use_tn = tn_x3 || (c.es == 2 && option_or(OPT_WGRAD_TN, 1) != 0);
   const bool grouped = option_or(OPT_WGRAD_GROUPS, 1) != 0;  // 0: one launch per block also in the row-major form (A/B timing)
   if (grp && grp->groups > 1 && (!use_tn || !grouped)) {  // the transposed-copies form has no groups: one call per group
     for (int g = 0; g < grp->groups; ++g) {
@@ -463,7 +465,8 @@ int weight_grad(const Ctx& c0, const WgTap* taps, int n_taps, int cin, const voi
     const void* xs[DN_MAX_TERMS]; int ldx[DN_MAX_TERMS], sh[DN_MAX_TERMS];
     for (int j = 0; j < n_taps; ++j) { xs[j] = taps[j].x; ldx[j] = taps[j].ldx; sh[j] = taps[j].shift; }
     float* part = slices > 1 ? reinterpret_cast<float*>(base) : nullptr;
-    int rc = wgrad_tn_launch(dy, lddy, cout, xs, ldx, sh, n_taps, cin, c.B, c.T, slices, part, slices > 1 ? nullptr : grad, c.s, tag, grp);
+    int rc = (tn_x3 ? wgrad_tn_x3_launch : wgrad_tn_launch)(dy, lddy, cout, xs, ldx, sh, n_taps, cin, c.B, c.T, slices, part,
+                                                            slices > 1 ? nullptr : grad, c.s, tag, grp);
     for (int g = 0; g < groups && rc == DN_OK && slices > 1; ++g)
       rc = dn_wgrad_reduce(part + (size_t)g * slices * cout * n_total, slices, cout, n_total, rows_w, n_taps,
                            grad + (grp ? g * grp->grad_gstride : 0), padn(cout), padk(cin), c.s);

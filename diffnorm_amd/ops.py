@@ -202,30 +202,42 @@ def convert_rows(src, dst, C_):
 
 
 def conv_weight_grad_tn(x: torch.Tensor, dy: torch.Tensor, T: int, cin: int, cout: int, shifts: Sequence[int],
-                        slices: int = 1) -> torch.Tensor:
+                        slices: int = 1, dtype: str = "bf16", grad: torch.Tensor = None) -> torch.Tensor:
     """conv_weight_grad without transposed operand copies (dn_conv_weight_grad_tn, bf16): the contraction over frames reads the
-    row-major x / dy through transposing LDS reads.  x [B*T, ldx], dy [B*T, lddy] with zero pad columns.  -> fp32 [taps, cout, cin]."""
+    row-major x / dy through transposing LDS reads.  x [B*T, ldx], dy [B*T, lddy] with zero pad columns.  -> fp32 [taps, cout, cin].
+
+    dtype "bf16x3" (dn_conv_weight_grad_tn_x3): x and dy are split rows in activation order (packing.split_rows of fp32 [B*T, ld],
+    ld a multiple of 32: bf16 tensors of 2 ld entries per row).  grad: a packed fp32 [taps, padn(cout), padk(cin)] gradient to
+    accumulate into instead of zeros (returned whole)."""
     import ctypes as C_
 
     lib = _lib.load()
+    assert dtype in ("bf16", "bf16x3"), dtype
+    x3 = dtype == "bf16x3"
     assert x.dtype == dy.dtype == torch.bfloat16 and x.dim() == 2 and dy.dim() == 2 and x.is_contiguous() and dy.is_contiguous()
+    fn, name = (lib.dn_conv_weight_grad_tn_x3, "dn_conv_weight_grad_tn_x3") if x3 else (lib.dn_conv_weight_grad_tn, "dn_conv_weight_grad_tn")
+    per = 2 if x3 else 1  # bf16 entries per element of a row
+    assert x.shape[1] % per == 0 and dy.shape[1] % per == 0
+    ldx, lddy = x.shape[1] // per, dy.shape[1] // per
     M = x.shape[0]
     B = M // T
     n_taps = len(shifts)
     rows_w, Np, Kp = (cin + 127) // 128 * 128, (cout + 127) // 128 * 128, (cin + 63) // 64 * 64
     xs = (C_.c_void_p * n_taps)(*([x.data_ptr()] * n_taps))
-    ld = (C_.c_int32 * n_taps)(*([x.shape[1]] * n_taps))
+    ld = (C_.c_int32 * n_taps)(*([ldx] * n_taps))
     sh = (C_.c_int32 * n_taps)(*[int(s_) for s_ in shifts])
-    grad = torch.zeros((n_taps, Np, Kp), device=x.device, dtype=torch.float32)
+    whole = grad is not None
+    if whole:
+        assert grad.dtype == torch.float32 and tuple(grad.shape) == (n_taps, Np, Kp) and grad.is_contiguous() and grad.device == x.device
+    else:
+        grad = torch.zeros((n_taps, Np, Kp), device=x.device, dtype=torch.float32)
     if slices == 1:
-        _lib.check(lib.dn_conv_weight_grad_tn(dy.data_ptr(), dy.shape[1], cout, xs, ld, sh, n_taps, cin, B, T, 1, None, grad.data_ptr(), _stream()),
-                   "dn_conv_weight_grad_tn")
+        _lib.check(fn(dy.data_ptr(), lddy, cout, xs, ld, sh, n_taps, cin, B, T, 1, None, grad.data_ptr(), _stream()), name)
     else:
         part = torch.empty((slices, cout, n_taps * rows_w), device=x.device, dtype=torch.float32)
-        _lib.check(lib.dn_conv_weight_grad_tn(dy.data_ptr(), dy.shape[1], cout, xs, ld, sh, n_taps, cin, B, T, slices, part.data_ptr(), None, _stream()),
-                   "dn_conv_weight_grad_tn")
+        _lib.check(fn(dy.data_ptr(), lddy, cout, xs, ld, sh, n_taps, cin, B, T, slices, part.data_ptr(), None, _stream()), name)
         _lib.check(lib.dn_wgrad_reduce(part.data_ptr(), slices, cout, n_taps * rows_w, rows_w, n_taps, grad.data_ptr(), Np, Kp, _stream()), "dn_wgrad_reduce")
-    return grad[:, :cout, :cin]
+    return grad if whole else grad[:, :cout, :cin]
 
 
 def conv_weight_grad(x: torch.Tensor, dy: torch.Tensor, T: int, cin: int, cout: int, shifts: Sequence[int],

@@ -494,6 +494,13 @@ int dn_add_broadcast(const float* src, float* dst, int32_t C, int32_t ld, int32_
 int dn_conv_weight_grad_tn(const void* dy, int32_t lddy, int32_t cout, const void* const* x, const int32_t* ldx, const int32_t* shift,
                            int32_t n_taps, int32_t cin, int32_t B, int32_t T, int32_t slices, float* part, float* grad, void* stream);
 
+/* The same from DN_BF16X3 split rows (autograd of CausalConv1d latent_module.py:476-485 / nn.Linear in split-operand arithmetic):
+ * dY and every X_tap are split rows in activation order ([hi | lo] per 32 elements); lddy, ldx, cin and cout count 4-byte elements
+ * and every ld is a multiple of 32 (pad columns may hold anything).  Per fragment pair three bf16 MFMAs into one fp32 accumulator,
+ * x_lo dy_hi + x_hi dy_lo + x_hi dy_hi (lo lo dropped).  part / grad / slices as in dn_conv_weight_grad_tn (plain fp32).        */
+int dn_conv_weight_grad_tn_x3(const void* dy, int32_t lddy, int32_t cout, const void* const* x, const int32_t* ldx, const int32_t* shift,
+                              int32_t n_taps, int32_t cin, int32_t B, int32_t T, int32_t slices, float* part, float* grad, void* stream);
+
 /* dn_transpose_pad for fp32 operands (exact-fp32 mode); chunk a multiple of 32. */
 int dn_transpose_pad_f32(const float* src, int32_t ld, int32_t B, int32_t T, int32_t C, int32_t front, int32_t Tp, float* dst,
                          int32_t rows, int32_t rows_total, int32_t row0, int32_t chunk, void* stream);
@@ -719,7 +726,8 @@ int dn_version(void);
  * start value.  Names: "taps_inner" (DN_TAPS_INNER: K order of a causal conv's taps -- 0 term-outer everywhere, 1 tap-inner on
  * the 256-row tiles [default], 2 tap contractions routed to those tiles by SHAPE whatever the batch size: a batch and its shards
  * then agree bit for bit), "fuse_norm" (DN_FUSE_NORM), "no_split_norm" (DN_NO_SPLIT_NORM), "kblock" (DN_KBLOCK: 0 never / 1 always
- * K-blocked operands), "wgrad_stream", "wgrad_tn", "wgrad_groups" (DN_WGRAD_*: A/B switches of the weight-gradient path).
+ * K-blocked operands), "wgrad_stream", "wgrad_tn", "wgrad_groups" (DN_WGRAD_*: A/B switches of the weight-gradient path),
+ * "wgrad_tn_x3" (DN_WGRAD_TN_X3: DN_BF16X3 weight gradients from the row-major split rows; "wgrad_tn" is the 2-byte modes only).
  * dn_get_option: *is_set = 0 when the option is neither set nor in the environment (the library's built-in choice applies). */
 #define DN_OPTION_DEFAULT (-2147483647 - 1)
 int dn_set_option(const char* name, int32_t value);
