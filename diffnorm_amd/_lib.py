@@ -134,6 +134,14 @@ class EpsTrainBatch(C.Structure):
                 ("dropout_seed_lo", C.c_uint32), ("dropout_seed_hi", C.c_uint32), ("pad_", C.c_int32)]
 
 
+REPACK_CONVERT, REPACK_KBLOCK, REPACK_COPY, REPACK_SUM = range(4)
+
+
+class RepackDesc(C.Structure):
+    _fields_ = [("src", C.c_int64), ("dst", C.c_void_p), ("kind", C.c_int32), ("mats", C.c_int32), ("rows", C.c_int32), ("K", C.c_int32),
+                ("count", C.c_int32), ("pad_", C.c_int32), ("stride", C.c_int64)]
+
+
 # every symbol include/diffnorm_hip.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _u64, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t
 SYMBOLS = {
@@ -192,6 +200,7 @@ SYMBOLS = {
     "dn_transpose_weights": (C.c_int, [_vp, _i32, _i32, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp]),
     "dn_split_rows": (C.c_int, [_vp, _i64, _vp, _i32, _vp]),
     "dn_transpose_slices": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "dn_repack_weights": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     "dn_wgrad_reduce": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "dn_conv_weight_grad_tn": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "dn_conv_weight_grad_tn_x3": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
@@ -216,6 +225,7 @@ SYMBOLS = {
     "dn_eps_forward_cond_ex": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _sz, _i32, _vp, _i32, _i32, _vp]),
     "dn_eps_cond_time_table_workspace_bytes": (_sz, [_vp, _i32]),
     "dn_eps_cond_time_table": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "dn_eps_weights_changed": (C.c_int, [_vp]),
     "dn_vae_create": (C.c_int, [C.POINTER(VaeConfig), C.POINTER(_vp), _i32, C.POINTER(_vp)]),
     "dn_vae_destroy": (None, [_vp]),
     "dn_vae_workspace_bytes": (_sz, [_vp, _i32, _i32]),

@@ -589,6 +589,13 @@ extern "C" int dn_eps_forward(DnEps* m, const float* x, const int32_t* t, const 
   return eps_core(m, x, b.gb, shared_t ? 0 : m->n_row, lengths, B, T, eps_out, b, s);
 }
 
+extern "C" int dn_eps_weights_changed(DnEps* m) {
+  DN_CHECK_ARG(m, "dn_eps_weights_changed: null engine");
+  m->table_ws = nullptr;  // DN_LOOP_KEEP_TABLE: the next call rebuilds the conditioning table
+  m->table_rows = 0;
+  return DN_OK;
+}
+
 static size_t ddim_extra_bytes(const DnEps* m, int B, int T, int start_step) {
   const size_t C = (size_t)m->cfg.dim * m->cfg.cond_mult;
   return (size_t)B * T * m->cfg.latent * 4 + (size_t)start_step * (m->n_row + C) * 4 + (size_t)start_step * m->n_cond * 4 +

@@ -67,6 +67,56 @@ class _Engine:
     def weight_bytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self.tensors)
 
+    _kind = None     # "eps" / "vae": which of packing's inference lists `self.tensors` is
+    _repack = None   # (layout key, device-resident DnRepackDesc array, number of descriptors, bytes read + written)
+
+    def _repack_descs(self, train_engine):
+        """The descriptors of dn_repack_weights for `train_engine`'s layout into this engine's packed tensors, built once per layout
+        and kept on the device.  The plan is checked against the tensors it will write (count, shape, dtype) and the master
+        buffer it will read, so a training engine of another configuration is refused here, on the host."""
+        key = (tuple(train_engine.offsets), int(train_engine.n_params))
+        if self._repack is not None and self._repack[0] == key:
+            return self._repack
+        plan = packing.repack_plan(train_engine.entries, train_engine.offsets, self.dtype, kind=self._kind)
+        if len(plan.shapes) != len(self.tensors):
+            raise ValueError(f"refresh_from: the training engine's layout gives {len(plan.shapes)} packed tensors, this engine has {len(self.tensors)}")
+        for i, (s, t) in enumerate(zip(plan.shapes, self.tensors)):
+            if s is not None and (tuple(t.shape) != tuple(s[0]) or t.dtype != s[1]):
+                raise ValueError(f"refresh_from: packed tensor {i} is {tuple(t.shape)} {t.dtype}, the training engine's layout gives {s[0]} {s[1]}")
+        descs = (_lib.RepackDesc * len(plan.items))()
+        moved = 0
+        for d, it in zip(descs, plan.items):
+            n = it.mats * it.rows * it.K
+            reads = n * max(1, it.count)
+            assert 0 <= it.src and it.src + (reads if it.count else n) <= train_engine.n_params, it
+            t = self.tensors[it.tensor]
+            out_bytes = n * (4 if it.kind in (_lib.REPACK_COPY, _lib.REPACK_SUM) or not packing._is16(self.dtype) else 2)
+            assert it.dst_byte + out_bytes <= t.numel() * t.element_size(), it
+            # the alignment contract of include/diffnorm_hip.h: the kernel's 16-byte accesses assume it (only COPY falls back)
+            dst = t.data_ptr() + it.dst_byte
+            assert it.src % 4 == 0, it
+            if it.kind in (_lib.REPACK_CONVERT, _lib.REPACK_KBLOCK):
+                assert n % 32 == 0 and it.K % 32 == 0 and dst % 128 == 0, it
+            elif it.kind == _lib.REPACK_SUM:
+                assert it.K % 4 == 0 and it.stride % 4 == 0 and it.mats == it.rows == 1 and dst % 16 == 0, it
+            d.src, d.dst, d.kind, d.mats, d.rows, d.K, d.count, d.stride = it.src, dst, it.kind, it.mats, it.rows, it.K, it.count, it.stride
+            moved += reads * 4 + out_bytes
+        dev = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(self.device)
+        self._repack = (key, dev, len(plan.items), moved)
+        return self._repack
+
+    def _refresh_from(self, train_engine):
+        master = train_engine.master
+        if master.device != self.device or master.dtype != torch.float32 or not master.is_contiguous():
+            raise ValueError("refresh_from: the training engine's master buffer must be a contiguous fp32 tensor on this engine's device")
+        _, descs, n, _ = self._repack_descs(train_engine)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.dn_repack_weights(master.data_ptr(), descs.data_ptr(), n, self.dtype, _lib.current_stream()), "dn_repack_weights")
+
+    def refresh_bytes(self) -> int:
+        """Bytes the last refresh_from's layout reads from the master plus writes to the packed tensors (0 before the first)."""
+        return 0 if self._repack is None else self._repack[3]
+
 
 class EpsEngine(_Engine):
     """eps-predictor `Model` (reference latent_module.py:709-876) on the GPU."""
@@ -87,6 +137,28 @@ class EpsEngine(_Engine):
         if getattr(self, "handle", None) and self.handle.value:
             self.lib.dn_eps_destroy(self.handle)
             self.handle = None
+
+    _kind = "eps"
+
+    def refresh_from(self, train_engine):
+        """Rewrites this engine's packed weights from `train_engine`'s (training.EpsTrainEngine) fp32 master buffer on the device
+        (dn_repack_weights into the existing `self.tensors`): bit-identical to `EpsEngine(train_engine.state_dict(), ...)` in this
+        engine's dtype, whatever the training dtype.  Stream-ordered on the current stream, no host synchronisation (the first call
+        for a layout builds the descriptors and uploads them once).  The device addresses do not change.  What the engine derived
+        from the weights, and what becomes of it:
+
+        * the conditioning table of a chain (dn_ddim_loop / dn_ddpm_loop: the time-conditioning MLP and the stacked FiLM /
+          adaptive-norm projections of every timestep, in the loop's workspace), which a `keep_table=True` continuation reuses:
+          forgotten (dn_eps_weights_changed) -- the next call rebuilds it whatever `keep_table` says;
+        * the captured hipGraph of the loop's step: kept.  It holds kernel launches over addresses (packed tensors, workspace,
+          the conditioning table's rows), no values; every table it reads is rebuilt from the new weights before it is replayed;
+        * the time table of a prompted chain (dn_eps_cond_time_table) lives for one `guided_ddim_chain` call only, and the
+          prompt-conditioned engine has no training engine: refused here;
+        * nothing else: the sinusoidal table and the placeholders do not depend on the parameters, workspaces hold activations."""
+        if self.conditional:
+            raise NotImplementedError("refresh_from covers the unconditional eps-predictor (the prompt-conditioned model has no training engine)")
+        self._refresh_from(train_engine)
+        _lib.check(self.lib.dn_eps_weights_changed(self.handle), "dn_eps_weights_changed")
 
     def workspace_bytes(self, B: int, T: int) -> int:
         return int(self.lib.dn_eps_workspace_bytes(self.handle, B, T))
@@ -293,6 +365,15 @@ class VaeEngine(_Engine):
         if getattr(self, "handle", None) and self.handle.value:
             self.lib.dn_vae_destroy(self.handle)
             self.handle = None
+
+    _kind = "vae"
+
+    def refresh_from(self, train_engine):
+        """Rewrites this engine's packed weights from `train_engine`'s (training.VaeTrainEngine: f32, bf16 or bf16x3) fp32 master
+        buffer on the device: bit-identical to `VaeEngine(train_engine.state_dict(), ...)` in this engine's dtype.  Stream-ordered,
+        no host synchronisation, same device addresses (see EpsEngine.refresh_from).  The VAE engine derives nothing from its
+        weights (DnVae holds the table's pointers only; no graph, no table), so there is nothing to invalidate."""
+        self._refresh_from(train_engine)
 
     def workspace_bytes(self, B: int, T: int) -> int:
         return int(self.lib.dn_vae_workspace_bytes(self.handle, B, T))

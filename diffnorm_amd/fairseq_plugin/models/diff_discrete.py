@@ -18,7 +18,8 @@ def _load_speech_decoder(args):
 
         models, _, _ = fairseq.checkpoint_utils.load_model_ensemble_and_task([path])
         return models[0]
-    vae = SpeechVAEEncoderDecoder(dim=getattr(args, "feature_dim", 768), latent_dim=args.latent_dim, dtype=dtype)
+    vae = SpeechVAEEncoderDecoder(dim=getattr(args, "feature_dim", 768), latent_dim=args.latent_dim, dtype=dtype,
+                                  sample_dtype=getattr(args, "hip_sample_dtype", None))
     if path:
         state = torch.load(path, map_location="cpu", weights_only=False)
         sd = state["model"] if "model" in state else state
@@ -57,7 +58,8 @@ class DiffDiscreteModel(FairseqEncoderModel):
         vae = speech_decoder.encoder
         z = vae.latent_channels() if hasattr(vae, "latent_channels") else args.latent_dim
         encoder = LatentDiscreteModel(speech_decoder, getattr(args, "denoiser_dim", 512), z, timesteps=getattr(args, "diffusion_timesteps", 200),
-                                      multitask=args.multitask, dtype=getattr(args, "hip_dtype", "bf16"))
+                                      multitask=args.multitask, dtype=getattr(args, "hip_dtype", "bf16"),
+                                      sample_dtype=getattr(args, "hip_sample_dtype", None))
         encoder.train_on_move = is_training_run(args)  # the training engine (one flat parameter) comes up with model.to(device)
         return cls(args, encoder)
 
@@ -71,6 +73,7 @@ class DiffDiscreteModel(FairseqEncoderModel):
         parser.add_argument("--diffusion-timesteps", type=int, default=200,
                             help="schedule length (upstream hard-codes 200 at diff_discrete.py:84)")
         parser.add_argument("--hip-dtype", default="bf16", choices=["bf16", "f16", "bf16x3", "f32"], help="MFMA arithmetic of the HIP engine (f16: IEEE-half operands, the 2-byte mode inside the 1e-2 budget, inference only; bf16: fastest, also the fast training mode; bf16x3: split-operand bf16, fp32-class results, inference only; f32: exact)")
+        parser.add_argument("--hip-sample-dtype", default=None, choices=["bf16", "f16", "bf16x3", "f32"], help="MFMA arithmetic of the sampling / inference engine when it differs from the training one (default: the same as --hip-dtype): a model in training keeps --hip-dtype for its updates and samples (validation) in this mode, its packed weights refreshed on the device after every update")
 
     def max_positions(self):
         return self.encoder.max_positions()

@@ -55,6 +55,13 @@ def label_smoothed_nll_loss(lprobs, target, epsilon, ignore_index=None, reduce=T
     return (1.0 - epsilon - eps_i) * nll + eps_i * smooth, nll
 
 
+def _sample_dtype(sample_dtype):
+    """`sample_dtype` of the module constructors: None (= the module's `dtype`) or an inference arithmetic mode."""
+    if sample_dtype is not None:
+        engine._dtype_code(sample_dtype)  # raises on an unknown mode
+    return sample_dtype
+
+
 class _ParamTree(nn.Module):
     """Owns parameters under dotted state-dict keys by growing anonymous sub-modules on demand."""
 
@@ -117,14 +124,25 @@ class _ParamTree(nn.Module):
         if not (want - set(got)):
             self._train_engine.load_state_dict({k: got[k] for k in want})
 
+    sample_dtype = None  # arithmetic of the inference engine when it differs from the training / default one (`arith`)
+
+    @property
+    def engine_dtype(self):
+        """The arithmetic `engine()` builds the inference engine in: `sample_dtype`, or the module's `dtype` when it is None."""
+        return self.arith if self.sample_dtype is None else self.sample_dtype
+
     def engine(self):
-        """The inference engine over the current parameters (`_build_engine(sd)`: the subclass's engine class), rebuilt when they
-        have changed: with a training engine, from its master buffer once an update has happened."""
+        """The inference engine over the current parameters (`_build_engine(sd)`: the subclass's engine class, in `engine_dtype`).
+        With a training engine: built once from its master buffer; after every later update the SAME engine's packed tensors are
+        rewritten on the device (`refresh_from`: the result is bit-identical to a rebuild, the device addresses and captured
+        graphs stay).  Without one: rebuilt when a parameter has changed."""
         if self._train_engine is not None:
             key = ("train", self._train_engine.update_count)
-            if self._engine is None or self._engine_key != key:
+            if self._engine is None:
                 self._engine = self._build_engine(self._train_engine.state_dict())
-                self._engine_key = key
+            elif self._engine_key != key:
+                self._engine.refresh_from(self._train_engine)
+            self._engine_key = key
             return self._engine
         key = self._state_key()
         if self._engine is None or self._engine_key != key:
@@ -143,7 +161,7 @@ class Model(_ParamTree):
 
     def __init__(self, dim, latent_dim, *, depth=12, dim_head=64, heads=8, ff_mult=4, wavenet_layers=8, wavenet_stacks=4,
                  dim_cond_mult=4, use_flash_attn=False, dim_prompt=None, num_latents_m=64, resampler_depth=2,
-                 cond_drop_prob=0., condition_on_prompt=False, dtype="bf16", seed=0):
+                 cond_drop_prob=0., condition_on_prompt=False, dtype="bf16", seed=0, sample_dtype=None):
         super().__init__()
         if ff_mult != 4:
             raise NotImplementedError("the engine packs ff_mult = 4 (the only value the recipe uses)")
@@ -155,7 +173,7 @@ class Model(_ParamTree):
         self.cfg = synthetic.eps_config(dim, latent_dim, depth, heads, dim_head, wavenet_layers, wavenet_stacks, dim_cond_mult,
                                         dim_prompt=dim_prompt if condition_on_prompt else 0, num_latents_m=num_latents_m,
                                         resampler_depth=resampler_depth)
-        self.arith = dtype
+        self.arith, self.sample_dtype = dtype, _sample_dtype(sample_dtype)
         self._adopt(synthetic.random_eps_state_dict(self.cfg, seed))
         self._attach("pos_embed._float_tensor", torch.zeros(1), buffer=True)  # key present upstream (:774-779)
         if self.condition_on_prompt:
@@ -165,7 +183,7 @@ class Model(_ParamTree):
 
     def _build_engine(self, sd) -> engine.EpsEngine:
         sd = {k: v for k, v in sd.items() if not k.endswith("._float_tensor")}
-        return engine.EpsEngine(sd, self.cfg, dtype=self.arith, device=self.device)
+        return engine.EpsEngine(sd, self.cfg, dtype=self.engine_dtype, device=self.device)
 
     def forward(self, x, times, prompt=None, prompt_mask=None, input_mask=None, cond=None, cond_drop_prob=None, drop_mask=None):
         """x [B,T,latent], times [B] (raw integer steps), input_mask [B,T] bool -> eps_hat [B,T,latent].  With
@@ -341,10 +359,10 @@ class SpeechVAEEncoderDecoder(_ParamTree):
     """reference latent_module.py:1035-1142 (WaveNet encoder -> diagonal Gaussian -> WaveNet + transformer decoder
     -> 1004-way unit logits).  `latent_dim` is the upstream constructor flag (16 / 32 / 128)."""
 
-    def __init__(self, dim=768, latent_dim=16, dtype="bf16", seed=1):
+    def __init__(self, dim=768, latent_dim=16, dtype="bf16", seed=1, sample_dtype=None):
         super().__init__()
         self.dim, self.latent_dim = dim, latent_dim
-        self.arith = dtype
+        self.arith, self.sample_dtype = dtype, _sample_dtype(sample_dtype)
         self.train_on_move = False  # the plugin's build_model sets it for a training run: see _apply
         self.attn_dropout = 0.1  # Attention(dropout=0.1) of the decoder transformer (:668); active in train() mode with the training engine
         self._adopt(synthetic.random_vae_state_dict(dim, latent_dim, seed=seed))
@@ -389,7 +407,7 @@ class SpeechVAEEncoderDecoder(_ParamTree):
         return eng
 
     def _build_engine(self, sd) -> engine.VaeEngine:
-        return engine.VaeEngine(sd, dim=self.dim, latent_dim=self.latent_dim, dtype=self.arith, device=self.device)
+        return engine.VaeEngine(sd, dim=self.dim, latent_dim=self.latent_dim, dtype=self.engine_dtype, device=self.device)
 
     def _posterior_noise(self, B, T, noise):
         e = self.engine()
@@ -442,14 +460,18 @@ class LatentDiscreteModel(nn.Module):
     def __init__(self, speech_decoder, dim, latent_dim, target_sample_hz=None, timesteps=1000, use_ddim=True,
                  noise_schedule='sigmoid', objective='v', schedule_kwargs: dict = dict(), time_difference=0.,
                  min_snr_loss_weight=True, min_snr_gamma=5, train_prob_self_cond=0.9, scale=1., use_cond=False,
-                 multitask=True, dtype="bf16"):
+                 multitask=True, dtype="bf16", sample_dtype=None):
+        """dtype: the arithmetic of training (and of sampling when `sample_dtype` is None).  sample_dtype: the arithmetic the
+        eps-predictor samples in (`ddim_sample` / `ddpm_sample`, any of f32 / bf16 / f16 / bf16x3) while `enable_training()` keeps
+        `dtype`: one model object that trains and samples in different arithmetic.  (The frozen VAE passed in keeps the sampling
+        arithmetic it was built with.)"""
         super().__init__()
         assert objective in {'x0', 'eps', 'v'}, 'objective must be either predict x0 or noise'
         self.speech_decoder = speech_decoder.encoder
         self.use_cond, self.multitask = use_cond, multitask
         # use_cond: Model(dim, latent_dim, condition_on_prompt=True, dim_prompt=768, num_latents_m=64) upstream (:1325-1333)
         self.model = Model(dim, latent_dim, condition_on_prompt=use_cond, dim_prompt=getattr(speech_decoder.encoder, "dim", 768) if use_cond else None,
-                           num_latents_m=64, dtype=dtype)
+                           num_latents_m=64, dtype=dtype, sample_dtype=sample_dtype)
         self.scheduler = DDPMScheduler(timesteps, scale=scale)
         self.dim, self.timesteps, self.objective = dim, timesteps, objective
         self.min_snr_loss_weight, self.min_snr_gamma = min_snr_loss_weight, min_snr_gamma

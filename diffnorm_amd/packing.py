@@ -11,6 +11,9 @@ over the tables:
   the same entries, weights converted to the arithmetic dtype, the transformer's stacked per tensor, plus the few tensors derived
   for inference only (summed skip bias, K-blocked copies, placeholders, the sinusoidal table).
 
+A third walk (`repack_plan`) describes the inference lists as a device pass over the training engine's flat master buffer
+(dn_repack_weights); `repack_emulate` is that pass in torch.
+
 Packing rules:
 
 * every weight becomes [rows padded to 128][K padded to 64] with K contiguous; pads are zeros, so padded channels stay exactly zero
@@ -23,7 +26,8 @@ Packing rules:
 * biases, norm gammas, the conditioning path, the Fourier frequencies and the sinusoidal table stay fp32.
 """
 import math
-from typing import Dict, List
+import re
+from typing import Dict, List, NamedTuple
 
 import torch
 
@@ -435,3 +439,147 @@ def pack_vae(sd: SD, dim: int, mults: List[int], depth: int, heads: int, dim_hea
              vocab: int, dtype: int) -> List[torch.Tensor]:
     waves, tf_layers, pred, tail = _vae_entries(dim, mults, depth, heads, dim_head, stacks, layers, vocab)
     return sum((_wavenet_tensors(w, sd, dtype) for w in waves), []) + _tf_tensors(tf_layers, pred, sd, dtype) + _pack(tail, sd, dtype)
+
+
+# ------------------------------------------------------------------------------------------ inference lists from the flat master buffer
+# The third walk over the tables: for a training engine's entry table and offsets, the descriptors of dn_repack_weights
+# (csrc/repack.hip), which writes the tensors pack_eps / pack_vae return straight from the flat fp32 master buffer on the device.
+# The master holds every entry's packed fp32 tensor, so what is left is the conversion to the arithmetic dtype (CONVERT), the
+# transformer's per-tensor stacking (one item per layer slice), the K-blocked copies (KBLOCK), fp32 copies (COPY) and the summed
+# skip bias (SUM).
+class RepackItem(NamedTuple):
+    """One DnRepackDesc (include/diffnorm_hip.h): `mats` matrices [rows][K] from element `src` of the master to byte `dst_byte` of
+    destination tensor `tensor` (its index in pack_eps / pack_vae's list)."""
+    tensor: int
+    dst_byte: int
+    src: int
+    kind: int
+    mats: int
+    rows: int
+    K: int
+    count: int = 0
+    stride: int = 0
+
+
+class RepackPlan(NamedTuple):
+    """items: the descriptors, in destination order.  shapes: per tensor of pack_eps / pack_vae's list its (shape, torch dtype), or
+    None for a tensor that does not depend on the parameters (the sinusoidal table, placeholders): those are not written."""
+    items: List[RepackItem]
+    shapes: list
+
+
+def _w_storage(shape, dtype: int):
+    """(shape, torch dtype) in which a weight of packed fp32 `shape` is stored in the arithmetic dtype."""
+    if dtype == _lib.DN_BF16X3:
+        return tuple(shape[:-1]) + (2 * shape[-1],), torch.bfloat16
+    return tuple(shape), _act_dtype(dtype)
+
+
+def repack_plan(entries: List[_Entry], offsets: List[int], dtype: int, kind: str = "eps") -> RepackPlan:
+    """entries / offsets: a training engine's table (eps_train_entries / vae_train_entries) and dn_*_train_offsets; dtype: the
+    inference engine's arithmetic.  kind "eps": the unconditional eps-predictor's list (pack_eps); "vae": pack_vae's."""
+    assert kind in ("eps", "vae") and len(entries) == len(offsets)
+    wes = 2 if _is16(dtype) else 4  # bytes per element of a stored weight (split rows: two bf16)
+    items, shapes = [], []
+
+    def put(e: _Entry, src: int, tensor: int, layer: int = 0):
+        n = math.prod(e.shape)
+        if e.arith == "weight":
+            *lead, rows, K = e.shape
+            items.append(RepackItem(tensor, layer * n * wes, src, _lib.REPACK_CONVERT, math.prod(lead), rows, K))
+        elif e.arith is None:
+            items.append(RepackItem(tensor, layer * n * 4, src, _lib.REPACK_COPY, 1, 1, n))
+        else:
+            raise NotImplementedError(f"{e.name}: activation-order entries belong to the prompt-conditioned model, which has no training engine")
+
+    def tensor_of(e: _Entry, lead=()):
+        shapes.append(_w_storage(lead + e.shape, dtype) if e.arith == "weight" else (lead + e.shape, torch.float32))
+        return len(shapes) - 1
+
+    def plain(e: _Entry, src: int):
+        put(e, src, tensor_of(e))
+
+    def kblocked(e: _Entry, srcs: List[int], lead=()):
+        """The K-blocked copy of a weight (stacked over len(srcs) layers when lead is given); a placeholder outside the 2-byte modes."""
+        if not _is16(dtype):
+            shapes.append(None)
+            return
+        *mid, rows, K = e.shape
+        shapes.append((lead + tuple(mid) + (K // 32, rows, 32), _act_dtype(dtype)))
+        for l, src in enumerate(srcs):
+            items.append(RepackItem(len(shapes) - 1, l * math.prod(e.shape) * wes, src, _lib.REPACK_KBLOCK, math.prod(mid), rows, K))
+
+    def wavenet(ents: List[_Entry], offs: List[int]):
+        init_W, init_b, conv_W, conv_b, res_W, res_b, skip_W, skip_b, final_W, final_b = ents
+        for e, o in zip(ents[:7], offs[:7]):
+            plain(e, o)
+        L, cp = skip_b.shape  # one bias for the summed skip path
+        shapes.append(((cp,), torch.float32))
+        items.append(RepackItem(len(shapes) - 1, 0, offs[7], _lib.REPACK_SUM, 1, 1, cp, L, cp))
+        plain(final_W, offs[8])
+        plain(final_b, offs[9])
+        kblocked(conv_W, [offs[2]])
+        kblocked(res_W, [offs[4]])
+
+    def transformer(layers: List[List[_Entry]], layer_offs: List[List[int]], pred: List[_Entry], pred_offs: List[int]):
+        depth, cols = len(layers), list(zip(*layers))
+        for j, col in enumerate(cols):
+            t = tensor_of(col[0], (depth,))
+            for l, e in enumerate(col):
+                assert e.shape == col[0].shape and e.arith == col[0].arith
+                put(e, layer_offs[l][j], t, l)
+        if len(cols) == 8:  # adaptive norms: no learned gammas, two placeholders
+            shapes.extend([None, None])
+        for e, o in zip(pred, pred_offs):
+            plain(e, o)
+        for j in (4, 2, 0):  # ffconv_W, ffin_W, qkv_W
+            kblocked(cols[j][0], [layer_offs[l][j] for l in range(depth)], (depth,))
+
+    layer_of = lambda e: re.search(r"(?:^|\.)layers\.(\d+)\.", e.name)
+    i = 0
+    while i < len(entries):
+        e = entries[i]
+        if e.name.endswith(".init_W"):  # a WaveNet's ten tensors
+            wavenet(entries[i: i + 10], offsets[i: i + 10])
+            i += 10
+        elif layer_of(e):  # the transformer: its layers' tables one after the other, then [final norm's gamma, to_pred]
+            layers, layer_offs = [], []
+            while i < len(entries) and layer_of(entries[i]):
+                l = int(layer_of(entries[i]).group(1))
+                if l == len(layers):
+                    layers.append([])
+                    layer_offs.append([])
+                layers[l].append(entries[i])
+                layer_offs[l].append(offsets[i])
+                i += 1
+            transformer(layers, layer_offs, entries[i: i + 2], offsets[i: i + 2])
+            i += 2
+        else:
+            plain(e, offsets[i])
+            i += 1
+    if kind == "eps":
+        shapes.append(None)  # the sinusoidal table of the frames' positions
+    return RepackPlan(items, shapes)
+
+
+def repack_emulate(master: torch.Tensor, plan: RepackPlan, dtype: int) -> list:
+    """What dn_repack_weights writes for `plan` from the flat fp32 `master`, in torch on the CPU: the list of destination tensors
+    (None where the plan leaves a tensor alone).  Bytes no item writes stay 0xFF."""
+    master = master.detach().float().cpu()
+    esize = lambda dt: torch.empty(0, dtype=dt).element_size()
+    bufs = [None if s is None else torch.full((math.prod(s[0]) * esize(s[1]),), 0xFF, dtype=torch.uint8) for s in plan.shapes]
+    for it in plan.items:
+        src = master[it.src: it.src + it.mats * it.rows * it.K].view(it.mats, it.rows, it.K)
+        if it.kind == _lib.REPACK_CONVERT:
+            out = _arith(src, dtype, weight=True)
+        elif it.kind == _lib.REPACK_KBLOCK:
+            out = kblock(_arith(src, dtype, weight=True))
+        elif it.kind == _lib.REPACK_COPY:
+            out = src
+        else:
+            out = torch.zeros(it.K)
+            for j in range(it.count):
+                out = out + master[it.src + j * it.stride: it.src + j * it.stride + it.K]
+        b = out.contiguous().view(torch.uint8).reshape(-1)
+        bufs[it.tensor][it.dst_byte: it.dst_byte + b.numel()] = b
+    return [None if s is None else b.view(s[1]).view(s[0]) for s, b in zip(plan.shapes, bufs)]

@@ -469,6 +469,34 @@ int dn_transpose_weights(const void* src, int32_t dtype, int32_t count, int64_t 
  * operand type of the contractions that replace torch's fp32 autograd of nn.Linear / CausalConv1d (latent_module.py:476-488). */
 int dn_split_rows(const float* src, int64_t n, void* dst, int32_t weight_order, void* stream);
 
+/* The inference engines' packed tensors (dn_eps_create / dn_vae_create tables) from a training engine's flat fp32 master buffer,
+ * on the device: what diffnorm_amd/packing.py::pack_eps / pack_vae make of the master's state dict, without the round trip through
+ * the host.  One descriptor per destination tensor, or per layer slice of a tensor stacked over the transformer's layers
+ * (packing.repack_plan); the array lives in device memory.  A descriptor covers `mats` matrices [rows][K] (padded sizes) that lie
+ * one after the other in the master and in the destination:
+ *   DN_REPACK_CONVERT  as they lie, in the arithmetic `dtype`: DN_F32 (copy), DN_BF16 / DN_F16 (round to nearest even; f16 saturates
+ *                      at +-65504 like the host packer) or DN_BF16X3 weight-order split rows ([lo | hi] per 32 elements,
+ *                      hi = bf16(x), lo = bf16(x - hi));  rows * K a multiple of 32, dst 128-byte aligned
+ *   DN_REPACK_KBLOCK   the same values in the K-blocked layout [K/32][rows][32] (DN_LAYOUT_W_KBLOCKED); the 2-byte dtypes only
+ *                      (the other modes have no K-blocked copies: such a descriptor writes nothing)
+ *   DN_REPACK_COPY     fp32 as it lies whatever `dtype` (biases, gammas, the conditioning path, Fourier frequencies): any length
+ *   DN_REPACK_SUM      fp32 dst[c] = ((0 + src[c]) + src[stride + c]) + ... over `count` rows of K elements (rows = mats = 1): the
+ *                      summed skip bias of a WaveNet, in the host packer's order;  K a multiple of 4, dst 16-byte aligned
+ * Stream-ordered, no allocation, no synchronisation.  The descriptors are trusted: the caller keeps src + mats * rows * K inside
+ * the master and the destination inside its tensor.                                                                            */
+enum { DN_REPACK_CONVERT = 0, DN_REPACK_KBLOCK = 1, DN_REPACK_COPY = 2, DN_REPACK_SUM = 3 };
+typedef struct {
+  int64_t src;        /* element offset of the source in the fp32 master (a multiple of 4)                        */
+  void* dst;          /* device address of the destination tensor or slice                                        */
+  int32_t kind;       /* DN_REPACK_*                                                                              */
+  int32_t mats;       /* matrices [rows][K], contiguous on both sides                                             */
+  int32_t rows, K;    /* padded sizes; COPY: rows * K * mats = number of elements                                 */
+  int32_t count;      /* SUM: number of addends                                                                   */
+  int32_t pad_;
+  int64_t stride;     /* SUM: elements between the addends                                                        */
+} DnRepackDesc;
+int dn_repack_weights(const float* master, const DnRepackDesc* descs, int32_t n, int32_t dtype, void* stream);
+
 /* The operand transpose of the training engines' weight gradient (autograd of CausalConv1d / nn.Linear, latent_module.py:476-485):
  * dst[j / chunk][row0 + c][j % chunk] = src[b * T + t, c] with j = b * Tp + front + t, zero for pad frames, channels >= C and the tail
  * columns [B * Tp, cols_total).  dtype DN_F32 / DN_BF16 / DN_BF16X3 (src split rows [hi | lo]; dst split rows in the order of its role:
@@ -558,6 +586,11 @@ int dn_eps_forward_cond_ex(DnEps* m, const float* x, const int32_t* t, const int
                            int32_t table_n, void* stream);
 size_t dn_eps_cond_time_table_workspace_bytes(const DnEps* m, int32_t n_t);
 int dn_eps_cond_time_table(DnEps* m, int32_t t0, int32_t n_t, float* table, void* workspace, size_t workspace_bytes, void* stream);
+
+/* After the packed weights behind `m` were rewritten in place (dn_repack_weights): forgets what the engine derived from them --
+ * the conditioning table a DN_LOOP_KEEP_TABLE call would reuse.  The captured hipGraph of the device loop stays: it holds
+ * addresses only, and every table it reads is rebuilt from the weights by the next dn_ddim_loop / dn_ddpm_loop call.        */
+int dn_eps_weights_changed(DnEps* m);
 
 int dn_vae_create(const DnVaeConfig* cfg, const void* const* weights, int32_t n_weights, DnVae** out);
 void dn_vae_destroy(DnVae* m);
