@@ -153,6 +153,8 @@ SYMBOLS = {
     "dn_transpose_pad": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32,
                                    C.c_int32, C.c_int32, _vp]),
     "dn_adam_step": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.POINTER(AdamParams), _vp, _vp, _vp]),
+    "dn_adam_step_ema": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.POINTER(AdamParams), _vp, _vp, _vp, C.c_double, _vp]),
+    "dn_ema_update": (C.c_int, [_vp, _vp, C.c_int64, C.c_double, _vp]),
     "dn_profile_start": (C.c_int, [_i32, _i32]),
     "dn_profile_stop": (C.c_int, [C.POINTER(C.c_float), C.POINTER(_i32)]),
     "dn_attention": (C.c_int, [C.POINTER(AttnParams), _vp]),

@@ -105,10 +105,16 @@ class _Engine:
         self._repack = (key, dev, len(plan.items), moved)
         return self._repack
 
-    def _refresh_from(self, train_engine):
-        master = train_engine.master
-        if master.device != self.device or master.dtype != torch.float32 or not master.is_contiguous():
-            raise ValueError("refresh_from: the training engine's master buffer must be a contiguous fp32 tensor on this engine's device")
+    def _refresh_from(self, train_engine, source: str = "model"):
+        """source: which flat fp32 buffer of the training engine is repacked -- "model" (master) or "ema" (its EMA, same layout: the
+        descriptors are offsets into the buffer and serve both)."""
+        if source not in ("model", "ema"):
+            raise ValueError(f"refresh_from: source {source!r} (use 'model' or 'ema')")
+        master = train_engine.master if source == "model" else getattr(train_engine, "ema", None)
+        if master is None:
+            raise ValueError("refresh_from: source 'ema' needs the training engine's EMA (enable_ema(), --store-ema)")
+        if master.device != self.device or master.dtype != torch.float32 or not master.is_contiguous() or master.numel() != train_engine.n_params:
+            raise ValueError("refresh_from: the training engine's master / EMA buffer must be a contiguous fp32 tensor of n_params elements on this engine's device")
         _, descs, n, _ = self._repack_descs(train_engine)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dn_repack_weights(master.data_ptr(), descs.data_ptr(), n, self.dtype, _lib.current_stream()), "dn_repack_weights")
@@ -140,8 +146,9 @@ class EpsEngine(_Engine):
 
     _kind = "eps"
 
-    def refresh_from(self, train_engine):
-        """Rewrites this engine's packed weights from `train_engine`'s (training.EpsTrainEngine) fp32 master buffer on the device
+    def refresh_from(self, train_engine, source: str = "model"):
+        """Rewrites this engine's packed weights from `train_engine`'s (training.EpsTrainEngine) fp32 master buffer (source="ema": its
+        EMA buffer) on the device
         (dn_repack_weights into the existing `self.tensors`): bit-identical to `EpsEngine(train_engine.state_dict(), ...)` in this
         engine's dtype, whatever the training dtype.  Stream-ordered on the current stream, no host synchronisation (the first call
         for a layout builds the descriptors and uploads them once).  The device addresses do not change.  What the engine derived
@@ -157,7 +164,7 @@ class EpsEngine(_Engine):
         * nothing else: the sinusoidal table and the placeholders do not depend on the parameters, workspaces hold activations."""
         if self.conditional:
             raise NotImplementedError("refresh_from covers the unconditional eps-predictor (the prompt-conditioned model has no training engine)")
-        self._refresh_from(train_engine)
+        self._refresh_from(train_engine, source)
         _lib.check(self.lib.dn_eps_weights_changed(self.handle), "dn_eps_weights_changed")
 
     def workspace_bytes(self, B: int, T: int) -> int:
@@ -368,12 +375,12 @@ class VaeEngine(_Engine):
 
     _kind = "vae"
 
-    def refresh_from(self, train_engine):
+    def refresh_from(self, train_engine, source: str = "model"):
         """Rewrites this engine's packed weights from `train_engine`'s (training.VaeTrainEngine: f32, bf16 or bf16x3) fp32 master
-        buffer on the device: bit-identical to `VaeEngine(train_engine.state_dict(), ...)` in this engine's dtype.  Stream-ordered,
+        buffer (source="ema": its EMA buffer) on the device: bit-identical to `VaeEngine(train_engine.state_dict(), ...)` in this engine's dtype.  Stream-ordered,
         no host synchronisation, same device addresses (see EpsEngine.refresh_from).  The VAE engine derives nothing from its
         weights (DnVae holds the table's pointers only; no graph, no table), so there is nothing to invalidate."""
-        self._refresh_from(train_engine)
+        self._refresh_from(train_engine, source)
 
     def workspace_bytes(self, B: int, T: int) -> int:
         return int(self.lib.dn_vae_workspace_bytes(self.handle, B, T))

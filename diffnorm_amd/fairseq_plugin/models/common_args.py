@@ -41,6 +41,33 @@ def add_inherited_args(parser):
     parser.add_argument("--classifier_guidance", type=float, default=1.0)
 
 
+def add_ema_args(parser):
+    """The reference's EMA flags (fairseq/dataclass/configs.py EMAConfig: --store-ema, --ema-decay, --ema-start-update,
+    --ema-update-freq, --ema-fp32) plus --hip-sample-from.  The EMA here is always fp32: --ema-fp32 is accepted and ignored;
+    --ema-seed-model is not supported.  Added by both archs and both tasks; a parser that already has them is left alone."""
+    have = {o for a in parser._actions for o in a.option_strings}
+    for flag, kw in (
+        ("--store-ema", dict(action="store_true", help="keep an exponential moving average of the trained parameters on the device (one flat fp32 buffer, updated inside the Adam kernel's pass); it is written to checkpoints as extra_state['ema']")),
+        ("--ema-decay", dict(type=float, default=0.9999, help="decay of the moving average")),
+        ("--ema-start-update", dict(type=int, default=0, help="the EMA copies the model (decay 0) until this many updates")),
+        ("--ema-update-freq", dict(type=int, default=1, help="update the EMA every this many model updates")),
+        ("--ema-fp32", dict(action="store_true", help="accepted for the reference's command lines: the EMA here is always fp32")),
+        ("--hip-sample-from", dict(default="model", choices=["model", "ema"], help="which weights the sampling / inference engine of a model in training holds: the trained parameters, or their EMA (needs --store-ema)")),
+    ):
+        if flag not in have:
+            parser.add_argument(flag, **kw)
+
+
+def ema_schedule(args):
+    """The optim.EmaSchedule of a namespace with --store-ema, else None."""
+    if not getattr(args, "store_ema", False):
+        return None
+    from ...optim import EmaSchedule
+
+    return EmaSchedule(decay=getattr(args, "ema_decay", 0.9999), start_update=getattr(args, "ema_start_update", 0),
+                       update_freq=getattr(args, "ema_update_freq", 1))
+
+
 _ARCH_DEFAULTS = dict(
     attn_type=None, pos_enc_type="abs", classifier_guidance=1.0, encoder_freezing_updates=0, conv_kernel_sizes="5,5",
     conv_channels=1024, conv_version="s2t_transformer", encoder_embed_dim=512, encoder_ffn_embed_dim=2048, encoder_layers=12,

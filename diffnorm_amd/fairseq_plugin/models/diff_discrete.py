@@ -5,7 +5,7 @@ import torch
 
 from ...latent_module import LatentDiscreteModel, SpeechVAEEncoderDecoder, lengths_to_mask
 from ..registry import HAVE_FAIRSEQ, FairseqEncoderModel, register_model, register_model_architecture
-from .common_args import add_inherited_args, apply_arch_defaults, is_training_run
+from .common_args import add_ema_args, add_inherited_args, apply_arch_defaults, is_training_run
 
 
 def _load_speech_decoder(args):
@@ -59,7 +59,9 @@ class DiffDiscreteModel(FairseqEncoderModel):
         z = vae.latent_channels() if hasattr(vae, "latent_channels") else args.latent_dim
         encoder = LatentDiscreteModel(speech_decoder, getattr(args, "denoiser_dim", 512), z, timesteps=getattr(args, "diffusion_timesteps", 200),
                                       multitask=args.multitask, dtype=getattr(args, "hip_dtype", "bf16"),
-                                      sample_dtype=getattr(args, "hip_sample_dtype", None))
+                                      sample_dtype=getattr(args, "hip_sample_dtype", None),
+                                      sample_from=getattr(args, "hip_sample_from", None) or "model")
+        encoder.store_ema = bool(getattr(args, "store_ema", False))  # the training engine comes up with its EMA buffer
         encoder.train_on_move = is_training_run(args)  # the training engine (one flat parameter) comes up with model.to(device)
         return cls(args, encoder)
 
@@ -74,6 +76,7 @@ class DiffDiscreteModel(FairseqEncoderModel):
                             help="schedule length (upstream hard-codes 200 at diff_discrete.py:84)")
         parser.add_argument("--hip-dtype", default="bf16", choices=["bf16", "f16", "bf16x3", "f32"], help="MFMA arithmetic of the HIP engine (f16: IEEE-half operands, the 2-byte mode inside the 1e-2 budget, inference only; bf16: fastest, also the fast training mode; bf16x3: split-operand bf16, fp32-class results, inference only; f32: exact)")
         parser.add_argument("--hip-sample-dtype", default=None, choices=["bf16", "f16", "bf16x3", "f32"], help="MFMA arithmetic of the sampling / inference engine when it differs from the training one (default: the same as --hip-dtype): a model in training keeps --hip-dtype for its updates and samples (validation) in this mode, its packed weights refreshed on the device after every update")
+        add_ema_args(parser)
 
     def max_positions(self):
         return self.encoder.max_positions()

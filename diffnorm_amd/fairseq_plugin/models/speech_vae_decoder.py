@@ -3,7 +3,7 @@ import torch
 
 from ...latent_module import SpeechVAEEncoderDecoder, lengths_to_mask
 from ..registry import FairseqEncoderModel, register_model, register_model_architecture
-from .common_args import add_inherited_args, apply_arch_defaults, is_training_run
+from .common_args import add_ema_args, add_inherited_args, apply_arch_defaults, is_training_run
 
 
 @register_model("speech_vae_decoder")
@@ -25,7 +25,9 @@ class SpeechVAEDecoder(FairseqEncoderModel):
     @classmethod
     def build_model(cls, args, task):
         encoder = SpeechVAEEncoderDecoder(dim=getattr(args, "feature_dim", 768), latent_dim=args.latent_dim,
-                                          dtype=getattr(args, "hip_dtype", "bf16"), sample_dtype=getattr(args, "hip_sample_dtype", None))
+                                          dtype=getattr(args, "hip_dtype", "bf16"), sample_dtype=getattr(args, "hip_sample_dtype", None),
+                                          sample_from=getattr(args, "hip_sample_from", None) or "model")
+        encoder.store_ema = bool(getattr(args, "store_ema", False))  # the training engine comes up with its EMA buffer
         encoder.train_on_move = is_training_run(args)  # the training engine (one flat parameter) comes up with model.to(device)
         return cls(args, encoder)
 
@@ -35,6 +37,7 @@ class SpeechVAEDecoder(FairseqEncoderModel):
         parser.add_argument("--latent_dim", type=int, default=16)
         parser.add_argument("--hip-dtype", default="bf16", choices=["bf16", "f16", "bf16x3", "f32"], help="MFMA arithmetic of the HIP engine (f16: IEEE-half operands, the 2-byte mode inside the 1e-2 budget, inference only; bf16: fastest, also the fast training mode; bf16x3: split-operand bf16, fp32-class results, also a training mode of this model; f32: exact)")
         parser.add_argument("--hip-sample-dtype", default=None, choices=["bf16", "f16", "bf16x3", "f32"], help="MFMA arithmetic of the sampling / inference engine when it differs from the training one (default: the same as --hip-dtype): a model in training keeps --hip-dtype for its updates and samples (validation) in this mode, its packed weights refreshed on the device after every update")
+        add_ema_args(parser)
 
     def max_positions(self):
         return self.encoder.max_positions()

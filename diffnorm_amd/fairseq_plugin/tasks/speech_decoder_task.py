@@ -13,6 +13,7 @@ import torch
 from ...data import ReprToReprUnitDataset, UnitDictionary
 from ...latent_module import wrapped_by_torch_ddp
 from ...profiling import profile_range
+from ..models.common_args import add_ema_args, ema_schedule
 from ..registry import MODEL_REGISTRY, ARCH_MODEL_REGISTRY, ARCH_CONFIG_REGISTRY, CRITERION_REGISTRY, FairseqTask, register_task
 
 
@@ -68,6 +69,17 @@ def _check_optimizer_holds_flat_params(enc, optimizer):
                            "model.to(device) makes the switch, or call model.encoder.enable_training() before building the optimizer")
 
 
+def _training_engine(model):
+    """The HIP training engine behind a plugin model (through DistributedDataParallel / fairseq's wrappers: `.module`)."""
+    m, seen = model, 0
+    while m is not None and seen < 8:
+        enc = getattr(m, "encoder", None)
+        if enc is not None and getattr(enc, "_train_engine", None) is not None:
+            return enc._train_engine
+        m, seen = getattr(m, "module", None), seen + 1
+    return None
+
+
 class _SpeechTaskBase(FairseqTask):
     @classmethod
     def add_args(cls, parser):
@@ -90,11 +102,13 @@ class _SpeechTaskBase(FairseqTask):
         parser.add_argument("--vocoder-config", type=str)
         parser.add_argument("--tgt-feat-dir", type=str)
         parser.add_argument("--src-feat-dir", type=str)
+        add_ema_args(parser)
 
     def __init__(self, args, tgt_dict):
         super().__init__(args)
         self.args = args
         self.tgt_dict = tgt_dict
+        self.ema_schedule = ema_schedule(args)  # --store-ema: see optimizer_step
 
     @classmethod
     def setup_task(cls, args, **kwargs):
@@ -165,7 +179,31 @@ class _SpeechTaskBase(FairseqTask):
         pass  # as upstream (speech_decoder_task.py:241-242)
 
     def optimizer_step(self, optimizer, model, update_num):
-        optimizer.step()
+        """With --store-ema the EMA of the parameters is stepped here, with the number of updates after this one (the reference's
+        trainer does it right after set_num_updates, fairseq/trainer.py:1018-1025): an optim.FlatOptimizer carries the schedule
+        and takes the fused dn_adam_step_ema; after any other optimizer (it moved the master buffer through `p.data`) the EMA
+        is one pass of its own, dn_ema_update."""
+        sched = self.ema_schedule
+        if sched is None:
+            return optimizer.step()
+        eng = _training_engine(model)
+        if eng is None or eng.ema is None:
+            raise RuntimeError("--store-ema: the model has no HIP training engine with an EMA (build it from a namespace with --store-ema)")
+        if getattr(optimizer, "engine", None) is eng and hasattr(optimizer, "ema"):
+            if optimizer.ema is None:
+                optimizer.ema = sched
+            optimizer.step(updates=update_num + 1)
+        else:
+            optimizer.step()
+            apply, decay = sched(update_num + 1)
+            if apply:
+                eng.step_ema(decay)
+
+    @property
+    def ema_decay(self):
+        """What the reference's trainer logs as `ema_decay` (fairseq/trainer.py:1026-1032): the schedule's current decay."""
+        sched = self.ema_schedule
+        return None if sched is None else sched.get_decay()
 
 
 @register_task("speech_decoder")

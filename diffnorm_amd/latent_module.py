@@ -55,6 +55,13 @@ def label_smoothed_nll_loss(lprobs, target, epsilon, ignore_index=None, reduce=T
     return (1.0 - epsilon - eps_i) * nll + eps_i * smooth, nll
 
 
+def _sample_from(sample_from):
+    """`sample_from` of the module constructors: which weights the inference engine of a model in training holds."""
+    if sample_from not in ("model", "ema"):
+        raise ValueError(f"sample_from {sample_from!r}: use 'model' (the trained weights) or 'ema' (their moving average, --hip-sample-from)")
+    return sample_from
+
+
 def _sample_dtype(sample_dtype):
     """`sample_dtype` of the module constructors: None (= the module's `dtype`) or an inference arithmetic mode."""
     if sample_dtype is not None:
@@ -125,6 +132,7 @@ class _ParamTree(nn.Module):
             self._train_engine.load_state_dict({k: got[k] for k in want})
 
     sample_dtype = None  # arithmetic of the inference engine when it differs from the training / default one (`arith`)
+    sample_from = "model"  # "ema": with a training engine, the inference engine holds the EMA of the parameters (--hip-sample-from)
 
     @property
     def engine_dtype(self):
@@ -135,13 +143,19 @@ class _ParamTree(nn.Module):
         """The inference engine over the current parameters (`_build_engine(sd)`: the subclass's engine class, in `engine_dtype`).
         With a training engine: built once from its master buffer; after every later update the SAME engine's packed tensors are
         rewritten on the device (`refresh_from`: the result is bit-identical to a rebuild, the device addresses and captured
-        graphs stay).  Without one: rebuilt when a parameter has changed."""
+        graphs stay); with `sample_from == "ema"` the same from the training engine's EMA buffer.  Without one: rebuilt when a
+        parameter has changed (there is no EMA to sample from: `sample_from` has no effect)."""
         if self._train_engine is not None:
-            key = ("train", self._train_engine.update_count)
+            te, ema = self._train_engine, self.sample_from == "ema"
+            if ema and te.ema is None:
+                raise ValueError("sample_from='ema' (--hip-sample-from ema) needs the EMA of the parameters: build the model with --store-ema, "
+                                 "or call enable_ema() on its training engine")
+            # the EMA moves only on the updates its schedule applies (and on loads): an update that skips it repacks nothing
+            key = ("ema", te.ema_count, te.ema_loads) if ema else ("train", te.update_count)
             if self._engine is None:
-                self._engine = self._build_engine(self._train_engine.state_dict())
+                self._engine = self._build_engine(te.ema_state_dict() if ema else te.state_dict())
             elif self._engine_key != key:
-                self._engine.refresh_from(self._train_engine)
+                self._engine.refresh_from(te, source=self.sample_from)
             self._engine_key = key
             return self._engine
         key = self._state_key()
@@ -161,7 +175,7 @@ class Model(_ParamTree):
 
     def __init__(self, dim, latent_dim, *, depth=12, dim_head=64, heads=8, ff_mult=4, wavenet_layers=8, wavenet_stacks=4,
                  dim_cond_mult=4, use_flash_attn=False, dim_prompt=None, num_latents_m=64, resampler_depth=2,
-                 cond_drop_prob=0., condition_on_prompt=False, dtype="bf16", seed=0, sample_dtype=None):
+                 cond_drop_prob=0., condition_on_prompt=False, dtype="bf16", seed=0, sample_dtype=None, sample_from="model"):
         super().__init__()
         if ff_mult != 4:
             raise NotImplementedError("the engine packs ff_mult = 4 (the only value the recipe uses)")
@@ -173,7 +187,7 @@ class Model(_ParamTree):
         self.cfg = synthetic.eps_config(dim, latent_dim, depth, heads, dim_head, wavenet_layers, wavenet_stacks, dim_cond_mult,
                                         dim_prompt=dim_prompt if condition_on_prompt else 0, num_latents_m=num_latents_m,
                                         resampler_depth=resampler_depth)
-        self.arith, self.sample_dtype = dtype, _sample_dtype(sample_dtype)
+        self.arith, self.sample_dtype, self.sample_from = dtype, _sample_dtype(sample_dtype), _sample_from(sample_from)
         self._adopt(synthetic.random_eps_state_dict(self.cfg, seed))
         self._attach("pos_embed._float_tensor", torch.zeros(1), buffer=True)  # key present upstream (:774-779)
         if self.condition_on_prompt:
@@ -359,11 +373,12 @@ class SpeechVAEEncoderDecoder(_ParamTree):
     """reference latent_module.py:1035-1142 (WaveNet encoder -> diagonal Gaussian -> WaveNet + transformer decoder
     -> 1004-way unit logits).  `latent_dim` is the upstream constructor flag (16 / 32 / 128)."""
 
-    def __init__(self, dim=768, latent_dim=16, dtype="bf16", seed=1, sample_dtype=None):
+    def __init__(self, dim=768, latent_dim=16, dtype="bf16", seed=1, sample_dtype=None, sample_from="model"):
         super().__init__()
         self.dim, self.latent_dim = dim, latent_dim
-        self.arith, self.sample_dtype = dtype, _sample_dtype(sample_dtype)
+        self.arith, self.sample_dtype, self.sample_from = dtype, _sample_dtype(sample_dtype), _sample_from(sample_from)
         self.train_on_move = False  # the plugin's build_model sets it for a training run: see _apply
+        self.store_ema = False  # --store-ema: the training engine keeps an EMA of the parameters from the start (enable_training)
         self.attn_dropout = 0.1  # Attention(dropout=0.1) of the decoder transformer (:668); active in train() mode with the training engine
         self._adopt(synthetic.random_vae_state_dict(dim, latent_dim, seed=seed))
 
@@ -403,6 +418,8 @@ class SpeechVAEEncoderDecoder(_ParamTree):
         sd = {k: v.detach().cpu() for k, v in self.state_dict().items()}
         dev = self.device
         eng = training.VaeTrainEngine(sd, dim=self.dim, latent_dim=self.latent_dim, dtype=self.arith, device=dev)
+        if self.store_ema:
+            eng.enable_ema()
         self._adopt_flat(eng)
         return eng
 
@@ -460,8 +477,9 @@ class LatentDiscreteModel(nn.Module):
     def __init__(self, speech_decoder, dim, latent_dim, target_sample_hz=None, timesteps=1000, use_ddim=True,
                  noise_schedule='sigmoid', objective='v', schedule_kwargs: dict = dict(), time_difference=0.,
                  min_snr_loss_weight=True, min_snr_gamma=5, train_prob_self_cond=0.9, scale=1., use_cond=False,
-                 multitask=True, dtype="bf16", sample_dtype=None):
-        """dtype: the arithmetic of training (and of sampling when `sample_dtype` is None).  sample_dtype: the arithmetic the
+                 multitask=True, dtype="bf16", sample_dtype=None, sample_from="model"):
+        """sample_from: "ema" samples the eps-predictor from the EMA of its parameters once it trains with one (--store-ema).
+        dtype: the arithmetic of training (and of sampling when `sample_dtype` is None).  sample_dtype: the arithmetic the
         eps-predictor samples in (`ddim_sample` / `ddpm_sample`, any of f32 / bf16 / f16 / bf16x3) while `enable_training()` keeps
         `dtype`: one model object that trains and samples in different arithmetic.  (The frozen VAE passed in keeps the sampling
         arithmetic it was built with.)"""
@@ -471,7 +489,7 @@ class LatentDiscreteModel(nn.Module):
         self.use_cond, self.multitask = use_cond, multitask
         # use_cond: Model(dim, latent_dim, condition_on_prompt=True, dim_prompt=768, num_latents_m=64) upstream (:1325-1333)
         self.model = Model(dim, latent_dim, condition_on_prompt=use_cond, dim_prompt=getattr(speech_decoder.encoder, "dim", 768) if use_cond else None,
-                           num_latents_m=64, dtype=dtype, sample_dtype=sample_dtype)
+                           num_latents_m=64, dtype=dtype, sample_dtype=sample_dtype, sample_from=sample_from)
         self.scheduler = DDPMScheduler(timesteps, scale=scale)
         self.dim, self.timesteps, self.objective = dim, timesteps, objective
         self.min_snr_loss_weight, self.min_snr_gamma = min_snr_loss_weight, min_snr_gamma
@@ -486,6 +504,7 @@ class LatentDiscreteModel(nn.Module):
 
     _train_engine = None
     train_on_move = False  # set by the plugin's build_model for a training run (see SpeechVAEEncoderDecoder._apply)
+    store_ema = False  # --store-ema: the eps-predictor's training engine keeps an EMA of its parameters (enable_training)
     attn_dropout = 0.1  # the eps-predictor's Attention(dropout=0.1) (:668); the frozen VAE stays in eval mode (:1530)
 
     def _apply(self, fn, recurse=True):
@@ -512,6 +531,8 @@ class LatentDiscreteModel(nn.Module):
         esd = {k: v.detach().cpu() for k, v in self.model.state_dict().items() if not k.startswith("pos_embed")}
         eng = training.EpsTrainEngine(esd, self.model.cfg, self._frozen_vae, timesteps=self.timesteps, dtype=self.model.arith, device=dev,
                                       multitask=self.multitask)
+        if self.store_ema:
+            eng.enable_ema()
         self.model._adopt_flat(eng)
         self._train_engine = eng
         return eng

@@ -42,6 +42,65 @@ class InverseSquareRootSchedule:
         return self.lr
 
 
+class EmaSchedule:
+    """When and with which decay the EMA of the parameters is updated: fairseq's EMA.step (fairseq/models/ema/ema.py:176-197) with
+    --ema-decay / --ema-start-update / --ema-update-freq.  Called once per model update with the number of updates AFTER the
+    increment (fairseq/trainer.py:1018-1025) -> (apply, decay): the decay is 0 (the EMA copies the model) while updates <
+    start_update; with update_freq > 1 a counter is bumped on every call and the update applied -- and the counter reset -- when it
+    reaches update_freq.  Pure host logic; `state_dict()` is what a checkpoint keeps so that a resumed run applies the same updates."""
+
+    def __init__(self, decay: float = 0.9999, start_update: int = 0, update_freq: int = 1):
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f"ema decay {decay} outside [0, 1)")
+        self.decay, self.start_update, self.update_freq = float(decay), int(start_update), int(update_freq)
+        self.counter = 0
+        self.current_decay = self.decay  # EMA.get_decay(): what the trainer logs as ema_decay (trainer.py:1026-1032)
+
+    def __call__(self, updates: Optional[int] = None) -> Tuple[bool, float]:
+        if updates is not None:  # ema.py:187-190
+            self.current_decay = 0.0 if updates < self.start_update else self.decay
+        if self.update_freq > 1:  # ema.py:191-195
+            self.counter += 1
+            if self.counter < self.update_freq:
+                return False, self.current_decay
+            self.counter = 0
+        return True, self.current_decay
+
+    def get_decay(self) -> float:
+        return self.current_decay
+
+    def state_dict(self) -> dict:
+        return {"counter": self.counter, "current_decay": self.current_decay}
+
+    def load_state_dict(self, sd: dict):
+        self.counter, self.current_decay = int(sd["counter"]), float(sd["current_decay"])
+
+
+def ema_update(ema: torch.Tensor, params: torch.Tensor, decay: float):
+    """ema <- ema * decay + params * (1 - decay) on the device (dn_ema_update): the EMA step after an optimizer that is not the
+    HIP one, and (decay 0: an exact copy) the restore."""
+    e, p = _flat_f32(ema, "ema"), _flat_f32(params, "params")
+    if e.numel() != p.numel():
+        raise ValueError("ema and params differ in length")
+    _lib.check(_lib.load().dn_ema_update(e.data_ptr(), p.data_ptr(), p.numel(), float(decay), _stream()), "dn_ema_update")
+
+
+def step_engine_ema(engine, schedule: "EmaSchedule", updates: int, adam_step):
+    """One optimizer step of a training engine with its EMA: `adam_step(**kw)` is the caller's Adam call with today's arguments; on
+    an update where `schedule` applies it receives ema= / ema_decay= (the fused dn_adam_step_ema) and the engine's count of
+    applied EMA updates moves.  `schedule` None: exactly the call without an EMA."""
+    if schedule is None:
+        return adam_step()
+    if getattr(engine, "ema", None) is None:
+        raise ValueError("an EMA schedule needs the engine's EMA buffer: call engine.enable_ema() first (--store-ema)")
+    apply, decay = schedule(updates)
+    if not apply:
+        return adam_step()
+    out = adam_step(ema=engine.ema, ema_decay=decay)
+    engine.ema_count += 1
+    return out
+
+
 class Adam:
     """fairseq.optim.adam.Adam over one flat fp32 parameter buffer (updated in place), with --clip-norm folded in.
 
@@ -75,9 +134,12 @@ class Adam:
                                      int(accumulate), _stream()), "dn_grad_sumsq")
         return self._scratch[1024:]
 
-    def step(self, grad: torch.Tensor, grad_scale: float = 1.0, grad_scale_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def step(self, grad: torch.Tensor, grad_scale: float = 1.0, grad_scale_dev: Optional[torch.Tensor] = None,
+             ema: Optional[torch.Tensor] = None, ema_decay: Optional[float] = None) -> torch.Tensor:
         """`grad_scale` (host) and `grad_scale_dev` (device scalar) are the trainer's multiply_grads factor (fairseq/trainer.py:
-        918-933), applied before the norm and the clip; returns the norm of the SCALED gradient (a device scalar)."""
+        918-933), applied before the norm and the clip; returns the norm of the SCALED gradient (a device scalar).  `ema` (a flat
+        fp32 buffer of the parameters' length) with `ema_decay`: the EMA of the updated parameters is stepped in the same pass
+        (dn_adam_step_ema)."""
         lib = _lib.load()
         g = _flat_f32(grad, "grad")
         if g.numel() != self.params.numel():
@@ -87,8 +149,15 @@ class Adam:
         hp = _lib.AdamParams(lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.weight_decay,
                              max_norm=self.clip_norm, step=self.step_count, grad_scale=grad_scale,
                              grad_scale_dev=_lib.ptr(grad_scale_dev))
-        _lib.check(lib.dn_adam_step(self.params.data_ptr(), g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                                    g.numel(), C.byref(hp), sumsq.data_ptr(), _lib.ptr(self.bf16_copy), _stream()), "dn_adam_step")
+        if ema is None:
+            _lib.check(lib.dn_adam_step(self.params.data_ptr(), g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                                        g.numel(), C.byref(hp), sumsq.data_ptr(), _lib.ptr(self.bf16_copy), _stream()), "dn_adam_step")
+        else:
+            if ema_decay is None or _flat_f32(ema, "ema").numel() != self.params.numel():
+                raise ValueError("ema: expected ema_decay and a buffer of the parameters' length")
+            _lib.check(lib.dn_adam_step_ema(self.params.data_ptr(), g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                                            g.numel(), C.byref(hp), sumsq.data_ptr(), _lib.ptr(self.bf16_copy), ema.data_ptr(),
+                                            float(ema_decay), _stream()), "dn_adam_step_ema")
         norm = sumsq.sqrt()[0] * grad_scale
         return norm * grad_scale_dev.reshape(-1)[0] if grad_scale_dev is not None else norm
 
@@ -99,8 +168,12 @@ class FlatOptimizer:
     engine (diffnorm_amd/training.py).  multiply_grads and the clip coefficient are not separate passes over the gradient:
     they are recorded and applied inside the Adam kernel (fairseq's own note at trainer.py:925-927 allows exactly this)."""
 
-    def __init__(self, engine, lr: float = 5e-4, betas=(0.9, 0.98), eps: float = 1e-8, weight_decay: float = 0.0):
+    def __init__(self, engine, lr: float = 5e-4, betas=(0.9, 0.98), eps: float = 1e-8, weight_decay: float = 0.0,
+                 ema: Optional[EmaSchedule] = None):
         self.engine = engine
+        self.ema = ema  # with a schedule, `step(updates=...)` steps the engine's EMA inside the Adam kernel's pass
+        if ema is not None and getattr(engine, "ema", None) is None:
+            engine.enable_ema()
         self.adam = Adam(engine.master, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, clip_norm=0.0,
                          bf16_copy=getattr(engine, "adam_copy", engine.work if engine.work is not engine.master else None))
         self._scale, self._scale_dev, self._max_norm = 1.0, None, 0.0
@@ -124,12 +197,15 @@ class FlatOptimizer:
             norm = self.adam.grad_sumsq(self.engine.grads).sqrt()[0] * self._scale
         return norm * self._scale_dev[0] if self._scale_dev is not None else norm
 
-    def step(self, closure=None):
+    def step(self, closure=None, updates: Optional[int] = None):
+        """`updates`: the number of model updates after this one (fairseq/trainer.py:1018-1025), for the EMA schedule; default: this
+        optimizer's own count of steps (adam.step_count, which a checkpoint restores)."""
         from .profiling import profile_range
 
         self.adam.clip_norm = self._max_norm
         with profile_range("optimizer"):  # fairseq/trainer.py:958
-            self.adam.step(self.engine.grads, grad_scale=self._scale, grad_scale_dev=self._scale_dev)
+            step_engine_ema(self.engine, self.ema, self.adam.step_count + 1 if updates is None else updates,
+                            lambda **kw: self.adam.step(self.engine.grads, grad_scale=self._scale, grad_scale_dev=self._scale_dev, **kw))
             self.engine.refresh()
         self._scale, self._scale_dev = 1.0, None
 

@@ -73,6 +73,8 @@ class _FlatEngine:
         self.update_count = 0      # refreshes so far: the cache key of the module layer's inference engine
         self.work_current = False  # set by refresh, cleared by the autograd bridge's backward (latent_module._prepare_step)
         self.attn_dropout, self.dropout_seed, self._dropout_calls = 0.0, 0, 0  # see _dropout_fields
+        self.ema: Optional[torch.Tensor] = None  # enable_ema(): the EMA of master, flat fp32 in the same layout
+        self.ema_count, self.ema_loads = 0, 0  # applied EMA updates / loads: together the cache key of a module that samples from the EMA
         self._ws: Optional[torch.Tensor] = None
         self._batch = None
         self._keep = None
@@ -113,6 +115,44 @@ class _FlatEngine:
         flat = packing.pack_flat(sd, self.entries, self.offsets, self.n_params)
         self.master.copy_(flat.to(self.device))
         self.sync_work()
+        self.reset_ema()
+
+    # ---- EMA of the parameters (fairseq/models/ema/ema.py; stepped by optim.step_engine_ema / the plugin's optimizer_step) ----
+    def enable_ema(self) -> torch.Tensor:
+        """Allocates `ema` (fp32, n_params, aligned like master) as a copy of the current parameters -- the reference deep-copies the
+        model (ema.py:79).  The EMA is always fp32 (the reference's --ema-fp32)."""
+        if self.ema is None:
+            with torch.cuda.device(self.device):
+                raw, view = _aligned_empty(self.n_params * 4, self.device)
+            self._own.append(raw)
+            self.ema = view.view(torch.float32)
+            self.reset_ema()
+        return self.ema
+
+    def reset_ema(self):
+        """ema <- master (whenever the parameters are loaded; dn_ema_update with decay 0 is the exact copy)."""
+        if self.ema is not None:
+            with torch.cuda.device(self.device):
+                optim.ema_update(self.ema, self.master, 0.0)
+            self.ema_loads += 1
+
+    def step_ema(self, decay: float):
+        """One EMA update as a pass of its own (dn_ema_update), after an optimizer that is not the HIP one has moved master."""
+        if self.ema is None:
+            raise ValueError("this engine keeps no EMA: call enable_ema() first (--store-ema)")
+        with torch.cuda.device(self.device):
+            optim.ema_update(self.ema, self.master, decay)
+        self.ema_count += 1
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The EMA under the reference's parameter names and shapes (what extra_state["ema"] holds, fairseq/trainer.py:421-423)."""
+        if self.ema is None:
+            raise ValueError("this engine keeps no EMA: call enable_ema() first (--store-ema)")
+        return packing.unpack_flat(self.ema, self.entries, self.offsets)
+
+    def load_ema_state_dict(self, sd: Dict[str, torch.Tensor]):
+        self.enable_ema().copy_(packing.pack_flat(sd, self.entries, self.offsets, self.n_params).to(self.device))
+        self.ema_loads += 1
 
     def sync_work(self):
         """work / aux <- master (after loading or an external update of the master buffer)."""
@@ -411,8 +451,11 @@ class VaeTrainer:
 
     def __init__(self, engine: VaeTrainEngine, lr: float = 5e-4, betas=(0.9, 0.98), eps: float = 1e-8, weight_decay: float = 0.0,
                  clip_norm: float = 2.0, warmup_updates: int = 10000, warmup_init_lr: float = 1e-7, group=None,
-                 bucket_mb: float = 64.0, adam=None, attn_dropout: float = 0.1, seed: int = 1):
+                 bucket_mb: float = 64.0, adam=None, attn_dropout: float = 0.1, seed: int = 1, ema: Optional[optim.EmaSchedule] = None):
         self.engine = engine
+        self.ema = ema  # the schedule of the engine's EMA (fairseq's --store-ema): stepped inside the Adam kernel's pass
+        if ema is not None and engine.ema is None:
+            engine.enable_ema()
         self.attn_dropout, self.seed = float(attn_dropout), int(seed)  # train mode of the reference: Attention(dropout=0.1)
         # `adam`: anything with set_lr / step(grads, grad_scale, grad_scale_dev) -- the CPU tests of the exchange logic pass a recorder
         self.adam = adam if adam is not None else optim.Adam(
@@ -457,7 +500,9 @@ class VaeTrainer:
         inv_sample_size = 1.0 / totals[8:9]  # sample_size = sum of nsentences over ranks and micro-batches (criterion :84)
         self.adam.set_lr(self.schedule.step_update(self.num_updates))
         with profile_range("optimizer"):  # multiply-grads and clip-grads are not passes of their own: both happen inside dn_adam_step
-            grad_norm = self.adam.step(eng.grads, grad_scale=1.0, grad_scale_dev=inv_sample_size)
+            # trainer.py:1018-1025: the EMA sees the number of updates after the increment
+            grad_norm = optim.step_engine_ema(eng, self.ema, self.num_updates + 1,
+                                              lambda **kw: self.adam.step(eng.grads, grad_scale=1.0, grad_scale_dev=inv_sample_size, **kw))
             eng.refresh()
         self.num_updates += 1
         logged = totals[:8] / totals[8]  # sample-size-weighted means, as reduce_metrics (:97-112)

@@ -359,6 +359,20 @@ int dn_transpose_pad(const void* src, int32_t ld, int32_t B, int32_t T, int32_t 
 int dn_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const DnAdamParams* hp,
                  const float* sumsq, void* param_bf16, void* stream);
 
+/* Exponential moving average of the parameters (fairseq/models/ema/ema.py:140-197, stepped after every update by fairseq/
+ * trainer.py:1018-1025): one more flat fp32 buffer of n elements, ema = ema * decay + param * (1 - decay) per element, as
+ * e = fma(p, (float)(1 - decay), e * (float)decay) with 1 - decay formed in double and rounded to fp32 once (the same bits from
+ * both entry points).  0 <= decay < 1; decay == 0 (the reference's phase before --ema-start-update) is an exact copy that does
+ * not read ema, which may hold anything before.  Buffers 16-byte aligned.
+ *
+ * dn_adam_step_ema: dn_adam_step (same arguments, same bits in param / exp_avg / exp_avg_sq / param_bf16) plus the EMA update of
+ * the freshly updated parameter in the same pass -- 8 B more per element instead of the 12 B and the launch of a pass of its own.
+ * ema == NULL is refused: the update without an EMA is dn_adam_step.
+ * dn_ema_update: the pass of its own, after an optimizer that is not this library's, and for restores (decay 0).            */
+int dn_adam_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const DnAdamParams* hp,
+                     const float* sumsq, void* param_bf16, float* ema, double ema_decay, void* stream);
+int dn_ema_update(float* ema, const float* param, int64_t n, double decay, void* stream);
+
 /* ------------------------------------------------------------------ backward ops ---------- */
 /* The contractions of a backward pass are dn_conv_gemm itself (data gradient: negative shifts + transposed packed weights from
  * dn_transpose_weights; weight gradient: dn_transpose_pad operands + split-K groups + dn_wgrad_reduce).  The entry points
