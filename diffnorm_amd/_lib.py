@@ -92,6 +92,7 @@ class GaussianStep(C.Structure):
 
 
 GD_COLS = 12
+DDIM_SCHED_COLS = 5  # DN_DDIM_SCHED_COLS
 
 
 class GaussianMoments(C.Structure):
@@ -236,6 +237,9 @@ SYMBOLS = {
     "dn_ddim_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
     "dn_ddim_loop": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _sz, _vp]),
     "dn_ddpm_loop": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, C.c_uint64, _vp, _i32, _vp, _sz, _vp]),
+    "dn_ddim_sched_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
+    "dn_ddim_sched_check": (C.c_int, [_vp, _i32, _i32]),
+    "dn_ddim_sched_loop": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, C.c_uint64, _vp, _i32, _vp, _sz, _vp]),
     "dn_cfg_combine": (C.c_int, [_vp, C.c_float, _i64, _vp, _vp]),
     "dn_nar_create": (C.c_int, [C.POINTER(NarConfig), C.POINTER(_vp), _i32, C.POINTER(_vp)]),
     "dn_nar_destroy": (None, [_vp]),

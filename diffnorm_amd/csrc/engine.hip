@@ -411,6 +411,7 @@ __global__ void fill_t_kernel(int32_t* t, int n, const int32_t* counter) {
 }
 __global__ void set_counter_kernel(int32_t* counter, int v) { *counter = v; }
 __global__ void dec_counter_kernel(int32_t* counter) { *counter -= 1; }
+__global__ void inc_counter_kernel(int32_t* counter) { *counter += 1; }  // dn_ddim_sched_loop counts step indices upwards
 
 }  // namespace
 
@@ -611,6 +612,9 @@ extern "C" size_t dn_ddim_workspace_bytes(const DnEps* m, int32_t B, int32_t T, 
 
 int dn_ddpm_step_launch(float* x, const float* eps, int M, int C, int T, const float* table, const int32_t* t, int clip, const float* noise,
                         int64_t noise_row, int t_top, uint64_t seed, hipStream_t stream);  // pointwise.hip
+int dn_ddim_sched_step_launch(float* x, const float* eps, int64_t elem0, int64_t n_elem, const float* coef, const int32_t* steps,
+                              const int32_t* counter, int eta_on, const float* noise, int64_t noise_row, uint64_t seed,
+                              hipStream_t stream);  // pointwise.hip
 
 namespace {
 // the scheduler update applied after every evaluation of the device loop
@@ -618,7 +622,11 @@ struct StepOp {
   bool ddpm = false;        // false: DDIM eta = 0 with `coef` [timesteps, 4]; true: ancestral step with `coef` = table [timesteps, DN_GD_COLS]
   int clip = 0;
   uint64_t seed = 0;
-  const float* noise = nullptr;  // injected noise rows (ddpm) or NULL
+  const float* noise = nullptr;  // injected noise rows (ddpm, scheduled DDIM with eta) or NULL
+  // dn_ddim_sched_loop: the chain's evaluation timesteps (device int32 [n_steps]) with `coef` [n_steps, DN_DDIM_SCHED_COLS]; the
+  // loop's counter then counts step indices 0 .. n_steps-1 and the conditioning table has one row per step
+  const int32_t* steps = nullptr;
+  int n_steps = 0, eta_on = 0;
 };
 }  // namespace
 
@@ -629,8 +637,15 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
   int use_graph = flags & DN_LOOP_GRAPH;
   const bool split = (flags & DN_LOOP_SPLIT2) && B >= 2;
   DN_CHECK_ARG(m && x && lengths && coef && workspace, "dn_ddim_loop: null argument");
-  DN_CHECK_ARG(start_step >= 1 && start_step <= timesteps - (op.ddpm ? 0 : 1), "dn_ddim_loop: start_step=%d must be in [1, %d]", start_step,
-               timesteps - (op.ddpm ? 0 : 1));
+  const bool sched = op.steps != nullptr;
+  if (sched) {  // (a strictly descending list inside [0, timesteps-1] has at most `timesteps` entries)
+    DN_CHECK_ARG(op.n_steps >= 1 && op.n_steps <= timesteps, "dn_ddim_sched_loop: n_steps=%d must be in [1, %d]", op.n_steps, timesteps);
+    DN_CHECK_ARG(B > 0 && T > 0 && T <= m->cfg.max_pos, "dn_ddim_sched_loop: B=%d T=%d (positional table: %d)", B, T, m->cfg.max_pos);
+    DN_CHECK_ARG(op.eta_on || !op.noise, "dn_ddim_sched_loop: injected noise needs eta_on (eta = 0 draws none)");
+  } else
+    DN_CHECK_ARG(start_step >= 1 && start_step <= timesteps - (op.ddpm ? 0 : 1), "dn_ddim_loop: start_step=%d must be in [1, %d]", start_step,
+                 timesteps - (op.ddpm ? 0 : 1));
+  if (sched) start_step = op.n_steps;  // rows of the conditioning table = evaluations of the chain
   hipStream_t s = (hipStream_t)stream;
   DN_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "dn_ddim_loop: workspace must be 256-byte aligned");
   const int z = m->cfg.latent, M = B * T, C = m->cfg.dim * m->cfg.cond_mult;
@@ -638,9 +653,13 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
   // fill / drain of one half's launches overlaps the other half's main loops (measured -5 % per step at [32,512]).
   const int B0 = split ? B / 2 : B, B1 = B - B0;
   const size_t core0 = eps_ws_core(m, B0, T), core1 = split ? eps_ws_core(m, B1, T) : 0, core = core0 + core1;
-  const size_t need = core + ddim_extra_bytes(m, B, T, start_step);
+  size_t need = core + ddim_extra_bytes(m, B, T, start_step);
+  if (sched) need = dn_ddim_workspace_bytes(m, B, T, start_step);  // the documented size, split or not (>= what this call lays out)
   if (need > workspace_bytes) {
-    dn_set_error("dn_ddim_loop: workspace %zu < required %zu (see dn_ddim_workspace_bytes)", workspace_bytes, need);
+    if (sched)
+      dn_set_error("dn_ddim_sched_loop: workspace %zu < required %zu (see dn_ddim_sched_workspace_bytes)", workspace_bytes, need);
+    else
+      dn_set_error("dn_ddim_loop: workspace %zu < required %zu (see dn_ddim_workspace_bytes)", workspace_bytes, need);
     return DN_EWORKSPACE;
   }
   Arena core_ar{(char*)workspace, 0, core0};
@@ -666,14 +685,32 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
   float* cond_all = (float*)ar.take((size_t)start_step * C * 4);
   void* table_h = m->cfg.dtype == DN_F32 ? nullptr : ar.take((size_t)start_step * m->n_cond * esize(m->cfg.dtype));
   int32_t* tall = (int32_t*)ar.take((size_t)start_step * 4);
-  const int last = (start_step == 1 || op.ddpm) ? 0 : 1;  // DDIM: the loop breaks after the t == 1 update (:1444-1445); p_sample_loop runs t = 0 too
-  int n_eval = start_step - last;             // t = start_step-1 ... last
+  const int last = (start_step == 1 || op.ddpm || sched) ? 0 : 1;  // DDIM: the loop breaks after the t == 1 update (:1444-1445); p_sample_loop runs t = 0 too
+  int n_eval = start_step - last;             // t = start_step-1 ... last (a schedule: every one of its steps)
   if (max_evals > 0 && max_evals < n_eval) n_eval = max_evals;  // partial chain (benchmarks, chunked sampling)
   // The 56 conditioning vectors depend only on t: build them for the whole chain once (fp32), so the
   // 117 M conditioning weights are not re-streamed at every step.
   const bool keep = (flags & DN_LOOP_KEEP_TABLE) && m->table_ws == workspace && m->table_B == B && m->table_T == T &&
                     m->table_split == (int)split && m->table_rows >= start_step;
-  if (!keep) {
+  const float* step_coef = coef;  // what the captured step reads
+  if (sched) {
+    // row i of the table belongs to steps[i].  The schedule and its coefficient rows move into the workspace, so a captured step
+    // holds workspace addresses only: the steps where the other loops keep 0..start_step-1, the coefficients over `cond_all`
+    // (dn_ddim_sched_workspace_bytes: dead once the table is built, and C >= 64 floats a row against DN_DDIM_SCHED_COLS).
+    static_assert(DN_DDIM_SCHED_COLS <= 64, "the coefficient rows live in cond_all");
+    if (hipMemcpyAsync(tall, op.steps, (size_t)start_step * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+      dn_set_error("dn_ddim_sched_loop: copying the schedule failed");
+      return DN_ELAUNCH;
+    }
+    DN_TRY(eps_cond_rows(m, tall, start_step, cond_all, table, table_h, s));
+    if (hipMemcpyAsync(cond_all, coef, (size_t)start_step * DN_DDIM_SCHED_COLS * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+      dn_set_error("dn_ddim_sched_loop: copying the coefficient rows failed");
+      return DN_ELAUNCH;
+    }
+    step_coef = cond_all;
+    m->table_ws = nullptr;  // (not a table DN_LOOP_KEEP_TABLE could continue on)
+    m->table_rows = 0;
+  } else if (!keep) {
     hipLaunchKernelGGL(iota_kernel, dim3((start_step + 255) / 256), dim3(256), 0, s, tall, start_step);
     DN_TRY(eps_cond_rows(m, tall, start_step, cond_all, table, table_h, s));
     m->table_ws = workspace; m->table_B = B; m->table_T = T; m->table_split = (int)split; m->table_rows = start_step;
@@ -681,7 +718,8 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
   const int noise_top = start_step - 1;  // injected noise: row (noise_top - t) belongs to step t
   const int32_t twin = split ? DN_GEMM_TWIN : 0;  // every contraction of a half batch has its twin beside it (tile choice)
   auto one_step = [&]() -> int {
-    hipLaunchKernelGGL(fill_t_kernel, dim3((B + 255) / 256), dim3(256), 0, s, tvec, B, counter);
+    if (!sched)  // (the scheduled update reads its row by the counter: no per-sample step vector)
+      hipLaunchKernelGGL(fill_t_kernel, dim3((B + 255) / 256), dim3(256), 0, s, tvec, B, counter);
     hipLaunchKernelGGL(copy_cond_row_kernel, dim3(32), dim3(256), 0, s, table, m->n_row, counter, bufs.gb);
     if (split) {  // fork: the second half runs on the side stream behind the shared conditioning row
       const size_t off = (size_t)B0 * T * z;
@@ -690,14 +728,19 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
         return DN_ELAUNCH;
       }
       DN_TRY(eps_core(m, x + off, bufs.gb, 0, lengths + B0, B1, T, eps + off, bufs1, s2, twin));
-      if (op.ddpm)
+      if (sched)  // (the whole batch's element index keys the draw: the halves share one stream of numbers)
+        DN_TRY(dn_ddim_sched_step_launch(x, eps, (int64_t)off, (int64_t)B1 * T * z, step_coef, tall, counter, op.eta_on, op.noise, (int64_t)M * z,
+                                         op.seed, s2));
+      else if (op.ddpm)
         DN_TRY(dn_ddpm_step_launch(x + off, eps + off, B1 * T, z, T, coef, tvec + B0, op.clip, op.noise ? op.noise + off : nullptr, (int64_t)M * z,
                                    noise_top, op.seed ^ 0x9E3779B97F4A7C15ull, s2));  // (the second half draws from its own key)
       else
         DN_TRY(dn_ddim_step(x + off, eps + off, x + off, nullptr, DN_F32, z, B1 * T, z, z, T, coef, tvec + B0, s2));
     }
     DN_TRY(eps_core(m, x, bufs.gb, 0, lengths, B0, T, eps, bufs, s, twin));
-    if (op.ddpm)
+    if (sched)
+      DN_TRY(dn_ddim_sched_step_launch(x, eps, 0, (int64_t)B0 * T * z, step_coef, tall, counter, op.eta_on, op.noise, (int64_t)M * z, op.seed, s));
+    else if (op.ddpm)
       DN_TRY(dn_ddpm_step_launch(x, eps, B0 * T, z, T, coef, tvec, op.clip, op.noise, (int64_t)M * z, noise_top, op.seed, s));
     else
       DN_TRY(dn_ddim_step(x, eps, x, nullptr, DN_F32, z, B0 * T, z, z, T, coef, tvec, s));
@@ -707,20 +750,25 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
         return DN_ELAUNCH;
       }
     }
-    hipLaunchKernelGGL(dec_counter_kernel, dim3(1), dim3(1), 0, s, counter);
+    if (sched)
+      hipLaunchKernelGGL(inc_counter_kernel, dim3(1), dim3(1), 0, s, counter);
+    else
+      hipLaunchKernelGGL(dec_counter_kernel, dim3(1), dim3(1), 0, s, counter);
     DN_CHECK_LAUNCH("dn_ddim_loop step");
     return DN_OK;
   };
-  hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(1), 0, s, counter, start_step - 1);
+  hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(1), 0, s, counter, sched ? 0 : start_step - 1);
   int done = 0;
   if (!s) use_graph = 0;  // the null stream cannot be captured
   if (use_graph && n_eval > 2) {
-    const int gflags = (flags & ~DN_LOOP_KEEP_TABLE) | (op.ddpm ? 1 << 16 : 0) | (op.clip ? 1 << 17 : 0);
+    // (a scheduled chain's graph is keyed by the workspace copy of its coefficients: an address that moves with n_steps)
+    const int gflags = (flags & ~DN_LOOP_KEEP_TABLE) | (op.ddpm ? 1 << 16 : 0) | (op.clip ? 1 << 17 : 0) | (sched ? 1 << 18 : 0) |
+                       (op.eta_on ? 1 << 19 : 0);
     // (an injected-noise chain bakes noise_top into the captured step: never served from the cache)
     // (a dn_set_option since the capture may route the contractions differently: a miss)
     const int opt_gen = dn::option_generation();
     const bool cached = m->graph_exec && m->graph_B == B && m->graph_T == T && m->graph_ws == workspace && m->graph_x == x &&
-                        m->graph_len == lengths && m->graph_coef == coef && m->graph_flags == gflags && !op.noise &&
+                        m->graph_len == lengths && m->graph_coef == step_coef && m->graph_flags == gflags && !op.noise &&
                         m->graph_seed == op.seed && m->graph_opt_gen == opt_gen;
     if (!cached) {
       DN_TRY(one_step());  // eager first step: also settles the per-kernel attributes outside capture
@@ -749,7 +797,7 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
         return DN_ELAUNCH;
       }
       m->graph_exec = exec; m->graph_B = B; m->graph_T = T; m->graph_ws = workspace; m->graph_x = x;
-      m->graph_len = lengths; m->graph_coef = coef; m->graph_flags = op.noise ? -1 : gflags; m->graph_seed = op.seed;
+      m->graph_len = lengths; m->graph_coef = step_coef; m->graph_flags = op.noise ? -1 : gflags; m->graph_seed = op.seed;
       m->graph_opt_gen = opt_gen;
     }
     for (; done < n_eval; ++done) {
@@ -777,6 +825,33 @@ extern "C" int dn_ddpm_loop(DnEps* m, float* x, const int32_t* lengths, int32_t 
   StepOp op;
   op.ddpm = true; op.clip = clip_denoised; op.seed = seed; op.noise = noise;
   return sampler_loop(m, x, lengths, B, T, start_step, max_evals, table, timesteps, flags, workspace, workspace_bytes, stream, op);
+}
+
+// rows of cond_all (C fp32 each) hold the chain's coefficient rows after the table is built: the same bytes as dn_ddim_loop's for
+// start_step = n_steps
+extern "C" size_t dn_ddim_sched_workspace_bytes(const DnEps* m, int32_t B, int32_t T, int32_t n_steps) {
+  return dn_ddim_workspace_bytes(m, B, T, n_steps);
+}
+
+extern "C" int dn_ddim_sched_check(const int32_t* steps, int32_t n_steps, int32_t timesteps) {
+  DN_CHECK_ARG(steps && timesteps >= 1, "dn_ddim_sched_check: null schedule or timesteps=%d", timesteps);
+  DN_CHECK_ARG(n_steps >= 1, "dn_ddim_sched_check: the schedule is empty");
+  DN_CHECK_ARG(n_steps <= timesteps, "dn_ddim_sched_check: %d steps do not fit into %d timesteps", n_steps, timesteps);
+  for (int i = 0; i < n_steps; ++i) {
+    DN_CHECK_ARG(steps[i] >= 0 && steps[i] < timesteps, "dn_ddim_sched_check: step %d = %d is outside [0, %d]", i, steps[i], timesteps - 1);
+    DN_CHECK_ARG(i == 0 || steps[i] < steps[i - 1], "dn_ddim_sched_check: step %d = %d does not descend from %d", i, steps[i], steps[i - 1]);
+  }
+  return DN_OK;
+}
+
+extern "C" int dn_ddim_sched_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, const int32_t* steps, const float* coef,
+                                  int32_t n_steps, int32_t timesteps, int32_t eta_on, uint64_t seed, const float* noise, int32_t flags,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  DN_CHECK_ARG(steps, "dn_ddim_sched_loop: null schedule");
+  DN_CHECK_ARG(!(flags & ~(DN_LOOP_GRAPH | DN_LOOP_SPLIT2)), "dn_ddim_sched_loop: flags=%d (DN_LOOP_GRAPH | DN_LOOP_SPLIT2 only)", flags);
+  StepOp op;
+  op.steps = steps; op.n_steps = n_steps; op.eta_on = eta_on != 0; op.seed = op.eta_on ? seed : 0; op.noise = noise;
+  return sampler_loop(m, x, lengths, B, T, 0, 0, coef, timesteps, flags, workspace, workspace_bytes, stream, op);
 }
 
 

@@ -308,6 +308,47 @@ __device__ __forceinline__ void philox_normal4(uint64_t seed, uint64_t ctr_lo, u
   }
 }
 
+// ------------------------------------------------------------------------------------------ scheduled DDIM step of the device loop
+// One update of a DDIM chain over a timestep schedule (dn_ddim_sched_loop): row i = *counter of `coef` [n, DN_DDIM_SCHED_COLS] =
+// {sqrt abar_e, sqrt(1-abar_e), sqrt abar_tgt, sqrt(1-abar_tgt-sigma^2), sigma}, uniform over the batch.  eta_on == 0: the
+// statements of ddim_step_kernel, product for product (as compiled: see the loop).  eta_on: + 1[e_i != 0] sigma z (diffusion/gaussian_diffusion.py:513-560), z
+// injected (row i of `noise`) or drawn here: Philox4x32-10, key = seed, counter = (element quad OF THE WHOLE BATCH, step index i) --
+// a half-batch launch passes its first quad (q0), so eager, graph replay and the two half-batch streams draw the same numbers.
+__global__ __launch_bounds__(256) void ddim_sched_step_kernel(float* x, const float* __restrict__ eps, int64_t q0, int64_t nquad,
+                                                              const float* __restrict__ coef, const int32_t* __restrict__ steps,
+                                                              const int32_t* __restrict__ counter, int eta_on,
+                                                              const float* __restrict__ noise, int64_t noise_row, uint64_t seed) {
+  const int step = *counter;
+  const float* cf = coef + (int64_t)step * DN_DDIM_SCHED_COLS;
+  const float sa = cf[0], s1 = cf[1], ct = cf[2], cd = cf[3];
+  const float sg = (eta_on && steps[step] != 0) ? cf[4] : 0.0f;
+  for (int64_t q = q0 + blockIdx.x * 256 + threadIdx.x; q < q0 + nquad; q += (int64_t)gridDim.x * 256) {
+    const int64_t i = q << 2;
+    const float4 xv = *reinterpret_cast<const float4*>(x + i), ev = *reinterpret_cast<const float4*>(eps + i);
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (eta_on) {
+      if (noise) {
+        const float4 nv = *reinterpret_cast<const float4*>(noise + (int64_t)step * noise_row + i);
+        z[0] = nv.x; z[1] = nv.y; z[2] = nv.z; z[3] = nv.w;
+      } else {
+        philox_normal4(seed, (uint64_t)q, (uint32_t)step, z);
+      }
+    }
+    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, es[4] = {ev.x, ev.y, ev.z, ev.w};
+    float o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      // ddim_step_kernel's statements as the compiler builds them (products contracted into the sums that take them: x - s1 eps,
+      // x - sa x1, and x1 c2 onto the rounded c3 pn), spelled out so that the two kernels cannot be contracted differently
+      const float x1 = __fdiv_rn(fmaf(-s1, es[j], xs[j]), fmaxf(sa, 1e-10f));
+      const float pn = __fdiv_rn(fmaf(-sa, x1, xs[j]), fmaxf(s1, 1e-10f));
+      const float r = fmaf(ct, x1, __fmul_rn(cd, pn));
+      o[j] = eta_on ? fmaf(sg, z[j], r) : r;
+    }
+    *reinterpret_cast<float4*>(x + i) = make_float4(o[0], o[1], o[2], o[3]);
+  }
+}
+
 // ------------------------------------------------------------------------------------------ convert rows
 __global__ __launch_bounds__(256) void convert_rows_kernel(const void* __restrict__ src, int sdt, int lds, void* __restrict__ dst, int ddt,
                                                            int ldd, int M, int C) {
@@ -567,6 +608,16 @@ int dn_ddpm_step_launch(float* x, const float* eps, int M, int C, int T, const f
   hipLaunchKernelGGL(ddpm_step_kernel, dim3(ew_grid(((int64_t)M * C) >> 2)), dim3(256), 0, stream, x, eps, M, C, T, table, t, clip, noise,
                      noise_row, t_top, seed);
   DN_CHECK_LAUNCH("dn_ddpm_loop step");
+  return DN_OK;
+}
+
+// (engine.hip: the update of dn_ddim_sched_loop; x, eps, noise: the whole batch's; [elem0, elem0 + n_elem): this launch's elements)
+int dn_ddim_sched_step_launch(float* x, const float* eps, int64_t elem0, int64_t n_elem, const float* coef, const int32_t* steps,
+                              const int32_t* counter, int eta_on, const float* noise, int64_t noise_row, uint64_t seed, hipStream_t stream) {
+  DN_CHECK_ARG(elem0 % 4 == 0 && n_elem % 4 == 0 && n_elem > 0, "dn_ddim_sched_loop: the latent width must be a multiple of 4");
+  hipLaunchKernelGGL(ddim_sched_step_kernel, dim3(ew_grid(n_elem >> 2)), dim3(256), 0, stream, x, eps, elem0 >> 2, n_elem >> 2, coef, steps,
+                     counter, eta_on, noise, noise_row, seed);
+  DN_CHECK_LAUNCH("dn_ddim_sched_loop step");
   return DN_OK;
 }
 

@@ -347,6 +347,36 @@ class EpsEngine(_Engine):
                                                     (1 if use_graph else 0) | (2 if split else 0) | (4 if keep_table else 0), wp, wn,
                                                     _lib.current_stream()), "dn_ddpm_loop")
 
+    def ddim_schedule_loop(self, x: torch.Tensor, lengths: torch.Tensor, steps: torch.Tensor, coef: torch.Tensor, eta: float = 0.0,
+                           seed: int = 0, noise: Optional[torch.Tensor] = None, use_graph: bool = True, split: bool = True,
+                           timesteps: Optional[int] = None) -> int:
+        """In-place DDIM chain on x [B,T,z] fp32 over a timestep schedule (dn_ddim_sched_loop): `steps` int32 [n] strictly descending,
+        `coef` fp32 [n, 5], both from `scheduler.ddim_schedule` (built with the same `eta`).  One evaluation per step; the
+        conditioning table and the workspace have n rows.  eta > 0 adds sigma z after every update but one at timestep 0: z drawn
+        in the update kernel (Philox keyed by `seed`, the step index and the element's index in the whole batch -- eager, graph and
+        split chains agree bit for bit) or injected, noise [n, B, T, z], row i for update i.  `timesteps`: the length of the noise
+        schedule the steps index (the entry refuses a list longer than that).  Returns the number of evaluations."""
+        B, T, z = x.shape
+        assert x.is_contiguous() and x.dtype == torch.float32 and x.device == self.device
+        n = int(steps.shape[0])
+        assert steps.dtype == torch.int32 and steps.is_contiguous() and steps.device == self.device and steps.dim() == 1
+        assert coef.dtype == torch.float32 and coef.is_contiguous() and coef.device == self.device and coef.shape == (n, _lib.DDIM_SCHED_COLS)
+        l32 = lengths if (lengths.dtype == torch.int32 and lengths.device == self.device) else _i32(lengths, self.device)
+        nz = None
+        if noise is not None:
+            if not eta > 0:
+                raise ValueError("ddim_schedule_loop: injected noise needs eta > 0 (eta = 0 draws none)")
+            nz = _f32(noise, self.device)
+            assert nz.shape == (n, B, T, z), (nz.shape, (n, B, T, z))
+        self._keep = (l32, steps, coef, nz)
+        ws = self._workspace(int(self.lib.dn_ddim_sched_workspace_bytes(self.handle, B, T, n)))
+        wp, wn = self._aligned(ws)
+        with torch.cuda.device(self.device):
+            return _lib.check(self.lib.dn_ddim_sched_loop(self.handle, x.data_ptr(), l32.data_ptr(), B, T, steps.data_ptr(), coef.data_ptr(), n,
+                                                          n if timesteps is None else int(timesteps), int(eta > 0), int(seed) & (2 ** 64 - 1), _lib.ptr(nz),
+                                                          (1 if use_graph else 0) | (2 if split else 0), wp, wn, _lib.current_stream()),
+                              "dn_ddim_sched_loop")
+
 
 class VaeEngine(_Engine):
     """SpeechVAEEncoderDecoder (reference latent_module.py:1035-1142) on the GPU."""

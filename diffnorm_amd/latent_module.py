@@ -546,8 +546,18 @@ class LatentDiscreteModel(nn.Module):
 
     @torch.no_grad()
     def ddim_sample(self, tgt_feature, prompt=None, prompt_mask=None, input_mask=None, cond_scale=1., ref_units=None,
-                    start_step=50, post_noise=None, start_noise=None, use_graph=True):
-        """-> (list of unit tensors, match, total, recon_feature), as upstream (:1385-1471)."""
+                    start_step=50, post_noise=None, start_noise=None, use_graph=True, sampling_steps=None, timestep_schedule=None,
+                    eta=0.0, seed=0, step_noise=None):
+        """-> (list of unit tensors, match, total, recon_feature), as upstream (:1385-1471).
+
+        `sampling_steps` = N runs the chain on N of the timesteps start_step-1 .. 1 (scheduler.ddim_steps: uniformly spread, N =
+        start_step-1 is every timestep), `timestep_schedule` on an explicit strictly descending list; `eta` > 0 adds the DDIM noise
+        (diffusion/gaussian_diffusion.py:513-560), drawn on the device from `seed` or injected as `step_noise` [n, B, T, z].  With
+        all of them unset the chain is the reference's: every timestep, eta = 0."""
+        scheduled = sampling_steps is not None or timestep_schedule is not None or eta != 0.0 or step_noise is not None
+        if scheduled and self.use_cond:
+            raise ValueError("ddim_sample: sampling_steps / timestep_schedule / eta cover the unconditional model (the prompted, "
+                             "guided chain walks every timestep)")
         dev = self.device
         coef, sa, s1 = self._tables()
         B, T, _ = tgt_feature.shape
@@ -568,6 +578,10 @@ class LatentDiscreteModel(nn.Module):
                 raise ValueError("use_cond: ddim_sample needs prompt and prompt_mask")
             plens = _mask_to_lengths(prompt_mask.to(dev))
             self.model.engine().guided_ddim_chain(x, lengths, prompt, plens, start_step, coef, cond_scale=cond_scale, use_graph=use_graph)
+        elif scheduled:
+            steps, rows = self.scheduler.ddim_schedule(start_step, sampling_steps, timestep_schedule, eta=eta, device=dev)
+            self.model.engine().ddim_schedule_loop(x, lengths, steps, rows, eta=eta, seed=seed, noise=step_noise, use_graph=use_graph,
+                                                   timesteps=self.timesteps)
         else:
             self.model.engine().ddim_loop(x, lengths, start_step, coef, use_graph=use_graph)    # (:1411-1445)
         recon, _, units = self.speech_decoder.engine().decode(x, lengths, want_logits=False)     # (:1448-1451)

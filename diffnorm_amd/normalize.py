@@ -70,9 +70,10 @@ def tsv_line(it: Utterance, pred_units: Sequence[int]) -> str:
 
 
 def normalize(ddim_sample: Callable, utterances: Sequence[Utterance], start_step: int = 50, batch_size: int = 100,
-              device="cuda:0", group=None) -> Optional[List[str]]:
+              device="cuda:0", group=None, sampling_steps: Optional[int] = None, eta: float = 0.0, seed: int = 0) -> Optional[List[str]]:
     """Runs `ddim_sample(feat, input_mask=..., ref_units=..., start_step=...)` (LatentDiscreteModel.ddim_sample) over this
-    rank's batches and gathers the TSV lines of all ranks in utterance order (every rank returns the full list)."""
+    rank's batches and gathers the TSV lines of all ranks in utterance order (every rank returns the full list).
+    `sampling_steps` (evaluations per chain instead of start_step-1), `eta` and `seed` reach `ddim_sample` only when set."""
     rank, world = sharding.rank_world(group)
     # A run must give the same results on any number of ranks (and whatever sizes the last batches have).  The 2-byte / f32
     # contractions' fast K order (taps of a causal conv innermost, one staged copy of the rows, on the two 256-row tiles) sums in a
@@ -89,12 +90,17 @@ def normalize(ddim_sample: Callable, utterances: Sequence[Utterance], start_step
     batches = sharding.batch_indices(len(utterances), batch_size)
     mine = sharding.my_batches(len(batches), rank, world)
     local = []
+    extra = {}
+    if sampling_steps is not None:
+        extra["sampling_steps"] = sampling_steps
+    if eta != 0.0:
+        extra.update(eta=eta, seed=seed)
     with _lib.option("taps_inner", 2 if chosen is None else chosen):
         for b in mine:
             items = [utterances[i] for i in batches[b]]
             feat, ref_units, lens = assemble_batch(items, device)
             mask = torch.arange(feat.shape[1], device=lens.device).view(1, -1) < lens.view(-1, 1)
-            pred, _, _, _ = ddim_sample(feat, input_mask=mask, cond_scale=1.0, ref_units=ref_units, start_step=start_step)
+            pred, _, _, _ = ddim_sample(feat, input_mask=mask, cond_scale=1.0, ref_units=ref_units, start_step=start_step, **extra)
             local.append([tsv_line(it, p.tolist()) for it, p in zip(items, pred)])
     per_batch = sharding.gather_in_order(local, mine, len(batches), group)
     return [line for lines in per_batch for line in lines]

@@ -82,6 +82,68 @@ class ScheduleTables:
         t = torch.stack([sa, s1, torch.sqrt(abp), torch.sqrt(1 - abp)], dim=1).contiguous()  # torch.sqrt, as upstream
         return t.to(device) if device is not None else t
 
+    def ddim_steps(self, start_step: int, sampling_steps=None, steps=None) -> list:
+        """The evaluation timesteps e_0 > ... > e_{n-1} of a DDIM chain entered at `start_step` (x noised by q_sample at
+        start_step and treated as level e_0 = start_step-1, reference latent_module.py:1405-1445):
+
+        * `steps`: an explicit list -- non-empty, strictly descending, inside [0, timesteps-1];
+        * `sampling_steps` = N evaluations spread uniformly over start_step-1 .. 1 (2 <= start_step, 1 <= N <= start_step-1):
+          e_i = (start_step-1) - floor((2 i (start_step-2) + (N-1)) / (2 (N-1))), integers, halves rounded up (N = 1: [start_step-1]);
+          N = start_step-1 is every timestep;
+        * neither: every timestep, start_step-1 .. 1 ([0] when start_step == 1) -- the chain of `ddim_coef_table`."""
+        T = self.num_timesteps
+        if steps is not None:
+            if sampling_steps is not None:
+                raise ValueError("ddim_schedule: give sampling_steps or an explicit list of steps, not both")
+            e = [int(v) for v in (steps.tolist() if hasattr(steps, "tolist") else steps)]
+            if not e:
+                raise ValueError("ddim_schedule: the schedule is empty")
+            for i, v in enumerate(e):
+                if not 0 <= v <= T - 1:
+                    raise ValueError(f"ddim_schedule: step {i} = {v} is outside [0, {T - 1}]")
+                if i and v >= e[i - 1]:
+                    raise ValueError(f"ddim_schedule: step {i} = {v} does not descend from {e[i - 1]}")
+            return e
+        s = int(start_step)
+        if not 1 <= s <= T - 1:
+            raise ValueError(f"ddim_schedule: start_step={s} must be in [1, {T - 1}]")
+        if sampling_steps is None:
+            return list(range(s - 1, 0, -1)) if s > 1 else [0]
+        N = int(sampling_steps)
+        if s < 2 or not 1 <= N <= s - 1:
+            raise ValueError(f"ddim_schedule: sampling_steps={N} must be in [1, start_step-1 = {s - 1}] (start_step >= 2)")
+        if N == 1:
+            return [s - 1]
+        return [(s - 1) - (2 * i * (s - 2) + (N - 1)) // (2 * (N - 1)) for i in range(N)]
+
+    def ddim_schedule(self, start_step: int, sampling_steps=None, steps=None, eta: float = 0.0, device=None):
+        """-> (steps int32 [n], coef fp32 [n, 5]) of dn_ddim_sched_loop for the chain `ddim_steps` selects.  Update i moves x from
+        abar[e_i] to abar_tgt(i) = abar[e_{i+1}]; the last one to abar[0], or to 1 (alphas_cumprod_prev[0]) when e_{n-1} == 0.
+        Row i = {sqrt abar_e, sqrt(1-abar_e), sqrt abar_tgt, sqrt(1-abar_tgt-sigma^2), sigma} with sigma = eta sqrt((1-abar_tgt) /
+        (1-abar_e)) sqrt(1 - abar_e/abar_tgt) (reference diffusion/gaussian_diffusion.py:513-560).  eta == 0: columns 0-3 are formed
+        as `ddim_coef_table` forms them (2 and 3 in fp32 from the fp32-cast abar_tgt), so every-timestep rows are its rows bit for
+        bit; eta > 0: columns 3 and 4 in float64, then cast."""
+        eta = float(eta)
+        if not eta >= 0.0:
+            raise ValueError(f"ddim_schedule: eta={eta} must be >= 0")
+        e = np.asarray(self.ddim_steps(start_step, sampling_steps, steps), dtype=np.int64)
+        ab = self.alphas_cumprod[e]
+        ab_tgt = np.append(self.alphas_cumprod[e[1:]], self.alphas_cumprod[0] if e[-1] >= 1 else 1.0)
+        abt32 = torch.from_numpy(ab_tgt.astype(np.float32))
+        sa = torch.from_numpy(self.sqrt_alphas_cumprod[e].astype(np.float32))
+        s1 = torch.from_numpy(self.sqrt_one_minus_alphas_cumprod[e].astype(np.float32))
+        if eta == 0.0:
+            direction, sigma = torch.sqrt(1 - abt32), torch.zeros_like(abt32)
+        else:
+            sg = eta * np.sqrt((1.0 - ab_tgt) / (1.0 - ab)) * np.sqrt(1.0 - ab / ab_tgt)
+            if (1.0 - ab_tgt - sg ** 2 < 0.0).any():
+                raise ValueError(f"ddim_schedule: eta={eta} leaves no variance for the direction term (sigma^2 > 1 - abar_tgt)")
+            direction = torch.from_numpy(np.sqrt(1.0 - ab_tgt - sg ** 2).astype(np.float32))
+            sigma = torch.from_numpy(sg.astype(np.float32))
+        coef = torch.stack([sa, s1, torch.sqrt(abt32), direction, sigma], dim=1).contiguous()
+        st = torch.from_numpy(e.astype(np.int32))
+        return (st.to(device), coef.to(device)) if device is not None else (st, coef)
+
 
 class DDPMScheduler(ScheduleTables):
     """Cosine schedule with the getters of the reference class (latent_module.py:1241-1297).

@@ -648,6 +648,31 @@ int dn_ddpm_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t 
                  const float* table, int32_t timesteps, int32_t clip_denoised, uint64_t seed, const float* noise, int32_t flags,
                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* A DDIM chain over a timestep schedule: strided steps and eta (GaussianDiffusion.ddim_sample, diffusion/gaussian_diffusion.py:
+ * 513-560, on a sub-sequence of the timesteps as SpacedDiffusion / space_timesteps select one, diffusion/respace.py:12-115; entered
+ * like LatentDiscreteModel.ddim_sample's loop, latent_module.py:1405-1445).  The chain is a strictly descending list of evaluation
+ * timesteps e_0 > ... > e_{n-1} >= 0 (steps: device int32 [n_steps]); x enters at level abar[e_0]; update i moves x from abar[e_i]
+ * to abar_tgt(i) = abar[e_{i+1}], the last one to abar[0] (e_{n-1} >= 1) or to 1 (e_{n-1} == 0).  e = [s-1 .. 1] is dn_ddim_loop's
+ * chain at start_step = s, bit for bit; e = [0] its start_step == 1.
+ * coef: device fp32 [n_steps, DN_DDIM_SCHED_COLS], row i = {sqrt abar_e, sqrt(1-abar_e), sqrt abar_tgt, sqrt(1-abar_tgt-sigma^2),
+ * sigma}, sigma = eta sqrt((1-abar_tgt)/(1-abar_e)) sqrt(1-abar_e/abar_tgt).  The update, fp32, safe-div form of dn_ddim_step:
+ *   x1 = (x - s1 eps) / max(sa, 1e-10); pn = (x - sa x1) / max(s1, 1e-10); x <- x1 c2 + c3 pn [+ 1[e_i != 0] sigma z when eta_on].
+ * z: injected -- noise fp32 [n_steps, B*T*latent], row i for update i -- or, noise == NULL, Philox4x32-10 keyed by `seed` with the
+ * counter (element quad of the whole batch, step index i): the draw of an element depends on (seed, i, element) only, so eager,
+ * graph replay and the two half-batch streams agree bit for bit.  eta_on == 0: no noise is drawn, `noise` must be NULL.
+ * The conditioning table has n_steps rows (row i for e_i), and the workspace scales with n_steps: dn_ddim_sched_workspace_bytes
+ * (= dn_ddim_workspace_bytes at start_step = n_steps).  steps and coef are copied into the workspace at chain start (device to
+ * device, on the stream): a captured step holds workspace addresses only.  flags: DN_LOOP_GRAPH | DN_LOOP_SPLIT2.  Unconditional
+ * model only.  Every argument check precedes the first HIP call; the CONTENT of `steps` is device memory the entry cannot read:
+ * dn_ddim_sched_check validates a HOST copy (non-empty, inside [0, timesteps-1], strictly descending) before it is uploaded.
+ * Returns the number of model evaluations (= n_steps) or a negative error.                                                       */
+#define DN_DDIM_SCHED_COLS 5
+size_t dn_ddim_sched_workspace_bytes(const DnEps* m, int32_t B, int32_t T, int32_t n_steps);
+int dn_ddim_sched_check(const int32_t* steps_host, int32_t n_steps, int32_t timesteps);
+int dn_ddim_sched_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, const int32_t* steps, const float* coef,
+                       int32_t n_steps, int32_t timesteps, int32_t eta_on, uint64_t seed, const float* noise, int32_t flags,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ VAE training step (BASELINE config 4) */
 /* speech_vae_decoder_loss training (reference SpeechVAEEncoderDecoder.forward latent_module.py:1118-1142 + the criterion
  * fairseq/criterions/speech_vae_decoder_loss.py:45-95) on flat buffers in the PACKED parameter layout (csrc/engine.h: rows
