@@ -228,6 +228,7 @@ SYMBOLS = {
     "dn_eps_forward_cond_ex": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _sz, _i32, _vp, _i32, _i32, _vp]),
     "dn_eps_cond_time_table_workspace_bytes": (_sz, [_vp, _i32]),
     "dn_eps_cond_time_table": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "dn_eps_cond_time_table_steps": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _sz, _vp]),
     "dn_eps_weights_changed": (C.c_int, [_vp]),
     "dn_vae_create": (C.c_int, [C.POINTER(VaeConfig), C.POINTER(_vp), _i32, C.POINTER(_vp)]),
     "dn_vae_destroy": (None, [_vp]),
@@ -240,6 +241,9 @@ SYMBOLS = {
     "dn_ddim_sched_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
     "dn_ddim_sched_check": (C.c_int, [_vp, _i32, _i32]),
     "dn_ddim_sched_loop": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, C.c_uint64, _vp, _i32, _vp, _sz, _vp]),
+    "dn_guided_ddim_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32, _i32]),
+    "dn_guided_ddim_loop": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _vp, _vp, _i32, _i32, _i32, C.c_uint64, _vp, _i32,
+                                      _vp, _sz, _vp]),
     "dn_cfg_combine": (C.c_int, [_vp, C.c_float, _i64, _vp, _vp]),
     "dn_nar_create": (C.c_int, [C.POINTER(NarConfig), C.POINTER(_vp), _i32, C.POINTER(_vp)]),
     "dn_nar_destroy": (None, [_vp]),

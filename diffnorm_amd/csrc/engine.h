@@ -127,6 +127,13 @@ struct DnEps {
   // DN_LOOP_KEEP_TABLE: the conditioning table built by the previous dn_ddim_loop call on this workspace
   void* table_ws;
   int table_B, table_T, table_split, table_rows;
+  // hipGraph cache of dn_guided_ddim_loop: a slot of its own (the unconditional loops neither serve nor evict it); the key is
+  // everything a captured kernel argument bakes in
+  void* gg_exec;
+  int gg_B, gg_T, gg_Tp, gg_n, gg_flags, gg_eta, gg_opt_gen;
+  uint32_t gg_scale_bits;
+  uint64_t gg_seed;
+  const void *gg_ws, *gg_x, *gg_len, *gg_prompt, *gg_plen, *gg_coef;
 };
 constexpr int kEpsTensors = 7 + dn::kWavenetTensors + dn::kTransformerTensors + 3;
 // conditional variant (cfg.dim_prompt > 0), appended to the table: tpc_W (fp32 [padn(C)][padk(P)]), tpc_b [C], null_prompt_cond [C],

@@ -459,6 +459,7 @@ extern "C" int dn_eps_create(const DnEpsConfig* cfg, const void* const* weights,
 extern "C" void dn_eps_destroy(DnEps* m) {
   if (!m) return;
   if (m->graph_exec) (void)hipGraphExecDestroy((hipGraphExec_t)m->graph_exec);
+  if (m->gg_exec) (void)hipGraphExecDestroy((hipGraphExec_t)m->gg_exec);
   if (m->ev_fork) (void)hipEventDestroy((hipEvent_t)m->ev_fork);
   if (m->ev_join) (void)hipEventDestroy((hipEvent_t)m->ev_join);
   if (m->side_stream) (void)hipStreamDestroy((hipStream_t)m->side_stream);
@@ -594,6 +595,8 @@ extern "C" int dn_eps_weights_changed(DnEps* m) {
   DN_CHECK_ARG(m, "dn_eps_weights_changed: null engine");
   m->table_ws = nullptr;  // DN_LOOP_KEEP_TABLE: the next call rebuilds the conditioning table
   m->table_rows = 0;
+  // dn_guided_ddim_loop keeps nothing derived from the weights across calls: every call rebuilds its time table, and its eager
+  // first step recomputes the prompt-only state; its captured step holds addresses only
   return DN_OK;
 }
 
@@ -995,21 +998,38 @@ extern "C" size_t dn_eps_cond_time_table_workspace_bytes(const DnEps* m, int32_t
   if (!m || n_t <= 0) return 0;
   return (size_t)n_t * ((size_t)m->cfg.dim * m->cfg.cond_mult + 1) * 4 + 512;
 }
+// table[i] for the timesteps times[i] (device int32 [n_t]); cond: n_t * C floats of the workspace
+static int cond_time_table_rows(const DnEps* m, const int32_t* times, int n_t, float* table, float* cond, hipStream_t s) {
+  const int D = m->cfg.dim, C = D * m->cfg.cond_mult;
+  DN_TRY(dn_time_cond(times, n_t, m->w_freq, D / 2, m->tc_W, m->tc_b, C, cond, nullptr, DN_F32, C, s));
+  DnGemmParams p = gemm_base(DN_F32, n_t, m->n_cond, C, 1);
+  p.terms[0].A = cond; p.terms[0].lda = C; p.terms[0].W = m->cond_W; p.terms[0].ldw = 2 * C;
+  p.out = table; p.ldo = m->n_cond; p.out_dtype = DN_F32;
+  return dn_conv_gemm(&p, s);
+}
 extern "C" int dn_eps_cond_time_table(DnEps* m, int32_t t0, int32_t n_t, float* table, void* workspace, size_t workspace_bytes, void* stream) {
   DN_CHECK_ARG(m && table && workspace && n_t > 0 && t0 >= 0, "dn_eps_cond_time_table: bad argument");
   DN_CHECK_ARG(m->cfg.dim_prompt > 0, "dn_eps_cond_time_table: the model was created without a prompt branch");
   DN_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && workspace_bytes >= dn_eps_cond_time_table_workspace_bytes(m, n_t) - 256, "dn_eps_cond_time_table: workspace");
   hipStream_t s = (hipStream_t)stream;
-  const int D = m->cfg.dim, C = D * m->cfg.cond_mult;
   int32_t* times = (int32_t*)workspace;
   float* cond = (float*)((char*)workspace + (((size_t)n_t * 4 + 255) & ~(size_t)255));
   hipLaunchKernelGGL(dn::iota_i32_kernel, dim3((n_t + 255) / 256), dim3(256), 0, s, t0, times, n_t);
-  DN_TRY(dn_time_cond(times, n_t, m->w_freq, D / 2, m->tc_W, m->tc_b, C, cond, nullptr, DN_F32, C, s));
-  DnGemmParams p = gemm_base(DN_F32, n_t, m->n_cond, C, 1);
-  p.terms[0].A = cond; p.terms[0].lda = C; p.terms[0].W = m->cond_W; p.terms[0].ldw = 2 * C;
-  p.out = table; p.ldo = m->n_cond; p.out_dtype = DN_F32;
-  DN_TRY(dn_conv_gemm(&p, s));
+  DN_TRY(cond_time_table_rows(m, times, n_t, table, cond, s));
   DN_CHECK_LAUNCH("dn_eps_cond_time_table");
+  return DN_OK;
+}
+// The same table for a device list of timesteps (row i for steps[i]: the schedule of dn_guided_ddim_loop); the workspace of
+// dn_eps_cond_time_table_workspace_bytes(m, n_steps)
+extern "C" int dn_eps_cond_time_table_steps(DnEps* m, const int32_t* steps, int32_t n_steps, float* table, void* workspace, size_t workspace_bytes,
+                                            void* stream) {
+  DN_CHECK_ARG(m && steps && table && workspace && n_steps > 0, "dn_eps_cond_time_table_steps: bad argument");
+  DN_CHECK_ARG(m->cfg.dim_prompt > 0, "dn_eps_cond_time_table_steps: the model was created without a prompt branch");
+  DN_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && workspace_bytes >= dn_eps_cond_time_table_workspace_bytes(m, n_steps) - 256,
+               "dn_eps_cond_time_table_steps: workspace");
+  float* cond = (float*)((char*)workspace + (((size_t)n_steps * 4 + 255) & ~(size_t)255));
+  DN_TRY(cond_time_table_rows(m, steps, n_steps, table, cond, (hipStream_t)stream));
+  DN_CHECK_LAUNCH("dn_eps_cond_time_table_steps");
   return DN_OK;
 }
 
@@ -1161,6 +1181,176 @@ extern "C" int dn_eps_forward_cond_ex(DnEps* m, const float* x, const int32_t* t
   DN_TRY(dn_conv_gemm(&p, s));
   DN_CHECK_LAUNCH("dn_eps_forward_cond");
   return DN_OK;
+}
+
+// ------------------------------------------------------------------------------------------ guided chain over a timestep schedule
+int dn_guided_sched_step_launch(float* x, float* xin, const float* both, int64_t n_elem, int guided, float scale, const float* coef,
+                                const int32_t* steps, const int32_t* counter, int eta_on, const float* noise, int64_t noise_row, uint64_t seed,
+                                hipStream_t stream);  // pointwise.hip
+
+namespace {
+// drop mask of the guided pass over n rows = [conditioned (first B) ; null]
+__global__ void drop_mask_kernel(int32_t* drop, int n, int B) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) drop[i] = i >= B ? 1 : 0;
+}
+
+// The workspace of dn_guided_ddim_loop behind the model pass's own (`core` bytes at its start).  State whose size does not depend
+// on n_steps first; the second halves exist for the guided (2B-row) pass only -- at cond_scale == 1 the model reads x itself and
+// the caller's lengths / prompt / prompt lengths.
+struct GuidedBufs {
+  size_t core;
+  float *both, *xin, *prompt2, *table, *coef;
+  int32_t *tvec, *counter, *drop, *len2, *plen2, *steps;
+  void* tt_ws;
+  size_t tt_bytes;
+};
+
+GuidedBufs plan_guided(const DnEps* m, int B, int T, int Tp, int n_steps, bool guided, Arena& ar) {
+  const size_t n = guided ? 2 * (size_t)B : (size_t)B, Mz = (size_t)B * T * m->cfg.latent;
+  GuidedBufs g;
+  memset(&g, 0, sizeof(g));
+  Arena core{nullptr, 0, 0};
+  (void)plan_eps_cond(m, (int)n, T, Tp, core);
+  g.core = (core.off + 255) & ~(size_t)255;
+  (void)ar.take(g.core);
+  g.both = (float*)ar.take(n * T * m->cfg.latent * 4);
+  g.tvec = (int32_t*)ar.take(n * 4);
+  g.counter = (int32_t*)ar.take(64);
+  g.drop = (int32_t*)ar.take(n * 4);
+  if (guided) {
+    g.xin = (float*)ar.take(2 * Mz * 4);
+    g.len2 = (int32_t*)ar.take(n * 4);
+    g.plen2 = (int32_t*)ar.take(n * 4);
+    g.prompt2 = (float*)ar.take(n * Tp * m->cfg.dim_prompt * 4);
+  }
+  g.steps = (int32_t*)ar.take((size_t)n_steps * 4);
+  g.table = (float*)ar.take((size_t)n_steps * m->n_cond * 4);  // row i: the time half of the conditioning rows of steps[i]
+  g.coef = (float*)ar.take((size_t)n_steps * DN_DDIM_SCHED_COLS * 4);
+  g.tt_bytes = dn_eps_cond_time_table_workspace_bytes(m, n_steps);  // (dead once the table is built)
+  g.tt_ws = ar.take(g.tt_bytes);
+  return g;
+}
+}  // namespace
+
+extern "C" size_t dn_guided_ddim_workspace_bytes(const DnEps* m, int32_t B, int32_t T, int32_t Tp, int32_t n_steps, int32_t guided) {
+  if (!m || m->cfg.dim_prompt <= 0 || B <= 0 || T <= 0 || Tp <= 0 || n_steps < 1) return 0;
+  Arena ar{nullptr, 0, 0};
+  (void)plan_guided(m, B, T, Tp, n_steps, guided != 0, ar);
+  return ar.off + 256;
+}
+
+extern "C" int dn_guided_ddim_loop(DnEps* m, float* x, const int32_t* lengths, const float* prompt, const int32_t* prompt_lengths, int32_t B,
+                                   int32_t T, int32_t Tp, float cond_scale, const int32_t* steps, const float* coef, int32_t n_steps,
+                                   int32_t timesteps, int32_t eta_on, uint64_t seed, const float* noise, int32_t flags, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  DN_CHECK_ARG(m && x && lengths && prompt && prompt_lengths && steps && coef && workspace, "dn_guided_ddim_loop: null argument");
+  DN_CHECK_ARG(m->cfg.dim_prompt > 0, "dn_guided_ddim_loop: the model was created without a prompt branch (cfg.dim_prompt == 0): use dn_ddim_sched_loop");
+  DN_CHECK_ARG(!(flags & DN_LOOP_SPLIT2), "dn_guided_ddim_loop: DN_LOOP_SPLIT2 is not offered (the prompt-only state lives in one workspace, and the "
+               "guided pass already runs 2B rows)");
+  DN_CHECK_ARG(!(flags & ~DN_LOOP_GRAPH), "dn_guided_ddim_loop: flags=%d (DN_LOOP_GRAPH only)", flags);
+  DN_CHECK_ARG(n_steps >= 1 && n_steps <= timesteps, "dn_guided_ddim_loop: n_steps=%d must be in [1, %d]", n_steps, timesteps);
+  DN_CHECK_ARG(B > 0 && T > 0 && Tp > 0 && T <= m->cfg.max_pos, "dn_guided_ddim_loop: B=%d T=%d Tp=%d (positional table: %d)", B, T, Tp, m->cfg.max_pos);
+  DN_CHECK_ARG(cond_scale == cond_scale, "dn_guided_ddim_loop: cond_scale is not a number");
+  eta_on = eta_on != 0;
+  DN_CHECK_ARG(eta_on || !noise, "dn_guided_ddim_loop: injected noise needs eta_on (eta = 0 draws none)");
+  DN_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "dn_guided_ddim_loop: workspace must be 256-byte aligned");
+  const bool guided = cond_scale != 1.0f;
+  const size_t need = dn_guided_ddim_workspace_bytes(m, B, T, Tp, n_steps, guided);
+  if (need > workspace_bytes) {
+    dn_set_error("dn_guided_ddim_loop: workspace %zu < required %zu (see dn_guided_ddim_workspace_bytes)", workspace_bytes, need);
+    return DN_EWORKSPACE;
+  }
+  if (!eta_on) seed = 0;
+  hipStream_t s = (hipStream_t)stream;
+  Arena ar{(char*)workspace, 0, workspace_bytes};
+  const GuidedBufs g = plan_guided(m, B, T, Tp, n_steps, guided, ar);
+  const int n = guided ? 2 * B : B, z = m->cfg.latent;
+  const size_t Mz = (size_t)B * T * z;
+  // ---- chain start: the static inputs of the 2B-row pass, the model's first input, the schedule, its coefficient rows and its
+  // time table, all in the workspace (a captured step holds workspace addresses and x only)
+  auto copy = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) == hipSuccess; };
+  bool ok = copy(g.steps, steps, (size_t)n_steps * 4) && copy(g.coef, coef, (size_t)n_steps * DN_DDIM_SCHED_COLS * 4);
+  if (guided) {
+    const size_t pb = (size_t)B * Tp * m->cfg.dim_prompt * 4;
+    ok = ok && copy(g.len2, lengths, (size_t)B * 4) && copy(g.len2 + B, lengths, (size_t)B * 4) && copy(g.plen2, prompt_lengths, (size_t)B * 4) &&
+         copy(g.plen2 + B, prompt_lengths, (size_t)B * 4) && copy(g.prompt2, prompt, pb) && copy((char*)g.prompt2 + pb, prompt, pb) &&
+         copy(g.xin, x, Mz * 4) && copy(g.xin + Mz, x, Mz * 4);
+  }
+  if (!ok) {
+    dn_set_error("dn_guided_ddim_loop: copying the chain's inputs into the workspace failed");
+    return DN_ELAUNCH;
+  }
+  hipLaunchKernelGGL(drop_mask_kernel, dim3((n + 255) / 256), dim3(256), 0, s, g.drop, n, B);
+  hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(1), 0, s, g.counter, 0);
+  DN_TRY(dn_eps_cond_time_table_steps(m, g.steps, n_steps, g.table, g.tt_ws, g.tt_bytes, s));
+  float* xin = guided ? g.xin : x;
+  const int32_t *len = guided ? g.len2 : lengths, *plen = guided ? g.plen2 : prompt_lengths;
+  const float* prm = guided ? g.prompt2 : prompt;
+  // one step: the step-index vector (with a time table the pass uses `t` only to pick the table's row), the pass over n rows, the
+  // fused combination + update + refill of the model's input, the counter.  `reuse`: every step but the chain's first
+  auto one_step = [&](bool reuse) -> int {
+    hipLaunchKernelGGL(fill_t_kernel, dim3((n + 255) / 256), dim3(256), 0, s, g.tvec, n, g.counter);
+    DN_TRY(dn_eps_forward_cond_ex(m, xin, g.tvec, len, prm, plen, g.drop, n, T, Tp, g.both, workspace, g.core, reuse ? DN_COND_REUSE_PROMPT : 0,
+                                  g.table, 0, n_steps, s));
+    DN_TRY(dn_guided_sched_step_launch(x, xin, g.both, (int64_t)Mz, guided, cond_scale, g.coef, g.steps, g.counter, eta_on, noise, (int64_t)Mz, seed, s));
+    hipLaunchKernelGGL(inc_counter_kernel, dim3(1), dim3(1), 0, s, g.counter);
+    DN_CHECK_LAUNCH("dn_guided_ddim_loop step");
+    return DN_OK;
+  };
+  DN_TRY(one_step(false));  // eager: the prompt-only work, and the per-kernel attributes settle outside capture
+  int done = 1;
+  if ((flags & DN_LOOP_GRAPH) && s && n_steps > 2) {  // (the null stream cannot be captured)
+    uint32_t scale_bits;
+    memcpy(&scale_bits, &cond_scale, 4);
+    const int opt_gen = dn::option_generation();
+    // (an injected-noise chain is never served from the cache; a dn_set_option since the capture may route the contractions differently)
+    const bool cached = m->gg_exec && !noise && m->gg_flags == flags && m->gg_B == B && m->gg_T == T && m->gg_Tp == Tp && m->gg_n == n_steps &&
+                        m->gg_ws == workspace && m->gg_x == x && m->gg_len == lengths && m->gg_prompt == prompt && m->gg_plen == prompt_lengths &&
+                        m->gg_coef == g.coef && m->gg_scale_bits == scale_bits && m->gg_eta == eta_on && m->gg_seed == seed &&
+                        m->gg_opt_gen == opt_gen;
+    if (!cached) {
+      if (m->gg_exec) {
+        (void)hipGraphExecDestroy((hipGraphExec_t)m->gg_exec);
+        m->gg_exec = nullptr;
+      }
+      hipGraph_t graph = nullptr;
+      if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) != hipSuccess) {
+        dn_set_error("dn_guided_ddim_loop: hipStreamBeginCapture failed");
+        return DN_ELAUNCH;
+      }
+      const int rc = one_step(true);
+      hipError_t e = hipStreamEndCapture(s, &graph);
+      if (rc != DN_OK) {
+        if (graph) (void)hipGraphDestroy(graph);
+        return rc;
+      }
+      if (e != hipSuccess || !graph) {
+        dn_set_error("dn_guided_ddim_loop: hipStreamEndCapture: %s", hipGetErrorString(e));
+        return DN_ELAUNCH;
+      }
+      hipGraphExec_t exec = nullptr;
+      e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+      (void)hipGraphDestroy(graph);
+      if (e != hipSuccess) {
+        dn_set_error("dn_guided_ddim_loop: hipGraphInstantiate: %s", hipGetErrorString(e));
+        return DN_ELAUNCH;
+      }
+      m->gg_exec = exec; m->gg_flags = noise ? -1 : flags; m->gg_B = B; m->gg_T = T; m->gg_Tp = Tp; m->gg_n = n_steps;
+      m->gg_ws = workspace; m->gg_x = x; m->gg_len = lengths; m->gg_prompt = prompt; m->gg_plen = prompt_lengths; m->gg_coef = g.coef;
+      m->gg_scale_bits = scale_bits; m->gg_eta = eta_on; m->gg_seed = seed; m->gg_opt_gen = opt_gen;
+    }
+    for (; done < n_steps; ++done) {
+      const hipError_t e = hipGraphLaunch((hipGraphExec_t)m->gg_exec, s);
+      if (e != hipSuccess) {
+        dn_set_error("dn_guided_ddim_loop: hipGraphLaunch: %s", hipGetErrorString(e));
+        return DN_ELAUNCH;
+      }
+    }
+  } else {
+    for (; done < n_steps; ++done) DN_TRY(one_step(true));
+  }
+  return n_steps;
 }
 
 // =========================================================================================== VAE

@@ -349,6 +349,63 @@ __global__ __launch_bounds__(256) void ddim_sched_step_kernel(float* x, const fl
   }
 }
 
+// ------------------------------------------------------------------------------------------ guided scheduled DDIM step of the device loop
+// One update of the prompted, guided chain over a timestep schedule (dn_guided_ddim_loop), per float4 quad of the B-row latent:
+// eps = the conditioned row of `both` (kGuided: combined with the null row, n elements further, by cfg_combine_kernel's three rounded
+// operations), then ddim_sched_step_kernel's update, statement for statement, with its coefficient row, noise mask and noise source
+// (the Philox counter is the quad of the B-row batch and the step index, so a scale-1 chain draws what dn_ddim_sched_loop draws).
+// The result goes to x and to the model's next input: xin[0:n] and (kGuided) xin[n:2n] -- one pass where the host-driven chain
+// copies x twice, combines, updates and decrements.  !kGuided: nothing past n is touched, and xin may be x itself.
+// HBM-bound: (2 + kGuided) reads and (1 + 1 + kGuided) writes of n floats; 16-byte accesses, grid-stride, no LDS.
+template <bool kGuided, bool kEta>
+__global__ __launch_bounds__(256) void guided_sched_step_kernel(float* x, float* xin, const float* __restrict__ both, int64_t nquad, float scale,
+                                                                const float* __restrict__ coef, const int32_t* __restrict__ steps,
+                                                                const int32_t* __restrict__ counter, const float* __restrict__ noise,
+                                                                int64_t noise_row, uint64_t seed) {
+  const int step = *counter;
+  const float* cf = coef + (int64_t)step * DN_DDIM_SCHED_COLS;
+  const float sa = cf[0], s1 = cf[1], ct = cf[2], cd = cf[3];
+  const float sg = (kEta && steps[step] != 0) ? cf[4] : 0.0f;
+  const int64_t n = nquad << 2;
+  for (int64_t q = blockIdx.x * 256 + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * 256) {
+    const int64_t i = q << 2;
+    const float4 xv = *reinterpret_cast<const float4*>(x + i), cv = *reinterpret_cast<const float4*>(both + i);
+    float es[4] = {cv.x, cv.y, cv.z, cv.w};
+    if (kGuided) {
+      const float4 uv = *reinterpret_cast<const float4*>(both + n + i);
+      const float us[4] = {uv.x, uv.y, uv.z, uv.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) es[j] = __fadd_rn(us[j], __fmul_rn(__fsub_rn(es[j], us[j]), scale));
+    }
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (kEta) {
+      if (noise) {
+        const float4 nv = *reinterpret_cast<const float4*>(noise + (int64_t)step * noise_row + i);
+        z[0] = nv.x; z[1] = nv.y; z[2] = nv.z; z[3] = nv.w;
+      } else {
+        philox_normal4(seed, (uint64_t)q, (uint32_t)step, z);
+      }
+    }
+    const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+    float o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {  // (ddim_sched_step_kernel's spelling)
+      const float x1 = __fdiv_rn(fmaf(-s1, es[j], xs[j]), fmaxf(sa, 1e-10f));
+      const float pn = __fdiv_rn(fmaf(-sa, x1, xs[j]), fmaxf(s1, 1e-10f));
+      const float r = fmaf(ct, x1, __fmul_rn(cd, pn));
+      o[j] = kEta ? fmaf(sg, z[j], r) : r;
+    }
+    const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<float4*>(x + i) = ov;
+    if (kGuided) {
+      *reinterpret_cast<float4*>(xin + i) = ov;
+      *reinterpret_cast<float4*>(xin + n + i) = ov;
+    } else if (xin != x) {
+      *reinterpret_cast<float4*>(xin + i) = ov;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------ convert rows
 __global__ __launch_bounds__(256) void convert_rows_kernel(const void* __restrict__ src, int sdt, int lds, void* __restrict__ dst, int ddt,
                                                            int ldd, int M, int C) {
@@ -618,6 +675,24 @@ int dn_ddim_sched_step_launch(float* x, const float* eps, int64_t elem0, int64_t
   hipLaunchKernelGGL(ddim_sched_step_kernel, dim3(ew_grid(n_elem >> 2)), dim3(256), 0, stream, x, eps, elem0 >> 2, n_elem >> 2, coef, steps,
                      counter, eta_on, noise, noise_row, seed);
   DN_CHECK_LAUNCH("dn_ddim_sched_loop step");
+  return DN_OK;
+}
+
+// (engine.hip: the update of dn_guided_ddim_loop; n_elem = B*T*latent of the B-row latent; both / xin hold 2 n_elem floats when guided)
+int dn_guided_sched_step_launch(float* x, float* xin, const float* both, int64_t n_elem, int guided, float scale, const float* coef,
+                                const int32_t* steps, const int32_t* counter, int eta_on, const float* noise, int64_t noise_row, uint64_t seed,
+                                hipStream_t stream) {
+  DN_CHECK_ARG(n_elem % 4 == 0 && n_elem > 0, "dn_guided_ddim_loop: the latent width must be a multiple of 4");
+  const dim3 grid(ew_grid(n_elem >> 2)), block(256);
+#define DN_GUIDED_STEP(G, E) \
+  hipLaunchKernelGGL((guided_sched_step_kernel<G, E>), grid, block, 0, stream, x, xin, both, n_elem >> 2, scale, coef, steps, counter, noise, noise_row, seed)
+  if (guided) {
+    if (eta_on) DN_GUIDED_STEP(true, true); else DN_GUIDED_STEP(true, false);
+  } else {
+    if (eta_on) DN_GUIDED_STEP(false, true); else DN_GUIDED_STEP(false, false);
+  }
+#undef DN_GUIDED_STEP
+  DN_CHECK_LAUNCH("dn_guided_ddim_loop step");
   return DN_OK;
 }
 

@@ -159,8 +159,8 @@ class EpsEngine(_Engine):
           forgotten (dn_eps_weights_changed) -- the next call rebuilds it whatever `keep_table` says;
         * the captured hipGraph of the loop's step: kept.  It holds kernel launches over addresses (packed tensors, workspace,
           the conditioning table's rows), no values; every table it reads is rebuilt from the new weights before it is replayed;
-        * the time table of a prompted chain (dn_eps_cond_time_table) lives for one `guided_ddim_chain` call only, and the
-          prompt-conditioned engine has no training engine: refused here;
+        * the time table of a prompted chain (dn_eps_cond_time_table) lives for one `guided_ddim_chain` /
+          `guided_ddim_schedule_loop` call only, and the prompt-conditioned engine has no training engine: refused here;
         * nothing else: the sinusoidal table and the placeholders do not depend on the parameters, workspaces hold activations."""
         if self.conditional:
             raise NotImplementedError("refresh_from covers the unconditional eps-predictor (the prompt-conditioned model has no training engine)")
@@ -376,6 +376,56 @@ class EpsEngine(_Engine):
                                                           n if timesteps is None else int(timesteps), int(eta > 0), int(seed) & (2 ** 64 - 1), _lib.ptr(nz),
                                                           (1 if use_graph else 0) | (2 if split else 0), wp, wn, _lib.current_stream()),
                               "dn_ddim_sched_loop")
+
+    def cond_time_table_steps(self, steps) -> torch.Tensor:
+        """The time half of the conditioning rows of the timesteps `steps` (any list or int tensor; dn_eps_cond_time_table_steps):
+        fp32 [n, n_cond], row i for steps[i]."""
+        st = _i32(torch.as_tensor(steps), self.device)
+        assert st.dim() == 1 and st.numel() > 0
+        n = int(st.numel())
+        n_cond = len(packing.eps_cond_modules(self.cfg)) * 2 * packing.padk(self.cfg.dim)
+        table = torch.empty(n, n_cond, dtype=torch.float32, device=self.device)
+        ws = torch.empty(int(self.lib.dn_eps_cond_time_table_workspace_bytes(self.handle, n)) + 256, dtype=torch.uint8, device=self.device)
+        wp, wn = self._aligned(ws)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.dn_eps_cond_time_table_steps(self.handle, st.data_ptr(), n, table.data_ptr(), wp, wn, _lib.current_stream()),
+                       "dn_eps_cond_time_table_steps")
+        return table
+
+    def guided_ddim_schedule_loop(self, x: torch.Tensor, lengths, prompt, prompt_lengths, steps: torch.Tensor, coef: torch.Tensor,
+                                  cond_scale: float = 1.0, eta: float = 0.0, seed: int = 0, noise: Optional[torch.Tensor] = None,
+                                  use_graph: bool = True, timesteps: Optional[int] = None) -> int:
+        """In-place prompted, guided DDIM chain on x [B,T,z] fp32 over a timestep schedule (dn_guided_ddim_loop): `ddim_schedule_loop`'s
+        chain -- `steps` int32 [n] strictly descending and `coef` fp32 [n, 5] from `scheduler.ddim_schedule` (built with the same
+        `eta`), `seed`, injected `noise` [n, B, T, z], `timesteps` with its meaning -- with the guided prediction of
+        `forward_with_cond_scale` (one pass over 2B rows, or B rows at scale 1).  The whole loop runs behind the C entry: time table
+        of n rows, prompt-only work in the first step, one fused combination + update kernel per step, hipGraph replay.  On the
+        every-timestep schedule at eta = 0 it is `guided_ddim_chain` bit for bit.  Returns the number of evaluations."""
+        B, T, z = x.shape
+        assert x.is_contiguous() and x.dtype == torch.float32 and x.device == self.device
+        n = int(steps.shape[0])
+        assert steps.dtype == torch.int32 and steps.is_contiguous() and steps.device == self.device and steps.dim() == 1
+        assert coef.dtype == torch.float32 and coef.is_contiguous() and coef.device == self.device and coef.shape == (n, _lib.DDIM_SCHED_COLS)
+        l32 = lengths if (lengths.dtype == torch.int32 and lengths.device == self.device) else _i32(lengths, self.device)
+        pl32 = prompt_lengths if (prompt_lengths.dtype == torch.int32 and prompt_lengths.device == self.device) else _i32(prompt_lengths, self.device)
+        p32 = prompt if (prompt.dtype == torch.float32 and prompt.device == self.device and prompt.is_contiguous()) else _f32(prompt, self.device)
+        assert p32.dim() == 3 and p32.shape[0] == B and p32.shape[2] == self.cfg.dim_prompt and l32.shape == (B,) and pl32.shape == (B,)
+        Tp = int(p32.shape[1])
+        nz = None
+        if noise is not None:
+            if not eta > 0:
+                raise ValueError("guided_ddim_schedule_loop: injected noise needs eta > 0 (eta = 0 draws none)")
+            nz = _f32(noise, self.device)
+            assert nz.shape == (n, B, T, z), (nz.shape, (n, B, T, z))
+        self._keep = (l32, pl32, p32, steps, coef, nz)
+        ws = self._workspace(int(self.lib.dn_guided_ddim_workspace_bytes(self.handle, B, T, Tp, n, int(float(cond_scale) != 1.0))))
+        wp, wn = self._aligned(ws)
+        with torch.cuda.device(self.device):
+            return _lib.check(self.lib.dn_guided_ddim_loop(self.handle, x.data_ptr(), l32.data_ptr(), p32.data_ptr(), pl32.data_ptr(), B, T, Tp,
+                                                           float(cond_scale), steps.data_ptr(), coef.data_ptr(), n,
+                                                           n if timesteps is None else int(timesteps), int(eta > 0), int(seed) & (2 ** 64 - 1),
+                                                           _lib.ptr(nz), 1 if use_graph else 0, wp, wn, _lib.current_stream()),
+                              "dn_guided_ddim_loop")
 
 
 class VaeEngine(_Engine):

@@ -595,6 +595,43 @@ class LatentDiscreteModel(nn.Module):
         return out_tokens, match, total, recon
 
     @torch.no_grad()
+    def prompted_ddim_sample(self, tgt_feature, prompt, prompt_mask, input_mask=None, cond_scale=1., ref_units=None, start_step=50,
+                             sampling_steps=None, timestep_schedule=None, eta=0.0, seed=0, step_noise=None, post_noise=None,
+                             start_noise=None, use_graph=True):
+        """`ddim_sample` for the prompted model (use_cond) over a timestep schedule -> the same (list of unit tensors, match, total,
+        recon_feature).  Encode and q_sample as `ddim_sample`; the chain is the device loop dn_guided_ddim_loop
+        (EpsEngine.guided_ddim_schedule_loop): the guided prediction forward_with_cond_scale (:813-826) at every step of the schedule
+        `scheduler.ddim_schedule` selects -- `sampling_steps` = N of the timesteps start_step-1 .. 1, an explicit `timestep_schedule`,
+        or with neither every timestep, which is `ddim_sample`'s prompted chain bit for bit -- with `eta`, `seed` and `step_noise`
+        [n, B, T, z] as `ddim_sample` takes them for the unconditional model.  `ddim_sample` itself keeps refusing a schedule for the
+        prompted model; folding the two entries together is a later change."""
+        if not self.use_cond:
+            raise ValueError("prompted_ddim_sample: the model was built without use_cond (ddim_sample covers the unconditional model)")
+        if prompt is None or prompt_mask is None:
+            raise ValueError("prompted_ddim_sample: needs prompt and prompt_mask")
+        steps, rows = self.scheduler.ddim_schedule(start_step, sampling_steps, timestep_schedule, eta=eta)  # (validates, on the host)
+        dev = self.device
+        _, sa, s1 = self._tables()
+        B, T, _ = tgt_feature.shape
+        if input_mask is None:
+            input_mask = torch.ones(B, T, dtype=torch.bool, device=dev)
+        input_mask = input_mask.to(dev)
+        lengths = _mask_to_lengths(input_mask).to(torch.int32)
+        z = self.speech_decoder.encode_feature(tgt_feature, noise=post_noise).transpose(1, 2).contiguous()
+        if start_noise is None:
+            start_noise = torch.randn(z.shape, device=dev)
+        t_start = torch.full((B,), start_step, dtype=torch.int32, device=dev)
+        x = ops.q_sample(z, start_noise.to(dev, torch.float32).contiguous(), sa, s1, t_start, T)  # (:1405-1409)
+        plens = _mask_to_lengths(prompt_mask.to(dev))
+        self.model.engine().guided_ddim_schedule_loop(x, lengths, prompt, plens, steps.to(dev), rows.to(dev), cond_scale=cond_scale, eta=eta,
+                                                      seed=seed, noise=step_noise, use_graph=use_graph, timesteps=self.timesteps)
+        recon, _, units = self.speech_decoder.engine().decode(x, lengths, want_logits=False)     # (:1448-1451)
+        pred_units = units.long()
+        match = (pred_units[input_mask] == ref_units.to(dev)[input_mask]).sum().item() if ref_units is not None else 0
+        lens = lengths.tolist()
+        return [pred_units[i, : lens[i]] for i in range(B)], match, int(input_mask.sum().item()), recon
+
+    @torch.no_grad()
     def ddpm_sample(self, tgt_feature, input_mask=None, ref_units=None, start_step=50, post_noise=None, start_noise=None, seed=0,
                     step_noise=None, fixed_large=False, clip_denoised=False, use_graph=True):
         """The chain of `ddim_sample` with the ancestral (DDPM) update -- GaussianDiffusion.p_sample (reference diffusion/

@@ -592,7 +592,9 @@ int dn_eps_forward_cond(DnEps* m, const float* x, const int32_t* t, const int32_
  * guarantees nothing else wrote the workspace in between and that prompt / prompt_lengths / drop are unchanged).  time_table
  * (optional, fp32 [table_n, n_cond] from dn_eps_cond_time_table, first row = timestep table_t0): the time half of the conditioning
  * rows of every step of the chain, so the 2 C x n_cond projection is not streamed inside the loop.  flags = 0, time_table = NULL
- * is dn_eps_forward_cond.                                                                                                     */
+ * is dn_eps_forward_cond.  With a time table `t` is used ONLY to pick the table's row, t[b] - table_t0 clamped into [0, table_n-1]
+ * (the time-conditioning MLP is skipped): a chain whose table has one row per step (dn_eps_cond_time_table_steps) passes its step
+ * index as `t` with table_t0 = 0, whatever timestep that step evaluates.                                                         */
 #define DN_COND_REUSE_PROMPT 1
 int dn_eps_forward_cond_ex(DnEps* m, const float* x, const int32_t* t, const int32_t* lengths, const float* prompt,
                            const int32_t* prompt_lengths, const int32_t* drop, int32_t B, int32_t T, int32_t Tp, float* eps_out,
@@ -600,10 +602,16 @@ int dn_eps_forward_cond_ex(DnEps* m, const float* x, const int32_t* t, const int
                            int32_t table_n, void* stream);
 size_t dn_eps_cond_time_table_workspace_bytes(const DnEps* m, int32_t n_t);
 int dn_eps_cond_time_table(DnEps* m, int32_t t0, int32_t n_t, float* table, void* workspace, size_t workspace_bytes, void* stream);
+/* The same table for a device list of timesteps: row i = the time half of the conditioning rows of timestep steps[i] (device int32
+ * [n_steps], any order; the schedule of dn_guided_ddim_loop).  Workspace: dn_eps_cond_time_table_workspace_bytes(m, n_steps).
+ * steps = t0 .. t0 + n_t - 1 is dn_eps_cond_time_table's result (time conditioning latent_module.py:841-842, 846-852).          */
+int dn_eps_cond_time_table_steps(DnEps* m, const int32_t* steps, int32_t n_steps, float* table, void* workspace, size_t workspace_bytes,
+                                 void* stream);
 
 /* After the packed weights behind `m` were rewritten in place (dn_repack_weights): forgets what the engine derived from them --
  * the conditioning table a DN_LOOP_KEEP_TABLE call would reuse.  The captured hipGraph of the device loop stays: it holds
- * addresses only, and every table it reads is rebuilt from the weights by the next dn_ddim_loop / dn_ddpm_loop call.        */
+ * addresses only, and every table it reads is rebuilt from the weights by the next dn_ddim_loop / dn_ddpm_loop call.  The
+ * guided loop (dn_guided_ddim_loop) needs nothing: every call rebuilds its time table and its first step the prompt-only state. */
 int dn_eps_weights_changed(DnEps* m);
 
 int dn_vae_create(const DnVaeConfig* cfg, const void* const* weights, int32_t n_weights, DnVae** out);
@@ -672,6 +680,32 @@ int dn_ddim_sched_check(const int32_t* steps_host, int32_t n_steps, int32_t time
 int dn_ddim_sched_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, const int32_t* steps, const float* coef,
                        int32_t n_steps, int32_t timesteps, int32_t eta_on, uint64_t seed, const float* noise, int32_t flags,
                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* The prompted, classifier-free-guided chain over a timestep schedule, as a device loop: dn_ddim_sched_loop's chain -- steps, coef,
+ * the level x enters at, the target of every update, eta_on / seed / noise [n_steps, B*T*latent] and the Philox key (seed, step
+ * index, element quad of the B-row batch) are its arguments with its meaning, dn_ddim_sched_check validates the schedule's host
+ * copy -- with the guided prediction of forward_with_cond_scale (latent_module.py:813-826) in place of the unconditional one:
+ * cond_scale == 1: one conditioned pass over B rows; otherwise one pass over 2B rows [conditioned ; null] (the drop mask is per
+ * sample, :843-859) combined as dn_cfg_combine combines them, null + (cond - null) * cond_scale.  prompt fp32 [B, Tp, dim_prompt],
+ * prompt_lengths int32 [B]; needs a model created with cfg.dim_prompt > 0.
+ * The entry owns, in the caller's workspace: the doubled lengths / prompt / prompt lengths and the drop mask [0..0 ; 1..1] of the
+ * 2B-row pass, the 2B-row model input and prediction, a step-index vector and the loop's device counter (step indices, upwards),
+ * copies of steps and coef, and a time table of n_steps rows (dn_eps_cond_time_table_steps: row i for e_i) -- all written at chain
+ * start by device-to-device copies and kernels on the stream; no allocation, no synchronisation.  One step: fill the index vector
+ * from the counter, dn_eps_forward_cond_ex (the chain's first step computes the prompt-only work, every later one passes
+ * DN_COND_REUSE_PROMPT), ONE kernel that forms the guided eps, applies dn_ddim_sched_loop's update to x and writes the result to
+ * both halves of the model's next input, and the counter's increment.  flags: DN_LOOP_GRAPH only (n_steps > 2: the first step runs
+ * eagerly, the later form of the step is captured once and replayed; the graph is cached in a slot of its own, keyed by B, T, Tp,
+ * n_steps, workspace, x, lengths, prompt, prompt_lengths, the bits of cond_scale, flags, eta_on, seed, the coefficient copy's
+ * address and the run-time options' generation; an injected-noise chain is never cached).  DN_LOOP_SPLIT2 is refused: the
+ * prompt-only state lives in one workspace and the guided pass already runs 2B rows.  Every argument check precedes the first HIP
+ * call.  Workspace: dn_guided_ddim_workspace_bytes (guided = cond_scale != 1; the guided = 0 size is the smaller one and leaves
+ * out every second half).  Returns the number of model evaluations (= n_steps) or a negative error.                            */
+size_t dn_guided_ddim_workspace_bytes(const DnEps* m, int32_t B, int32_t T, int32_t Tp, int32_t n_steps, int32_t guided);
+int dn_guided_ddim_loop(DnEps* m, float* x, const int32_t* lengths, const float* prompt, const int32_t* prompt_lengths, int32_t B, int32_t T,
+                        int32_t Tp, float cond_scale, const int32_t* steps, const float* coef, int32_t n_steps, int32_t timesteps,
+                        int32_t eta_on, uint64_t seed, const float* noise, int32_t flags, void* workspace, size_t workspace_bytes,
+                        void* stream);
 
 /* ------------------------------------------------------------------ VAE training step (BASELINE config 4) */
 /* speech_vae_decoder_loss training (reference SpeechVAEEncoderDecoder.forward latent_module.py:1118-1142 + the criterion
