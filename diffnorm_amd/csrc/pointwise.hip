@@ -236,7 +236,7 @@ __global__ __launch_bounds__(256) void randn_kernel(float* __restrict__ out, int
     float r[4];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0,1)
+      const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0,1]: 16777215 + 0.5 ties to 2^24
       const float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
       const float rad = sqrtf(-2.0f * logf(u1));
       float sn, cs;
@@ -297,7 +297,7 @@ __device__ __forceinline__ void philox_normal4(uint64_t seed, uint64_t ctr_lo, u
     k1 += 0xBB67AE85u;
   }
 #pragma unroll
-  for (int h = 0; h < 2; ++h) {  // Box-Muller on (0,1) uniforms, as randn_kernel
+  for (int h = 0; h < 2; ++h) {  // Box-Muller on (0,1] uniforms, as randn_kernel
     const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);
     const float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
     const float rad = sqrtf(-2.0f * logf(u1));
