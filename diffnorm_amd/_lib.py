@@ -93,6 +93,7 @@ class GaussianStep(C.Structure):
 
 GD_COLS = 12
 DDIM_SCHED_COLS = 5  # DN_DDIM_SCHED_COLS
+DPM_COLS = 6  # DN_DPM_COLS
 
 
 class GaussianMoments(C.Structure):
@@ -241,6 +242,9 @@ SYMBOLS = {
     "dn_ddim_sched_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
     "dn_ddim_sched_check": (C.c_int, [_vp, _i32, _i32]),
     "dn_ddim_sched_loop": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, C.c_uint64, _vp, _i32, _vp, _sz, _vp]),
+    "dn_dpm2m_step": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "dn_dpm_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
+    "dn_dpm_loop": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "dn_guided_ddim_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32, _i32]),
     "dn_guided_ddim_loop": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _vp, _vp, _i32, _i32, _i32, C.c_uint64, _vp, _i32,
                                       _vp, _sz, _vp]),

@@ -618,6 +618,8 @@ int dn_ddpm_step_launch(float* x, const float* eps, int M, int C, int T, const f
 int dn_ddim_sched_step_launch(float* x, const float* eps, int64_t elem0, int64_t n_elem, const float* coef, const int32_t* steps,
                               const int32_t* counter, int eta_on, const float* noise, int64_t noise_row, uint64_t seed,
                               hipStream_t stream);  // pointwise.hip
+int dn_dpm2m_step_launch(float* x, const float* eps, float* hist, int64_t elem0, int64_t n_elem, const float* coef, const int32_t* counter,
+                         hipStream_t stream);  // pointwise.hip
 
 namespace {
 // the scheduler update applied after every evaluation of the device loop
@@ -630,6 +632,9 @@ struct StepOp {
   // loop's counter then counts step indices 0 .. n_steps-1 and the conditioning table has one row per step
   const int32_t* steps = nullptr;
   int n_steps = 0, eta_on = 0;
+  // dn_dpm_loop: a scheduled chain whose update is DPM-Solver++(2M) with `coef` [n_steps, DN_DPM_COLS] and one more persistent
+  // buffer, the previous step's data prediction
+  bool dpm = false;
 };
 }  // namespace
 
@@ -641,9 +646,10 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
   const bool split = (flags & DN_LOOP_SPLIT2) && B >= 2;
   DN_CHECK_ARG(m && x && lengths && coef && workspace, "dn_ddim_loop: null argument");
   const bool sched = op.steps != nullptr;
+  const char* who = op.dpm ? "dn_dpm_loop" : "dn_ddim_sched_loop";
   if (sched) {  // (a strictly descending list inside [0, timesteps-1] has at most `timesteps` entries)
-    DN_CHECK_ARG(op.n_steps >= 1 && op.n_steps <= timesteps, "dn_ddim_sched_loop: n_steps=%d must be in [1, %d]", op.n_steps, timesteps);
-    DN_CHECK_ARG(B > 0 && T > 0 && T <= m->cfg.max_pos, "dn_ddim_sched_loop: B=%d T=%d (positional table: %d)", B, T, m->cfg.max_pos);
+    DN_CHECK_ARG(op.n_steps >= 1 && op.n_steps <= timesteps, "%s: n_steps=%d must be in [1, %d]", who, op.n_steps, timesteps);
+    DN_CHECK_ARG(B > 0 && T > 0 && T <= m->cfg.max_pos, "%s: B=%d T=%d (positional table: %d)", who, B, T, m->cfg.max_pos);
     DN_CHECK_ARG(op.eta_on || !op.noise, "dn_ddim_sched_loop: injected noise needs eta_on (eta = 0 draws none)");
   } else
     DN_CHECK_ARG(start_step >= 1 && start_step <= timesteps - (op.ddpm ? 0 : 1), "dn_ddim_loop: start_step=%d must be in [1, %d]", start_step,
@@ -658,8 +664,11 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
   const size_t core0 = eps_ws_core(m, B0, T), core1 = split ? eps_ws_core(m, B1, T) : 0, core = core0 + core1;
   size_t need = core + ddim_extra_bytes(m, B, T, start_step);
   if (sched) need = dn_ddim_workspace_bytes(m, B, T, start_step);  // the documented size, split or not (>= what this call lays out)
+  if (op.dpm) need = dn_dpm_workspace_bytes(m, B, T, start_step);
   if (need > workspace_bytes) {
-    if (sched)
+    if (op.dpm)
+      dn_set_error("dn_dpm_loop: workspace %zu < required %zu (see dn_dpm_workspace_bytes)", workspace_bytes, need);
+    else if (sched)
       dn_set_error("dn_ddim_sched_loop: workspace %zu < required %zu (see dn_ddim_sched_workspace_bytes)", workspace_bytes, need);
     else
       dn_set_error("dn_ddim_loop: workspace %zu < required %zu (see dn_ddim_workspace_bytes)", workspace_bytes, need);
@@ -682,6 +691,7 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
   Arena ar{(char*)workspace + core, 0, workspace_bytes - core};
   // fixed-size state first, so a cached graph stays valid when only start_step changes
   float* eps = (float*)ar.take((size_t)M * z * 4);
+  float* hist = op.dpm ? (float*)ar.take((size_t)M * z * 4) : nullptr;  // dn_dpm_loop: x0 of the previous step, the whole batch's
   int32_t* tvec = (int32_t*)ar.take((size_t)B * 4);
   int32_t* counter = (int32_t*)ar.take(64);
   float* table = (float*)ar.take((size_t)start_step * m->n_row * 4);  // conditioning rows for t = 0..start_step-1
@@ -700,14 +710,15 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
     // row i of the table belongs to steps[i].  The schedule and its coefficient rows move into the workspace, so a captured step
     // holds workspace addresses only: the steps where the other loops keep 0..start_step-1, the coefficients over `cond_all`
     // (dn_ddim_sched_workspace_bytes: dead once the table is built, and C >= 64 floats a row against DN_DDIM_SCHED_COLS).
-    static_assert(DN_DDIM_SCHED_COLS <= 64, "the coefficient rows live in cond_all");
+    static_assert(DN_DDIM_SCHED_COLS <= 64 && DN_DPM_COLS <= 64, "the coefficient rows live in cond_all");
+    const size_t cols = op.dpm ? DN_DPM_COLS : DN_DDIM_SCHED_COLS;
     if (hipMemcpyAsync(tall, op.steps, (size_t)start_step * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
-      dn_set_error("dn_ddim_sched_loop: copying the schedule failed");
+      dn_set_error("%s: copying the schedule failed", who);
       return DN_ELAUNCH;
     }
     DN_TRY(eps_cond_rows(m, tall, start_step, cond_all, table, table_h, s));
-    if (hipMemcpyAsync(cond_all, coef, (size_t)start_step * DN_DDIM_SCHED_COLS * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
-      dn_set_error("dn_ddim_sched_loop: copying the coefficient rows failed");
+    if (hipMemcpyAsync(cond_all, coef, (size_t)start_step * cols * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+      dn_set_error("%s: copying the coefficient rows failed", who);
       return DN_ELAUNCH;
     }
     step_coef = cond_all;
@@ -731,7 +742,9 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
         return DN_ELAUNCH;
       }
       DN_TRY(eps_core(m, x + off, bufs.gb, 0, lengths + B0, B1, T, eps + off, bufs1, s2, twin));
-      if (sched)  // (the whole batch's element index keys the draw: the halves share one stream of numbers)
+      if (op.dpm)  // (each half on its own element range of the shared x / eps / hist)
+        DN_TRY(dn_dpm2m_step_launch(x, eps, hist, (int64_t)off, (int64_t)B1 * T * z, step_coef, counter, s2));
+      else if (sched)  // (the whole batch's element index keys the draw: the halves share one stream of numbers)
         DN_TRY(dn_ddim_sched_step_launch(x, eps, (int64_t)off, (int64_t)B1 * T * z, step_coef, tall, counter, op.eta_on, op.noise, (int64_t)M * z,
                                          op.seed, s2));
       else if (op.ddpm)
@@ -741,7 +754,9 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
         DN_TRY(dn_ddim_step(x + off, eps + off, x + off, nullptr, DN_F32, z, B1 * T, z, z, T, coef, tvec + B0, s2));
     }
     DN_TRY(eps_core(m, x, bufs.gb, 0, lengths, B0, T, eps, bufs, s, twin));
-    if (sched)
+    if (op.dpm)
+      DN_TRY(dn_dpm2m_step_launch(x, eps, hist, 0, (int64_t)B0 * T * z, step_coef, counter, s));
+    else if (sched)
       DN_TRY(dn_ddim_sched_step_launch(x, eps, 0, (int64_t)B0 * T * z, step_coef, tall, counter, op.eta_on, op.noise, (int64_t)M * z, op.seed, s));
     else if (op.ddpm)
       DN_TRY(dn_ddpm_step_launch(x, eps, B0 * T, z, T, coef, tvec, op.clip, op.noise, (int64_t)M * z, noise_top, op.seed, s));
@@ -766,7 +781,7 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
   if (use_graph && n_eval > 2) {
     // (a scheduled chain's graph is keyed by the workspace copy of its coefficients: an address that moves with n_steps)
     const int gflags = (flags & ~DN_LOOP_KEEP_TABLE) | (op.ddpm ? 1 << 16 : 0) | (op.clip ? 1 << 17 : 0) | (sched ? 1 << 18 : 0) |
-                       (op.eta_on ? 1 << 19 : 0);
+                       (op.eta_on ? 1 << 19 : 0) | (op.dpm ? 1 << 20 : 0);
     // (an injected-noise chain bakes noise_top into the captured step: never served from the cache)
     // (a dn_set_option since the capture may route the contractions differently: a miss)
     const int opt_gen = dn::option_generation();
@@ -854,6 +869,25 @@ extern "C" int dn_ddim_sched_loop(DnEps* m, float* x, const int32_t* lengths, in
   DN_CHECK_ARG(!(flags & ~(DN_LOOP_GRAPH | DN_LOOP_SPLIT2)), "dn_ddim_sched_loop: flags=%d (DN_LOOP_GRAPH | DN_LOOP_SPLIT2 only)", flags);
   StepOp op;
   op.steps = steps; op.n_steps = n_steps; op.eta_on = eta_on != 0; op.seed = op.eta_on ? seed : 0; op.noise = noise;
+  return sampler_loop(m, x, lengths, B, T, 0, 0, coef, timesteps, flags, workspace, workspace_bytes, stream, op);
+}
+
+// dn_ddim_sched_loop's layout with the history buffer taken beside eps (one more 256-byte aligned block of the latent's size)
+extern "C" size_t dn_dpm_workspace_bytes(const DnEps* m, int32_t B, int32_t T, int32_t n_steps) {
+  const size_t base = dn_ddim_workspace_bytes(m, B, T, n_steps);
+  if (!base) return 0;
+  return base + (((size_t)B * T * m->cfg.latent * 4 + 255) & ~size_t(255));
+}
+
+extern "C" int dn_dpm_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, const int32_t* steps, const float* coef,
+                           int32_t n_steps, int32_t timesteps, int32_t flags, void* workspace, size_t workspace_bytes, void* stream) {
+  DN_CHECK_ARG(m, "dn_dpm_loop: null engine");
+  DN_CHECK_ARG(m->cfg.dim_prompt == 0, "dn_dpm_loop: the solver covers the unconditional model (the prompted, guided chain is dn_guided_ddim_loop)");
+  DN_CHECK_ARG(steps, "dn_dpm_loop: null schedule");
+  DN_CHECK_ARG(!(flags & ~(DN_LOOP_GRAPH | DN_LOOP_SPLIT2)), "dn_dpm_loop: flags=%d (DN_LOOP_GRAPH | DN_LOOP_SPLIT2 only)", flags);
+  DN_CHECK_ARG(x && lengths && coef && workspace, "dn_dpm_loop: null argument");
+  StepOp op;
+  op.steps = steps; op.n_steps = n_steps; op.dpm = true;
   return sampler_loop(m, x, lengths, B, T, 0, 0, coef, timesteps, flags, workspace, workspace_bytes, stream, op);
 }
 

@@ -349,6 +349,38 @@ __global__ __launch_bounds__(256) void ddim_sched_step_kernel(float* x, const fl
   }
 }
 
+// ------------------------------------------------------------------------------------------ DPM-Solver++(2M) step of the device loop
+// One update of a DPM-Solver++(2M) chain over a timestep schedule (dn_dpm_loop; Lu et al. 2022, data-prediction multistep form): row
+// i = *counter of `coef` [n, DN_DPM_COLS] = {alpha_s, sigma_s, a, b, c1, c0}, uniform over the batch:
+//   x0_i = (x - sigma_s eps) / max(alpha_s, 1e-10);  x <- a x + b (c1 x0_i + c0 x0_{i-1});  hist <- x0_i.
+// hist holds x0_{i-1} of the whole batch and is read only by a second-order row (c0 != 0: uniform over the launch), so the first row of
+// a chain never reads what an earlier chain left there.  Deterministic: no draws.  A half-batch launch passes its first quad (q0).
+// Every product and sum is spelled out, so eager, graph replay and the two half-batch streams cannot be contracted differently.
+// HBM-bound: 2 (+1) reads and 2 writes of 16 bytes per quad; grid-stride, no LDS.
+__global__ __launch_bounds__(256) void dpm2m_step_kernel(float* x, const float* __restrict__ eps, float* hist, int64_t q0, int64_t nquad,
+                                                         const float* __restrict__ coef, const int32_t* __restrict__ counter) {
+  const float* cf = coef + (int64_t)(*counter) * DN_DPM_COLS;
+  const float as = fmaxf(cf[0], 1e-10f), ss = cf[1], a = cf[2], b = cf[3], c1 = cf[4], c0 = cf[5];
+  const bool two = c0 != 0.0f;
+  for (int64_t q = q0 + blockIdx.x * 256 + threadIdx.x; q < q0 + nquad; q += (int64_t)gridDim.x * 256) {
+    const int64_t i = q << 2;
+    const float4 xv = *reinterpret_cast<const float4*>(x + i), ev = *reinterpret_cast<const float4*>(eps + i);
+    float4 hv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (two) hv = *reinterpret_cast<const float4*>(hist + i);
+    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, es[4] = {ev.x, ev.y, ev.z, ev.w}, hs[4] = {hv.x, hv.y, hv.z, hv.w};
+    float o[4], p[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      p[j] = __fdiv_rn(fmaf(-ss, es[j], xs[j]), as);
+      float d = __fmul_rn(c1, p[j]);
+      if (two) d = fmaf(c0, hs[j], d);
+      o[j] = fmaf(a, xs[j], __fmul_rn(b, d));
+    }
+    *reinterpret_cast<float4*>(x + i) = make_float4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<float4*>(hist + i) = make_float4(p[0], p[1], p[2], p[3]);
+  }
+}
+
 // ------------------------------------------------------------------------------------------ guided scheduled DDIM step of the device loop
 // One update of the prompted, guided chain over a timestep schedule (dn_guided_ddim_loop), per float4 quad of the B-row latent:
 // eps = the conditioned row of `both` (kGuided: combined with the null row, n elements further, by cfg_combine_kernel's three rounded
@@ -676,6 +708,22 @@ int dn_ddim_sched_step_launch(float* x, const float* eps, int64_t elem0, int64_t
                      counter, eta_on, noise, noise_row, seed);
   DN_CHECK_LAUNCH("dn_ddim_sched_loop step");
   return DN_OK;
+}
+
+// (engine.hip: the update of dn_dpm_loop; x, eps, hist: the whole batch's; [elem0, elem0 + n_elem): this launch's elements)
+int dn_dpm2m_step_launch(float* x, const float* eps, float* hist, int64_t elem0, int64_t n_elem, const float* coef, const int32_t* counter,
+                         hipStream_t stream) {
+  DN_CHECK_ARG(elem0 % 4 == 0 && n_elem % 4 == 0 && n_elem > 0, "dn_dpm_loop: the latent width must be a multiple of 4");
+  hipLaunchKernelGGL(dpm2m_step_kernel, dim3(ew_grid(n_elem >> 2)), dim3(256), 0, stream, x, eps, hist, elem0 >> 2, n_elem >> 2, coef, counter);
+  DN_CHECK_LAUNCH("dn_dpm_loop step");
+  return DN_OK;
+}
+
+extern "C" int dn_dpm2m_step(float* x, const float* eps, float* hist, int64_t n, const float* coef, const int32_t* step_index, void* stream) {
+  DN_CHECK_ARG(x && eps && hist && coef && step_index, "dn_dpm2m_step: null argument");
+  DN_CHECK_ARG(n > 0 && n % 4 == 0, "dn_dpm2m_step: n=%lld must be a positive multiple of 4", (long long)n);
+  DN_CHECK_ARG((((uintptr_t)x | (uintptr_t)eps | (uintptr_t)hist) & 15) == 0, "dn_dpm2m_step: x, eps and hist must be 16-byte aligned");
+  return dn_dpm2m_step_launch(x, eps, hist, 0, n, coef, step_index, (hipStream_t)stream);
 }
 
 // (engine.hip: the update of dn_guided_ddim_loop; n_elem = B*T*latent of the B-row latent; both / xin hold 2 n_elem floats when guided)

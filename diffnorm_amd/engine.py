@@ -377,6 +377,35 @@ class EpsEngine(_Engine):
                                                           (1 if use_graph else 0) | (2 if split else 0), wp, wn, _lib.current_stream()),
                               "dn_ddim_sched_loop")
 
+    def dpm_schedule_loop(self, x: torch.Tensor, lengths: torch.Tensor, steps: torch.Tensor, rows: torch.Tensor, use_graph: bool = True,
+                          split: bool = True, timesteps: Optional[int] = None) -> int:
+        """In-place DPM-Solver++(2M) chain on x [B,T,z] fp32 over a timestep schedule (dn_dpm_loop): `steps` int32 [n] strictly
+        descending and `rows` fp32 [n, 6], both from `scheduler.dpm_schedule`.  `ddim_schedule_loop`'s chain -- one evaluation per
+        step, conditioning table of n rows, hipGraph replay, two half-batch streams -- with the second-order multistep update; the
+        workspace holds one more latent-sized buffer, the previous step's data prediction.  Deterministic: no eta, no noise.  `steps`
+        may also be a list or a host tensor: it is then validated by dn_ddim_sched_check against `timesteps` and uploaded.
+        Returns the number of evaluations."""
+        B, T, z = x.shape
+        assert x.is_contiguous() and x.dtype == torch.float32 and x.device == self.device
+        nt = None if timesteps is None else int(timesteps)
+        if not (isinstance(steps, torch.Tensor) and steps.device == self.device):
+            host = torch.as_tensor(steps, dtype=torch.int32).contiguous().view(-1)
+            if self.lib.dn_ddim_sched_check(host.data_ptr() if host.numel() else None, int(host.numel()),
+                                            int(host.numel()) if nt is None else nt) != 0:
+                raise ValueError("dpm_schedule_loop: " + (self.lib.dn_last_error() or b"").decode())
+            steps = host.to(self.device)
+        n = int(steps.shape[0])
+        assert steps.dtype == torch.int32 and steps.is_contiguous() and steps.dim() == 1
+        assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.device == self.device and rows.shape == (n, _lib.DPM_COLS)
+        l32 = lengths if (lengths.dtype == torch.int32 and lengths.device == self.device) else _i32(lengths, self.device)
+        self._keep = (l32, steps, rows)
+        ws = self._workspace(int(self.lib.dn_dpm_workspace_bytes(self.handle, B, T, n)))
+        wp, wn = self._aligned(ws)
+        with torch.cuda.device(self.device):
+            return _lib.check(self.lib.dn_dpm_loop(self.handle, x.data_ptr(), l32.data_ptr(), B, T, steps.data_ptr(), rows.data_ptr(), n,
+                                                   n if nt is None else nt, (1 if use_graph else 0) | (2 if split else 0), wp, wn,
+                                                   _lib.current_stream()), "dn_dpm_loop")
+
     def cond_time_table_steps(self, steps) -> torch.Tensor:
         """The time half of the conditioning rows of the timesteps `steps` (any list or int tensor; dn_eps_cond_time_table_steps):
         fp32 [n, n_cond], row i for steps[i]."""

@@ -547,13 +547,28 @@ class LatentDiscreteModel(nn.Module):
     @torch.no_grad()
     def ddim_sample(self, tgt_feature, prompt=None, prompt_mask=None, input_mask=None, cond_scale=1., ref_units=None,
                     start_step=50, post_noise=None, start_noise=None, use_graph=True, sampling_steps=None, timestep_schedule=None,
-                    eta=0.0, seed=0, step_noise=None):
+                    eta=0.0, seed=0, step_noise=None, solver=None, solver_order=2):
         """-> (list of unit tensors, match, total, recon_feature), as upstream (:1385-1471).
 
         `sampling_steps` = N runs the chain on N of the timesteps start_step-1 .. 1 (scheduler.ddim_steps: uniformly spread, N =
         start_step-1 is every timestep), `timestep_schedule` on an explicit strictly descending list; `eta` > 0 adds the DDIM noise
         (diffusion/gaussian_diffusion.py:513-560), drawn on the device from `seed` or injected as `step_noise` [n, B, T, z].  With
-        all of them unset the chain is the reference's: every timestep, eta = 0."""
+        all of them unset the chain is the reference's: every timestep, eta = 0.
+
+        `solver="dpmpp_2m"` runs the chain the same arguments select with the DPM-Solver++(2M) update (scheduler.dpm_schedule,
+        EpsEngine.dpm_schedule_loop; `solver_order` 1 or 2) in place of DDIM's: second order in the step, for short chains
+        (`sampling_steps` 10-20 from start_step = 50).  It is deterministic -- `eta` and `step_noise` do not apply -- and covers the
+        unconditional model.  `solver=None` is the code above, unchanged."""
+        if solver is not None:
+            if solver != "dpmpp_2m":
+                raise ValueError(f"ddim_sample: unknown solver {solver!r} (None or 'dpmpp_2m')")
+            if eta != 0.0 or step_noise is not None:
+                raise ValueError("ddim_sample: solver='dpmpp_2m' is deterministic: eta and step_noise do not apply")
+            if self.use_cond:
+                raise ValueError("ddim_sample: solver='dpmpp_2m' covers the unconditional model (the prompted, guided chain keeps DDIM: "
+                                 "prompted_ddim_sample)")
+            if solver_order not in (1, 2):
+                raise ValueError(f"ddim_sample: solver_order={solver_order} must be 1 or 2")
         scheduled = sampling_steps is not None or timestep_schedule is not None or eta != 0.0 or step_noise is not None
         if scheduled and self.use_cond:
             raise ValueError("ddim_sample: sampling_steps / timestep_schedule / eta cover the unconditional model (the prompted, "
@@ -578,6 +593,9 @@ class LatentDiscreteModel(nn.Module):
                 raise ValueError("use_cond: ddim_sample needs prompt and prompt_mask")
             plens = _mask_to_lengths(prompt_mask.to(dev))
             self.model.engine().guided_ddim_chain(x, lengths, prompt, plens, start_step, coef, cond_scale=cond_scale, use_graph=use_graph)
+        elif solver is not None:
+            steps, rows = self.scheduler.dpm_schedule(start_step, sampling_steps, timestep_schedule, order=solver_order, device=dev)
+            self.model.engine().dpm_schedule_loop(x, lengths, steps, rows, use_graph=use_graph, timesteps=self.timesteps)
         elif scheduled:
             steps, rows = self.scheduler.ddim_schedule(start_step, sampling_steps, timestep_schedule, eta=eta, device=dev)
             self.model.engine().ddim_schedule_loop(x, lengths, steps, rows, eta=eta, seed=seed, noise=step_noise, use_graph=use_graph,

@@ -70,10 +70,12 @@ def tsv_line(it: Utterance, pred_units: Sequence[int]) -> str:
 
 
 def normalize(ddim_sample: Callable, utterances: Sequence[Utterance], start_step: int = 50, batch_size: int = 100,
-              device="cuda:0", group=None, sampling_steps: Optional[int] = None, eta: float = 0.0, seed: int = 0) -> Optional[List[str]]:
+              device="cuda:0", group=None, sampling_steps: Optional[int] = None, eta: float = 0.0, seed: int = 0,
+              solver: Optional[str] = None) -> Optional[List[str]]:
     """Runs `ddim_sample(feat, input_mask=..., ref_units=..., start_step=...)` (LatentDiscreteModel.ddim_sample) over this
     rank's batches and gathers the TSV lines of all ranks in utterance order (every rank returns the full list).
-    `sampling_steps` (evaluations per chain instead of start_step-1), `eta` and `seed` reach `ddim_sample` only when set."""
+    `sampling_steps` (evaluations per chain instead of start_step-1), `eta`, `seed` and `solver` ("dpmpp_2m": the second-order
+    update for short chains) reach `ddim_sample` only when set."""
     rank, world = sharding.rank_world(group)
     # A run must give the same results on any number of ranks (and whatever sizes the last batches have).  The 2-byte / f32
     # contractions' fast K order (taps of a causal conv innermost, one staged copy of the rows, on the two 256-row tiles) sums in a
@@ -95,6 +97,8 @@ def normalize(ddim_sample: Callable, utterances: Sequence[Utterance], start_step
         extra["sampling_steps"] = sampling_steps
     if eta != 0.0:
         extra.update(eta=eta, seed=seed)
+    if solver is not None:
+        extra["solver"] = solver
     with _lib.option("taps_inner", 2 if chosen is None else chosen):
         for b in mine:
             items = [utterances[i] for i in batches[b]]

@@ -144,6 +144,66 @@ class ScheduleTables:
         st = torch.from_numpy(e.astype(np.int32))
         return (st.to(device), coef.to(device)) if device is not None else (st, coef)
 
+    def dpm_rows64(self, steps, order: int = 2, lower_order_final: bool = True) -> np.ndarray:
+        """float64 [n, 6] coefficient rows of DPM-Solver++(2M) (Lu et al. 2022, data-prediction multistep form) for the validated
+        evaluation timesteps `steps`; see `dpm_schedule`."""
+        if order not in (1, 2):
+            raise ValueError(f"dpm_schedule: order={order} must be 1 or 2")
+        e = np.asarray(steps, dtype=np.int64)
+        n = len(e)
+        ab = self.alphas_cumprod[e]
+        ab_tgt = np.append(self.alphas_cumprod[e[1:]], self.alphas_cumprod[0] if e[-1] >= 1 else 1.0)
+        al_s, sg_s = np.sqrt(ab), np.sqrt(1.0 - ab)
+        lam_s = np.log(al_s / sg_s)
+        rows = np.zeros((n, 6), dtype=np.float64)
+        for i in range(n):
+            c1, c0 = 1.0, 0.0
+            if ab_tgt[i] >= 1.0:  # to the clean level: x <- x0, formed without evaluating lambda_t = inf
+                a, b = 0.0, 1.0
+            else:
+                al_t, sg_t = np.sqrt(ab_tgt[i]), np.sqrt(1.0 - ab_tgt[i])
+                h = np.log(al_t / sg_t) - lam_s[i]
+                a, b = sg_t / sg_s[i], -al_t * np.expm1(-h)
+                if order == 2 and i > 0 and not (lower_order_final and i == n - 1):
+                    r = (lam_s[i] - lam_s[i - 1]) / h
+                    c1, c0 = 1.0 + 0.5 / r, -0.5 / r
+            rows[i] = (al_s[i], sg_s[i], a, b, c1, c0)
+        return rows
+
+    def dpm_schedule(self, start_step: int, sampling_steps=None, steps=None, order: int = 2, lower_order_final: bool = True, device=None):
+        """-> (steps int32 [n], coef fp32 [n, DN_DPM_COLS = 6]) of dn_dpm_loop for the chain `ddim_steps` selects (the same selection
+        rule and validation as `ddim_schedule`).  With alpha = sqrt abar, sigma = sqrt(1 - abar), lambda = log(alpha / sigma), s =
+        e_i, t = `ddim_schedule`'s target level of update i (abar[e_{i+1}]; the last one abar[0], or 1 when e_{n-1} == 0) and h_i =
+        lambda_t - lambda_s, row i = {alpha_s, sigma_s, a, b, c1, c0} drives
+
+            x0_i = (x - sigma_s eps) / max(alpha_s, 1e-10);  x <- a x + b (c1 x0_i + c0 x0_{i-1})
+
+        a = sigma_t / sigma_s, b = -alpha_t expm1(-h_i).  First-order rows (c1 = 1, c0 = 0): row 0, every row when order == 1, the
+        last row under `lower_order_final`, and a row whose target level is 1 (there a = 0, b = 1).  Second-order rows: r =
+        (lambda_{e_i} - lambda_{e_{i-1}}) / h_i, c1 = 1 + 1/(2r), c0 = -1/(2r).  Everything is formed in float64 and cast once."""
+        if order not in (1, 2):
+            raise ValueError(f"dpm_schedule: order={order} must be 1 or 2")
+        try:
+            e = self.ddim_steps(start_step, sampling_steps, steps)
+        except ValueError as err:
+            raise ValueError(str(err).replace("ddim_schedule:", "dpm_schedule:", 1)) from None
+        coef = torch.from_numpy(self.dpm_rows64(e, order, lower_order_final).astype(np.float32)).contiguous()
+        st = torch.from_numpy(np.asarray(e, dtype=np.int32))
+        return (st.to(device), coef.to(device)) if device is not None else (st, coef)
+
+
+def dpm_chain_reference(x, eps_fn, steps, coef64):
+    """The chain `dpm_schedule`'s rows drive, stepped on the host in whatever precision `x` and `coef64` carry (float64 rows from
+    `dpm_rows64` for a reference): eps_fn(x, e_i) -> eps.  Returns the end point."""
+    prev = None
+    for i, e in enumerate(steps):
+        al, sg, a, b, c1, c0 = (coef64[i][j] for j in range(6))
+        x0 = (x - sg * eps_fn(x, int(e))) / max(al, 1e-10)
+        d = c1 * x0 + (c0 * prev if c0 != 0.0 else 0.0)
+        x = a * x + b * d
+        prev = x0
+    return x
+
 
 class DDPMScheduler(ScheduleTables):
     """Cosine schedule with the getters of the reference class (latent_module.py:1241-1297).

@@ -681,6 +681,31 @@ int dn_ddim_sched_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, in
                        int32_t n_steps, int32_t timesteps, int32_t eta_on, uint64_t seed, const float* noise, int32_t flags,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* DPM-Solver++(2M) over a timestep schedule, as a device loop (Lu et al. 2022, "DPM-Solver++", the data-prediction multistep solver,
+ * eq. 11-12 / algorithm 2): dn_ddim_sched_loop's chain -- the strictly descending evaluation timesteps e_0 > ... > e_{n-1}, the level
+ * x enters at, the target level abar_tgt(i) of update i, one evaluation per step -- with a second-order deterministic update.  With
+ * alpha = sqrt abar, sigma = sqrt(1 - abar), lambda = log(alpha / sigma), s = e_i, t = the target of update i, h_i = lambda_t - lambda_s:
+ *   x0_i = (x - sigma_s eps) / max(alpha_s, 1e-10)
+ *   x <- a x + b (c1 x0_i + c0 x0_{i-1}),  a = sigma_t / sigma_s,  b = -alpha_t expm1(-h_i)
+ * first-order rows (the first row, order 1, the last row under lower_order_final, a target level of 1 where a = 0, b = 1): c1 = 1,
+ * c0 = 0 -- DDIM at eta = 0 in another arithmetic; second-order rows: r = (lambda_{e_i} - lambda_{e_{i-1}}) / h_i, c1 = 1 + 1/(2r),
+ * c0 = -1/(2r).  coef: device fp32 [n_steps, DN_DPM_COLS], row i = {alpha_s, sigma_s, a, b, c1, c0}, formed in float64 on the host
+ * (scheduler.dpm_schedule).  No noise is drawn: the solver is deterministic.
+ * dn_dpm2m_step is the update alone on n (a multiple of 4) contiguous fp32 elements, 16-byte aligned: row *step_index (device int32) of
+ * coef; hist holds x0_{i-1} on entry -- read only when the row's c0 != 0 -- and x0_i on return.
+ * dn_dpm_loop keeps hist in its workspace beside eps: dn_dpm_workspace_bytes = dn_ddim_workspace_bytes(m, B, T, n_steps) + B T latent
+ * fp32 rounded up to 256 bytes.  Row 0 is first order, so a chain never reads what an earlier call left there.  steps and coef are
+ * copied into the workspace at chain start; flags: DN_LOOP_GRAPH | DN_LOOP_SPLIT2 (the captured step is cached under a key bit of its
+ * own: a dn_ddim_sched_loop step is never replayed for this loop nor the other way round; the two half-batch streams each update their
+ * own element range of the shared x / eps / hist).  Unconditional model only (the prompted chain is dn_guided_ddim_loop).  Every
+ * argument check precedes the first HIP call; dn_ddim_sched_check validates a host copy of the steps.  Returns the number of model
+ * evaluations (= n_steps) or a negative error.                                                                                    */
+#define DN_DPM_COLS 6
+int dn_dpm2m_step(float* x, const float* eps, float* hist, int64_t n, const float* coef, const int32_t* step_index, void* stream);
+size_t dn_dpm_workspace_bytes(const DnEps* m, int32_t B, int32_t T, int32_t n_steps);
+int dn_dpm_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, const int32_t* steps, const float* coef, int32_t n_steps,
+                int32_t timesteps, int32_t flags, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The prompted, classifier-free-guided chain over a timestep schedule, as a device loop: dn_ddim_sched_loop's chain -- steps, coef,
  * the level x enters at, the target of every update, eta_on / seed / noise [n_steps, B*T*latent] and the Philox key (seed, step
  * index, element quad of the B-row batch) are its arguments with its meaning, dn_ddim_sched_check validates the schedule's host
