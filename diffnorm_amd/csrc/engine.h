@@ -97,6 +97,25 @@ constexpr int WGRAD_TN_X3_DEFAULT = 1;  // option wgrad_tn_x3 when unset (DESIGN
 int wgrad_tn_x3_launch(const void* dy, int lddy, int cout, const void* const* x, const int* ldx, const int* shift, int n_taps, int cin, int B, int T,
                        int slices, float* part, float* grad, void* stream, int tag, const WgTnGroups* grp);
 
+// One captured step of a device sampling loop.  The key is everything a captured kernel argument bakes in; it is memset to zero
+// before it is filled (padding compares equal) and compared with memcmp.  A loop fills the fields it has and leaves the rest zero.
+struct StepKey {
+  const void *ws, *x, *len, *coef;  // (a scheduled chain: the workspace copy of its coefficients, an address that moves with n_steps)
+  const void *prompt, *plen;        // guided loop
+  uint64_t seed;                    // the Philox key of a drawing chain
+  int32_t B, T, Tp, n_steps;        // Tp, n_steps: guided loop (the unconditional slot serves any start_step / max_evals)
+  int32_t flags;                    // DN_LOOP_* without DN_LOOP_KEEP_TABLE
+  int32_t opt_gen;                  // dn::option_generation() at capture: the run-time options its routes were chosen under
+  uint32_t scale_bits;              // guided loop: cond_scale
+  uint16_t ancestral, clip, scheduled, eta, dpm;  // which update the step applies
+  uint16_t injected;                // injected noise bakes its row base into the step: stored (it evicts), never served
+};
+static_assert(sizeof(StepKey) == 6 * sizeof(void*) + 8 + 7 * 4 + 6 * 2, "StepKey has no padding: copies of a key compare equal too");
+struct StepGraph {
+  void* exec;  // hipGraphExec_t, null while empty
+  StepKey key;
+};
+
 }  // namespace dn
 
 struct DnEps {
@@ -113,27 +132,13 @@ struct DnEps {
   // conditional variant (kEpsCondTensors; null when cfg.dim_prompt == 0)
   const float *tpc_W, *tpc_b, *null_pc, *lat_pos, *rffin_b, *rffout_b, *rnorm_g, *proj_b;
   const void *null_tok, *proj_W, *rq_W, *rkv_W, *rout_W, *rffin_W, *rffout_W, *cq_W, *ckv_W, *cout_W;
-  // hipGraph cache for dn_ddim_loop
-  void* graph_exec;
-  int graph_B, graph_T;
-  void* graph_ws;
-  float* graph_x;
-  const int32_t* graph_len;
-  const float* graph_coef;
-  int graph_flags;
-  uint64_t graph_seed;  // dn_ddpm_loop: the Philox key baked into the captured step
-  int graph_opt_gen;    // dn::option_generation() at capture: the run-time options its routes were chosen under
+  // hipGraph caches of the device sampling loops: one slot for the four unconditional loops, one for dn_guided_ddim_loop (the
+  // guided loop neither serves nor evicts the others)
+  dn::StepGraph loop_graph, guided_graph;
   void *side_stream, *ev_fork, *ev_join;  // DN_LOOP_SPLIT2: second half-batch stream and its fork/join events
   // DN_LOOP_KEEP_TABLE: the conditioning table built by the previous dn_ddim_loop call on this workspace
   void* table_ws;
   int table_B, table_T, table_split, table_rows;
-  // hipGraph cache of dn_guided_ddim_loop: a slot of its own (the unconditional loops neither serve nor evict it); the key is
-  // everything a captured kernel argument bakes in
-  void* gg_exec;
-  int gg_B, gg_T, gg_Tp, gg_n, gg_flags, gg_eta, gg_opt_gen;
-  uint32_t gg_scale_bits;
-  uint64_t gg_seed;
-  const void *gg_ws, *gg_x, *gg_len, *gg_prompt, *gg_plen, *gg_coef;
 };
 constexpr int kEpsTensors = 7 + dn::kWavenetTensors + dn::kTransformerTensors + 3;
 // conditional variant (cfg.dim_prompt > 0), appended to the table: tpc_W (fp32 [padn(C)][padk(P)]), tpc_b [C], null_prompt_cond [C],

@@ -3,6 +3,7 @@
 // allocates or synchronises; every intermediate lives in the caller's workspace (bump-allocated by
 // the plan_* functions, which also serve the *_workspace_bytes queries).
 #include <algorithm>
+#include <functional>
 #include <new>
 #include <stdlib.h>
 #include <string.h>
@@ -458,8 +459,8 @@ extern "C" int dn_eps_create(const DnEpsConfig* cfg, const void* const* weights,
 
 extern "C" void dn_eps_destroy(DnEps* m) {
   if (!m) return;
-  if (m->graph_exec) (void)hipGraphExecDestroy((hipGraphExec_t)m->graph_exec);
-  if (m->gg_exec) (void)hipGraphExecDestroy((hipGraphExec_t)m->gg_exec);
+  for (StepGraph* g : {&m->loop_graph, &m->guided_graph})
+    if (g->exec) (void)hipGraphExecDestroy((hipGraphExec_t)g->exec);
   if (m->ev_fork) (void)hipEventDestroy((hipEvent_t)m->ev_fork);
   if (m->ev_join) (void)hipEventDestroy((hipEvent_t)m->ev_join);
   if (m->side_stream) (void)hipStreamDestroy((hipStream_t)m->side_stream);
@@ -622,39 +623,93 @@ int dn_dpm2m_step_launch(float* x, const float* eps, float* hist, int64_t elem0,
                          hipStream_t stream);  // pointwise.hip
 
 namespace {
-// the scheduler update applied after every evaluation of the device loop
-struct StepOp {
-  bool ddpm = false;        // false: DDIM eta = 0 with `coef` [timesteps, 4]; true: ancestral step with `coef` = table [timesteps, DN_GD_COLS]
-  int clip = 0;
-  uint64_t seed = 0;
-  const float* noise = nullptr;  // injected noise rows (ddpm, scheduled DDIM with eta) or NULL
-  // dn_ddim_sched_loop: the chain's evaluation timesteps (device int32 [n_steps]) with `coef` [n_steps, DN_DDIM_SCHED_COLS]; the
-  // loop's counter then counts step indices 0 .. n_steps-1 and the conditioning table has one row per step
-  const int32_t* steps = nullptr;
-  int n_steps = 0, eta_on = 0;
-  // dn_dpm_loop: a scheduled chain whose update is DPM-Solver++(2M) with `coef` [n_steps, DN_DPM_COLS] and one more persistent
-  // buffer, the previous step's data prediction
-  bool dpm = false;
+// Runs n steps of a chain on `s` as replays of one captured step.  A hit of `slot` replays all n.  A miss evicts the slot, captures
+// `step` (recorded, not run), instantiates, stores the graph under `key` and replays it; with eager_first it runs one step eagerly
+// before the capture (which also settles the per-kernel attributes outside capture) and replays n - 1.
+template <class Step>
+int replay_steps(StepGraph& slot, const StepKey& key, bool eager_first, int n, hipStream_t s, const char* who, Step&& step) {
+  if (!slot.exec || key.injected || memcmp(&slot.key, &key, sizeof(key)) != 0) {
+    if (eager_first) {
+      DN_TRY(step());
+      --n;
+    }
+    if (slot.exec) {
+      (void)hipGraphExecDestroy((hipGraphExec_t)slot.exec);
+      slot.exec = nullptr;
+    }
+    hipGraph_t graph = nullptr;
+    if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) != hipSuccess) {
+      dn_set_error("%s: hipStreamBeginCapture failed", who);
+      return DN_ELAUNCH;
+    }
+    int rc = step();
+    hipError_t e = hipStreamEndCapture(s, &graph);
+    if (rc == DN_OK && (e != hipSuccess || !graph)) {
+      dn_set_error("%s: hipStreamEndCapture: %s", who, hipGetErrorString(e));
+      rc = DN_ELAUNCH;
+    }
+    hipGraphExec_t exec = nullptr;
+    if (rc == DN_OK && (e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0)) != hipSuccess) {
+      dn_set_error("%s: hipGraphInstantiate: %s", who, hipGetErrorString(e));
+      rc = DN_ELAUNCH;
+    }
+    if (graph) (void)hipGraphDestroy(graph);  // on every path: the executable graph keeps what it needs
+    if (rc != DN_OK) return rc;
+    slot.exec = exec;
+    slot.key = key;
+  }
+  for (; n > 0; --n) {
+    const hipError_t e = hipGraphLaunch((hipGraphExec_t)slot.exec, s);
+    if (e != hipSuccess) {
+      dn_set_error("%s: hipGraphLaunch: %s", who, hipGetErrorString(e));
+      return DN_ELAUNCH;
+    }
+  }
+  return DN_OK;
+}
+
+// what an update of the unconditional device loops works on: the whole batch's buffers (an update offsets them to its half itself)
+struct StepBufs {
+  float *x, *eps, *hist;
+  const float* coef;  // what the captured step reads: the caller's table, or a schedule's rows in the workspace
+  const int32_t *tvec, *steps, *counter;
+  int T, z;
+  int64_t all;    // elements of the whole batch: the row stride of injected noise
+  int noise_top;  // injected ancestral noise: row (noise_top - t) belongs to step t
+};
+
+// One unconditional device loop: what sampler_loop needs to know beyond its arguments.
+struct LoopDesc {
+  const char* name;  // for messages (dn_ddpm_loop has always reported under dn_ddim_loop's)
+  const char* ws_name;
+  size_t (*ws_bytes)(const DnEps*, int32_t, int32_t, int32_t);
+  // a loop over a timestep schedule (device int32 [n_steps], coefficient rows [n_steps, coef_cols]): the counter counts step indices
+  // 0 .. n_steps-1 upwards and the conditioning table has one row per step; steps == NULL: timesteps start_step-1 downwards
+  const int32_t* steps;
+  int n_steps, coef_cols;
+  bool history;  // one more persistent buffer of the latent's size (dn_dpm_loop: the previous step's data prediction)
+  StepKey kind;  // ancestral, clip, scheduled, eta, dpm, seed, injected: the loop's part of the graph key
+  // the scheduler update after an evaluation, applied to batch rows [b0, b0 + nb) = half 0 or 1 on `stream`
+  std::function<int(const StepBufs&, int half, int b0, int nb, hipStream_t stream)> update;
 };
 }  // namespace
 
 static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, int32_t start_step, int32_t max_evals,
                         const float* coef, int32_t timesteps, int32_t flags, void* workspace, size_t workspace_bytes, void* stream,
-                        const StepOp& op) {
+                        const LoopDesc& d) {
   DN_CHECK_ARG(m && m->cfg.dim_prompt == 0, "dn_ddim_loop: the device loop covers the unconditional model (prompted chains step through dn_eps_forward_cond)");
   int use_graph = flags & DN_LOOP_GRAPH;
   const bool split = (flags & DN_LOOP_SPLIT2) && B >= 2;
   DN_CHECK_ARG(m && x && lengths && coef && workspace, "dn_ddim_loop: null argument");
-  const bool sched = op.steps != nullptr;
-  const char* who = op.dpm ? "dn_dpm_loop" : "dn_ddim_sched_loop";
+  const bool sched = d.steps != nullptr, ancestral = d.kind.ancestral;
   if (sched) {  // (a strictly descending list inside [0, timesteps-1] has at most `timesteps` entries)
-    DN_CHECK_ARG(op.n_steps >= 1 && op.n_steps <= timesteps, "%s: n_steps=%d must be in [1, %d]", who, op.n_steps, timesteps);
-    DN_CHECK_ARG(B > 0 && T > 0 && T <= m->cfg.max_pos, "%s: B=%d T=%d (positional table: %d)", who, B, T, m->cfg.max_pos);
-    DN_CHECK_ARG(op.eta_on || !op.noise, "dn_ddim_sched_loop: injected noise needs eta_on (eta = 0 draws none)");
+    DN_CHECK_ARG(d.n_steps >= 1 && d.n_steps <= timesteps, "%s: n_steps=%d must be in [1, %d]", d.name, d.n_steps, timesteps);
+    DN_CHECK_ARG(B > 0 && T > 0 && T <= m->cfg.max_pos, "%s: B=%d T=%d (positional table: %d)", d.name, B, T, m->cfg.max_pos);
+    DN_CHECK_ARG(d.kind.eta || !d.kind.injected, "dn_ddim_sched_loop: injected noise needs eta_on (eta = 0 draws none)");
   } else
-    DN_CHECK_ARG(start_step >= 1 && start_step <= timesteps - (op.ddpm ? 0 : 1), "dn_ddim_loop: start_step=%d must be in [1, %d]", start_step,
-                 timesteps - (op.ddpm ? 0 : 1));
-  if (sched) start_step = op.n_steps;  // rows of the conditioning table = evaluations of the chain
+    DN_CHECK_ARG(start_step >= 1 && start_step <= timesteps - (ancestral ? 0 : 1), "dn_ddim_loop: start_step=%d must be in [1, %d]", start_step,
+                 timesteps - (ancestral ? 0 : 1));
+  if (sched) start_step = d.n_steps;  // rows of the conditioning table = evaluations of the chain
   hipStream_t s = (hipStream_t)stream;
   DN_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "dn_ddim_loop: workspace must be 256-byte aligned");
   const int z = m->cfg.latent, M = B * T, C = m->cfg.dim * m->cfg.cond_mult;
@@ -662,16 +717,10 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
   // fill / drain of one half's launches overlaps the other half's main loops (measured -5 % per step at [32,512]).
   const int B0 = split ? B / 2 : B, B1 = B - B0;
   const size_t core0 = eps_ws_core(m, B0, T), core1 = split ? eps_ws_core(m, B1, T) : 0, core = core0 + core1;
-  size_t need = core + ddim_extra_bytes(m, B, T, start_step);
-  if (sched) need = dn_ddim_workspace_bytes(m, B, T, start_step);  // the documented size, split or not (>= what this call lays out)
-  if (op.dpm) need = dn_dpm_workspace_bytes(m, B, T, start_step);
+  // a schedule: the documented size, split or not (>= what this call lays out); a timestep loop: what this call lays out
+  const size_t need = sched ? d.ws_bytes(m, B, T, start_step) : core + ddim_extra_bytes(m, B, T, start_step);
   if (need > workspace_bytes) {
-    if (op.dpm)
-      dn_set_error("dn_dpm_loop: workspace %zu < required %zu (see dn_dpm_workspace_bytes)", workspace_bytes, need);
-    else if (sched)
-      dn_set_error("dn_ddim_sched_loop: workspace %zu < required %zu (see dn_ddim_sched_workspace_bytes)", workspace_bytes, need);
-    else
-      dn_set_error("dn_ddim_loop: workspace %zu < required %zu (see dn_ddim_workspace_bytes)", workspace_bytes, need);
+    dn_set_error("%s: workspace %zu < required %zu (see %s)", d.name, workspace_bytes, need, d.ws_name);
     return DN_EWORKSPACE;
   }
   Arena core_ar{(char*)workspace, 0, core0};
@@ -691,37 +740,36 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
   Arena ar{(char*)workspace + core, 0, workspace_bytes - core};
   // fixed-size state first, so a cached graph stays valid when only start_step changes
   float* eps = (float*)ar.take((size_t)M * z * 4);
-  float* hist = op.dpm ? (float*)ar.take((size_t)M * z * 4) : nullptr;  // dn_dpm_loop: x0 of the previous step, the whole batch's
+  float* hist = d.history ? (float*)ar.take((size_t)M * z * 4) : nullptr;  // (the whole batch's)
   int32_t* tvec = (int32_t*)ar.take((size_t)B * 4);
   int32_t* counter = (int32_t*)ar.take(64);
   float* table = (float*)ar.take((size_t)start_step * m->n_row * 4);  // conditioning rows for t = 0..start_step-1
   float* cond_all = (float*)ar.take((size_t)start_step * C * 4);
   void* table_h = m->cfg.dtype == DN_F32 ? nullptr : ar.take((size_t)start_step * m->n_cond * esize(m->cfg.dtype));
   int32_t* tall = (int32_t*)ar.take((size_t)start_step * 4);
-  const int last = (start_step == 1 || op.ddpm || sched) ? 0 : 1;  // DDIM: the loop breaks after the t == 1 update (:1444-1445); p_sample_loop runs t = 0 too
+  const int last = (start_step == 1 || ancestral || sched) ? 0 : 1;  // DDIM: the loop breaks after the t == 1 update (:1444-1445); p_sample_loop runs t = 0 too
   int n_eval = start_step - last;             // t = start_step-1 ... last (a schedule: every one of its steps)
   if (max_evals > 0 && max_evals < n_eval) n_eval = max_evals;  // partial chain (benchmarks, chunked sampling)
   // The 56 conditioning vectors depend only on t: build them for the whole chain once (fp32), so the
   // 117 M conditioning weights are not re-streamed at every step.
   const bool keep = (flags & DN_LOOP_KEEP_TABLE) && m->table_ws == workspace && m->table_B == B && m->table_T == T &&
                     m->table_split == (int)split && m->table_rows >= start_step;
-  const float* step_coef = coef;  // what the captured step reads
+  StepBufs sb = {x, eps, hist, coef, tvec, tall, counter, T, z, (int64_t)M * z, start_step - 1};
   if (sched) {
     // row i of the table belongs to steps[i].  The schedule and its coefficient rows move into the workspace, so a captured step
     // holds workspace addresses only: the steps where the other loops keep 0..start_step-1, the coefficients over `cond_all`
     // (dn_ddim_sched_workspace_bytes: dead once the table is built, and C >= 64 floats a row against DN_DDIM_SCHED_COLS).
     static_assert(DN_DDIM_SCHED_COLS <= 64 && DN_DPM_COLS <= 64, "the coefficient rows live in cond_all");
-    const size_t cols = op.dpm ? DN_DPM_COLS : DN_DDIM_SCHED_COLS;
-    if (hipMemcpyAsync(tall, op.steps, (size_t)start_step * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
-      dn_set_error("%s: copying the schedule failed", who);
+    if (hipMemcpyAsync(tall, d.steps, (size_t)start_step * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+      dn_set_error("%s: copying the schedule failed", d.name);
       return DN_ELAUNCH;
     }
     DN_TRY(eps_cond_rows(m, tall, start_step, cond_all, table, table_h, s));
-    if (hipMemcpyAsync(cond_all, coef, (size_t)start_step * cols * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
-      dn_set_error("%s: copying the coefficient rows failed", who);
+    if (hipMemcpyAsync(cond_all, coef, (size_t)start_step * d.coef_cols * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+      dn_set_error("%s: copying the coefficient rows failed", d.name);
       return DN_ELAUNCH;
     }
-    step_coef = cond_all;
+    sb.coef = cond_all;
     m->table_ws = nullptr;  // (not a table DN_LOOP_KEEP_TABLE could continue on)
     m->table_rows = 0;
   } else if (!keep) {
@@ -729,7 +777,6 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
     DN_TRY(eps_cond_rows(m, tall, start_step, cond_all, table, table_h, s));
     m->table_ws = workspace; m->table_B = B; m->table_T = T; m->table_split = (int)split; m->table_rows = start_step;
   }
-  const int noise_top = start_step - 1;  // injected noise: row (noise_top - t) belongs to step t
   const int32_t twin = split ? DN_GEMM_TWIN : 0;  // every contraction of a half batch has its twin beside it (tile choice)
   auto one_step = [&]() -> int {
     if (!sched)  // (the scheduled update reads its row by the counter: no per-sample step vector)
@@ -742,26 +789,10 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
         return DN_ELAUNCH;
       }
       DN_TRY(eps_core(m, x + off, bufs.gb, 0, lengths + B0, B1, T, eps + off, bufs1, s2, twin));
-      if (op.dpm)  // (each half on its own element range of the shared x / eps / hist)
-        DN_TRY(dn_dpm2m_step_launch(x, eps, hist, (int64_t)off, (int64_t)B1 * T * z, step_coef, counter, s2));
-      else if (sched)  // (the whole batch's element index keys the draw: the halves share one stream of numbers)
-        DN_TRY(dn_ddim_sched_step_launch(x, eps, (int64_t)off, (int64_t)B1 * T * z, step_coef, tall, counter, op.eta_on, op.noise, (int64_t)M * z,
-                                         op.seed, s2));
-      else if (op.ddpm)
-        DN_TRY(dn_ddpm_step_launch(x + off, eps + off, B1 * T, z, T, coef, tvec + B0, op.clip, op.noise ? op.noise + off : nullptr, (int64_t)M * z,
-                                   noise_top, op.seed ^ 0x9E3779B97F4A7C15ull, s2));  // (the second half draws from its own key)
-      else
-        DN_TRY(dn_ddim_step(x + off, eps + off, x + off, nullptr, DN_F32, z, B1 * T, z, z, T, coef, tvec + B0, s2));
+      DN_TRY(d.update(sb, 1, B0, B1, s2));
     }
     DN_TRY(eps_core(m, x, bufs.gb, 0, lengths, B0, T, eps, bufs, s, twin));
-    if (op.dpm)
-      DN_TRY(dn_dpm2m_step_launch(x, eps, hist, 0, (int64_t)B0 * T * z, step_coef, counter, s));
-    else if (sched)
-      DN_TRY(dn_ddim_sched_step_launch(x, eps, 0, (int64_t)B0 * T * z, step_coef, tall, counter, op.eta_on, op.noise, (int64_t)M * z, op.seed, s));
-    else if (op.ddpm)
-      DN_TRY(dn_ddpm_step_launch(x, eps, B0 * T, z, T, coef, tvec, op.clip, op.noise, (int64_t)M * z, noise_top, op.seed, s));
-    else
-      DN_TRY(dn_ddim_step(x, eps, x, nullptr, DN_F32, z, B0 * T, z, z, T, coef, tvec, s));
+    DN_TRY(d.update(sb, 0, 0, B0, s));
     if (split) {  // join
       if (hipEventRecord((hipEvent_t)m->ev_join, s2) != hipSuccess || hipStreamWaitEvent(s, (hipEvent_t)m->ev_join, 0) != hipSuccess) {
         dn_set_error("dn_ddim_loop: join failed");
@@ -776,73 +807,54 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
     return DN_OK;
   };
   hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(1), 0, s, counter, sched ? 0 : start_step - 1);
-  int done = 0;
   if (!s) use_graph = 0;  // the null stream cannot be captured
   if (use_graph && n_eval > 2) {
-    // (a scheduled chain's graph is keyed by the workspace copy of its coefficients: an address that moves with n_steps)
-    const int gflags = (flags & ~DN_LOOP_KEEP_TABLE) | (op.ddpm ? 1 << 16 : 0) | (op.clip ? 1 << 17 : 0) | (sched ? 1 << 18 : 0) |
-                       (op.eta_on ? 1 << 19 : 0) | (op.dpm ? 1 << 20 : 0);
-    // (an injected-noise chain bakes noise_top into the captured step: never served from the cache)
-    // (a dn_set_option since the capture may route the contractions differently: a miss)
-    const int opt_gen = dn::option_generation();
-    const bool cached = m->graph_exec && m->graph_B == B && m->graph_T == T && m->graph_ws == workspace && m->graph_x == x &&
-                        m->graph_len == lengths && m->graph_coef == step_coef && m->graph_flags == gflags && !op.noise &&
-                        m->graph_seed == op.seed && m->graph_opt_gen == opt_gen;
-    if (!cached) {
-      DN_TRY(one_step());  // eager first step: also settles the per-kernel attributes outside capture
-      done = 1;
-      if (m->graph_exec) {
-        (void)hipGraphExecDestroy((hipGraphExec_t)m->graph_exec);
-        m->graph_exec = nullptr;
-      }
-      hipGraph_t graph = nullptr;
-      if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) != hipSuccess) {
-        dn_set_error("dn_ddim_loop: hipStreamBeginCapture failed");
-        return DN_ELAUNCH;
-      }
-      int rc = one_step();
-      hipError_t e = hipStreamEndCapture(s, &graph);
-      if (rc != DN_OK) return rc;
-      if (e != hipSuccess || !graph) {
-        dn_set_error("dn_ddim_loop: hipStreamEndCapture: %s", hipGetErrorString(e));
-        return DN_ELAUNCH;
-      }
-      hipGraphExec_t exec = nullptr;
-      e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(graph);
-      if (e != hipSuccess) {
-        dn_set_error("dn_ddim_loop: hipGraphInstantiate: %s", hipGetErrorString(e));
-        return DN_ELAUNCH;
-      }
-      m->graph_exec = exec; m->graph_B = B; m->graph_T = T; m->graph_ws = workspace; m->graph_x = x;
-      m->graph_len = lengths; m->graph_coef = step_coef; m->graph_flags = op.noise ? -1 : gflags; m->graph_seed = op.seed;
-      m->graph_opt_gen = opt_gen;
-    }
-    for (; done < n_eval; ++done) {
-      hipError_t e = hipGraphLaunch((hipGraphExec_t)m->graph_exec, s);
-      if (e != hipSuccess) {
-        dn_set_error("dn_ddim_loop: hipGraphLaunch: %s", hipGetErrorString(e));
-        return DN_ELAUNCH;
-      }
-    }
+    // what the captured step bakes in, and no more: any start_step / max_evals is served (the fixed-size state is laid out first);
+    // a dn_set_option since the capture may route the contractions differently, so the option generation is part of it
+    StepKey key = d.kind;
+    key.ws = workspace; key.x = x; key.len = lengths; key.coef = sb.coef;
+    key.B = B; key.T = T; key.flags = flags & ~DN_LOOP_KEEP_TABLE; key.opt_gen = dn::option_generation();
+    DN_TRY(replay_steps(m->loop_graph, key, true, n_eval, s, d.name, one_step));
   } else {
-    for (; done < n_eval; ++done) DN_TRY(one_step());
+    for (int done = 0; done < n_eval; ++done) DN_TRY(one_step());
   }
   return n_eval;
+}
+
+// the loop's part of a graph key (memset first: the key is compared with memcmp)
+static StepKey step_kind(uint64_t seed, const float* noise) {
+  StepKey k;
+  memset(&k, 0, sizeof(k));
+  k.seed = seed;
+  k.injected = noise != nullptr;
+  return k;
 }
 
 extern "C" int dn_ddim_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, int32_t start_step, int32_t max_evals,
                             const float* coef, int32_t timesteps, int32_t flags, void* workspace, size_t workspace_bytes,
                             void* stream) {
-  return sampler_loop(m, x, lengths, B, T, start_step, max_evals, coef, timesteps, flags, workspace, workspace_bytes, stream, StepOp());
+  // DDIM eta = 0 with `coef` [timesteps, 4], on the half's own rows
+  LoopDesc d = {"dn_ddim_loop", "dn_ddim_workspace_bytes", dn_ddim_workspace_bytes, nullptr, 0, 0, false, step_kind(0, nullptr), nullptr};
+  d.update = [](const StepBufs& b, int, int b0, int nb, hipStream_t st) {
+    float* xh = b.x + (size_t)b0 * b.T * b.z;
+    return dn_ddim_step(xh, b.eps + (size_t)b0 * b.T * b.z, xh, nullptr, DN_F32, b.z, nb * b.T, b.z, b.z, b.T, b.coef, b.tvec + b0, st);
+  };
+  return sampler_loop(m, x, lengths, B, T, start_step, max_evals, coef, timesteps, flags, workspace, workspace_bytes, stream, d);
 }
 
 extern "C" int dn_ddpm_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, int32_t start_step, int32_t max_evals,
                             const float* table, int32_t timesteps, int32_t clip_denoised, uint64_t seed, const float* noise, int32_t flags,
                             void* workspace, size_t workspace_bytes, void* stream) {
-  StepOp op;
-  op.ddpm = true; op.clip = clip_denoised; op.seed = seed; op.noise = noise;
-  return sampler_loop(m, x, lengths, B, T, start_step, max_evals, table, timesteps, flags, workspace, workspace_bytes, stream, op);
+  // the ancestral step with `table` [timesteps, DN_GD_COLS], on the half's own rows; the second half draws from its own key
+  LoopDesc d = {"dn_ddim_loop", "dn_ddim_workspace_bytes", dn_ddim_workspace_bytes, nullptr, 0, 0, false, step_kind(seed, noise), nullptr};
+  d.kind.ancestral = 1;
+  d.kind.clip = clip_denoised != 0;
+  d.update = [=](const StepBufs& b, int half, int b0, int nb, hipStream_t st) {
+    const size_t off = (size_t)b0 * b.T * b.z;
+    return dn_ddpm_step_launch(b.x + off, b.eps + off, nb * b.T, b.z, b.T, b.coef, b.tvec + b0, clip_denoised, noise ? noise + off : nullptr, b.all,
+                               b.noise_top, half ? seed ^ 0x9E3779B97F4A7C15ull : seed, st);
+  };
+  return sampler_loop(m, x, lengths, B, T, start_step, max_evals, table, timesteps, flags, workspace, workspace_bytes, stream, d);
 }
 
 // rows of cond_all (C fp32 each) hold the chain's coefficient rows after the table is built: the same bytes as dn_ddim_loop's for
@@ -867,9 +879,19 @@ extern "C" int dn_ddim_sched_loop(DnEps* m, float* x, const int32_t* lengths, in
                                   void* workspace, size_t workspace_bytes, void* stream) {
   DN_CHECK_ARG(steps, "dn_ddim_sched_loop: null schedule");
   DN_CHECK_ARG(!(flags & ~(DN_LOOP_GRAPH | DN_LOOP_SPLIT2)), "dn_ddim_sched_loop: flags=%d (DN_LOOP_GRAPH | DN_LOOP_SPLIT2 only)", flags);
-  StepOp op;
-  op.steps = steps; op.n_steps = n_steps; op.eta_on = eta_on != 0; op.seed = op.eta_on ? seed : 0; op.noise = noise;
-  return sampler_loop(m, x, lengths, B, T, 0, 0, coef, timesteps, flags, workspace, workspace_bytes, stream, op);
+  eta_on = eta_on != 0;
+  if (!eta_on) seed = 0;
+  // the scheduled update on the half's element range of the whole batch: the whole batch's element index keys the draw, so the halves
+  // share one stream of numbers
+  LoopDesc d = {"dn_ddim_sched_loop", "dn_ddim_sched_workspace_bytes", dn_ddim_sched_workspace_bytes, steps, n_steps, DN_DDIM_SCHED_COLS,
+                false, step_kind(seed, noise), nullptr};
+  d.kind.scheduled = 1;
+  d.kind.eta = (uint16_t)eta_on;
+  d.update = [=](const StepBufs& b, int, int b0, int nb, hipStream_t st) {
+    return dn_ddim_sched_step_launch(b.x, b.eps, (int64_t)b0 * b.T * b.z, (int64_t)nb * b.T * b.z, b.coef, b.steps, b.counter, eta_on, noise, b.all,
+                                     seed, st);
+  };
+  return sampler_loop(m, x, lengths, B, T, 0, 0, coef, timesteps, flags, workspace, workspace_bytes, stream, d);
 }
 
 // dn_ddim_sched_loop's layout with the history buffer taken beside eps (one more 256-byte aligned block of the latent's size)
@@ -886,9 +908,13 @@ extern "C" int dn_dpm_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B
   DN_CHECK_ARG(steps, "dn_dpm_loop: null schedule");
   DN_CHECK_ARG(!(flags & ~(DN_LOOP_GRAPH | DN_LOOP_SPLIT2)), "dn_dpm_loop: flags=%d (DN_LOOP_GRAPH | DN_LOOP_SPLIT2 only)", flags);
   DN_CHECK_ARG(x && lengths && coef && workspace, "dn_dpm_loop: null argument");
-  StepOp op;
-  op.steps = steps; op.n_steps = n_steps; op.dpm = true;
-  return sampler_loop(m, x, lengths, B, T, 0, 0, coef, timesteps, flags, workspace, workspace_bytes, stream, op);
+  // DPM-Solver++(2M) on the half's element range of the shared x / eps / hist
+  LoopDesc d = {"dn_dpm_loop", "dn_dpm_workspace_bytes", dn_dpm_workspace_bytes, steps, n_steps, DN_DPM_COLS, true, step_kind(0, nullptr), nullptr};
+  d.kind.scheduled = d.kind.dpm = 1;
+  d.update = [](const StepBufs& b, int, int b0, int nb, hipStream_t st) {
+    return dn_dpm2m_step_launch(b.x, b.eps, b.hist, (int64_t)b0 * b.T * b.z, (int64_t)nb * b.T * b.z, b.coef, b.counter, st);
+  };
+  return sampler_loop(m, x, lengths, B, T, 0, 0, coef, timesteps, flags, workspace, workspace_bytes, stream, d);
 }
 
 
@@ -1333,56 +1359,17 @@ extern "C" int dn_guided_ddim_loop(DnEps* m, float* x, const int32_t* lengths, c
     return DN_OK;
   };
   DN_TRY(one_step(false));  // eager: the prompt-only work, and the per-kernel attributes settle outside capture
-  int done = 1;
   if ((flags & DN_LOOP_GRAPH) && s && n_steps > 2) {  // (the null stream cannot be captured)
-    uint32_t scale_bits;
-    memcpy(&scale_bits, &cond_scale, 4);
-    const int opt_gen = dn::option_generation();
     // (an injected-noise chain is never served from the cache; a dn_set_option since the capture may route the contractions differently)
-    const bool cached = m->gg_exec && !noise && m->gg_flags == flags && m->gg_B == B && m->gg_T == T && m->gg_Tp == Tp && m->gg_n == n_steps &&
-                        m->gg_ws == workspace && m->gg_x == x && m->gg_len == lengths && m->gg_prompt == prompt && m->gg_plen == prompt_lengths &&
-                        m->gg_coef == g.coef && m->gg_scale_bits == scale_bits && m->gg_eta == eta_on && m->gg_seed == seed &&
-                        m->gg_opt_gen == opt_gen;
-    if (!cached) {
-      if (m->gg_exec) {
-        (void)hipGraphExecDestroy((hipGraphExec_t)m->gg_exec);
-        m->gg_exec = nullptr;
-      }
-      hipGraph_t graph = nullptr;
-      if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) != hipSuccess) {
-        dn_set_error("dn_guided_ddim_loop: hipStreamBeginCapture failed");
-        return DN_ELAUNCH;
-      }
-      const int rc = one_step(true);
-      hipError_t e = hipStreamEndCapture(s, &graph);
-      if (rc != DN_OK) {
-        if (graph) (void)hipGraphDestroy(graph);
-        return rc;
-      }
-      if (e != hipSuccess || !graph) {
-        dn_set_error("dn_guided_ddim_loop: hipStreamEndCapture: %s", hipGetErrorString(e));
-        return DN_ELAUNCH;
-      }
-      hipGraphExec_t exec = nullptr;
-      e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(graph);
-      if (e != hipSuccess) {
-        dn_set_error("dn_guided_ddim_loop: hipGraphInstantiate: %s", hipGetErrorString(e));
-        return DN_ELAUNCH;
-      }
-      m->gg_exec = exec; m->gg_flags = noise ? -1 : flags; m->gg_B = B; m->gg_T = T; m->gg_Tp = Tp; m->gg_n = n_steps;
-      m->gg_ws = workspace; m->gg_x = x; m->gg_len = lengths; m->gg_prompt = prompt; m->gg_plen = prompt_lengths; m->gg_coef = g.coef;
-      m->gg_scale_bits = scale_bits; m->gg_eta = eta_on; m->gg_seed = seed; m->gg_opt_gen = opt_gen;
-    }
-    for (; done < n_steps; ++done) {
-      const hipError_t e = hipGraphLaunch((hipGraphExec_t)m->gg_exec, s);
-      if (e != hipSuccess) {
-        dn_set_error("dn_guided_ddim_loop: hipGraphLaunch: %s", hipGetErrorString(e));
-        return DN_ELAUNCH;
-      }
-    }
+    StepKey key;
+    memset(&key, 0, sizeof(key));
+    key.ws = workspace; key.x = x; key.len = lengths; key.coef = g.coef; key.prompt = prompt; key.plen = prompt_lengths;
+    key.seed = seed; key.B = B; key.T = T; key.Tp = Tp; key.n_steps = n_steps; key.flags = flags; key.opt_gen = dn::option_generation();
+    memcpy(&key.scale_bits, &cond_scale, 4);
+    key.eta = (uint16_t)eta_on; key.injected = noise != nullptr;
+    DN_TRY(replay_steps(m->guided_graph, key, false, n_steps - 1, s, "dn_guided_ddim_loop", [&] { return one_step(true); }));
   } else {
-    for (; done < n_steps; ++done) DN_TRY(one_step(true));
+    for (int done = 1; done < n_steps; ++done) DN_TRY(one_step(true));
   }
   return n_steps;
 }

@@ -311,40 +311,53 @@ __device__ __forceinline__ void philox_normal4(uint64_t seed, uint64_t ctr_lo, u
 // ------------------------------------------------------------------------------------------ scheduled DDIM step of the device loop
 // One update of a DDIM chain over a timestep schedule (dn_ddim_sched_loop): row i = *counter of `coef` [n, DN_DDIM_SCHED_COLS] =
 // {sqrt abar_e, sqrt(1-abar_e), sqrt abar_tgt, sqrt(1-abar_tgt-sigma^2), sigma}, uniform over the batch.  eta_on == 0: the
-// statements of ddim_step_kernel, product for product (as compiled: see the loop).  eta_on: + 1[e_i != 0] sigma z (diffusion/gaussian_diffusion.py:513-560), z
+// statements of ddim_step_kernel, product for product (as compiled: see sched_update).  eta_on: + 1[e_i != 0] sigma z (diffusion/gaussian_diffusion.py:513-560), z
 // injected (row i of `noise`) or drawn here: Philox4x32-10, key = seed, counter = (element quad OF THE WHOLE BATCH, step index i) --
 // a half-batch launch passes its first quad (q0), so eager, graph replay and the two half-batch streams draw the same numbers.
+// The three pieces below are the one definition of that update: dn_guided_ddim_loop's kernel applies them too, and the two chains are
+// tested bit-equal.
+struct SchedCoef {
+  float sa, s1, ct, cd, sg;
+};
+// row `step` of `coef`, with sigma masked to 0 without eta and at timestep 0
+__device__ __forceinline__ SchedCoef sched_coef(const float* __restrict__ coef, const int32_t* __restrict__ steps, int step, bool eta_on) {
+  const float* cf = coef + (int64_t)step * DN_DDIM_SCHED_COLS;
+  return {cf[0], cf[1], cf[2], cf[3], (eta_on && steps[step] != 0) ? cf[4] : 0.0f};
+}
+// the four normals of quad q (elements i .. i+3) at `step`: the injected row, or Philox keyed by (q, step)
+__device__ __forceinline__ void sched_normal4(const float* __restrict__ noise, int64_t noise_row, uint64_t seed, int64_t q, int64_t i, int step,
+                                              float (&z)[4]) {
+  if (noise) {
+    const float4 nv = *reinterpret_cast<const float4*>(noise + (int64_t)step * noise_row + i);
+    z[0] = nv.x; z[1] = nv.y; z[2] = nv.z; z[3] = nv.w;
+  } else {
+    philox_normal4(seed, (uint64_t)q, (uint32_t)step, z);
+  }
+}
+// ddim_step_kernel's statements as the compiler builds them (products contracted into the sums that take them: x - s1 eps,
+// x - sa x1, and x1 c2 onto the rounded c3 pn), spelled out so that no two kernels can be contracted differently
+__device__ __forceinline__ float sched_update(const SchedCoef& c, float x, float e, float z, bool eta_on) {
+  const float x1 = __fdiv_rn(fmaf(-c.s1, e, x), fmaxf(c.sa, 1e-10f));
+  const float pn = __fdiv_rn(fmaf(-c.sa, x1, x), fmaxf(c.s1, 1e-10f));
+  const float r = fmaf(c.ct, x1, __fmul_rn(c.cd, pn));
+  return eta_on ? fmaf(c.sg, z, r) : r;
+}
+
 __global__ __launch_bounds__(256) void ddim_sched_step_kernel(float* x, const float* __restrict__ eps, int64_t q0, int64_t nquad,
                                                               const float* __restrict__ coef, const int32_t* __restrict__ steps,
                                                               const int32_t* __restrict__ counter, int eta_on,
                                                               const float* __restrict__ noise, int64_t noise_row, uint64_t seed) {
   const int step = *counter;
-  const float* cf = coef + (int64_t)step * DN_DDIM_SCHED_COLS;
-  const float sa = cf[0], s1 = cf[1], ct = cf[2], cd = cf[3];
-  const float sg = (eta_on && steps[step] != 0) ? cf[4] : 0.0f;
+  const SchedCoef c = sched_coef(coef, steps, step, eta_on);
   for (int64_t q = q0 + blockIdx.x * 256 + threadIdx.x; q < q0 + nquad; q += (int64_t)gridDim.x * 256) {
     const int64_t i = q << 2;
     const float4 xv = *reinterpret_cast<const float4*>(x + i), ev = *reinterpret_cast<const float4*>(eps + i);
     float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (eta_on) {
-      if (noise) {
-        const float4 nv = *reinterpret_cast<const float4*>(noise + (int64_t)step * noise_row + i);
-        z[0] = nv.x; z[1] = nv.y; z[2] = nv.z; z[3] = nv.w;
-      } else {
-        philox_normal4(seed, (uint64_t)q, (uint32_t)step, z);
-      }
-    }
+    if (eta_on) sched_normal4(noise, noise_row, seed, q, i, step, z);
     const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, es[4] = {ev.x, ev.y, ev.z, ev.w};
     float o[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      // ddim_step_kernel's statements as the compiler builds them (products contracted into the sums that take them: x - s1 eps,
-      // x - sa x1, and x1 c2 onto the rounded c3 pn), spelled out so that the two kernels cannot be contracted differently
-      const float x1 = __fdiv_rn(fmaf(-s1, es[j], xs[j]), fmaxf(sa, 1e-10f));
-      const float pn = __fdiv_rn(fmaf(-sa, x1, xs[j]), fmaxf(s1, 1e-10f));
-      const float r = fmaf(ct, x1, __fmul_rn(cd, pn));
-      o[j] = eta_on ? fmaf(sg, z[j], r) : r;
-    }
+    for (int j = 0; j < 4; ++j) o[j] = sched_update(c, xs[j], es[j], z[j], eta_on);
     *reinterpret_cast<float4*>(x + i) = make_float4(o[0], o[1], o[2], o[3]);
   }
 }
@@ -384,7 +397,7 @@ __global__ __launch_bounds__(256) void dpm2m_step_kernel(float* x, const float* 
 // ------------------------------------------------------------------------------------------ guided scheduled DDIM step of the device loop
 // One update of the prompted, guided chain over a timestep schedule (dn_guided_ddim_loop), per float4 quad of the B-row latent:
 // eps = the conditioned row of `both` (kGuided: combined with the null row, n elements further, by cfg_combine_kernel's three rounded
-// operations), then ddim_sched_step_kernel's update, statement for statement, with its coefficient row, noise mask and noise source
+// operations), then ddim_sched_step_kernel's update through the same three helpers: its coefficient row, noise mask and noise source
 // (the Philox counter is the quad of the B-row batch and the step index, so a scale-1 chain draws what dn_ddim_sched_loop draws).
 // The result goes to x and to the model's next input: xin[0:n] and (kGuided) xin[n:2n] -- one pass where the host-driven chain
 // copies x twice, combines, updates and decrements.  !kGuided: nothing past n is touched, and xin may be x itself.
@@ -395,9 +408,7 @@ __global__ __launch_bounds__(256) void guided_sched_step_kernel(float* x, float*
                                                                 const int32_t* __restrict__ counter, const float* __restrict__ noise,
                                                                 int64_t noise_row, uint64_t seed) {
   const int step = *counter;
-  const float* cf = coef + (int64_t)step * DN_DDIM_SCHED_COLS;
-  const float sa = cf[0], s1 = cf[1], ct = cf[2], cd = cf[3];
-  const float sg = (kEta && steps[step] != 0) ? cf[4] : 0.0f;
+  const SchedCoef c = sched_coef(coef, steps, step, kEta);
   const int64_t n = nquad << 2;
   for (int64_t q = blockIdx.x * 256 + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * 256) {
     const int64_t i = q << 2;
@@ -410,23 +421,11 @@ __global__ __launch_bounds__(256) void guided_sched_step_kernel(float* x, float*
       for (int j = 0; j < 4; ++j) es[j] = __fadd_rn(us[j], __fmul_rn(__fsub_rn(es[j], us[j]), scale));
     }
     float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (kEta) {
-      if (noise) {
-        const float4 nv = *reinterpret_cast<const float4*>(noise + (int64_t)step * noise_row + i);
-        z[0] = nv.x; z[1] = nv.y; z[2] = nv.z; z[3] = nv.w;
-      } else {
-        philox_normal4(seed, (uint64_t)q, (uint32_t)step, z);
-      }
-    }
+    if (kEta) sched_normal4(noise, noise_row, seed, q, i, step, z);
     const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
     float o[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {  // (ddim_sched_step_kernel's spelling)
-      const float x1 = __fdiv_rn(fmaf(-s1, es[j], xs[j]), fmaxf(sa, 1e-10f));
-      const float pn = __fdiv_rn(fmaf(-sa, x1, xs[j]), fmaxf(s1, 1e-10f));
-      const float r = fmaf(ct, x1, __fmul_rn(cd, pn));
-      o[j] = kEta ? fmaf(sg, z[j], r) : r;
-    }
+    for (int j = 0; j < 4; ++j) o[j] = sched_update(c, xs[j], es[j], z[j], kEta);
     const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
     *reinterpret_cast<float4*>(x + i) = ov;
     if (kGuided) {

@@ -44,6 +44,10 @@ def _f32(t: torch.Tensor, device) -> torch.Tensor:
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
+def _loop_flags(use_graph: bool, split: bool = False, keep_table: bool = False) -> int:
+    return (1 if use_graph else 0) | (2 if split else 0) | (4 if keep_table else 0)  # DN_LOOP_GRAPH | DN_LOOP_SPLIT2 | DN_LOOP_KEEP_TABLE
+
+
 class _Engine:
     def __init__(self, device, tensors: List[torch.Tensor]):
         self.device = _require_cuda(device)
@@ -63,6 +67,9 @@ class _Engine:
         p = ws.data_ptr()
         a = (p + 255) & ~255
         return a, ws.numel() - (a - p)
+
+    def _aligned_workspace(self, nbytes):
+        return self._aligned(self._workspace(int(nbytes)))
 
     def weight_bytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self.tensors)
@@ -178,8 +185,7 @@ class EpsEngine(_Engine):
         x = _f32(x, self.device)
         t32, l32 = _i32(times, self.device), _i32(lengths, self.device)
         out = torch.empty_like(x) if out is None else out
-        ws = self._workspace(self.workspace_bytes(B, T))
-        wp, wn = self._aligned(ws)
+        wp, wn = self._aligned_workspace(self.workspace_bytes(B, T))
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dn_eps_forward(self.handle, x.data_ptr(), t32.data_ptr(), l32.data_ptr(), B, T,
                                                int(shared_t), out.data_ptr(), wp, wn, _lib.current_stream()),
@@ -210,8 +216,7 @@ class EpsEngine(_Engine):
         t32, l32, p32 = _i32(times, self.device), _i32(lengths, self.device), _i32(prompt_lengths, self.device)
         d32 = torch.zeros(B, dtype=torch.int32, device=self.device) if drop is None else _i32(drop, self.device)
         out = torch.empty_like(x) if out is None else out
-        ws = self._workspace(int(self.lib.dn_eps_cond_workspace_bytes(self.handle, B, T, Tp)))
-        wp, wn = self._aligned(ws)
+        wp, wn = self._aligned_workspace(int(self.lib.dn_eps_cond_workspace_bytes(self.handle, B, T, Tp)))
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dn_eps_forward_cond_ex(self.handle, x.data_ptr(), t32.data_ptr(), l32.data_ptr(), prompt.data_ptr(), p32.data_ptr(),
                                                        d32.data_ptr(), B, T, Tp, out.data_ptr(), wp, wn, int(bool(reuse_prompt)),
@@ -250,8 +255,7 @@ class EpsEngine(_Engine):
         issues graph launches.  Returns the number of model evaluations."""
         from . import ops
 
-        B, T, z = x.shape
-        assert x.is_contiguous() and x.dtype == torch.float32 and x.device == self.device
+        B, T, z = self._loop_x(x)
         guided = cond_scale != 1.0
         n = 2 * B if guided else B
         if guided:
@@ -302,25 +306,48 @@ class EpsEngine(_Engine):
                 one_step()
         return n_eval
 
+    # ---- what the device sampling loops' wrappers share
+    def _loop_x(self, x: torch.Tensor):
+        assert x.is_contiguous() and x.dtype == torch.float32 and x.device == self.device
+        return x.shape
+
+    def _on_device(self, t: torch.Tensor, dtype, contiguous: bool = False) -> torch.Tensor:
+        # (the loops' graph caches are keyed by device addresses: a copy where none is needed would turn a hit into a miss)
+        if t.dtype == dtype and t.device == self.device and (t.is_contiguous() or not contiguous):
+            return t
+        return t.to(device=self.device, dtype=dtype).contiguous()
+
+    def _loop_schedule(self, steps: torch.Tensor, coef: torch.Tensor, cols: int) -> int:
+        n = int(steps.shape[0])
+        assert steps.dtype == torch.int32 and steps.is_contiguous() and steps.device == self.device and steps.dim() == 1
+        assert coef.dtype == torch.float32 and coef.is_contiguous() and coef.device == self.device and coef.shape == (n, cols)
+        return n
+
+    def _loop_noise(self, noise, shape, who: str = "", eta: Optional[float] = None):
+        if noise is None:
+            return None
+        if eta is not None and not eta > 0:
+            raise ValueError(f"{who}: injected noise needs eta > 0 (eta = 0 draws none)")
+        nz = _f32(noise, self.device)
+        assert nz.shape == shape, (nz.shape, shape)
+        return nz
+
     def ddim_loop(self, x: torch.Tensor, lengths: torch.Tensor, start_step: int, coef: torch.Tensor,
                   use_graph: bool = True, max_evals: int = 0, split: bool = True, keep_table: bool = False) -> int:
         """In-place DDIM eta=0 chain on x [B,T,z] fp32 (reference latent_module.py:1411-1445).
         coef: fp32 [timesteps,4] from `scheduler.ddim_coef_table`.  Returns the number of model evaluations.
         `max_evals` stops early; the caller continues with start_step - max_evals and may pass `keep_table=True` when
         nothing else used this engine in between (the conditioning table of the first call is then reused)."""
-        B, T, z = x.shape
-        assert x.is_contiguous() and x.dtype == torch.float32 and x.device == self.device
+        B, T, z = self._loop_x(x)
         assert coef.dtype == torch.float32 and coef.is_contiguous() and coef.device == self.device
-        l32 = lengths if (lengths.dtype == torch.int32 and lengths.device == self.device) else _i32(lengths, self.device)
+        l32 = self._on_device(lengths, torch.int32)
         self._keep = (l32, coef)
-        ws = self._workspace(int(self.lib.dn_ddim_workspace_bytes(self.handle, B, T, start_step)))
-        wp, wn = self._aligned(ws)
+        wp, wn = self._aligned_workspace(self.lib.dn_ddim_workspace_bytes(self.handle, B, T, start_step))
         with torch.cuda.device(self.device):
             return _lib.check(self.lib.dn_ddim_loop(self.handle, x.data_ptr(), l32.data_ptr(), B, T, start_step,
                                                     max_evals, coef.data_ptr(), coef.shape[0],
-                                                    (1 if use_graph else 0) | (2 if split else 0) | (4 if keep_table else 0), wp, wn,
+                                                    _loop_flags(use_graph, split, keep_table), wp, wn,
                                                     _lib.current_stream()), "dn_ddim_loop")
-
 
     def ddpm_loop(self, x: torch.Tensor, lengths: torch.Tensor, start_step: int, table: torch.Tensor, seed: int = 0,
                   noise: Optional[torch.Tensor] = None, clip_denoised: bool = False, use_graph: bool = True, max_evals: int = 0,
@@ -330,21 +357,16 @@ class EpsEngine(_Engine):
         configs[2] read literally).  table: fp32 [timesteps, 12] from `scheduler.gaussian_table`.  The noise of a step is drawn
         in the update kernel (Philox keyed by `seed` and the step) or injected: noise [start_step, B, T, z], row k for
         t = start_step-1-k.  Returns the number of model evaluations."""
-        B, T, z = x.shape
-        assert x.is_contiguous() and x.dtype == torch.float32 and x.device == self.device
+        B, T, z = self._loop_x(x)
         assert table.dtype == torch.float32 and table.is_contiguous() and table.device == self.device and table.shape[1] == 12
-        l32 = lengths if (lengths.dtype == torch.int32 and lengths.device == self.device) else _i32(lengths, self.device)
-        nz = None
-        if noise is not None:
-            nz = _f32(noise, self.device)
-            assert nz.shape == (start_step, B, T, z), (nz.shape, (start_step, B, T, z))
+        l32 = self._on_device(lengths, torch.int32)
+        nz = self._loop_noise(noise, (start_step, B, T, z))
         self._keep = (l32, table, nz)
-        ws = self._workspace(int(self.lib.dn_ddim_workspace_bytes(self.handle, B, T, start_step)))
-        wp, wn = self._aligned(ws)
+        wp, wn = self._aligned_workspace(self.lib.dn_ddim_workspace_bytes(self.handle, B, T, start_step))
         with torch.cuda.device(self.device):
             return _lib.check(self.lib.dn_ddpm_loop(self.handle, x.data_ptr(), l32.data_ptr(), B, T, start_step, max_evals, table.data_ptr(),
                                                     table.shape[0], int(clip_denoised), int(seed) & (2 ** 64 - 1), _lib.ptr(nz),
-                                                    (1 if use_graph else 0) | (2 if split else 0) | (4 if keep_table else 0), wp, wn,
+                                                    _loop_flags(use_graph, split, keep_table), wp, wn,
                                                     _lib.current_stream()), "dn_ddpm_loop")
 
     def ddim_schedule_loop(self, x: torch.Tensor, lengths: torch.Tensor, steps: torch.Tensor, coef: torch.Tensor, eta: float = 0.0,
@@ -356,25 +378,16 @@ class EpsEngine(_Engine):
         in the update kernel (Philox keyed by `seed`, the step index and the element's index in the whole batch -- eager, graph and
         split chains agree bit for bit) or injected, noise [n, B, T, z], row i for update i.  `timesteps`: the length of the noise
         schedule the steps index (the entry refuses a list longer than that).  Returns the number of evaluations."""
-        B, T, z = x.shape
-        assert x.is_contiguous() and x.dtype == torch.float32 and x.device == self.device
-        n = int(steps.shape[0])
-        assert steps.dtype == torch.int32 and steps.is_contiguous() and steps.device == self.device and steps.dim() == 1
-        assert coef.dtype == torch.float32 and coef.is_contiguous() and coef.device == self.device and coef.shape == (n, _lib.DDIM_SCHED_COLS)
-        l32 = lengths if (lengths.dtype == torch.int32 and lengths.device == self.device) else _i32(lengths, self.device)
-        nz = None
-        if noise is not None:
-            if not eta > 0:
-                raise ValueError("ddim_schedule_loop: injected noise needs eta > 0 (eta = 0 draws none)")
-            nz = _f32(noise, self.device)
-            assert nz.shape == (n, B, T, z), (nz.shape, (n, B, T, z))
+        B, T, z = self._loop_x(x)
+        n = self._loop_schedule(steps, coef, _lib.DDIM_SCHED_COLS)
+        l32 = self._on_device(lengths, torch.int32)
+        nz = self._loop_noise(noise, (n, B, T, z), "ddim_schedule_loop", eta)
         self._keep = (l32, steps, coef, nz)
-        ws = self._workspace(int(self.lib.dn_ddim_sched_workspace_bytes(self.handle, B, T, n)))
-        wp, wn = self._aligned(ws)
+        wp, wn = self._aligned_workspace(self.lib.dn_ddim_sched_workspace_bytes(self.handle, B, T, n))
         with torch.cuda.device(self.device):
             return _lib.check(self.lib.dn_ddim_sched_loop(self.handle, x.data_ptr(), l32.data_ptr(), B, T, steps.data_ptr(), coef.data_ptr(), n,
                                                           n if timesteps is None else int(timesteps), int(eta > 0), int(seed) & (2 ** 64 - 1), _lib.ptr(nz),
-                                                          (1 if use_graph else 0) | (2 if split else 0), wp, wn, _lib.current_stream()),
+                                                          _loop_flags(use_graph, split), wp, wn, _lib.current_stream()),
                               "dn_ddim_sched_loop")
 
     def dpm_schedule_loop(self, x: torch.Tensor, lengths: torch.Tensor, steps: torch.Tensor, rows: torch.Tensor, use_graph: bool = True,
@@ -385,8 +398,7 @@ class EpsEngine(_Engine):
         workspace holds one more latent-sized buffer, the previous step's data prediction.  Deterministic: no eta, no noise.  `steps`
         may also be a list or a host tensor: it is then validated by dn_ddim_sched_check against `timesteps` and uploaded.
         Returns the number of evaluations."""
-        B, T, z = x.shape
-        assert x.is_contiguous() and x.dtype == torch.float32 and x.device == self.device
+        B, T, z = self._loop_x(x)
         nt = None if timesteps is None else int(timesteps)
         if not (isinstance(steps, torch.Tensor) and steps.device == self.device):
             host = torch.as_tensor(steps, dtype=torch.int32).contiguous().view(-1)
@@ -394,16 +406,13 @@ class EpsEngine(_Engine):
                                             int(host.numel()) if nt is None else nt) != 0:
                 raise ValueError("dpm_schedule_loop: " + (self.lib.dn_last_error() or b"").decode())
             steps = host.to(self.device)
-        n = int(steps.shape[0])
-        assert steps.dtype == torch.int32 and steps.is_contiguous() and steps.dim() == 1
-        assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.device == self.device and rows.shape == (n, _lib.DPM_COLS)
-        l32 = lengths if (lengths.dtype == torch.int32 and lengths.device == self.device) else _i32(lengths, self.device)
+        n = self._loop_schedule(steps, rows, _lib.DPM_COLS)
+        l32 = self._on_device(lengths, torch.int32)
         self._keep = (l32, steps, rows)
-        ws = self._workspace(int(self.lib.dn_dpm_workspace_bytes(self.handle, B, T, n)))
-        wp, wn = self._aligned(ws)
+        wp, wn = self._aligned_workspace(self.lib.dn_dpm_workspace_bytes(self.handle, B, T, n))
         with torch.cuda.device(self.device):
             return _lib.check(self.lib.dn_dpm_loop(self.handle, x.data_ptr(), l32.data_ptr(), B, T, steps.data_ptr(), rows.data_ptr(), n,
-                                                   n if nt is None else nt, (1 if use_graph else 0) | (2 if split else 0), wp, wn,
+                                                   n if nt is None else nt, _loop_flags(use_graph, split), wp, wn,
                                                    _lib.current_stream()), "dn_dpm_loop")
 
     def cond_time_table_steps(self, steps) -> torch.Tensor:
@@ -430,30 +439,21 @@ class EpsEngine(_Engine):
         `forward_with_cond_scale` (one pass over 2B rows, or B rows at scale 1).  The whole loop runs behind the C entry: time table
         of n rows, prompt-only work in the first step, one fused combination + update kernel per step, hipGraph replay.  On the
         every-timestep schedule at eta = 0 it is `guided_ddim_chain` bit for bit.  Returns the number of evaluations."""
-        B, T, z = x.shape
-        assert x.is_contiguous() and x.dtype == torch.float32 and x.device == self.device
-        n = int(steps.shape[0])
-        assert steps.dtype == torch.int32 and steps.is_contiguous() and steps.device == self.device and steps.dim() == 1
-        assert coef.dtype == torch.float32 and coef.is_contiguous() and coef.device == self.device and coef.shape == (n, _lib.DDIM_SCHED_COLS)
-        l32 = lengths if (lengths.dtype == torch.int32 and lengths.device == self.device) else _i32(lengths, self.device)
-        pl32 = prompt_lengths if (prompt_lengths.dtype == torch.int32 and prompt_lengths.device == self.device) else _i32(prompt_lengths, self.device)
-        p32 = prompt if (prompt.dtype == torch.float32 and prompt.device == self.device and prompt.is_contiguous()) else _f32(prompt, self.device)
+        B, T, z = self._loop_x(x)
+        n = self._loop_schedule(steps, coef, _lib.DDIM_SCHED_COLS)
+        l32 = self._on_device(lengths, torch.int32)
+        pl32 = self._on_device(prompt_lengths, torch.int32)
+        p32 = self._on_device(prompt, torch.float32, contiguous=True)
         assert p32.dim() == 3 and p32.shape[0] == B and p32.shape[2] == self.cfg.dim_prompt and l32.shape == (B,) and pl32.shape == (B,)
         Tp = int(p32.shape[1])
-        nz = None
-        if noise is not None:
-            if not eta > 0:
-                raise ValueError("guided_ddim_schedule_loop: injected noise needs eta > 0 (eta = 0 draws none)")
-            nz = _f32(noise, self.device)
-            assert nz.shape == (n, B, T, z), (nz.shape, (n, B, T, z))
+        nz = self._loop_noise(noise, (n, B, T, z), "guided_ddim_schedule_loop", eta)
         self._keep = (l32, pl32, p32, steps, coef, nz)
-        ws = self._workspace(int(self.lib.dn_guided_ddim_workspace_bytes(self.handle, B, T, Tp, n, int(float(cond_scale) != 1.0))))
-        wp, wn = self._aligned(ws)
+        wp, wn = self._aligned_workspace(self.lib.dn_guided_ddim_workspace_bytes(self.handle, B, T, Tp, n, int(float(cond_scale) != 1.0)))
         with torch.cuda.device(self.device):
             return _lib.check(self.lib.dn_guided_ddim_loop(self.handle, x.data_ptr(), l32.data_ptr(), p32.data_ptr(), pl32.data_ptr(), B, T, Tp,
                                                            float(cond_scale), steps.data_ptr(), coef.data_ptr(), n,
                                                            n if timesteps is None else int(timesteps), int(eta > 0), int(seed) & (2 ** 64 - 1),
-                                                           _lib.ptr(nz), 1 if use_graph else 0, wp, wn, _lib.current_stream()),
+                                                           _lib.ptr(nz), _loop_flags(use_graph), wp, wn, _lib.current_stream()),
                               "dn_guided_ddim_loop")
 
 
@@ -499,8 +499,7 @@ class VaeEngine(_Engine):
         B, T, _ = feat.shape
         feat = _f32(feat, self.device)
         out = torch.empty(B, T, 2 * self.z, dtype=torch.float32, device=self.device)
-        ws = self._workspace(self.workspace_bytes(B, T))
-        wp, wn = self._aligned(ws)
+        wp, wn = self._aligned_workspace(self.workspace_bytes(B, T))
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dn_vae_encode_params(self.handle, feat.data_ptr(), B, T, out.data_ptr(), wp, wn,
                                                      _lib.current_stream()), "dn_vae_encode_params")
@@ -534,8 +533,7 @@ class VaeEngine(_Engine):
         recon = torch.empty(B, T, self.dim, dtype=torch.float32, device=self.device) if want_recon else None
         logits = torch.empty(B, T, self.vocab, dtype=torch.float32, device=self.device) if want_logits else None
         units = torch.empty(B, T, dtype=torch.int32, device=self.device) if want_units else None
-        ws = self._workspace(self.workspace_bytes(B, T))
-        wp, wn = self._aligned(ws)
+        wp, wn = self._aligned_workspace(self.workspace_bytes(B, T))
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dn_vae_decode(self.handle, latent.data_ptr(), l32.data_ptr(), B, T, _lib.ptr(recon),
                                               _lib.ptr(logits), _lib.ptr(units), wp, wn, _lib.current_stream()),

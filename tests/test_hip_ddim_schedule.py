@@ -288,6 +288,63 @@ def test_graph_cache_keeps_the_loops_apart(eng, golden):
     assert not torch.equal(got[1], got[4]) and torch.equal(got[1], got[5])
 
 
+def test_graph_cache_serves_a_repeated_chain(eng, golden):
+    """A served hit of the unconditional loops' graph slot: every loop captured twice back to back on one stream, one workspace and
+    one x address (reset to the same start) -- the second call replays the first call's graph, and both equal the eager run bit for
+    bit.  Then what the benchmark does, a kept-table continuation from a smaller start step served by the same graph, and a chain
+    with another seed, which must not be."""
+    engine, scheduler = eng
+    e = engine.EpsEngine(O.make_eps_state_dict(CHAIN_EPS, "chain"), CHAIN_EPS, dtype="f16", device=DEV)
+    sched = scheduler.DDPMScheduler(200)
+    lens = T_(golden("chain_small")["lens"]).to(DEV).int()
+    coef, table = sched.ddim_coef_table(DEV), sched.gaussian_table(DEV)
+    s0, c0 = sched.ddim_schedule(50, sampling_steps=7, device=DEV)
+    s1, c1 = sched.ddim_schedule(50, sampling_steps=7, eta=1.0, device=DEV)
+    sd, cd = sched.dpm_schedule(50, sampling_steps=7, device=DEV)
+    e._workspace(max(int(e.lib.dn_ddim_workspace_bytes(e.handle, B, T, 50)), int(e.lib.dn_dpm_workspace_bytes(e.handle, B, T, 7))))
+    ws_ptr = e._ws.data_ptr()
+    chains = [lambda x, g: e.ddpm_loop(x, lens, 8, table, seed=3, use_graph=g),
+              lambda x, g: e.ddim_schedule_loop(x, lens, s0, c0, eta=0.0, use_graph=g, timesteps=200),
+              lambda x, g: e.ddim_schedule_loop(x, lens, s1, c1, eta=1.0, seed=7, use_graph=g, timesteps=200),
+              lambda x, g: e.dpm_schedule_loop(x, lens, sd, cd, use_graph=g, timesteps=200),
+              lambda x, g: e.ddim_loop(x, lens, 50, coef, use_graph=g, max_evals=4)]  # (last: the continuation follows it)
+    evals = [8, 7, 7, 7, 4]  # each of 3 .. 8 evaluations: long enough to be captured
+    x = torch.empty(B, T, CHAIN_VAE.z, device=DEV)
+    stream = torch.cuda.Stream()
+
+    def captured(chain, start=None):
+        if start is not None:
+            x.copy_(start)
+        torch.cuda.synchronize()
+        with torch.cuda.stream(stream):
+            n = chain(x, True)
+        torch.cuda.synchronize()
+        return n, x.cpu()
+
+    got = []
+    for chain, n in zip(chains, evals):
+        (n1, first), (n2, second) = captured(chain, x_start()), captured(chain, x_start())
+        assert n1 == n2 == n
+        assert torch.equal(first, second), len(got)
+        got.append(second)
+    # x now stands at step 46 of the DDIM chain: continue on the kept table, from the graph captured at start step 50
+    n, cont = captured(lambda xx, g: e.ddim_loop(xx, lens, 46, coef, use_graph=g, max_evals=4, keep_table=True))
+    assert n == 4
+    n, other_seed = captured(lambda xx, g: e.ddpm_loop(xx, lens, 8, table, seed=4, use_graph=g), x_start())
+    assert n == 8 and e._ws.data_ptr() == ws_ptr
+
+    def eager(chain, start):
+        ref = start.to(DEV).clone()
+        on_stream(lambda: chain(ref, False))
+        return ref.cpu()
+
+    for i, chain in enumerate(chains):
+        assert torch.equal(got[i], eager(chain, x_start())), i
+    assert torch.equal(cont, eager(lambda xx, g: e.ddim_loop(xx, lens, 46, coef, use_graph=g, max_evals=4), got[4]))
+    assert not torch.equal(other_seed, got[0])
+    assert torch.equal(other_seed, eager(lambda xx, g: e.ddpm_loop(xx, lens, 8, table, seed=4, use_graph=g), x_start()))
+
+
 def test_schedule_graph_observes_run_time_options(eng):
     """As test_sampling_graph_observes_run_time_options asks of dn_ddim_loop: a schedule chain captured under the default K order
     is not replayed after taps_inner changed."""
