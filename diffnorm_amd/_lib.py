@@ -248,6 +248,8 @@ SYMBOLS = {
     "dn_guided_ddim_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32, _i32]),
     "dn_guided_ddim_loop": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _vp, _vp, _i32, _i32, _i32, C.c_uint64, _vp, _i32,
                                       _vp, _sz, _vp]),
+    "dn_guided_dpm_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32, _i32]),
+    "dn_guided_dpm_loop": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "dn_cfg_combine": (C.c_int, [_vp, C.c_float, _i64, _vp, _vp]),
     "dn_nar_create": (C.c_int, [C.POINTER(NarConfig), C.POINTER(_vp), _i32, C.POINTER(_vp)]),
     "dn_nar_destroy": (None, [_vp]),

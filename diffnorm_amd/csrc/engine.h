@@ -132,8 +132,8 @@ struct DnEps {
   // conditional variant (kEpsCondTensors; null when cfg.dim_prompt == 0)
   const float *tpc_W, *tpc_b, *null_pc, *lat_pos, *rffin_b, *rffout_b, *rnorm_g, *proj_b;
   const void *null_tok, *proj_W, *rq_W, *rkv_W, *rout_W, *rffin_W, *rffout_W, *cq_W, *ckv_W, *cout_W;
-  // hipGraph caches of the device sampling loops: one slot for the four unconditional loops, one for dn_guided_ddim_loop (the
-  // guided loop neither serves nor evicts the others)
+  // hipGraph caches of the device sampling loops: one slot for the four unconditional loops, one for dn_guided_ddim_loop and
+  // dn_guided_dpm_loop (a guided loop neither serves nor evicts the unconditional ones; StepKey.dpm keeps the two guided loops apart)
   dn::StepGraph loop_graph, guided_graph;
   void *side_stream, *ev_fork, *ev_join;  // DN_LOOP_SPLIT2: second half-batch stream and its fork/join events
   // DN_LOOP_KEEP_TABLE: the conditioning table built by the previous dn_ddim_loop call on this workspace

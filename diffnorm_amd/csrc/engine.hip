@@ -596,8 +596,8 @@ extern "C" int dn_eps_weights_changed(DnEps* m) {
   DN_CHECK_ARG(m, "dn_eps_weights_changed: null engine");
   m->table_ws = nullptr;  // DN_LOOP_KEEP_TABLE: the next call rebuilds the conditioning table
   m->table_rows = 0;
-  // dn_guided_ddim_loop keeps nothing derived from the weights across calls: every call rebuilds its time table, and its eager
-  // first step recomputes the prompt-only state; its captured step holds addresses only
+  // dn_guided_ddim_loop and dn_guided_dpm_loop keep nothing derived from the weights across calls: every call rebuilds its time table, and
+  // its eager first step recomputes the prompt-only state; a captured step holds addresses only
   return DN_OK;
 }
 
@@ -1247,6 +1247,8 @@ extern "C" int dn_eps_forward_cond_ex(DnEps* m, const float* x, const int32_t* t
 int dn_guided_sched_step_launch(float* x, float* xin, const float* both, int64_t n_elem, int guided, float scale, const float* coef,
                                 const int32_t* steps, const int32_t* counter, int eta_on, const float* noise, int64_t noise_row, uint64_t seed,
                                 hipStream_t stream);  // pointwise.hip
+int dn_guided_dpm_step_launch(float* x, float* xin, const float* both, float* hist, int64_t n_elem, int guided, float scale, const float* coef,
+                              const int32_t* counter, hipStream_t stream);  // pointwise.hip
 
 namespace {
 // drop mask of the guided pass over n rows = [conditioned (first B) ; null]
@@ -1255,18 +1257,19 @@ __global__ void drop_mask_kernel(int32_t* drop, int n, int B) {
   if (i < n) drop[i] = i >= B ? 1 : 0;
 }
 
-// The workspace of dn_guided_ddim_loop behind the model pass's own (`core` bytes at its start).  State whose size does not depend
+// The workspace of a guided loop behind the model pass's own (`core` bytes at its start).  State whose size does not depend
 // on n_steps first; the second halves exist for the guided (2B-row) pass only -- at cond_scale == 1 the model reads x itself and
-// the caller's lengths / prompt / prompt lengths.
+// the caller's lengths / prompt / prompt lengths.  `history` (dn_guided_dpm_loop): one more B-row latent beside the prediction, the
+// previous step's data prediction; without it and with DN_DDIM_SCHED_COLS columns the layout is dn_guided_ddim_loop's, byte for byte.
 struct GuidedBufs {
   size_t core;
-  float *both, *xin, *prompt2, *table, *coef;
+  float *both, *hist, *xin, *prompt2, *table, *coef;
   int32_t *tvec, *counter, *drop, *len2, *plen2, *steps;
   void* tt_ws;
   size_t tt_bytes;
 };
 
-GuidedBufs plan_guided(const DnEps* m, int B, int T, int Tp, int n_steps, bool guided, Arena& ar) {
+GuidedBufs plan_guided(const DnEps* m, int B, int T, int Tp, int n_steps, bool guided, bool history, int coef_cols, Arena& ar) {
   const size_t n = guided ? 2 * (size_t)B : (size_t)B, Mz = (size_t)B * T * m->cfg.latent;
   GuidedBufs g;
   memset(&g, 0, sizeof(g));
@@ -1275,6 +1278,7 @@ GuidedBufs plan_guided(const DnEps* m, int B, int T, int Tp, int n_steps, bool g
   g.core = (core.off + 255) & ~(size_t)255;
   (void)ar.take(g.core);
   g.both = (float*)ar.take(n * T * m->cfg.latent * 4);
+  if (history) g.hist = (float*)ar.take(Mz * 4);
   g.tvec = (int32_t*)ar.take(n * 4);
   g.counter = (int32_t*)ar.take(64);
   g.drop = (int32_t*)ar.take(n * 4);
@@ -1286,51 +1290,60 @@ GuidedBufs plan_guided(const DnEps* m, int B, int T, int Tp, int n_steps, bool g
   }
   g.steps = (int32_t*)ar.take((size_t)n_steps * 4);
   g.table = (float*)ar.take((size_t)n_steps * m->n_cond * 4);  // row i: the time half of the conditioning rows of steps[i]
-  g.coef = (float*)ar.take((size_t)n_steps * DN_DDIM_SCHED_COLS * 4);
+  g.coef = (float*)ar.take((size_t)n_steps * coef_cols * 4);
   g.tt_bytes = dn_eps_cond_time_table_workspace_bytes(m, n_steps);  // (dead once the table is built)
   g.tt_ws = ar.take(g.tt_bytes);
   return g;
 }
-}  // namespace
 
-extern "C" size_t dn_guided_ddim_workspace_bytes(const DnEps* m, int32_t B, int32_t T, int32_t Tp, int32_t n_steps, int32_t guided) {
+size_t guided_ws_bytes(const DnEps* m, int32_t B, int32_t T, int32_t Tp, int32_t n_steps, int32_t guided, bool history, int coef_cols) {
   if (!m || m->cfg.dim_prompt <= 0 || B <= 0 || T <= 0 || Tp <= 0 || n_steps < 1) return 0;
   Arena ar{nullptr, 0, 0};
-  (void)plan_guided(m, B, T, Tp, n_steps, guided != 0, ar);
+  (void)plan_guided(m, B, T, Tp, n_steps, guided != 0, history, coef_cols, ar);
   return ar.off + 256;
 }
 
-extern "C" int dn_guided_ddim_loop(DnEps* m, float* x, const int32_t* lengths, const float* prompt, const int32_t* prompt_lengths, int32_t B,
-                                   int32_t T, int32_t Tp, float cond_scale, const int32_t* steps, const float* coef, int32_t n_steps,
-                                   int32_t timesteps, int32_t eta_on, uint64_t seed, const float* noise, int32_t flags, void* workspace,
-                                   size_t workspace_bytes, void* stream) {
-  DN_CHECK_ARG(m && x && lengths && prompt && prompt_lengths && steps && coef && workspace, "dn_guided_ddim_loop: null argument");
-  DN_CHECK_ARG(m->cfg.dim_prompt > 0, "dn_guided_ddim_loop: the model was created without a prompt branch (cfg.dim_prompt == 0): use dn_ddim_sched_loop");
-  DN_CHECK_ARG(!(flags & DN_LOOP_SPLIT2), "dn_guided_ddim_loop: DN_LOOP_SPLIT2 is not offered (the prompt-only state lives in one workspace, and the "
-               "guided pass already runs 2B rows)");
-  DN_CHECK_ARG(!(flags & ~DN_LOOP_GRAPH), "dn_guided_ddim_loop: flags=%d (DN_LOOP_GRAPH only)", flags);
-  DN_CHECK_ARG(n_steps >= 1 && n_steps <= timesteps, "dn_guided_ddim_loop: n_steps=%d must be in [1, %d]", n_steps, timesteps);
-  DN_CHECK_ARG(B > 0 && T > 0 && Tp > 0 && T <= m->cfg.max_pos, "dn_guided_ddim_loop: B=%d T=%d Tp=%d (positional table: %d)", B, T, Tp, m->cfg.max_pos);
-  DN_CHECK_ARG(cond_scale == cond_scale, "dn_guided_ddim_loop: cond_scale is not a number");
-  eta_on = eta_on != 0;
-  DN_CHECK_ARG(eta_on || !noise, "dn_guided_ddim_loop: injected noise needs eta_on (eta = 0 draws none)");
-  DN_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "dn_guided_ddim_loop: workspace must be 256-byte aligned");
+// One guided device loop: what guided_loop needs to know beyond its arguments.
+struct GuidedDesc {
+  const char *name, *ws_name, *uncond_name;  // for messages; uncond_name: the entry an unconditional model is sent to
+  int coef_cols;
+  bool history;  // GuidedBufs::hist
+  StepKey kind;  // eta, dpm, seed, injected: the loop's part of the graph key
+  // the fused combination + update + refill of the model's input after a pass (n_elem = B T latent)
+  std::function<int(const GuidedBufs&, float* x, float* xin, int64_t n_elem, int guided, float scale, hipStream_t stream)> update;
+};
+}  // namespace
+
+// The body of the two guided loops: the argument checks, the chain-start copies, the drop mask, the time table, the step, the graph key
+// and the replays.  The entries differ in the workspace plan (d.history, d.coef_cols), the update (d.update) and the key (d.kind).
+static int guided_loop(DnEps* m, float* x, const int32_t* lengths, const float* prompt, const int32_t* prompt_lengths, int32_t B, int32_t T,
+                       int32_t Tp, float cond_scale, const int32_t* steps, const float* coef, int32_t n_steps, int32_t timesteps, int32_t flags,
+                       void* workspace, size_t workspace_bytes, void* stream, const GuidedDesc& d) {
+  DN_CHECK_ARG(m && x && lengths && prompt && prompt_lengths && steps && coef && workspace, "%s: null argument", d.name);
+  DN_CHECK_ARG(m->cfg.dim_prompt > 0, "%s: the model was created without a prompt branch (cfg.dim_prompt == 0): use %s", d.name, d.uncond_name);
+  DN_CHECK_ARG(!(flags & DN_LOOP_SPLIT2), "%s: DN_LOOP_SPLIT2 is not offered (the prompt-only state lives in one workspace, and the "
+               "guided pass already runs 2B rows)", d.name);
+  DN_CHECK_ARG(!(flags & ~DN_LOOP_GRAPH), "%s: flags=%d (DN_LOOP_GRAPH only)", d.name, flags);
+  DN_CHECK_ARG(n_steps >= 1 && n_steps <= timesteps, "%s: n_steps=%d must be in [1, %d]", d.name, n_steps, timesteps);
+  DN_CHECK_ARG(B > 0 && T > 0 && Tp > 0 && T <= m->cfg.max_pos, "%s: B=%d T=%d Tp=%d (positional table: %d)", d.name, B, T, Tp, m->cfg.max_pos);
+  DN_CHECK_ARG(cond_scale == cond_scale, "%s: cond_scale is not a number", d.name);
+  DN_CHECK_ARG(d.kind.eta || !d.kind.injected, "%s: injected noise needs eta_on (eta = 0 draws none)", d.name);
+  DN_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", d.name);
   const bool guided = cond_scale != 1.0f;
-  const size_t need = dn_guided_ddim_workspace_bytes(m, B, T, Tp, n_steps, guided);
+  const size_t need = guided_ws_bytes(m, B, T, Tp, n_steps, guided, d.history, d.coef_cols);
   if (need > workspace_bytes) {
-    dn_set_error("dn_guided_ddim_loop: workspace %zu < required %zu (see dn_guided_ddim_workspace_bytes)", workspace_bytes, need);
+    dn_set_error("%s: workspace %zu < required %zu (see %s)", d.name, workspace_bytes, need, d.ws_name);
     return DN_EWORKSPACE;
   }
-  if (!eta_on) seed = 0;
   hipStream_t s = (hipStream_t)stream;
   Arena ar{(char*)workspace, 0, workspace_bytes};
-  const GuidedBufs g = plan_guided(m, B, T, Tp, n_steps, guided, ar);
+  const GuidedBufs g = plan_guided(m, B, T, Tp, n_steps, guided, d.history, d.coef_cols, ar);
   const int n = guided ? 2 * B : B, z = m->cfg.latent;
   const size_t Mz = (size_t)B * T * z;
   // ---- chain start: the static inputs of the 2B-row pass, the model's first input, the schedule, its coefficient rows and its
   // time table, all in the workspace (a captured step holds workspace addresses and x only)
   auto copy = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) == hipSuccess; };
-  bool ok = copy(g.steps, steps, (size_t)n_steps * 4) && copy(g.coef, coef, (size_t)n_steps * DN_DDIM_SCHED_COLS * 4);
+  bool ok = copy(g.steps, steps, (size_t)n_steps * 4) && copy(g.coef, coef, (size_t)n_steps * d.coef_cols * 4);
   if (guided) {
     const size_t pb = (size_t)B * Tp * m->cfg.dim_prompt * 4;
     ok = ok && copy(g.len2, lengths, (size_t)B * 4) && copy(g.len2 + B, lengths, (size_t)B * 4) && copy(g.plen2, prompt_lengths, (size_t)B * 4) &&
@@ -1338,7 +1351,7 @@ extern "C" int dn_guided_ddim_loop(DnEps* m, float* x, const int32_t* lengths, c
          copy(g.xin, x, Mz * 4) && copy(g.xin + Mz, x, Mz * 4);
   }
   if (!ok) {
-    dn_set_error("dn_guided_ddim_loop: copying the chain's inputs into the workspace failed");
+    dn_set_error("%s: copying the chain's inputs into the workspace failed", d.name);
     return DN_ELAUNCH;
   }
   hipLaunchKernelGGL(drop_mask_kernel, dim3((n + 255) / 256), dim3(256), 0, s, g.drop, n, B);
@@ -1353,25 +1366,67 @@ extern "C" int dn_guided_ddim_loop(DnEps* m, float* x, const int32_t* lengths, c
     hipLaunchKernelGGL(fill_t_kernel, dim3((n + 255) / 256), dim3(256), 0, s, g.tvec, n, g.counter);
     DN_TRY(dn_eps_forward_cond_ex(m, xin, g.tvec, len, prm, plen, g.drop, n, T, Tp, g.both, workspace, g.core, reuse ? DN_COND_REUSE_PROMPT : 0,
                                   g.table, 0, n_steps, s));
-    DN_TRY(dn_guided_sched_step_launch(x, xin, g.both, (int64_t)Mz, guided, cond_scale, g.coef, g.steps, g.counter, eta_on, noise, (int64_t)Mz, seed, s));
+    DN_TRY(d.update(g, x, xin, (int64_t)Mz, guided, cond_scale, s));
     hipLaunchKernelGGL(inc_counter_kernel, dim3(1), dim3(1), 0, s, g.counter);
-    DN_CHECK_LAUNCH("dn_guided_ddim_loop step");
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+      dn_set_error("%s step: %s", d.name, hipGetErrorString(e));
+      return DN_ELAUNCH;
+    }
     return DN_OK;
   };
   DN_TRY(one_step(false));  // eager: the prompt-only work, and the per-kernel attributes settle outside capture
   if ((flags & DN_LOOP_GRAPH) && s && n_steps > 2) {  // (the null stream cannot be captured)
     // (an injected-noise chain is never served from the cache; a dn_set_option since the capture may route the contractions differently)
-    StepKey key;
-    memset(&key, 0, sizeof(key));
+    StepKey key = d.kind;
     key.ws = workspace; key.x = x; key.len = lengths; key.coef = g.coef; key.prompt = prompt; key.plen = prompt_lengths;
-    key.seed = seed; key.B = B; key.T = T; key.Tp = Tp; key.n_steps = n_steps; key.flags = flags; key.opt_gen = dn::option_generation();
+    key.B = B; key.T = T; key.Tp = Tp; key.n_steps = n_steps; key.flags = flags; key.opt_gen = dn::option_generation();
     memcpy(&key.scale_bits, &cond_scale, 4);
-    key.eta = (uint16_t)eta_on; key.injected = noise != nullptr;
-    DN_TRY(replay_steps(m->guided_graph, key, false, n_steps - 1, s, "dn_guided_ddim_loop", [&] { return one_step(true); }));
+    DN_TRY(replay_steps(m->guided_graph, key, false, n_steps - 1, s, d.name, [&] { return one_step(true); }));
   } else {
     for (int done = 1; done < n_steps; ++done) DN_TRY(one_step(true));
   }
   return n_steps;
+}
+
+extern "C" size_t dn_guided_ddim_workspace_bytes(const DnEps* m, int32_t B, int32_t T, int32_t Tp, int32_t n_steps, int32_t guided) {
+  return guided_ws_bytes(m, B, T, Tp, n_steps, guided, false, DN_DDIM_SCHED_COLS);
+}
+
+extern "C" int dn_guided_ddim_loop(DnEps* m, float* x, const int32_t* lengths, const float* prompt, const int32_t* prompt_lengths, int32_t B,
+                                   int32_t T, int32_t Tp, float cond_scale, const int32_t* steps, const float* coef, int32_t n_steps,
+                                   int32_t timesteps, int32_t eta_on, uint64_t seed, const float* noise, int32_t flags, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  eta_on = eta_on != 0;
+  if (!eta_on) seed = 0;
+  GuidedDesc d = {"dn_guided_ddim_loop", "dn_guided_ddim_workspace_bytes", "dn_ddim_sched_loop", DN_DDIM_SCHED_COLS, false, step_kind(seed, noise),
+                  nullptr};
+  d.kind.eta = (uint16_t)eta_on;
+  d.update = [=](const GuidedBufs& g, float* xb, float* xin, int64_t n_elem, int guided, float scale, hipStream_t st) {
+    return dn_guided_sched_step_launch(xb, xin, g.both, n_elem, guided, scale, g.coef, g.steps, g.counter, eta_on, noise, n_elem, seed, st);
+  };
+  return guided_loop(m, x, lengths, prompt, prompt_lengths, B, T, Tp, cond_scale, steps, coef, n_steps, timesteps, flags, workspace,
+                     workspace_bytes, stream, d);
+}
+
+// DPM-Solver++(2M) (Lu et al. 2022, "DPM-Solver++", the data-prediction multistep solver, eq. 11-12 / algorithm 2) on the guided
+// prediction of forward_with_cond_scale (reference latent_module.py:813-826, which the fused step replaces together with the update):
+// dn_guided_ddim_loop's body with dn_dpm_loop's rows, one more B-row latent (the previous step's data prediction) and a key bit of
+// its own in the guided slot of the graph cache.
+extern "C" size_t dn_guided_dpm_workspace_bytes(const DnEps* m, int32_t B, int32_t T, int32_t Tp, int32_t n_steps, int32_t guided) {
+  return guided_ws_bytes(m, B, T, Tp, n_steps, guided, true, DN_DPM_COLS);
+}
+
+extern "C" int dn_guided_dpm_loop(DnEps* m, float* x, const int32_t* lengths, const float* prompt, const int32_t* prompt_lengths, int32_t B,
+                                  int32_t T, int32_t Tp, float cond_scale, const int32_t* steps, const float* coef, int32_t n_steps,
+                                  int32_t timesteps, int32_t flags, void* workspace, size_t workspace_bytes, void* stream) {
+  GuidedDesc d = {"dn_guided_dpm_loop", "dn_guided_dpm_workspace_bytes", "dn_dpm_loop", DN_DPM_COLS, true, step_kind(0, nullptr), nullptr};
+  d.kind.dpm = 1;
+  d.update = [](const GuidedBufs& g, float* xb, float* xin, int64_t n_elem, int guided, float scale, hipStream_t st) {
+    return dn_guided_dpm_step_launch(xb, xin, g.both, g.hist, n_elem, guided, scale, g.coef, g.counter, st);
+  };
+  return guided_loop(m, x, lengths, prompt, prompt_lengths, B, T, Tp, cond_scale, steps, coef, n_steps, timesteps, flags, workspace,
+                     workspace_bytes, stream, d);
 }
 
 // =========================================================================================== VAE

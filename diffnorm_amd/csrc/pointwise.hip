@@ -437,6 +437,56 @@ __global__ __launch_bounds__(256) void guided_sched_step_kernel(float* x, float*
   }
 }
 
+// ------------------------------------------------------------------------------------------ guided DPM-Solver++(2M) step of the device loop
+// One update of the prompted, guided DPM-Solver++(2M) chain (dn_guided_dpm_loop), per float4 quad of the B-row latent: eps formed as
+// guided_sched_step_kernel forms it (the conditioned row of `both`; kGuided: combined with the null row, n elements further, by
+// cfg_combine_kernel's three rounded operations), then dpm2m_step_kernel's update statement for statement: row *counter of `coef`
+// [n_steps, DN_DPM_COLS], x0 = (x - sigma_s eps) / max(alpha_s, 1e-10), x <- a x + b (c1 x0 + c0 hist), hist <- x0.  hist is read only
+// by a second-order row (c0 != 0: uniform over the launch), so a chain's first row never reads what an earlier chain left there.
+// Deterministic: no draws.  The result goes to x and to the model's next input: xin[0:n] and (kGuided) xin[n:2n]; !kGuided: nothing
+// past n is touched, and xin may be x itself.
+// HBM-bound: (2 + kGuided + second-order) reads and (2 + 1 + kGuided) writes of 16 bytes per quad; grid-stride, no LDS.
+template <bool kGuided>
+__global__ __launch_bounds__(256) void guided_dpm_step_kernel(float* x, float* xin, const float* __restrict__ both, float* hist, int64_t nquad,
+                                                              float scale, const float* __restrict__ coef,
+                                                              const int32_t* __restrict__ counter) {
+  const float* cf = coef + (int64_t)(*counter) * DN_DPM_COLS;
+  const float as = fmaxf(cf[0], 1e-10f), ss = cf[1], a = cf[2], b = cf[3], c1 = cf[4], c0 = cf[5];
+  const bool two = c0 != 0.0f;
+  const int64_t n = nquad << 2;
+  for (int64_t q = blockIdx.x * 256 + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * 256) {
+    const int64_t i = q << 2;
+    const float4 xv = *reinterpret_cast<const float4*>(x + i), cv = *reinterpret_cast<const float4*>(both + i);
+    float es[4] = {cv.x, cv.y, cv.z, cv.w};
+    if (kGuided) {
+      const float4 uv = *reinterpret_cast<const float4*>(both + n + i);
+      const float us[4] = {uv.x, uv.y, uv.z, uv.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) es[j] = __fadd_rn(us[j], __fmul_rn(__fsub_rn(es[j], us[j]), scale));
+    }
+    float4 hv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (two) hv = *reinterpret_cast<const float4*>(hist + i);
+    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, hs[4] = {hv.x, hv.y, hv.z, hv.w};
+    float o[4], p[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      p[j] = __fdiv_rn(fmaf(-ss, es[j], xs[j]), as);
+      float d = __fmul_rn(c1, p[j]);
+      if (two) d = fmaf(c0, hs[j], d);
+      o[j] = fmaf(a, xs[j], __fmul_rn(b, d));
+    }
+    const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<float4*>(x + i) = ov;
+    *reinterpret_cast<float4*>(hist + i) = make_float4(p[0], p[1], p[2], p[3]);
+    if (kGuided) {
+      *reinterpret_cast<float4*>(xin + i) = ov;
+      *reinterpret_cast<float4*>(xin + n + i) = ov;
+    } else if (xin != x) {
+      *reinterpret_cast<float4*>(xin + i) = ov;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------ convert rows
 __global__ __launch_bounds__(256) void convert_rows_kernel(const void* __restrict__ src, int sdt, int lds, void* __restrict__ dst, int ddt,
                                                            int ldd, int M, int C) {
@@ -740,6 +790,19 @@ int dn_guided_sched_step_launch(float* x, float* xin, const float* both, int64_t
   }
 #undef DN_GUIDED_STEP
   DN_CHECK_LAUNCH("dn_guided_ddim_loop step");
+  return DN_OK;
+}
+
+// (engine.hip: the update of dn_guided_dpm_loop; n_elem = B*T*latent of the B-row latent -- x and hist; both / xin hold 2 n_elem floats when guided)
+int dn_guided_dpm_step_launch(float* x, float* xin, const float* both, float* hist, int64_t n_elem, int guided, float scale, const float* coef,
+                              const int32_t* counter, hipStream_t stream) {
+  DN_CHECK_ARG(n_elem % 4 == 0 && n_elem > 0, "dn_guided_dpm_loop: the latent width must be a multiple of 4");
+  const dim3 grid(ew_grid(n_elem >> 2)), block(256);
+  if (guided)
+    hipLaunchKernelGGL(guided_dpm_step_kernel<true>, grid, block, 0, stream, x, xin, both, hist, n_elem >> 2, scale, coef, counter);
+  else
+    hipLaunchKernelGGL(guided_dpm_step_kernel<false>, grid, block, 0, stream, x, xin, both, hist, n_elem >> 2, scale, coef, counter);
+  DN_CHECK_LAUNCH("dn_guided_dpm_loop step");
   return DN_OK;
 }
 

@@ -456,6 +456,36 @@ class EpsEngine(_Engine):
                                                            _lib.ptr(nz), _loop_flags(use_graph), wp, wn, _lib.current_stream()),
                               "dn_guided_ddim_loop")
 
+    def guided_dpm_schedule_loop(self, x: torch.Tensor, lengths, prompt, prompt_lengths, steps: torch.Tensor, rows: torch.Tensor,
+                                 cond_scale: float = 1.0, use_graph: bool = True, timesteps: Optional[int] = None) -> int:
+        """In-place prompted, guided DPM-Solver++(2M) chain on x [B,T,z] fp32 over a timestep schedule (dn_guided_dpm_loop):
+        `guided_ddim_schedule_loop`'s chain -- the guided prediction of `forward_with_cond_scale` over 2B rows (B at scale 1), time
+        table of n rows, prompt-only work in the first step, one fused combination + update kernel per step, hipGraph replay -- with
+        `dpm_schedule_loop`'s update: `steps` int32 [n] strictly descending and `rows` fp32 [n, 6], both from
+        `scheduler.dpm_schedule`; the workspace holds one more latent-sized buffer, the previous step's data prediction.
+        Deterministic: no eta, no noise.  `steps` may also be a list or a host tensor: it is then validated by dn_ddim_sched_check
+        against `timesteps` and uploaded.  Returns the number of evaluations."""
+        B, T, z = self._loop_x(x)
+        nt = None if timesteps is None else int(timesteps)
+        if not (isinstance(steps, torch.Tensor) and steps.device == self.device):
+            host = torch.as_tensor(steps, dtype=torch.int32).contiguous().view(-1)
+            if self.lib.dn_ddim_sched_check(host.data_ptr() if host.numel() else None, int(host.numel()),
+                                            int(host.numel()) if nt is None else nt) != 0:
+                raise ValueError("guided_dpm_schedule_loop: " + (self.lib.dn_last_error() or b"").decode())
+            steps = host.to(self.device)
+        n = self._loop_schedule(steps, rows, _lib.DPM_COLS)
+        l32 = self._on_device(lengths, torch.int32)
+        pl32 = self._on_device(prompt_lengths, torch.int32)
+        p32 = self._on_device(prompt, torch.float32, contiguous=True)
+        assert p32.dim() == 3 and p32.shape[0] == B and p32.shape[2] == self.cfg.dim_prompt and l32.shape == (B,) and pl32.shape == (B,)
+        Tp = int(p32.shape[1])
+        self._keep = (l32, pl32, p32, steps, rows)
+        wp, wn = self._aligned_workspace(self.lib.dn_guided_dpm_workspace_bytes(self.handle, B, T, Tp, n, int(float(cond_scale) != 1.0)))
+        with torch.cuda.device(self.device):
+            return _lib.check(self.lib.dn_guided_dpm_loop(self.handle, x.data_ptr(), l32.data_ptr(), p32.data_ptr(), pl32.data_ptr(), B, T, Tp,
+                                                          float(cond_scale), steps.data_ptr(), rows.data_ptr(), n, n if nt is None else nt,
+                                                          _loop_flags(use_graph), wp, wn, _lib.current_stream()), "dn_guided_dpm_loop")
+
 
 class VaeEngine(_Engine):
     """SpeechVAEEncoderDecoder (reference latent_module.py:1035-1142) on the GPU."""

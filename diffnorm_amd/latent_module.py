@@ -615,19 +615,33 @@ class LatentDiscreteModel(nn.Module):
     @torch.no_grad()
     def prompted_ddim_sample(self, tgt_feature, prompt, prompt_mask, input_mask=None, cond_scale=1., ref_units=None, start_step=50,
                              sampling_steps=None, timestep_schedule=None, eta=0.0, seed=0, step_noise=None, post_noise=None,
-                             start_noise=None, use_graph=True):
+                             start_noise=None, use_graph=True, solver=None, solver_order=2):
         """`ddim_sample` for the prompted model (use_cond) over a timestep schedule -> the same (list of unit tensors, match, total,
         recon_feature).  Encode and q_sample as `ddim_sample`; the chain is the device loop dn_guided_ddim_loop
         (EpsEngine.guided_ddim_schedule_loop): the guided prediction forward_with_cond_scale (:813-826) at every step of the schedule
         `scheduler.ddim_schedule` selects -- `sampling_steps` = N of the timesteps start_step-1 .. 1, an explicit `timestep_schedule`,
         or with neither every timestep, which is `ddim_sample`'s prompted chain bit for bit -- with `eta`, `seed` and `step_noise`
         [n, B, T, z] as `ddim_sample` takes them for the unconditional model.  `ddim_sample` itself keeps refusing a schedule for the
-        prompted model; folding the two entries together is a later change."""
+        prompted model; folding the two entries together is a later change.
+
+        `solver="dpmpp_2m"` runs the chain the same arguments select with the DPM-Solver++(2M) update (scheduler.dpm_schedule,
+        EpsEngine.guided_dpm_schedule_loop, dn_guided_dpm_loop; `solver_order` 1 or 2) in place of DDIM's, on the same guided
+        prediction.  It is deterministic: `eta` and `step_noise` do not apply.  `solver=None` is the code above, unchanged."""
+        if solver is not None:
+            if solver != "dpmpp_2m":
+                raise ValueError(f"prompted_ddim_sample: unknown solver {solver!r} (None or 'dpmpp_2m')")
+            if eta != 0.0 or step_noise is not None:
+                raise ValueError("prompted_ddim_sample: solver='dpmpp_2m' is deterministic: eta and step_noise do not apply")
+            if solver_order not in (1, 2):
+                raise ValueError(f"prompted_ddim_sample: solver_order={solver_order} must be 1 or 2")
         if not self.use_cond:
             raise ValueError("prompted_ddim_sample: the model was built without use_cond (ddim_sample covers the unconditional model)")
         if prompt is None or prompt_mask is None:
             raise ValueError("prompted_ddim_sample: needs prompt and prompt_mask")
-        steps, rows = self.scheduler.ddim_schedule(start_step, sampling_steps, timestep_schedule, eta=eta)  # (validates, on the host)
+        if solver is not None:
+            steps, rows = self.scheduler.dpm_schedule(start_step, sampling_steps, timestep_schedule, order=solver_order)  # (validates, on the host)
+        else:
+            steps, rows = self.scheduler.ddim_schedule(start_step, sampling_steps, timestep_schedule, eta=eta)  # (validates, on the host)
         dev = self.device
         _, sa, s1 = self._tables()
         B, T, _ = tgt_feature.shape
@@ -641,8 +655,12 @@ class LatentDiscreteModel(nn.Module):
         t_start = torch.full((B,), start_step, dtype=torch.int32, device=dev)
         x = ops.q_sample(z, start_noise.to(dev, torch.float32).contiguous(), sa, s1, t_start, T)  # (:1405-1409)
         plens = _mask_to_lengths(prompt_mask.to(dev))
-        self.model.engine().guided_ddim_schedule_loop(x, lengths, prompt, plens, steps.to(dev), rows.to(dev), cond_scale=cond_scale, eta=eta,
-                                                      seed=seed, noise=step_noise, use_graph=use_graph, timesteps=self.timesteps)
+        if solver is not None:
+            self.model.engine().guided_dpm_schedule_loop(x, lengths, prompt, plens, steps.to(dev), rows.to(dev), cond_scale=cond_scale,
+                                                         use_graph=use_graph, timesteps=self.timesteps)
+        else:
+            self.model.engine().guided_ddim_schedule_loop(x, lengths, prompt, plens, steps.to(dev), rows.to(dev), cond_scale=cond_scale, eta=eta,
+                                                          seed=seed, noise=step_noise, use_graph=use_graph, timesteps=self.timesteps)
         recon, _, units = self.speech_decoder.engine().decode(x, lengths, want_logits=False)     # (:1448-1451)
         pred_units = units.long()
         match = (pred_units[input_mask] == ref_units.to(dev)[input_mask]).sum().item() if ref_units is not None else 0

@@ -732,6 +732,27 @@ int dn_guided_ddim_loop(DnEps* m, float* x, const int32_t* lengths, const float*
                         int32_t eta_on, uint64_t seed, const float* noise, int32_t flags, void* workspace, size_t workspace_bytes,
                         void* stream);
 
+/* DPM-Solver++(2M) for the prompted, classifier-free-guided chain, as a device loop (Lu et al. 2022, "DPM-Solver++", the
+ * data-prediction multistep solver, eq. 11-12 / algorithm 2): dn_guided_ddim_loop's chain -- the same steps, the level x enters at,
+ * the target of every update, the guided prediction of forward_with_cond_scale (latent_module.py:813-826) over B or 2B rows, the
+ * same workspace state and the same step sequence -- with dn_dpm_loop's second-order deterministic update in place of DDIM's.
+ * coef: device fp32 [n_steps, DN_DPM_COLS], the rows of dn_dpm_loop (scheduler.dpm_schedule).  One step: fill the index vector from
+ * the counter, dn_eps_forward_cond_ex, ONE kernel that forms the guided eps as dn_cfg_combine forms it, applies dn_dpm2m_step's
+ * update statement for statement to x, keeps x0_i in `hist` and writes the result to both halves of the model's next input, and the
+ * counter's increment.  hist (B T latent fp32) lives in the workspace and is read only by a second-order row; row 0 is first order, so
+ * a chain never reads what an earlier call left there.  No noise is drawn: there is no eta, seed or noise argument.
+ * flags: DN_LOOP_GRAPH only (n_steps > 2 on a non-null stream: the first step runs eagerly, the later form of the step is captured
+ * once and replayed).  The graph shares dn_guided_ddim_loop's cache slot under a key bit of its own: a DDIM step is never replayed for
+ * this loop nor the other way round, on whatever workspace, x, prompt and n_steps.  DN_LOOP_SPLIT2 is refused.  Every argument check
+ * precedes the first HIP call; dn_ddim_sched_check validates a host copy of the steps.
+ * Workspace: dn_guided_dpm_workspace_bytes = dn_guided_ddim_loop's layout with hist beside the prediction and DN_DPM_COLS columns in
+ * the coefficient copy (>= dn_guided_ddim_workspace_bytes + B T latent fp32).  Returns the number of model evaluations (= n_steps) or
+ * a negative error.                                                                                                              */
+size_t dn_guided_dpm_workspace_bytes(const DnEps* m, int32_t B, int32_t T, int32_t Tp, int32_t n_steps, int32_t guided);
+int dn_guided_dpm_loop(DnEps* m, float* x, const int32_t* lengths, const float* prompt, const int32_t* prompt_lengths, int32_t B, int32_t T,
+                       int32_t Tp, float cond_scale, const int32_t* steps, const float* coef, int32_t n_steps, int32_t timesteps,
+                       int32_t flags, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ VAE training step (BASELINE config 4) */
 /* speech_vae_decoder_loss training (reference SpeechVAEEncoderDecoder.forward latent_module.py:1118-1142 + the criterion
  * fairseq/criterions/speech_vae_decoder_loss.py:45-95) on flat buffers in the PACKED parameter layout (csrc/engine.h: rows

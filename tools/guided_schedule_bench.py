@@ -9,9 +9,15 @@ timesteps = 1000, start_step = 999.
     growth), set-up = the time table of N rows (`cond_time_table_steps`, timed alone) + the prompt-only work (a 2B-row pass without
     minus one with DN_COND_REUSE_PROMPT), and ms per evaluation = (wall - set-up) / N.
 
+(c) `--solver dpmpp_2m`, instead of (a) and (b): the guided DPM-Solver++(2M) loop (EpsEngine.guided_dpm_schedule_loop, dn_guided_dpm_loop)
+    against dn_guided_ddim_loop on the same schedule from `--solver-start` (50) at N in `--solver-steps` (49 20 10) evaluations: a warm-up
+    call of each (capture, workspace), then alternating pairs in this process; median and range of whole-chain ms per evaluation and of
+    the pair's ratio.  dn_guided_ddim_loop is the baseline: the update adds one latent-sized read and one write to a step.
+
 One process; `--only a` / `--only b` and `--steps` let a caller put each part under a time limit of its own.  Prints one JSON line.
 
     python tools/guided_schedule_bench.py [--dtype f16] [--batch 32] [--frames 512] [--prompt-frames 512] [--scale 2.0] [--only a|b]
+    python tools/guided_schedule_bench.py --solver dpmpp_2m [--solver-steps 49 20 10] [--pairs 3]
 """
 import argparse
 import json
@@ -38,6 +44,9 @@ def main():
     ap.add_argument("--steps", type=int, nargs="+", default=[998, 100, 50, 20])
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--only", choices=["a", "b"], default=None)
+    ap.add_argument("--solver", choices=["dpmpp_2m"], default=None)
+    ap.add_argument("--solver-start", type=int, default=50)
+    ap.add_argument("--solver-steps", type=int, nargs="+", default=[49, 20, 10])
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     B, T, Tp, start = a.batch, a.frames, a.prompt_frames, a.timesteps - 1
@@ -67,6 +76,32 @@ def main():
         return st, lambda: eng.guided_ddim_schedule_loop(x, lengths, prompt, plens, st, rows, cond_scale=a.scale, timesteps=a.timesteps)
 
     out = {"dtype": a.dtype, "B": B, "T": T, "Tp": Tp, "scale": a.scale, "timesteps": a.timesteps, "start_step": start}
+    if a.solver is not None:
+        assert a.pairs >= 3, "at least three alternating pairs"
+        out["start_step"], out["solver"], out["solver_chains"] = a.solver_start, a.solver, {}
+        for n in a.solver_steps:
+            sd, cd = sched.ddim_schedule(a.solver_start, sampling_steps=n, device=dev)
+            sp, cp = sched.dpm_schedule(a.solver_start, sampling_steps=n, device=dev)
+            ddim = lambda: eng.guided_ddim_schedule_loop(x, lengths, prompt, plens, sd, cd, cond_scale=a.scale, timesteps=a.timesteps)  # noqa: E731
+            dpm = lambda: eng.guided_dpm_schedule_loop(x, lengths, prompt, plens, sp, cp, cond_scale=a.scale, timesteps=a.timesteps)  # noqa: E731
+            timed(ddim)
+            timed(dpm)  # warm-up of each: capture, workspace growth
+            pairs = []
+            for _ in range(a.pairs):
+                wd, nd = timed(ddim)
+                wp, np_ = timed(dpm)
+                assert nd == np_ == n and bool(torch.isfinite(x).all())
+                pairs.append({"ddim_ms_per_eval": wd / n, "dpm_ms_per_eval": wp / n, "ratio": wp / wd})
+                print(f"  N = {n:3d} pair: dn_guided_ddim_loop {wd / n:7.3f} ms / evaluation   dn_guided_dpm_loop {wp / n:7.3f}   ratio {wp / wd:.4f}", flush=True)
+            row = {"pairs": pairs}
+            for k in ("ddim_ms_per_eval", "dpm_ms_per_eval", "ratio"):
+                v = [p[k] for p in pairs]
+                row[k] = {"median": statistics.median(v), "min": min(v), "max": max(v)}
+            row["workspace_bytes"] = {"ddim": int(eng.lib.dn_guided_ddim_workspace_bytes(eng.handle, B, T, Tp, n, int(a.scale != 1.0))),
+                                      "dpm": int(eng.lib.dn_guided_dpm_workspace_bytes(eng.handle, B, T, Tp, n, int(a.scale != 1.0)))}
+            out["solver_chains"][str(n)] = row
+        print(json.dumps(out))
+        return
     if a.only in (None, "a"):
         n = start - 1
         _, loop = loop_of(n)
