@@ -155,6 +155,17 @@ def time_cond(times_i32, w_freq, W, bias, out, out_act=None):
     return out
 
 
+def time_cond_backward(times_i32, w_freq, W, bias, dcond, dw_freq, dW, dbias):
+    """Backward of `time_cond`: dcond fp32 [B, ldd >= C]; dw_freq [half], dW [C, 2 half + 1] and dbias [C] are accumulated in place."""
+    lib = _lib.load()
+    B, Cn = times_i32.numel(), W.shape[0]
+    ds = torch.empty(B, Cn, dtype=torch.float32, device=W.device)
+    _lib.check(lib.dn_time_cond_backward(times_i32.data_ptr(), B, w_freq.data_ptr(), w_freq.numel(), W.data_ptr(), bias.data_ptr(), Cn,
+                                         dcond.data_ptr(), dcond.stride(0), ds.data_ptr(), dw_freq.data_ptr(), dW.data_ptr(),
+                                         dbias.data_ptr(), _stream()), "dn_time_cond_backward")
+    return dw_freq, dW, dbias
+
+
 def ddim_step(x, eps, coef, t_i32, T, out=None):
     """x, eps fp32 [B,T,C] dense -> x_prev (reference latent_module.py:1419-1442)."""
     lib = _lib.load()
