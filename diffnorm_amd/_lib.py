@@ -205,6 +205,9 @@ SYMBOLS = {
     "dn_split_rows": (C.c_int, [_vp, _i64, _vp, _i32, _vp]),
     "dn_transpose_slices": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "dn_repack_weights": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
+    "dn_ffn_fold": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "dn_eps_set_ffn_fold": (C.c_int, [_vp, _vp, _vp]),
+    "dn_vae_set_ffn_fold": (C.c_int, [_vp, _vp, _vp]),
     "dn_wgrad_reduce": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "dn_conv_weight_grad_tn": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "dn_conv_weight_grad_tn_x3": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),

@@ -77,10 +77,15 @@ constexpr int kWavenetTensors = 12;
 //   ffout_W [depth][padn(D)][padk(inner)]                           ffout_b [depth][padk(D)]
 //   g1, g2 [depth][D] learned RMSNorm gammas (NULL when time-conditioned)
 //   pred_gamma [D]   pred_W [padn(D)][padk(D)]
+// Beside the table (dn_ffn_fold writes them, dn_eps_set_ffn_fold / dn_vae_set_ffn_fold attach them; NULL: the two-stage form):
+//   fold_W [depth][3][padn(D)][padk(inner)] = ffout_W . ffconv_W tap by tap, in the operand format      fold_b [depth][padk(D)]
 struct TransformerW {
   int dim, depth, heads, dim_head, inner;
   const void *qkv_W, *out_W, *ffin_W, *ffconv_W, *ffout_W, *pred_W, *ffconv_Wkb, *ffin_Wkb, *qkv_Wkb;
   const float *ffin_b, *ffconv_b, *ffout_b, *g1, *g2, *pred_gamma;
+  const void* fold_W;
+  const float* fold_b;
+  int fold_default;  // option ffn_fold when unset: 1, but 0 in DN_BF16 (the two-stage form there: DESIGN 11)
 };
 constexpr int kTransformerTensors = 15;
 
@@ -137,7 +142,7 @@ struct DnEps {
   dn::StepGraph loop_graph, guided_graph;
   void *side_stream, *ev_fork, *ev_join;  // DN_LOOP_SPLIT2: second half-batch stream and its fork/join events
   // DN_LOOP_KEEP_TABLE: the conditioning table built by the previous dn_ddim_loop call on this workspace
-  void* table_ws;
+  void *table_ws, *table_at;  // (table_at: where in the workspace it lies -- the plan in front of it moves with option ffn_fold)
   int table_B, table_T, table_split, table_rows;
 };
 constexpr int kEpsTensors = 7 + dn::kWavenetTensors + dn::kTransformerTensors + 3;

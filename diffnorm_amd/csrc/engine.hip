@@ -145,6 +145,10 @@ struct TfBufs { void *xn, *qkv, *ao, *gg, *fc; float* ssq; };
 // can fetch a row's partials with two 16-byte loads at kernel start
 inline int ssq_ld(int Dp) { const int n = Dp / 64; return n <= 8 ? 8 : (n + 3) / 4 * 4; }
 
+// Option ffn_fold (default on, off in DN_BF16: TransformerW.fold_default): with folded weights attached, the FFN's causal conv and output projection run as one contraction.
+// 1: on the tile the route table chooses; 2 / 3: forced to 256 x 128 / 256 x 256 (A/B timing); 0: two stages.
+inline int ffn_fold_mode(const TransformerW& w) { return w.fold_W && w.fold_b ? option_or(OPT_FFN_FOLD, w.fold_default) : 0; }
+
 TfBufs plan_tf(const TransformerW& w, int M, int es, Arena& ar) {
   const int hd = w.heads * w.dim_head;
   TfBufs b;
@@ -152,7 +156,7 @@ TfBufs plan_tf(const TransformerW& w, int M, int es, Arena& ar) {
   b.qkv = ar.take((size_t)M * 3 * hd * es);
   b.ao = ar.take((size_t)M * hd * es);
   b.gg = ar.take((size_t)M * padk(w.inner) * es);
-  b.fc = ar.take((size_t)M * padk(w.inner) * es);
+  b.fc = ffn_fold_mode(w) ? nullptr : ar.take((size_t)M * padk(w.inner) * es);  // (folded: the conv's output is never formed)
   b.ssq = (float*)ar.take((size_t)M * ssq_ld(padk(w.dim)) * 4);  // split RMSNorm: per-64-column sums of squares
   return b;
 }
@@ -236,6 +240,7 @@ int run_transformer(const TransformerW& w, int dtype, float* xres, int B, int T,
   }
   // option qkv_192: the projection's 3 x 512 columns are 8 x 192 but 6 x 256 -- at [32,512] 512 tiles of 256 x 192 are two full rounds
   // of the chip, 384 tiles of 256 x 256 one and a half
+  const int fold = ffn_fold_mode(w);
   const bool qkv_192 = option_or(OPT_QKV_192, 0) != 0 && dn::dn_is16(dtype) && (3 * hd) % 192 == 0 && M >= 2048;
   for (int l = 0; l < w.depth; ++l) {
     {  // to_q ; to_kv in one contraction (:930-931,945)
@@ -302,6 +307,45 @@ int run_transformer(const TransformerW& w, int dtype, float* xres, int B, int T,
       }
       if (!fuse && !split) DN_TRY(standalone_norm(l, 2));
     }
+    // The last contraction of the layer closes the residual [+ the next layer's attention norm (:691) or to_pred's norm (:677)]
+    auto close_residual = [&](DnGemmParams& p) -> int {
+      p.epilogue = DN_EPI_RESADD; p.res = xres; p.ldr = Dp; p.out = xres; p.ldo = Dp; p.out_dtype = DN_F32;
+      const NormSrc ns = norm_src(w, gb, l + 1, 0, nj);
+      if (fuse) set_norm(p, tb.xn, Dp, D, dtype, ns.gamma, ns.gb, gb_ld);
+      else if (split) set_split_norm(p, tb, Dp, D, dtype, ns.gamma, ns.gb, gb_ld);
+      if (qkv_kb && l + 1 < w.depth) p.norm_split = 2;  // the next layer's q/kv projection reads it K-blocked (to_pred: row-major)
+      return dn_conv_gemm(&p, s);
+    };
+    if (fold) {
+      // CausalConv1d(inner, inner, 3) and Linear(inner -> D) (:894,902) folded into one causal conv of three taps inner -> D
+      // (dn_ffn_fold: nothing but the identity sits between them at inference): the conv's [M, inner] output is never formed
+      {  // Linear(D -> 2*inner) + GEGLU (:899,881-884)
+        DnGemmParams p = gemm_base(dtype, M, ip, Dp, T, gemm_flags);
+        p.terms[0].A = tb.xn; p.terms[0].lda = Dp; p.terms[0].W = eoff(w.ffin_W, (size_t)l * 2 * ip * Dp, es);
+        if (geglu_kb) {
+          p.terms[0].W = eoff(w.ffin_Wkb, (size_t)l * 2 * ip * Dp, es);
+          p.terms[0].layout = DN_LAYOUT_A_KBLOCKED | DN_LAYOUT_W_KBLOCKED;
+        }
+        p.bias = w.ffin_b + (size_t)l * 2 * ip;
+        p.epilogue = DN_EPI_GEGLU; p.out = tb.gg; p.ldo = ip;
+        if (mid2 & 2) p.flags |= DN_TILE_256X128_2WG << DN_GEMM_TILE_SHIFT;
+        if (scaled) set_row_scale(p, tb, Dp, D, rb ? rb + (size_t)l * rb_layer + 3 * hd + (cx ? hd : 0) : nullptr, rb_ld);
+        DN_TRY(dn_conv_gemm(&p, s));
+      }
+      DnGemmParams p = gemm_base(dtype, M, Dp, ip, T, gemm_flags);
+      p.n_terms = 3;
+      for (int j = 0; j < 3; ++j) {
+        p.terms[j].A = tb.gg; p.terms[j].lda = ip; p.terms[j].shift = 2 - j;
+        p.terms[j].W = eoff(w.fold_W, ((size_t)l * 3 + j) * Dn * ip, es);
+      }
+      p.bias = w.fold_b + (size_t)l * Dp;
+      p.flags |= DN_TAG_FFN_CONV << DN_GEMM_TAG_SHIFT;
+      // The route table sends it to the 128 x 128 tile at [32,512] (512 workgroups over the two half-batch streams, two per CU);
+      // forcing 256 x 128 (one per CU) measured level with it, 256 x 256 (half the CUs idle) 10 % slower per step: DESIGN 11
+      const int fold_tile = fold == 2 ? DN_TILE_256X128 : fold == 3 ? DN_TILE_256X256 : 0;
+      if (fold_tile && !fuse) p.flags |= fold_tile << DN_GEMM_TILE_SHIFT;
+      DN_TRY(close_residual(p));
+    } else {
     // CausalConv1d(inner, inner, 3) (:894), set up first: when it runs on one of the two 256-row tiles its operands go K-blocked --
     // the GEGLU projection writes its output that way and the weights come from their K-blocked copy (the tile then stages
     // 1 KiB pieces of whole cache lines instead of sixteen half-lines: -5 % on this contraction; DN_KBLOCK=0 disables)
@@ -336,16 +380,12 @@ int run_transformer(const TransformerW& w, int dtype, float* xres, int B, int T,
       DN_TRY(dn_conv_gemm(&p, s));
     }
     DN_TRY(dn_conv_gemm(&pc, s));
-    {  // Linear(inner -> D) + residual (:902,704) [+ the next layer's attention norm (:691) or to_pred's norm (:677)]
+    {  // Linear(inner -> D) + residual (:902,704)
       DnGemmParams p = gemm_base(dtype, M, Dp, ip, T, gemm_flags);
       p.terms[0].A = tb.fc; p.terms[0].lda = ip; p.terms[0].W = eoff(w.ffout_W, (size_t)l * Dn * ip, es);
       p.bias = w.ffout_b + (size_t)l * Dp;
-      p.epilogue = DN_EPI_RESADD; p.res = xres; p.ldr = Dp; p.out = xres; p.ldo = Dp; p.out_dtype = DN_F32;
-      const NormSrc ns = norm_src(w, gb, l + 1, 0, nj);
-      if (fuse) set_norm(p, tb.xn, Dp, D, dtype, ns.gamma, ns.gb, gb_ld);
-      else if (split) set_split_norm(p, tb, Dp, D, dtype, ns.gamma, ns.gb, gb_ld);
-      if (qkv_kb && l + 1 < w.depth) p.norm_split = 2;  // the next layer's q/kv projection reads it K-blocked (to_pred: row-major)
-      DN_TRY(dn_conv_gemm(&p, s));
+      DN_TRY(close_residual(p));
+    }
     }
     if (!fuse && !split) DN_TRY(standalone_norm(l + 1, 0));
   }
@@ -454,6 +494,20 @@ extern "C" int dn_eps_create(const DnEpsConfig* cfg, const void* const* weights,
     m->cq_W = c[15]; m->ckv_W = c[16]; m->cout_W = c[17];
   }
   *out = m;
+  return DN_OK;
+}
+
+// see include/diffnorm_hip.h
+extern "C" int dn_eps_set_ffn_fold(DnEps* m, const void* fold_W, const float* fold_b) {
+  DN_CHECK_ARG(m && (fold_W != nullptr) == (fold_b != nullptr), "dn_eps_set_ffn_fold: null engine, or one of the two buffers without the other");
+  DN_CHECK_ARG(((uintptr_t)fold_W & 127) == 0 && ((uintptr_t)fold_b & 15) == 0, "dn_eps_set_ffn_fold: fold_W 128-byte, fold_b 16-byte aligned");
+  m->tf.fold_W = fold_W; m->tf.fold_b = fold_b;
+  m->tf.fold_default = m->cfg.dtype == DN_BF16 ? 0 : 1;
+  for (StepGraph* g : {&m->loop_graph, &m->guided_graph}) {  // a captured step holds the launches of the other form
+    if (g->exec) (void)hipGraphExecDestroy((hipGraphExec_t)g->exec);
+    g->exec = nullptr;
+  }
+  m->table_ws = nullptr;
   return DN_OK;
 }
 
@@ -752,7 +806,7 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
   if (max_evals > 0 && max_evals < n_eval) n_eval = max_evals;  // partial chain (benchmarks, chunked sampling)
   // The 56 conditioning vectors depend only on t: build them for the whole chain once (fp32), so the
   // 117 M conditioning weights are not re-streamed at every step.
-  const bool keep = (flags & DN_LOOP_KEEP_TABLE) && m->table_ws == workspace && m->table_B == B && m->table_T == T &&
+  const bool keep = (flags & DN_LOOP_KEEP_TABLE) && m->table_ws == workspace && m->table_at == table && m->table_B == B && m->table_T == T &&
                     m->table_split == (int)split && m->table_rows >= start_step;
   StepBufs sb = {x, eps, hist, coef, tvec, tall, counter, T, z, (int64_t)M * z, start_step - 1};
   if (sched) {
@@ -775,7 +829,7 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
   } else if (!keep) {
     hipLaunchKernelGGL(iota_kernel, dim3((start_step + 255) / 256), dim3(256), 0, s, tall, start_step);
     DN_TRY(eps_cond_rows(m, tall, start_step, cond_all, table, table_h, s));
-    m->table_ws = workspace; m->table_B = B; m->table_T = T; m->table_split = (int)split; m->table_rows = start_step;
+    m->table_ws = workspace; m->table_at = table; m->table_B = B; m->table_T = T; m->table_split = (int)split; m->table_rows = start_step;
   }
   const int32_t twin = split ? DN_GEMM_TWIN : 0;  // every contraction of a half batch has its twin beside it (tile choice)
   auto one_step = [&]() -> int {
@@ -1469,6 +1523,15 @@ extern "C" int dn_vae_create(const DnVaeConfig* cfg, const void* const* weights,
 }
 
 extern "C" void dn_vae_destroy(DnVae* m) { delete m; }
+
+// see include/diffnorm_hip.h
+extern "C" int dn_vae_set_ffn_fold(DnVae* m, const void* fold_W, const float* fold_b) {
+  DN_CHECK_ARG(m && (fold_W != nullptr) == (fold_b != nullptr), "dn_vae_set_ffn_fold: null engine, or one of the two buffers without the other");
+  DN_CHECK_ARG(((uintptr_t)fold_W & 127) == 0 && ((uintptr_t)fold_b & 15) == 0, "dn_vae_set_ffn_fold: fold_W 128-byte, fold_b 16-byte aligned");
+  m->tf.fold_W = fold_W; m->tf.fold_b = fold_b;
+  m->tf.fold_default = m->cfg.dtype == DN_BF16 ? 0 : 1;
+  return DN_OK;
+}
 
 namespace {
 struct VaeBufs {

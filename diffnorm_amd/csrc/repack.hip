@@ -87,6 +87,63 @@ __global__ __launch_bounds__(256) void repack_kernel(const float* __restrict__ m
   }
 }
 
+// dn_ffn_fold: the feed-forward block's CausalConv1d(inner, inner, 3) and the Linear(inner, dim) after it as ONE causal conv of three
+// taps inner -> dim (nothing but the identity sits between the two at inference): W'_j = W_out . W_conv_j, b' = W_out . b_conv + b_out.
+// fp32 products summed over k = 0 .. inner-1 in that order by one lane per output, so a refreshed engine and a freshly built one
+// get the same bits from the same sources; the result is rounded once, into the engine's operand format.  A lane owns 4 rows x 8
+// consecutive columns of one (layer, tap): W_out's elements are wave-uniform loads, W_conv's row pieces 32 contiguous bytes per lane.
+struct FoldArgs {
+  const float *conv_W, *conv_b, *out_W, *out_b;
+  int64_t conv_W_ls, conv_b_ls, out_W_ls, out_b_ls;  // elements between the layers' sources
+  int dim, inner, ip, in_n, Dp, Dn;
+  void* W;   // [depth][3][Dn][ip] in the operand format
+  float* b;  // [depth][Dp]
+};
+
+template <int DT>
+__global__ __launch_bounds__(64) void ffn_fold_w_kernel(FoldArgs a) {
+  const int u = blockIdx.x * 64 + threadIdx.x, n0 = blockIdx.y * 4, l = blockIdx.z / 3, tap = blockIdx.z % 3;
+  if (u * 8 >= a.ip) return;
+  const int c = u * 8;
+  const float* __restrict__ wc = a.conv_W + l * a.conv_W_ls + (int64_t)tap * a.in_n * a.ip + c;
+  const float* __restrict__ wo = a.out_W + l * a.out_W_ls + (int64_t)n0 * a.ip;
+  float acc[4][8];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[r][i] = 0.f;
+  for (int k = 0; k < a.inner; ++k) {
+    const float4 x0 = *reinterpret_cast<const float4*>(wc + (int64_t)k * a.ip), x1 = *reinterpret_cast<const float4*>(wc + (int64_t)k * a.ip + 4);
+    const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float w = wo[(int64_t)r * a.ip + k];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc[r][i] = fmaf(w, x[i], acc[r][i]);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {  // padding rows and columns are zeros whatever the sources' padding holds
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = (n0 + r < a.dim && c + i < a.inner) ? acc[r][i] : 0.f;
+    store8<DT>(a.W, (((int64_t)blockIdx.z * a.Dn) + n0 + r) * a.ip + c, make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]));
+  }
+}
+
+__global__ __launch_bounds__(64) void ffn_fold_b_kernel(FoldArgs a) {
+  const int n = blockIdx.x * 64 + threadIdx.x, l = blockIdx.y;
+  if (n >= a.Dp) return;
+  float acc = 0.f;
+  if (n < a.dim) {
+    const float* __restrict__ wo = a.out_W + l * a.out_W_ls + (int64_t)n * a.ip;
+    const float* __restrict__ bc = a.conv_b + l * a.conv_b_ls;
+    for (int k = 0; k < a.inner; ++k) acc = fmaf(wo[k], bc[k], acc);
+    acc += a.out_b[l * a.out_b_ls + n];
+  }
+  a.b[(int64_t)l * a.Dp + n] = acc;
+}
+
 }  // namespace
 }  // namespace dn
 
@@ -103,5 +160,30 @@ extern "C" int dn_repack_weights(const float* master, const DnRepackDesc* descs,
   else if (dtype == DN_F16) hipLaunchKernelGGL(dn::repack_kernel<DN_F16>, grid, block, 0, s, master, descs);
   else hipLaunchKernelGGL(dn::repack_kernel<DN_BF16X3>, grid, block, 0, s, master, descs);
   DN_CHECK_LAUNCH("dn_repack_weights");
+  return DN_OK;
+}
+
+// see include/diffnorm_hip.h
+extern "C" int dn_ffn_fold(const float* conv_W, const float* conv_b, const float* out_W, const float* out_b, int64_t conv_W_stride,
+                           int64_t conv_b_stride, int64_t out_W_stride, int64_t out_b_stride, int32_t depth, int32_t dim, int32_t inner,
+                           int32_t dtype, void* fold_W, float* fold_b, void* stream) {
+  DN_CHECK_ARG(conv_W && conv_b && out_W && out_b && fold_W && fold_b, "dn_ffn_fold: null argument");
+  DN_CHECK_ARG(depth >= 1 && 3 * depth <= 65535 && dim >= 1 && inner >= 1, "dn_ffn_fold: depth=%d dim=%d inner=%d", depth, dim, inner);
+  DN_CHECK_ARG(dtype == DN_F32 || dtype == DN_BF16 || dtype == DN_BF16X3 || dtype == DN_F16, "dn_ffn_fold: dtype=%d", dtype);
+  DN_CHECK_ARG((conv_W_stride | out_W_stride) % 4 == 0 && (((uintptr_t)conv_W | (uintptr_t)out_W) & 15) == 0 && ((uintptr_t)fold_W & 127) == 0,
+               "dn_ffn_fold: the weight sources must be 16-byte aligned (strides multiples of 4), the folded weights 128-byte aligned");
+  dn::FoldArgs a;
+  a.conv_W = conv_W; a.conv_b = conv_b; a.out_W = out_W; a.out_b = out_b;
+  a.conv_W_ls = conv_W_stride; a.conv_b_ls = conv_b_stride; a.out_W_ls = out_W_stride; a.out_b_ls = out_b_stride;
+  a.dim = dim; a.inner = inner; a.ip = (inner + 63) / 64 * 64; a.in_n = (inner + 127) / 128 * 128; a.Dp = (dim + 63) / 64 * 64; a.Dn = (dim + 127) / 128 * 128;
+  a.W = fold_W; a.b = fold_b;
+  const dim3 grid((a.ip / 8 + 63) / 64, a.Dn / 4, 3 * depth), block(64);
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == DN_F32) hipLaunchKernelGGL(dn::ffn_fold_w_kernel<DN_F32>, grid, block, 0, s, a);
+  else if (dtype == DN_BF16) hipLaunchKernelGGL(dn::ffn_fold_w_kernel<DN_BF16>, grid, block, 0, s, a);
+  else if (dtype == DN_F16) hipLaunchKernelGGL(dn::ffn_fold_w_kernel<DN_F16>, grid, block, 0, s, a);
+  else hipLaunchKernelGGL(dn::ffn_fold_w_kernel<DN_BF16X3>, grid, block, 0, s, a);
+  hipLaunchKernelGGL(dn::ffn_fold_b_kernel, dim3((a.Dp + 63) / 64, depth), block, 0, s, a);
+  DN_CHECK_LAUNCH("dn_ffn_fold");
   return DN_OK;
 }

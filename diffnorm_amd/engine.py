@@ -125,6 +125,47 @@ class _Engine:
         _, descs, n, _ = self._repack_descs(train_engine)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dn_repack_weights(master.data_ptr(), descs.data_ptr(), n, self.dtype, _lib.current_stream()), "dn_repack_weights")
+        self._fold_from_flat(train_engine, master)
+
+    # ---- the folded feed-forward weights (dn_ffn_fold), kept beside the packed table
+    fold_W: Optional[torch.Tensor] = None
+    fold_b: Optional[torch.Tensor] = None
+
+    def _tf_dims(self):
+        """(dim, depth) of the engine's transformer and the C entry that attaches its folded weights."""
+        raise NotImplementedError
+
+    def _fold_call(self, srcs, strides, depth, layer0):
+        dim, _, _ = self._tf_dims()
+        inner = int(dim * 4 * 2 / 3)
+        (_, _), b_shape = packing.ffn_fold_storage(dim, 1, self.dtype)
+        w_off = layer0 * self.fold_W[0].numel() * self.fold_W.element_size()
+        _lib.check(self.lib.dn_ffn_fold(*srcs, *strides, depth, dim, inner, self.dtype, self.fold_W.data_ptr() + w_off,
+                                        self.fold_b.data_ptr() + layer0 * b_shape[1] * 4, _lib.current_stream()), "dn_ffn_fold")
+
+    def _fold_from_state_dict(self, tf_layers, sd):
+        """Allocates the folded buffers, forms them layer by layer from the state dict's packed fp32 tensors and attaches them."""
+        dim, depth, attach = self._tf_dims()
+        (w_shape, w_dtype), b_shape = packing.ffn_fold_storage(dim, depth, self.dtype)
+        with torch.cuda.device(self.device):
+            self.fold_W = torch.empty(w_shape, dtype=w_dtype, device=self.device)
+            self.fold_b = torch.empty(b_shape, dtype=torch.float32, device=self.device)
+            for l, layer in enumerate(tf_layers):
+                srcs = [t.to(self.device) for t in packing.ffn_fold_sources(layer, sd)]
+                self._fold_call([t.data_ptr() for t in srcs], (0, 0, 0, 0), 1, l)
+        _lib.check(attach(self.handle, self.fold_W.data_ptr(), self.fold_b.data_ptr()), "set_ffn_fold")
+
+    def _fold_from_flat(self, train_engine, master):
+        """The same entry on a training engine's flat fp32 buffer (master or EMA), after its repack: same sources, same bits."""
+        if self.fold_W is None:
+            return
+        _, depth, _ = self._tf_dims()
+        offs, strides = packing.ffn_fold_offsets(train_engine.entries, train_engine.offsets)
+        with torch.cuda.device(self.device):
+            self._fold_call([master.data_ptr() + 4 * o for o in offs], strides, depth, 0)
+
+    def fold_bytes(self) -> int:
+        return 0 if self.fold_W is None else sum(t.numel() * t.element_size() for t in (self.fold_W, self.fold_b))
 
     def refresh_bytes(self) -> int:
         """Bytes the last refresh_from's layout reads from the master plus writes to the packed tensors (0 before the first)."""
@@ -145,6 +186,10 @@ class EpsEngine(_Engine):
                            getattr(cfg, "resampler_depth", 0) if self.conditional else 0)
         _lib.check(self.lib.dn_eps_create(C.byref(c), self._table, len(self.tensors), C.byref(self.handle)),
                    "dn_eps_create")
+        self._fold_from_state_dict(packing._eps_entries(cfg)[2], state_dict)
+
+    def _tf_dims(self):
+        return self.cfg.dim, self.cfg.depth, self.lib.dn_eps_set_ffn_fold
 
     def __del__(self):
         if getattr(self, "handle", None) and self.handle.value:
@@ -506,6 +551,11 @@ class VaeEngine(_Engine):
         c = _lib.VaeConfig(dim, self.z, depth, heads, dim_head, stacks, layers, vocab, len(self.mults), mults, self.dtype)
         _lib.check(self.lib.dn_vae_create(C.byref(c), self._table, len(self.tensors), C.byref(self.handle)),
                    "dn_vae_create")
+        self._tf = (dim, depth)
+        self._fold_from_state_dict(packing._vae_entries(dim, self.mults, depth, heads, dim_head, stacks, layers, vocab)[1], state_dict)
+
+    def _tf_dims(self):
+        return self._tf[0], self._tf[1], self.lib.dn_vae_set_ffn_fold
 
     def __del__(self):
         if getattr(self, "handle", None) and self.handle.value:

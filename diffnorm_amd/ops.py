@@ -37,7 +37,7 @@ def conv_gemm(terms: Sequence[Tuple[torch.Tensor, torch.Tensor, int]], out: torc
               norm_ssq: Optional[torch.Tensor] = None, row_ssq: Optional[torch.Tensor] = None, row_D: int = 0,
               row_bias: Optional[torch.Tensor] = None, row_bias_shared: bool = False, a_kblocked: bool = False,
               w_kblocked: bool = False, out_kblocked: bool = False, band: int = 0, x3: bool = False,
-              shared_rows: Optional[bool] = None, pre_out: Optional[torch.Tensor] = None):
+              shared_rows: Optional[bool] = None, pre_out: Optional[torch.Tensor] = None, norm_kblocked: bool = False):
     """out = epilogue(sum_terms shift(A) @ W^T).
 
     terms: (A [G?,M,lda], W [G?,Np,K], shift).  With groups > 1 the leading dim of A (unless
@@ -94,7 +94,7 @@ def conv_gemm(terms: Sequence[Tuple[torch.Tensor, torch.Tensor, int]], out: torc
         p.norm_gb_half = norm_gb_half
         if norm_ssq is not None:  # split norm, producer side: norm_out = row * gamma, norm_ssq = partial sums of squares
             assert norm_ssq.dtype == torch.float32 and norm_ssq.shape[-1] * 64 >= N
-            p.norm_split, p.norm_ssq, p.norm_ssq_ld = 1, norm_ssq.data_ptr(), norm_ssq.shape[-1]
+            p.norm_split, p.norm_ssq, p.norm_ssq_ld = (2 if norm_kblocked else 1), norm_ssq.data_ptr(), norm_ssq.shape[-1]  # 2: norm_out K-blocked
     if row_ssq is not None:  # split norm, consumer side
         assert row_ssq.dtype == torch.float32 and row_D > 0
         p.row_ssq, p.row_ssq_ld, p.row_ssq_parts, p.row_D = row_ssq.data_ptr(), row_ssq.shape[-1], row_ssq.shape[-1], float(row_D)

@@ -441,6 +441,39 @@ def pack_vae(sd: SD, dim: int, mults: List[int], depth: int, heads: int, dim_hea
     return sum((_wavenet_tensors(w, sd, dtype) for w in waves), []) + _tf_tensors(tf_layers, pred, sd, dtype) + _pack(tail, sd, dtype)
 
 
+# ------------------------------------------------------------------------------------------ inference: the folded feed-forward weights
+# Beside the lists, not in them (csrc/engine.h TransformerW.fold_W / fold_b): dn_ffn_fold (csrc/repack.hip) forms them on the device
+# from the packed fp32 sources below -- here from a state dict, in engine.py from a training engine's flat buffer.
+_FOLD_COLS = (4, 5, 6, 7)  # ffconv_W, ffconv_b, ffout_W, ffout_b in _tf_layer_entries' order
+
+
+def ffn_fold_sources(layer: List[_Entry], sd: SD) -> List[torch.Tensor]:
+    """One transformer layer's packed fp32 (conv_W [3][padn(inner)][padk(inner)], conv_b, out_W [padn(dim)][padk(inner)], out_b)."""
+    return [layer[j].pack(sd).float().contiguous() for j in _FOLD_COLS]
+
+
+def ffn_fold_offsets(entries: List[_Entry], offsets: List[int]):
+    """Where a training engine's flat buffer holds those four tensors: (layer 0's element offsets, the elements between layers)."""
+    per = [[o for e, o in zip(entries, offsets) if re.search(r"(?:^|\.)layers\.\d+\." + n + "$", e.name)] for n in ("ffconv_W", "ffconv_b", "ffout_W", "ffout_b")]
+    depth = len(per[0])
+    assert depth >= 1 and all(len(p) == depth for p in per)
+    strides = [p[1] - p[0] if depth > 1 else 0 for p in per]
+    assert all(p[l] == p[0] + l * st for p, st in zip(per, strides) for l in range(depth)), "the layers' tables lie a constant distance apart"
+    return [p[0] for p in per], strides
+
+
+def ffn_fold_storage(dim: int, depth: int, dtype: int):
+    """((shape, torch dtype) of fold_W, shape of fold_b) for a transformer of width `dim` in the arithmetic `dtype`."""
+    inner = int(dim * 4 * 2 / 3)
+    return _w_storage((depth, 3, padn(dim), padk(inner)), dtype), (depth, padk(dim))
+
+
+def ffn_fold_ref(conv_W: torch.Tensor, conv_b: torch.Tensor, out_W: torch.Tensor, out_b: torch.Tensor):
+    """The fold in float64 from the reference's tensors (conv_W [inner, inner, 3], out_W [dim, inner]): (W' [3, dim, inner], b' [dim])."""
+    cw, ow = conv_W.double(), out_W.double()
+    return torch.stack([ow @ cw[:, :, j] for j in range(3)]), ow @ conv_b.double() + out_b.double()
+
+
 # ------------------------------------------------------------------------------------------ inference lists from the flat master buffer
 # The third walk over the tables: for a training engine's entry table and offsets, the descriptors of dn_repack_weights
 # (csrc/repack.hip), which writes the tensors pack_eps / pack_vae return straight from the flat fp32 master buffer on the device.

@@ -511,6 +511,22 @@ typedef struct {
 } DnRepackDesc;
 int dn_repack_weights(const float* master, const DnRepackDesc* descs, int32_t n, int32_t dtype, void* stream);
 
+/* The sampling engines' folded feed-forward weights.  FeedForward (latent_module.py:887-903) ends in CausalConv1d(inner, inner, 3)
+ * -> Linear(inner, dim) with nothing but (at inference) the identity between them, and causal zero padding commutes with a linear
+ * map: the two are one causal conv of three taps inner -> dim,
+ *   W'_j = W_out . W_conv_j  (j = 0, 1, 2)      b' = W_out . b_conv + b_out
+ * Sources: the packed fp32 tensors of `depth` layers (diffnorm_amd/packing.py: conv_W [3][padn(inner)][padk(inner)], conv_b
+ * [padk(inner)], out_W [padn(dim)][padk(inner)], out_b [padk(dim)]), layer l at element l * its stride -- stacked tensors, or a
+ * training engine's flat master / EMA buffer, whose layers lie a constant distance apart.  The products are fp32, summed over
+ * k = 0 .. inner-1 in that order (one result per lane: the same sources give the same bits), and rounded once into the arithmetic
+ * `dtype`'s weight format: fold_W [depth][3][padn(dim)][padk(inner)] (DN_F32 / DN_BF16 / DN_F16 row-major, DN_BF16X3 weight-order
+ * split rows), 128-byte aligned; fold_b fp32 [depth][padk(dim)].  Padding rows and columns are written as zeros.  Stream-ordered,
+ * no allocation, no synchronisation.  The training engines keep the two-stage form (their weights change every update and the
+ * backward needs both stages).                                                                                                  */
+int dn_ffn_fold(const float* conv_W, const float* conv_b, const float* out_W, const float* out_b, int64_t conv_W_stride,
+                int64_t conv_b_stride, int64_t out_W_stride, int64_t out_b_stride, int32_t depth, int32_t dim, int32_t inner,
+                int32_t dtype, void* fold_W, float* fold_b, void* stream);
+
 /* The operand transpose of the training engines' weight gradient (autograd of CausalConv1d / nn.Linear, latent_module.py:476-485):
  * dst[j / chunk][row0 + c][j % chunk] = src[b * T + t, c] with j = b * Tp + front + t, zero for pad frames, channels >= C and the tail
  * columns [B * Tp, cols_total).  dtype DN_F32 / DN_BF16 / DN_BF16X3 (src split rows [hi | lo]; dst split rows in the order of its role:
@@ -613,9 +629,16 @@ int dn_eps_cond_time_table_steps(DnEps* m, const int32_t* steps, int32_t n_steps
  * addresses only, and every table it reads is rebuilt from the weights by the next dn_ddim_loop / dn_ddpm_loop call.  The
  * guided loop (dn_guided_ddim_loop) needs nothing: every call rebuilds its time table and its first step the prompt-only state. */
 int dn_eps_weights_changed(DnEps* m);
+/* Attaches dn_ffn_fold's buffers (the engine keeps the pointers, like the table's; NULL, NULL detaches).  With them, and option
+ * "ffn_fold" not 0, every transformer layer runs GEGLU projection -> ONE three-tap contraction (A = the GEGLU output, shifts 2/1/0,
+ * RESADD into the residual stream with the split-norm producer, tagged DN_TAG_FFN_CONV) instead of conv + output projection, and
+ * the conv's [M, padk(inner)] buffer leaves the workspace plan.  Captured steps are dropped.  After the packed weights were
+ * rewritten, dn_ffn_fold into the same buffers refreshes them: the addresses stay attached.                                      */
+int dn_eps_set_ffn_fold(DnEps* m, const void* fold_W, const float* fold_b);
 
 int dn_vae_create(const DnVaeConfig* cfg, const void* const* weights, int32_t n_weights, DnVae** out);
 void dn_vae_destroy(DnVae* m);
+int dn_vae_set_ffn_fold(DnVae* m, const void* fold_W, const float* fold_b); /* as dn_eps_set_ffn_fold, the decoder's transformer */
 size_t dn_vae_workspace_bytes(const DnVae* m, int32_t B, int32_t T);
 /* encoder WaveNets of encode_feature (latent_module.py:1099-1106): feat fp32 [B,T,dim] -> params fp32 [B,T,2z] */
 int dn_vae_encode_params(DnVae* m, const float* feat, int32_t B, int32_t T, float* params, void* workspace,
@@ -879,7 +902,10 @@ int dn_version(void);
  * the 256-row tiles [default], 2 tap contractions routed to those tiles by SHAPE whatever the batch size: a batch and its shards
  * then agree bit for bit), "fuse_norm" (DN_FUSE_NORM), "no_split_norm" (DN_NO_SPLIT_NORM), "kblock" (DN_KBLOCK: 0 never / 1 always
  * K-blocked operands), "wgrad_stream", "wgrad_tn", "wgrad_groups" (DN_WGRAD_*: A/B switches of the weight-gradient path),
- * "wgrad_tn_x3" (DN_WGRAD_TN_X3: DN_BF16X3 weight gradients from the row-major split rows; "wgrad_tn" is the 2-byte modes only).
+ * "wgrad_tn_x3" (DN_WGRAD_TN_X3: DN_BF16X3 weight gradients from the row-major split rows; "wgrad_tn" is the 2-byte modes only),
+ * "ffn_fold" (DN_FFN_FOLD: sampling engines with folded weights attached -- 0 the FFN's causal conv and output projection as two
+ * contractions, 1 [default; DN_BF16 engines default to 0] one folded contraction on the routed tile, 2 / 3 the same forced to the 256 x 128 / 256 x 256
+ * tile; like every option it is part of the captured-step cache keys through the option generation).
  * dn_get_option: *is_set = 0 when the option is neither set nor in the environment (the library's built-in choice applies). */
 #define DN_OPTION_DEFAULT (-2147483647 - 1)
 int dn_set_option(const char* name, int32_t value);
