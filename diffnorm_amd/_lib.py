@@ -222,6 +222,8 @@ SYMBOLS = {
     "dn_posterior_sample": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "dn_argmax_units": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "dn_randn": (C.c_int, [_vp, _i64, _u64, _u64, _vp]),
+    "dn_randn_keyed": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.c_uint32, _vp]),
+    "dn_chain_start": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dn_convert_rows": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "dn_eps_create": (C.c_int, [C.POINTER(EpsConfig), C.POINTER(_vp), _i32, C.POINTER(_vp)]),
     "dn_eps_destroy": (None, [_vp]),

@@ -221,6 +221,21 @@ __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint
   c[2] = n2;
 }
 
+// Box-Muller on the four output words of one Philox call: two 24-bit uniforms in (0,1] per pair (16777215 + 0.5 ties to 2^24), the
+// one definition every generator below ends in
+__device__ __forceinline__ void box_muller4(const uint32_t (&c)[4], float (&r)[4]) {
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float rad = sqrtf(-2.0f * logf(u1));
+    float sn, cs;
+    sincosf(6.28318530717958647692f * u2, &sn, &cs);
+    r[2 * h] = rad * cs;
+    r[2 * h + 1] = rad * sn;
+  }
+}
+
 __global__ __launch_bounds__(256) void randn_kernel(float* __restrict__ out, int64_t n, uint64_t seed, uint64_t offset) {
   const int64_t nquad = (n + 3) >> 2;
   for (int64_t q = blockIdx.x * 256 + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * 256) {
@@ -234,16 +249,7 @@ __global__ __launch_bounds__(256) void randn_kernel(float* __restrict__ out, int
       k1 += 0xBB67AE85u;
     }
     float r[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0,1]: 16777215 + 0.5 ties to 2^24
-      const float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-      const float rad = sqrtf(-2.0f * logf(u1));
-      float sn, cs;
-      sincosf(6.28318530717958647692f * u2, &sn, &cs);
-      r[2 * h] = rad * cs;
-      r[2 * h + 1] = rad * sn;
-    }
+    box_muller4(c, r);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       if (q * 4 + j < n) out[q * 4 + j] = r[j];
@@ -296,15 +302,70 @@ __device__ __forceinline__ void philox_normal4(uint64_t seed, uint64_t ctr_lo, u
     k0 += 0x9E3779B9u;
     k1 += 0xBB67AE85u;
   }
+  box_muller4(c, r);
+}
+
+// ------------------------------------------------------------------------------------------ keyed chain-start noise
+// One noise stream per utterance: Philox4x32-10 under key = keys[b] (low, high), counter = (q low, q high, stream_id, "STRT"),
+// q = frame * (Z / 4) + channel quad WITHIN the utterance -- a draw depends on the key, the frame and the channel only, not on the
+// row b, the batch size, the padded length or the launch.  stream_id 0: posterior noise, 1: chain-start noise.  The fourth word
+// keeps the stream apart from dn_randn's (0) and the update kernels' ("DPMP").
+__device__ __forceinline__ void philox_keyed4(uint64_t key, uint64_t q, uint32_t stream_id, float (&r)[4]) {
+  uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), stream_id, 0x53545254u};
+  uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
 #pragma unroll
-  for (int h = 0; h < 2; ++h) {  // Box-Muller on (0,1] uniforms, as randn_kernel
-    const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float rad = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincosf(6.28318530717958647692f * u2, &sn, &cs);
-    r[2 * h] = rad * cs;
-    r[2 * h + 1] = rad * sn;
+  for (int i = 0; i < 10; ++i) {
+    philox_round(c, k0, k1);
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  box_muller4(c, r);
+}
+
+// out [B, T, Z] dense; one thread per quad of channels (Z is a multiple of 4: a quad stays inside one frame)
+__global__ __launch_bounds__(256) void randn_keyed_kernel(float* __restrict__ out, const uint64_t* __restrict__ keys, int64_t nquad,
+                                                          int64_t row_quads, uint32_t stream_id) {
+  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < nquad; i += (int64_t)gridDim.x * 256) {
+    const int64_t b = i / row_quads;
+    float r[4];
+    philox_keyed4(keys[b], (uint64_t)(i - b * row_quads), stream_id, r);
+    *reinterpret_cast<float4*>(out + (i << 2)) = make_float4(r[0], r[1], r[2], r[3]);
+  }
+}
+
+// Posterior sample + q_sample in one pass (distributions.py:24-41, latent_module.py:1405-1409): posterior_kernel's and
+// q_sample_kernel's statements in their order on the keyed draws n0 (stream 0) and n1 (stream 1); params [B*T, ldp] = [mean ; logvar],
+// x and z (optional) dense [B*T, Z].  Pad frames are drawn like any other.
+__global__ __launch_bounds__(256) void chain_start_kernel(const float* __restrict__ params, int ldp, const uint64_t* __restrict__ keys,
+                                                          int64_t nquad, int64_t row_quads, int Z, const float* __restrict__ ca,
+                                                          const float* __restrict__ cb, const int32_t* __restrict__ t,
+                                                          float* __restrict__ x, float* __restrict__ z_out) {
+  const int zq = Z >> 2;
+  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < nquad; i += (int64_t)gridDim.x * 256) {
+    const int64_t b = i / row_quads, m = i / zq;
+    const int c = (int)(i - m * zq) << 2;
+    const float* pr = params + m * ldp + c;
+    const float4 mv = *reinterpret_cast<const float4*>(pr), lv4 = *reinterpret_cast<const float4*>(pr + Z);
+    const uint64_t key = keys[b], q = (uint64_t)(i - b * row_quads);
+    float n0[4], n1[4];
+    philox_keyed4(key, q, 0u, n0);
+    philox_keyed4(key, q, 1u, n1);
+    const int tb = t[b];
+    const float a = ca[tb], s = cb[tb];
+    const float mean[4] = {mv.x, mv.y, mv.z, mv.w}, logvar[4] = {lv4.x, lv4.y, lv4.z, lv4.w};
+    float zs[4], xs[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float lv = fminf(fmaxf(logvar[j], -30.0f), 20.0f);
+      const float sd = expf(0.5f * lv);
+      // z = __fadd_rn(mean, __fmul_rn(sd, n0)), x = __fadd_rn(__fmul_rn(a, z), __fmul_rn(s, n1)) as the compiler builds them in
+      // posterior_kernel and q_sample_kernel (sd n0 contracted into its sum; a z onto the rounded s n1), spelled out so that this
+      // kernel cannot be contracted differently (as sched_update does for ddim_step_kernel)
+      zs[j] = fmaf(sd, n0[j], mean[j]);
+      xs[j] = fmaf(a, zs[j], __fmul_rn(s, n1[j]));
+    }
+    *reinterpret_cast<float4*>(x + (i << 2)) = make_float4(xs[0], xs[1], xs[2], xs[3]);
+    if (z_out) *reinterpret_cast<float4*>(z_out + (i << 2)) = make_float4(zs[0], zs[1], zs[2], zs[3]);
   }
 }
 
@@ -836,6 +897,30 @@ extern "C" int dn_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, v
   DN_CHECK_ARG(out && n > 0, "dn_randn: bad args");
   hipLaunchKernelGGL(randn_kernel, dim3(ew_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, out, n, seed, offset);
   DN_CHECK_LAUNCH("dn_randn");
+  return DN_OK;
+}
+
+extern "C" int dn_randn_keyed(float* out, const uint64_t* keys, int32_t B, int32_t T, int32_t Z, uint32_t stream_id, void* stream) {
+  DN_CHECK_ARG(out && keys, "dn_randn_keyed: null argument");
+  DN_CHECK_ARG(B > 0 && T > 0 && Z > 0 && Z % 4 == 0, "dn_randn_keyed: B=%d T=%d must be positive, Z=%d a positive multiple of 4", B, T, Z);
+  DN_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)keys & 7) == 0, "dn_randn_keyed: out must be 16-byte, keys 8-byte aligned");
+  const int64_t row_quads = (int64_t)T * (Z >> 2), nquad = (int64_t)B * row_quads;
+  hipLaunchKernelGGL(randn_keyed_kernel, dim3(ew_grid(nquad)), dim3(256), 0, (hipStream_t)stream, out, keys, nquad, row_quads, stream_id);
+  DN_CHECK_LAUNCH("dn_randn_keyed");
+  return DN_OK;
+}
+
+extern "C" int dn_chain_start(const float* params, int32_t ldp, const uint64_t* keys, int32_t B, int32_t T, int32_t Z, const float* coef_a,
+                              const float* coef_b, const int32_t* t, float* x, float* z_out, void* stream) {
+  DN_CHECK_ARG(params && keys && coef_a && coef_b && t && x, "dn_chain_start: null argument");
+  DN_CHECK_ARG(B > 0 && T > 0 && Z > 0 && Z % 4 == 0, "dn_chain_start: B=%d T=%d must be positive, Z=%d a positive multiple of 4", B, T, Z);
+  DN_CHECK_ARG(ldp >= 2 * Z && ldp % 4 == 0, "dn_chain_start: ldp=%d must be a multiple of 4 and at least 2 Z = %d", ldp, 2 * Z);
+  DN_CHECK_ARG((((uintptr_t)params | (uintptr_t)x | (uintptr_t)z_out) & 15) == 0 && ((uintptr_t)keys & 7) == 0,
+               "dn_chain_start: params, x and z_out must be 16-byte, keys 8-byte aligned");
+  const int64_t row_quads = (int64_t)T * (Z >> 2), nquad = (int64_t)B * row_quads;
+  hipLaunchKernelGGL(chain_start_kernel, dim3(ew_grid(nquad)), dim3(256), 0, (hipStream_t)stream, params, ldp, keys, nquad, row_quads, Z,
+                     coef_a, coef_b, t, x, z_out);
+  DN_CHECK_LAUNCH("dn_chain_start");
   return DN_OK;
 }
 

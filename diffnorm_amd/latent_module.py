@@ -471,6 +471,37 @@ class SpeechVAEEncoderDecoder(_ParamTree):
         return mse, logits, kl.mean()
 
 
+def _chain_start(self, tgt_feature, input_mask, t_index, post_noise, start_noise, noise_keys):
+    """The prologue of LatentDiscreteModel's three samplers (`self`: the model -- a plain function, so it needs only the model's
+    device, tables and VAE): mask and lengths, VAE posterior sample, noise to index `t_index` (:1405-1409)
+    -> (dev, B, input_mask, lengths, x).  noise_keys=None: the posterior noise from torch's CPU generator and the start noise
+    from its device generator (or both injected), indexed by position in the padded batch.  noise_keys (int64 [B], the uint64 bit
+    patterns of sharding.utterance_keys): both drawn on the device from the utterance's own key (ops.chain_start), so an
+    utterance's start latent does not depend on the batch it is in."""
+    dev = self.device
+    _, sa, s1 = self._tables()
+    B, T, _ = tgt_feature.shape
+    if noise_keys is not None:
+        if post_noise is not None or start_noise is not None:
+            raise ValueError("noise_keys draws the posterior and the start noise: post_noise / start_noise cannot be given with it")
+        if not (torch.is_tensor(noise_keys) and noise_keys.dtype == torch.int64 and tuple(noise_keys.shape) == (B,)):
+            raise ValueError(f"noise_keys must be a torch.int64 tensor [{B}] (the uint64 bit patterns, one key per utterance)")
+    if input_mask is None:
+        input_mask = torch.ones(B, T, dtype=torch.bool, device=dev)
+    input_mask = input_mask.to(dev)
+    lengths = _mask_to_lengths(input_mask).to(torch.int32)
+    if noise_keys is not None:
+        params = self.speech_decoder.engine().encode_params(tgt_feature)
+        t_start = torch.full((B,), t_index, dtype=torch.int32, device=dev)
+        return dev, B, input_mask, lengths, ops.chain_start(params, noise_keys, sa, s1, t_start)
+    z = self.speech_decoder.encode_feature(tgt_feature, noise=post_noise).transpose(1, 2).contiguous()
+    if start_noise is None:
+        start_noise = torch.randn(z.shape, device=dev)
+    t_start = torch.full((B,), t_index, dtype=torch.int32, device=dev)
+    x = ops.q_sample(z, start_noise.to(dev, torch.float32).contiguous(), sa, s1, t_start, T)  # (:1405-1409)
+    return dev, B, input_mask, lengths, x
+
+
 class LatentDiscreteModel(nn.Module):
     """reference latent_module.py:1300-1613.  `speech_decoder` is the fairseq model whose `.encoder` is the VAE."""
 
@@ -547,8 +578,13 @@ class LatentDiscreteModel(nn.Module):
     @torch.no_grad()
     def ddim_sample(self, tgt_feature, prompt=None, prompt_mask=None, input_mask=None, cond_scale=1., ref_units=None,
                     start_step=50, post_noise=None, start_noise=None, use_graph=True, sampling_steps=None, timestep_schedule=None,
-                    eta=0.0, seed=0, step_noise=None, solver=None, solver_order=2):
+                    eta=0.0, seed=0, step_noise=None, solver=None, solver_order=2, noise_keys=None):
         """-> (list of unit tensors, match, total, recon_feature), as upstream (:1385-1471).
+
+        `noise_keys` (int64 [B], sharding.utterance_keys): the posterior and the start noise of row b are drawn on the device from
+        key b alone (dn_chain_start), so the result for an utterance does not depend on the batch it sits in; it excludes
+        `post_noise` / `start_noise`.  The per-step noise of `eta` > 0 stays indexed by position in the batch (keyed per-step noise
+        is not implemented): with eta > 0 results still depend on batch composition.
 
         `sampling_steps` = N runs the chain on N of the timesteps start_step-1 .. 1 (scheduler.ddim_steps: uniformly spread, N =
         start_step-1 is every timestep), `timestep_schedule` on an explicit strictly descending list; `eta` > 0 adds the DDIM noise
@@ -573,18 +609,8 @@ class LatentDiscreteModel(nn.Module):
         if scheduled and self.use_cond:
             raise ValueError("ddim_sample: sampling_steps / timestep_schedule / eta cover the unconditional model (the prompted, "
                              "guided chain walks every timestep)")
-        dev = self.device
-        coef, sa, s1 = self._tables()
-        B, T, _ = tgt_feature.shape
-        if input_mask is None:
-            input_mask = torch.ones(B, T, dtype=torch.bool, device=dev)
-        input_mask = input_mask.to(dev)
-        lengths = _mask_to_lengths(input_mask).to(torch.int32)
-        z = self.speech_decoder.encode_feature(tgt_feature, noise=post_noise).transpose(1, 2).contiguous()
-        if start_noise is None:
-            start_noise = torch.randn(z.shape, device=dev)
-        t_start = torch.full((B,), start_step, dtype=torch.int32, device=dev)
-        x = ops.q_sample(z, start_noise.to(dev, torch.float32).contiguous(), sa, s1, t_start, T)  # (:1405-1409)
+        coef = self._tables()[0]
+        dev, B, input_mask, lengths, x = _chain_start(self, tgt_feature, input_mask, start_step, post_noise, start_noise, noise_keys)
         if self.use_cond:
             # prompted chain (f3): the reference's loop drops the prompt it was given (:1413-1417 -- with use_cond it cannot run at
             # all); here every step is the guided prediction forward_with_cond_scale (:813-826) -- conditioned and null rows in ONE pass of
@@ -615,7 +641,7 @@ class LatentDiscreteModel(nn.Module):
     @torch.no_grad()
     def prompted_ddim_sample(self, tgt_feature, prompt, prompt_mask, input_mask=None, cond_scale=1., ref_units=None, start_step=50,
                              sampling_steps=None, timestep_schedule=None, eta=0.0, seed=0, step_noise=None, post_noise=None,
-                             start_noise=None, use_graph=True, solver=None, solver_order=2):
+                             start_noise=None, use_graph=True, solver=None, solver_order=2, noise_keys=None):
         """`ddim_sample` for the prompted model (use_cond) over a timestep schedule -> the same (list of unit tensors, match, total,
         recon_feature).  Encode and q_sample as `ddim_sample`; the chain is the device loop dn_guided_ddim_loop
         (EpsEngine.guided_ddim_schedule_loop): the guided prediction forward_with_cond_scale (:813-826) at every step of the schedule
@@ -626,7 +652,10 @@ class LatentDiscreteModel(nn.Module):
 
         `solver="dpmpp_2m"` runs the chain the same arguments select with the DPM-Solver++(2M) update (scheduler.dpm_schedule,
         EpsEngine.guided_dpm_schedule_loop, dn_guided_dpm_loop; `solver_order` 1 or 2) in place of DDIM's, on the same guided
-        prediction.  It is deterministic: `eta` and `step_noise` do not apply.  `solver=None` is the code above, unchanged."""
+        prediction.  It is deterministic: `eta` and `step_noise` do not apply.  `solver=None` is the code above, unchanged.
+
+        `noise_keys` as `ddim_sample`: keyed posterior and start noise; the per-step noise of `eta` > 0 stays indexed by position
+        in the batch."""
         if solver is not None:
             if solver != "dpmpp_2m":
                 raise ValueError(f"prompted_ddim_sample: unknown solver {solver!r} (None or 'dpmpp_2m')")
@@ -642,18 +671,7 @@ class LatentDiscreteModel(nn.Module):
             steps, rows = self.scheduler.dpm_schedule(start_step, sampling_steps, timestep_schedule, order=solver_order)  # (validates, on the host)
         else:
             steps, rows = self.scheduler.ddim_schedule(start_step, sampling_steps, timestep_schedule, eta=eta)  # (validates, on the host)
-        dev = self.device
-        _, sa, s1 = self._tables()
-        B, T, _ = tgt_feature.shape
-        if input_mask is None:
-            input_mask = torch.ones(B, T, dtype=torch.bool, device=dev)
-        input_mask = input_mask.to(dev)
-        lengths = _mask_to_lengths(input_mask).to(torch.int32)
-        z = self.speech_decoder.encode_feature(tgt_feature, noise=post_noise).transpose(1, 2).contiguous()
-        if start_noise is None:
-            start_noise = torch.randn(z.shape, device=dev)
-        t_start = torch.full((B,), start_step, dtype=torch.int32, device=dev)
-        x = ops.q_sample(z, start_noise.to(dev, torch.float32).contiguous(), sa, s1, t_start, T)  # (:1405-1409)
+        dev, B, input_mask, lengths, x = _chain_start(self, tgt_feature, input_mask, start_step, post_noise, start_noise, noise_keys)
         plens = _mask_to_lengths(prompt_mask.to(dev))
         if solver is not None:
             self.model.engine().guided_dpm_schedule_loop(x, lengths, prompt, plens, steps.to(dev), rows.to(dev), cond_scale=cond_scale,
@@ -669,24 +687,16 @@ class LatentDiscreteModel(nn.Module):
 
     @torch.no_grad()
     def ddpm_sample(self, tgt_feature, input_mask=None, ref_units=None, start_step=50, post_noise=None, start_noise=None, seed=0,
-                    step_noise=None, fixed_large=False, clip_denoised=False, use_graph=True):
+                    step_noise=None, fixed_large=False, clip_denoised=False, use_graph=True, noise_keys=None):
         """The chain of `ddim_sample` with the ancestral (DDPM) update -- GaussianDiffusion.p_sample (reference diffusion/
         gaussian_diffusion.py:376-417) on this model's cosine schedule: encode, noise to index start_step-1 (q_sample), then
         t = start_step-1 .. 0 on the device (dn_ddpm_loop; the per-step noise drawn in the kernel from `seed`, or `step_noise`
         [start_step, B, T, z] injected), decode, units.  BASELINE configs[2] read literally; the reference's LatentDiscreteModel
-        itself only has the DDIM sampler.  -> (list of unit tensors, match, total, recon_feature)."""
-        dev = self.device
-        _, sa, s1 = self._tables()
-        B, T, _ = tgt_feature.shape
-        if input_mask is None:
-            input_mask = torch.ones(B, T, dtype=torch.bool, device=dev)
-        input_mask = input_mask.to(dev)
-        lengths = _mask_to_lengths(input_mask).to(torch.int32)
-        z = self.speech_decoder.encode_feature(tgt_feature, noise=post_noise).transpose(1, 2).contiguous()
-        if start_noise is None:
-            start_noise = torch.randn(z.shape, device=dev)
-        t_start = torch.full((B,), start_step - 1, dtype=torch.int32, device=dev)
-        x = ops.q_sample(z, start_noise.to(dev, torch.float32).contiguous(), sa, s1, t_start, T)
+        itself only has the DDIM sampler.  -> (list of unit tensors, match, total, recon_feature).
+
+        `noise_keys` as `ddim_sample`: keyed posterior and start noise only.  The per-step noise of every ancestral update stays
+        indexed by position in the batch, so this sampler's results depend on batch composition with or without keys."""
+        dev, B, input_mask, lengths, x = _chain_start(self, tgt_feature, input_mask, start_step - 1, post_noise, start_noise, noise_keys)
         key = ("gd", bool(fixed_large))
         if getattr(self, "_gd_table", (None,))[0] != key or self._gd_table[1].device != dev:
             self._gd_table = (key, self.scheduler.gaussian_table(dev, fixed_large=fixed_large))

@@ -43,8 +43,9 @@ class Utterance:
         return self.feat
 
 
-def assemble_batch(items: Sequence[Utterance], device):
-    """Selects the first frame of every unit run, zero-pads to the longest utterance (reference :132-171)."""
+def assemble_batch(items: Sequence[Utterance], device, pad_to: Optional[int] = None):
+    """Selects the first frame of every unit run, zero-pads to the longest utterance (reference :132-171), or to `pad_to` frames
+    when given (at least the longest)."""
     feats, units = [], []
     for it in items:
         _, _, keep = reduce_token(list(it.tgt_unit))
@@ -54,6 +55,9 @@ def assemble_batch(items: Sequence[Utterance], device):
         units.append(torch.tensor(list(it.reduce_tgt_unit), dtype=torch.long))
     lens = torch.tensor([f.shape[0] for f in feats], dtype=torch.long)
     B, T = len(items), int(lens.max())
+    if pad_to is not None:
+        assert pad_to >= T, f"pad_to={pad_to} is shorter than the batch's longest utterance ({T})"
+        T = pad_to
     feat = torch.zeros(B, T, feats[0].shape[1])
     unit = torch.zeros(B, T, dtype=torch.long)
     for b in range(B):
@@ -71,11 +75,22 @@ def tsv_line(it: Utterance, pred_units: Sequence[int]) -> str:
 
 def normalize(ddim_sample: Callable, utterances: Sequence[Utterance], start_step: int = 50, batch_size: int = 100,
               device="cuda:0", group=None, sampling_steps: Optional[int] = None, eta: float = 0.0, seed: int = 0,
-              solver: Optional[str] = None) -> Optional[List[str]]:
+              solver: Optional[str] = None, noise_seed: Optional[int] = None, max_tokens: Optional[int] = None,
+              max_sentences: Optional[int] = None, pad_multiple: int = 1) -> Optional[List[str]]:
     """Runs `ddim_sample(feat, input_mask=..., ref_units=..., start_step=...)` (LatentDiscreteModel.ddim_sample) over this
     rank's batches and gathers the TSV lines of all ranks in utterance order (every rank returns the full list).
     `sampling_steps` (evaluations per chain instead of start_step-1), `eta`, `seed` and `solver` ("dpmpp_2m": the second-order
-    update for short chains) reach `ddim_sample` only when set."""
+    update for short chains) reach `ddim_sample` only when set.
+
+    `noise_seed`: every utterance draws its posterior and chain-start noise from its own key (sharding.utterance_keys of the seed and
+    the utterance's position in `utterances`; passed as `noise_keys=`), on the device, so its result does not depend on the batch
+    it is in, on torch's generators or on the number of ranks.  `max_tokens` (needs `noise_seed`): batches are formed by a frame
+    budget instead of `batch_size` consecutive utterances -- sharding.plan_batches over the de-duplicated lengths (length-sorted, at
+    most `max_sentences` utterances, T rounded up to `pad_multiple`), spread over the ranks by cost (sharding.balanced_batches).
+    `pad_multiple` > 1 also rounds the consecutive batches' T up.  With the four unset this is the reference's batching and noise."""
+    if noise_seed is not None or max_tokens is not None or max_sentences is not None or pad_multiple != 1:
+        return _normalize_keyed(ddim_sample, utterances, start_step, batch_size, device, group, sampling_steps, eta, solver,
+                                noise_seed, max_tokens, max_sentences, pad_multiple)
     rank, world = sharding.rank_world(group)
     # A run must give the same results on any number of ranks (and whatever sizes the last batches have).  The 2-byte / f32
     # contractions' fast K order (taps of a causal conv innermost, one staged copy of the rows, on the two 256-row tiles) sums in a
@@ -108,3 +123,51 @@ def normalize(ddim_sample: Callable, utterances: Sequence[Utterance], start_step
             local.append([tsv_line(it, p.tolist()) for it, p in zip(items, pred)])
     per_batch = sharding.gather_in_order(local, mine, len(batches), group)
     return [line for lines in per_batch for line in lines]
+
+
+def _normalize_keyed(ddim_sample, utterances, start_step, batch_size, device, group, sampling_steps, eta, solver, noise_seed,
+                     max_tokens, max_sentences, pad_multiple) -> List[str]:
+    """normalize() with per-utterance noise keys and, under `max_tokens`, frame-budget batches (see normalize)."""
+    if noise_seed is None:
+        raise ValueError("normalize: max_tokens / max_sentences / pad_multiple re-form the batches, which changes the results unless "
+                         "every utterance has its own noise: set noise_seed")
+    if eta != 0.0:
+        raise ValueError("normalize: noise_seed keys the posterior and chain-start noise only; the per-step noise of eta != 0 is "
+                         "indexed by batch position, so the results would still depend on the batches")
+    if max_tokens is None and max_sentences is not None:
+        raise ValueError("normalize: max_sentences caps the batches max_tokens forms; without max_tokens use batch_size")
+    from . import _lib
+
+    rank, world = sharding.rank_world(group)
+    lengths = [len(u.reduce_tgt_unit) for u in utterances]  # no feature is loaded to plan
+    if max_tokens is not None:
+        batches = sharding.plan_batches(lengths, max_tokens, max_sentences, pad_multiple)
+    else:
+        batches = [list(r) for r in sharding.batch_indices(len(utterances), batch_size)]
+    padded = [sharding.padded_length(max(lengths[i] for i in ids), pad_multiple) for ids in batches]
+    if max_tokens is not None:
+        mine = sharding.balanced_batches([len(ids) * T for ids, T in zip(batches, padded)], rank, world)
+    else:
+        mine = sharding.my_batches(len(batches), rank, world)
+    extra = {}
+    if sampling_steps is not None:
+        extra["sampling_steps"] = sampling_steps
+    if solver is not None:
+        extra["solver"] = solver
+    chosen = _lib.get_option("taps_inner")
+    local = []
+    with _lib.option("taps_inner", 2 if chosen is None else chosen):  # routing by shape, as normalize()
+        for b in mine:
+            items = [utterances[i] for i in batches[b]]
+            feat, ref_units, lens = assemble_batch(items, device, pad_to=padded[b])
+            mask = torch.arange(feat.shape[1], device=lens.device).view(1, -1) < lens.view(-1, 1)
+            keys = sharding.utterance_keys(noise_seed, batches[b])
+            pred, _, _, _ = ddim_sample(feat, input_mask=mask, cond_scale=1.0, ref_units=ref_units, start_step=start_step,
+                                        noise_keys=keys, **extra)
+            local.append([tsv_line(it, p.tolist()) for it, p in zip(items, pred)])
+    per_batch = sharding.gather_in_order(local, mine, len(batches), group)
+    lines = [None] * len(utterances)  # back to utterance order
+    for ids, got in zip(batches, per_batch):
+        for i, line in zip(ids, got):
+            lines[i] = line
+    return lines

@@ -204,6 +204,43 @@ def randn(shape, seed: int, offset: int = 0, device="cuda:0"):
     return out
 
 
+def _keys(keys, device):
+    """`keys`: torch.int64 [B] holding uint64 bit patterns (sharding.utterance_keys) -> the same, contiguous on `device`."""
+    if not (torch.is_tensor(keys) and keys.dtype == torch.int64 and keys.dim() == 1 and keys.numel() > 0):
+        raise ValueError("keys must be a non-empty torch.int64 tensor [B] (the uint64 bit patterns)")
+    return keys.to(device).contiguous()
+
+
+def randn_keyed(keys, T: int, Z: int, stream_id: int, device="cuda:0"):
+    """-> fp32 [B, T, Z]: row b is the noise stream of keys[b] (dn_randn_keyed: element (t, c) depends on the key, t and c only).
+    stream_id 0 = the posterior noise, 1 = the chain-start noise of `chain_start`."""
+    lib = _lib.load()
+    keys = _keys(keys, device)
+    out = torch.empty(keys.numel(), T, Z, dtype=torch.float32, device=keys.device)
+    with torch.cuda.device(keys.device):
+        _lib.check(lib.dn_randn_keyed(out.data_ptr(), keys.data_ptr(), keys.numel(), T, Z, stream_id, _stream()), "dn_randn_keyed")
+    return out
+
+
+def chain_start(params, keys, coef_a, coef_b, t_i32, want_z=False):
+    """params fp32 [B,T,2z] = [mean ; logvar] -> x [B,T,z] = a[t_b] * z + b[t_b] * n1, z = the posterior sample on n0, with n0 / n1 the
+    keyed streams 0 / 1 (dn_chain_start: sample_posterior + q_sample on randn_keyed's draws, bit for bit).  want_z: -> (x, z)."""
+    lib = _lib.load()
+    B, T, two_z = params.shape
+    Z = two_z // 2
+    if params.dtype != torch.float32 or params.stride(2) != 1 or params.stride(0) != T * params.stride(1):
+        raise ValueError("chain_start: params must be fp32 rows [B*T, ldp] (a [B,T,2z] tensor or its leading columns of a wider one)")
+    keys = _keys(keys, params.device)
+    if keys.numel() != B:
+        raise ValueError(f"chain_start: {keys.numel()} keys for a batch of {B}")
+    x = torch.empty(B, T, Z, dtype=torch.float32, device=params.device)
+    z = torch.empty_like(x) if want_z else None
+    with torch.cuda.device(params.device):
+        _lib.check(lib.dn_chain_start(params.data_ptr(), params.stride(1), keys.data_ptr(), B, T, Z, coef_a.data_ptr(), coef_b.data_ptr(),
+                                      t_i32.data_ptr(), x.data_ptr(), _lib.ptr(z), _stream()), "dn_chain_start")
+    return (x, z) if want_z else x
+
+
 def convert_rows(src, dst, C_):
     lib = _lib.load()
     M = src.numel() // src.shape[-1]

@@ -317,6 +317,20 @@ int dn_argmax_units(const float* logits, int32_t ld, int32_t M, int32_t V, int32
  * (the reference draws with torch.randn, latent_module.py:1409, distributions.py:38).             */
 int dn_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream);
 
+/* One noise stream per utterance (chain-start noise that does not depend on how batches are formed): element (b, t, c) of a dense
+ * fp32 [B, T, Z] tensor is normal c & 3 of the Philox4x32-10 call with key (keys[b] low, keys[b] high) and counter (q low, q high,
+ * stream_id, 0x53545254), q = t * (Z / 4) + c / 4 as a 64-bit value; Box-Muller as dn_randn.  The draw depends on the key, the
+ * frame and the channel only.  stream_id 0: posterior noise (distributions.py:24-41), 1: chain-start noise
+ * (latent_module.py:1405-1409).  Z a multiple of 4, out 16-byte aligned.                                              */
+int dn_randn_keyed(float* out, const uint64_t* keys, int32_t B, int32_t T, int32_t Z, uint32_t stream_id, void* stream);
+
+/* Posterior sample + q_sample in one pass on those draws (distributions.py:24-41, latent_module.py:1405-1409): params fp32
+ * [B*T, ldp] = [mean ; logvar], n0 / n1 = dn_randn_keyed's streams 0 / 1; z = mean + exp(0.5*clamp(logvar,-30,20))*n0,
+ * x = coef_a[t_b]*z + coef_b[t_b]*n1 -- dn_posterior_sample's and dn_q_sample's statements, bit for bit.  x and z_out (may be
+ * NULL) dense fp32 [B*T, Z]; Z and ldp multiples of 4, ldp >= 2 Z, params / x / z_out 16-byte aligned; t int32 [B].      */
+int dn_chain_start(const float* params, int32_t ldp, const uint64_t* keys, int32_t B, int32_t T, int32_t Z,
+                   const float* coef_a, const float* coef_b, const int32_t* t, float* x, float* z_out, void* stream);
+
 /* dtype conversion / zero-padded row copy: dst[m, 0:C] = src[m, 0:C], dst[m, C:ldd] = 0. */
 int dn_convert_rows(const void* src, int32_t src_dtype, int32_t lds, void* dst, int32_t dst_dtype,
                     int32_t ldd, int32_t M, int32_t C, void* stream);
