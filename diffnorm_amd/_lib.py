@@ -248,6 +248,12 @@ SYMBOLS = {
     "dn_ddim_sched_check": (C.c_int, [_vp, _i32, _i32]),
     "dn_ddim_sched_loop": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, C.c_uint64, _vp, _i32, _vp, _sz, _vp]),
     "dn_dpm2m_step": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "dn_ddim_sched_step": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i32, C.c_uint64, _vp, _vp]),
+    "dn_ddim_sched_step_keyed": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "dn_ddim_sched_loop_keyed": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _sz, _vp]),
+    "dn_ddpm_loop_keyed": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _sz, _vp]),
+    "dn_guided_ddim_loop_keyed": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _sz,
+                                            _vp]),
     "dn_dpm_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
     "dn_dpm_loop": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "dn_guided_ddim_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32, _i32]),

@@ -107,7 +107,9 @@ int wgrad_tn_x3_launch(const void* dy, int lddy, int cout, const void* const* x,
 struct StepKey {
   const void *ws, *x, *len, *coef;  // (a scheduled chain: the workspace copy of its coefficients, an address that moves with n_steps)
   const void *prompt, *plen;        // guided loop
-  uint64_t seed;                    // the Philox key of a drawing chain
+  const void* keys;                 // a keyed chain: the ADDRESS of its per-utterance keys (a replay reads keys[b] from memory, so new
+                                    // contents at the same address give new draws; another address is a miss); else null
+  uint64_t seed;                    // the Philox key of a seed-drawn chain (0 for a keyed one)
   int32_t B, T, Tp, n_steps;        // Tp, n_steps: guided loop (the unconditional slot serves any start_step / max_evals)
   int32_t flags;                    // DN_LOOP_* without DN_LOOP_KEEP_TABLE
   int32_t opt_gen;                  // dn::option_generation() at capture: the run-time options its routes were chosen under
@@ -115,7 +117,7 @@ struct StepKey {
   uint16_t ancestral, clip, scheduled, eta, dpm;  // which update the step applies
   uint16_t injected;                // injected noise bakes its row base into the step: stored (it evicts), never served
 };
-static_assert(sizeof(StepKey) == 6 * sizeof(void*) + 8 + 7 * 4 + 6 * 2, "StepKey has no padding: copies of a key compare equal too");
+static_assert(sizeof(StepKey) == 7 * sizeof(void*) + 8 + 7 * 4 + 6 * 2, "StepKey has no padding: copies of a key compare equal too");
 struct StepGraph {
   void* exec;  // hipGraphExec_t, null while empty
   StepKey key;

@@ -669,10 +669,10 @@ extern "C" size_t dn_ddim_workspace_bytes(const DnEps* m, int32_t B, int32_t T, 
 }
 
 int dn_ddpm_step_launch(float* x, const float* eps, int M, int C, int T, const float* table, const int32_t* t, int clip, const float* noise,
-                        int64_t noise_row, int t_top, uint64_t seed, hipStream_t stream);  // pointwise.hip
+                        int64_t noise_row, int t_top, uint64_t seed, const uint64_t* keys, int b0, hipStream_t stream);  // pointwise.hip
 int dn_ddim_sched_step_launch(float* x, const float* eps, int64_t elem0, int64_t n_elem, const float* coef, const int32_t* steps,
-                              const int32_t* counter, int eta_on, const float* noise, int64_t noise_row, uint64_t seed,
-                              hipStream_t stream);  // pointwise.hip
+                              const int32_t* counter, int eta_on, const float* noise, int64_t noise_row, uint64_t seed, const uint64_t* keys,
+                              int64_t row_quads, hipStream_t stream);  // pointwise.hip
 int dn_dpm2m_step_launch(float* x, const float* eps, float* hist, int64_t elem0, int64_t n_elem, const float* coef, const int32_t* counter,
                          hipStream_t stream);  // pointwise.hip
 
@@ -742,7 +742,7 @@ struct LoopDesc {
   const int32_t* steps;
   int n_steps, coef_cols;
   bool history;  // one more persistent buffer of the latent's size (dn_dpm_loop: the previous step's data prediction)
-  StepKey kind;  // ancestral, clip, scheduled, eta, dpm, seed, injected: the loop's part of the graph key
+  StepKey kind;  // ancestral, clip, scheduled, eta, dpm, seed, keys, injected: the loop's part of the graph key
   // the scheduler update after an evaluation, applied to batch rows [b0, b0 + nb) = half 0 or 1 on `stream`
   std::function<int(const StepBufs&, int half, int b0, int nb, hipStream_t stream)> update;
 };
@@ -875,13 +875,23 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
   return n_eval;
 }
 
-// the loop's part of a graph key (memset first: the key is compared with memcmp)
-static StepKey step_kind(uint64_t seed, const float* noise) {
+// the loop's part of a graph key (memset first: the key is compared with memcmp).  A keyed chain carries the address of its keys and
+// seed 0: the captured step bakes in that address, never the keys' contents.
+static StepKey step_kind(uint64_t seed, const float* noise, const uint64_t* keys = nullptr) {
   StepKey k;
   memset(&k, 0, sizeof(k));
-  k.seed = seed;
+  k.seed = keys ? 0 : seed;
+  k.keys = keys;
   k.injected = noise != nullptr;
   return k;
+}
+
+// what every keyed loop entry refuses before anything is written
+static int check_keys(const char* who, const DnEps* m, const uint64_t* keys) {
+  DN_CHECK_ARG(m && keys, "%s: null engine or keys", who);
+  DN_CHECK_ARG(((uintptr_t)keys & 7) == 0, "%s: keys must be 8-byte aligned", who);
+  DN_CHECK_ARG(m->cfg.latent % 4 == 0, "%s: the latent width %d must be a multiple of 4", who, m->cfg.latent);
+  return DN_OK;
 }
 
 extern "C" int dn_ddim_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, int32_t start_step, int32_t max_evals,
@@ -896,19 +906,36 @@ extern "C" int dn_ddim_loop(DnEps* m, float* x, const int32_t* lengths, int32_t 
   return sampler_loop(m, x, lengths, B, T, start_step, max_evals, coef, timesteps, flags, workspace, workspace_bytes, stream, d);
 }
 
-extern "C" int dn_ddpm_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, int32_t start_step, int32_t max_evals,
-                            const float* table, int32_t timesteps, int32_t clip_denoised, uint64_t seed, const float* noise, int32_t flags,
-                            void* workspace, size_t workspace_bytes, void* stream) {
-  // the ancestral step with `table` [timesteps, DN_GD_COLS], on the half's own rows; the second half draws from its own key
-  LoopDesc d = {"dn_ddim_loop", "dn_ddim_workspace_bytes", dn_ddim_workspace_bytes, nullptr, 0, 0, false, step_kind(seed, noise), nullptr};
+// dn_ddpm_loop (keys == NULL) and dn_ddpm_loop_keyed
+static int ddpm_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, int32_t start_step, int32_t max_evals, const float* table,
+                     int32_t timesteps, int32_t clip_denoised, uint64_t seed, const float* noise, const uint64_t* keys, int32_t flags,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+  // the ancestral step with `table` [timesteps, DN_GD_COLS], on the half's own rows; seed-drawn, the second half draws from its own
+  // key; keyed, both halves draw under the utterances' keys (the launch is told its first batch row), so the chain is split-invariant
+  LoopDesc d = {"dn_ddim_loop", "dn_ddim_workspace_bytes", dn_ddim_workspace_bytes, nullptr, 0, 0, false, step_kind(seed, noise, keys), nullptr};
   d.kind.ancestral = 1;
   d.kind.clip = clip_denoised != 0;
   d.update = [=](const StepBufs& b, int half, int b0, int nb, hipStream_t st) {
     const size_t off = (size_t)b0 * b.T * b.z;
     return dn_ddpm_step_launch(b.x + off, b.eps + off, nb * b.T, b.z, b.T, b.coef, b.tvec + b0, clip_denoised, noise ? noise + off : nullptr, b.all,
-                               b.noise_top, half ? seed ^ 0x9E3779B97F4A7C15ull : seed, st);
+                               b.noise_top, half ? seed ^ 0x9E3779B97F4A7C15ull : seed, keys, b0, st);
   };
   return sampler_loop(m, x, lengths, B, T, start_step, max_evals, table, timesteps, flags, workspace, workspace_bytes, stream, d);
+}
+
+extern "C" int dn_ddpm_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, int32_t start_step, int32_t max_evals,
+                            const float* table, int32_t timesteps, int32_t clip_denoised, uint64_t seed, const float* noise, int32_t flags,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  return ddpm_loop(m, x, lengths, B, T, start_step, max_evals, table, timesteps, clip_denoised, seed, noise, nullptr, flags, workspace,
+                   workspace_bytes, stream);
+}
+
+extern "C" int dn_ddpm_loop_keyed(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, int32_t start_step, int32_t max_evals,
+                                  const float* table, int32_t timesteps, int32_t clip_denoised, const uint64_t* keys, int32_t flags,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  DN_TRY(check_keys("dn_ddpm_loop_keyed", m, keys));
+  return ddpm_loop(m, x, lengths, B, T, start_step, max_evals, table, timesteps, clip_denoised, 0, nullptr, keys, flags, workspace,
+                   workspace_bytes, stream);
 }
 
 // rows of cond_all (C fp32 each) hold the chain's coefficient rows after the table is built: the same bytes as dn_ddim_loop's for
@@ -928,24 +955,40 @@ extern "C" int dn_ddim_sched_check(const int32_t* steps, int32_t n_steps, int32_
   return DN_OK;
 }
 
-extern "C" int dn_ddim_sched_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, const int32_t* steps, const float* coef,
-                                  int32_t n_steps, int32_t timesteps, int32_t eta_on, uint64_t seed, const float* noise, int32_t flags,
-                                  void* workspace, size_t workspace_bytes, void* stream) {
-  DN_CHECK_ARG(steps, "dn_ddim_sched_loop: null schedule");
-  DN_CHECK_ARG(!(flags & ~(DN_LOOP_GRAPH | DN_LOOP_SPLIT2)), "dn_ddim_sched_loop: flags=%d (DN_LOOP_GRAPH | DN_LOOP_SPLIT2 only)", flags);
+// dn_ddim_sched_loop (keys == NULL) and dn_ddim_sched_loop_keyed (eta on)
+static int ddim_sched_loop(const char* who, DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, const int32_t* steps,
+                           const float* coef, int32_t n_steps, int32_t timesteps, int32_t eta_on, uint64_t seed, const float* noise,
+                           const uint64_t* keys, int32_t flags, void* workspace, size_t workspace_bytes, void* stream) {
+  DN_CHECK_ARG(steps, "%s: null schedule", who);
+  DN_CHECK_ARG(!(flags & ~(DN_LOOP_GRAPH | DN_LOOP_SPLIT2)), "%s: flags=%d (DN_LOOP_GRAPH | DN_LOOP_SPLIT2 only)", who, flags);
   eta_on = eta_on != 0;
   if (!eta_on) seed = 0;
-  // the scheduled update on the half's element range of the whole batch: the whole batch's element index keys the draw, so the halves
-  // share one stream of numbers
-  LoopDesc d = {"dn_ddim_sched_loop", "dn_ddim_sched_workspace_bytes", dn_ddim_sched_workspace_bytes, steps, n_steps, DN_DDIM_SCHED_COLS,
-                false, step_kind(seed, noise), nullptr};
+  // the scheduled update on the half's element range of the whole batch: the whole batch's element index keys the draw (or finds the
+  // utterance's key), so the halves share one stream of numbers
+  LoopDesc d = {who, "dn_ddim_sched_workspace_bytes", dn_ddim_sched_workspace_bytes, steps, n_steps, DN_DDIM_SCHED_COLS,
+                false, step_kind(seed, noise, keys), nullptr};
   d.kind.scheduled = 1;
   d.kind.eta = (uint16_t)eta_on;
   d.update = [=](const StepBufs& b, int, int b0, int nb, hipStream_t st) {
     return dn_ddim_sched_step_launch(b.x, b.eps, (int64_t)b0 * b.T * b.z, (int64_t)nb * b.T * b.z, b.coef, b.steps, b.counter, eta_on, noise, b.all,
-                                     seed, st);
+                                     seed, keys, (int64_t)b.T * (b.z >> 2), st);
   };
   return sampler_loop(m, x, lengths, B, T, 0, 0, coef, timesteps, flags, workspace, workspace_bytes, stream, d);
+}
+
+extern "C" int dn_ddim_sched_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, const int32_t* steps, const float* coef,
+                                  int32_t n_steps, int32_t timesteps, int32_t eta_on, uint64_t seed, const float* noise, int32_t flags,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  return ddim_sched_loop("dn_ddim_sched_loop", m, x, lengths, B, T, steps, coef, n_steps, timesteps, eta_on, seed, noise, nullptr, flags,
+                         workspace, workspace_bytes, stream);
+}
+
+extern "C" int dn_ddim_sched_loop_keyed(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, const int32_t* steps,
+                                        const float* coef, int32_t n_steps, int32_t timesteps, const uint64_t* keys, int32_t flags,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+  DN_TRY(check_keys("dn_ddim_sched_loop_keyed", m, keys));
+  return ddim_sched_loop("dn_ddim_sched_loop_keyed", m, x, lengths, B, T, steps, coef, n_steps, timesteps, 1, 0, nullptr, keys, flags,
+                         workspace, workspace_bytes, stream);
 }
 
 // dn_ddim_sched_loop's layout with the history buffer taken beside eps (one more 256-byte aligned block of the latent's size)
@@ -1300,7 +1343,7 @@ extern "C" int dn_eps_forward_cond_ex(DnEps* m, const float* x, const int32_t* t
 // ------------------------------------------------------------------------------------------ guided chain over a timestep schedule
 int dn_guided_sched_step_launch(float* x, float* xin, const float* both, int64_t n_elem, int guided, float scale, const float* coef,
                                 const int32_t* steps, const int32_t* counter, int eta_on, const float* noise, int64_t noise_row, uint64_t seed,
-                                hipStream_t stream);  // pointwise.hip
+                                const uint64_t* keys, int64_t row_quads, hipStream_t stream);  // pointwise.hip
 int dn_guided_dpm_step_launch(float* x, float* xin, const float* both, float* hist, int64_t n_elem, int guided, float scale, const float* coef,
                               const int32_t* counter, hipStream_t stream);  // pointwise.hip
 
@@ -1362,7 +1405,7 @@ struct GuidedDesc {
   const char *name, *ws_name, *uncond_name;  // for messages; uncond_name: the entry an unconditional model is sent to
   int coef_cols;
   bool history;  // GuidedBufs::hist
-  StepKey kind;  // eta, dpm, seed, injected: the loop's part of the graph key
+  StepKey kind;  // eta, dpm, seed, keys, injected: the loop's part of the graph key
   // the fused combination + update + refill of the model's input after a pass (n_elem = B T latent)
   std::function<int(const GuidedBufs&, float* x, float* xin, int64_t n_elem, int guided, float scale, hipStream_t stream)> update;
 };
@@ -1447,20 +1490,38 @@ extern "C" size_t dn_guided_ddim_workspace_bytes(const DnEps* m, int32_t B, int3
   return guided_ws_bytes(m, B, T, Tp, n_steps, guided, false, DN_DDIM_SCHED_COLS);
 }
 
+// dn_guided_ddim_loop (keys == NULL) and dn_guided_ddim_loop_keyed (eta on)
+static int guided_ddim_loop(const char* who, DnEps* m, float* x, const int32_t* lengths, const float* prompt, const int32_t* prompt_lengths,
+                            int32_t B, int32_t T, int32_t Tp, float cond_scale, const int32_t* steps, const float* coef, int32_t n_steps,
+                            int32_t timesteps, int32_t eta_on, uint64_t seed, const float* noise, const uint64_t* keys, int32_t flags,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  eta_on = eta_on != 0;
+  if (!eta_on) seed = 0;
+  GuidedDesc d = {who, "dn_guided_ddim_workspace_bytes", "dn_ddim_sched_loop", DN_DDIM_SCHED_COLS, false, step_kind(seed, noise, keys), nullptr};
+  d.kind.eta = (uint16_t)eta_on;
+  d.update = [=](const GuidedBufs& g, float* xb, float* xin, int64_t n_elem, int guided, float scale, hipStream_t st) {
+    return dn_guided_sched_step_launch(xb, xin, g.both, n_elem, guided, scale, g.coef, g.steps, g.counter, eta_on, noise, n_elem, seed, keys,
+                                       n_elem / B / 4, st);
+  };
+  return guided_loop(m, x, lengths, prompt, prompt_lengths, B, T, Tp, cond_scale, steps, coef, n_steps, timesteps, flags, workspace,
+                     workspace_bytes, stream, d);
+}
+
 extern "C" int dn_guided_ddim_loop(DnEps* m, float* x, const int32_t* lengths, const float* prompt, const int32_t* prompt_lengths, int32_t B,
                                    int32_t T, int32_t Tp, float cond_scale, const int32_t* steps, const float* coef, int32_t n_steps,
                                    int32_t timesteps, int32_t eta_on, uint64_t seed, const float* noise, int32_t flags, void* workspace,
                                    size_t workspace_bytes, void* stream) {
-  eta_on = eta_on != 0;
-  if (!eta_on) seed = 0;
-  GuidedDesc d = {"dn_guided_ddim_loop", "dn_guided_ddim_workspace_bytes", "dn_ddim_sched_loop", DN_DDIM_SCHED_COLS, false, step_kind(seed, noise),
-                  nullptr};
-  d.kind.eta = (uint16_t)eta_on;
-  d.update = [=](const GuidedBufs& g, float* xb, float* xin, int64_t n_elem, int guided, float scale, hipStream_t st) {
-    return dn_guided_sched_step_launch(xb, xin, g.both, n_elem, guided, scale, g.coef, g.steps, g.counter, eta_on, noise, n_elem, seed, st);
-  };
-  return guided_loop(m, x, lengths, prompt, prompt_lengths, B, T, Tp, cond_scale, steps, coef, n_steps, timesteps, flags, workspace,
-                     workspace_bytes, stream, d);
+  return guided_ddim_loop("dn_guided_ddim_loop", m, x, lengths, prompt, prompt_lengths, B, T, Tp, cond_scale, steps, coef, n_steps, timesteps,
+                          eta_on, seed, noise, nullptr, flags, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dn_guided_ddim_loop_keyed(DnEps* m, float* x, const int32_t* lengths, const float* prompt, const int32_t* prompt_lengths,
+                                         int32_t B, int32_t T, int32_t Tp, float cond_scale, const int32_t* steps, const float* coef,
+                                         int32_t n_steps, int32_t timesteps, const uint64_t* keys, int32_t flags, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+  DN_TRY(check_keys("dn_guided_ddim_loop_keyed", m, keys));
+  return guided_ddim_loop("dn_guided_ddim_loop_keyed", m, x, lengths, prompt, prompt_lengths, B, T, Tp, cond_scale, steps, coef, n_steps,
+                          timesteps, 1, 0, nullptr, keys, flags, workspace, workspace_bytes, stream);
 }
 
 // DPM-Solver++(2M) (Lu et al. 2022, "DPM-Solver++", the data-prediction multistep solver, eq. 11-12 / algorithm 2) on the guided

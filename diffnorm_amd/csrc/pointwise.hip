@@ -260,11 +260,15 @@ __global__ __launch_bounds__(256) void randn_kernel(float* __restrict__ out, int
 // p_sample (diffusion/gaussian_diffusion.py:376-417) with a fixed variance, the arithmetic of gaussian_step_kernel's sampler 0;
 // the noise is injected (`noise`, the row of this step) or drawn here: Philox4x32-10, key = seed, counter = (element quad, t) --
 // t comes from the per-sample step vector the loop fills from its device counter, so graph replays draw fresh noise.
+// kKeyed (dn_ddpm_loop_keyed): drawn from the utterance's key instead (step_noise_keyed4 below) -- x, eps and t are the launch's (a
+// half batch's), keys the WHOLE batch's and quad0 the launch's first quad in it, so both halves draw under the keys alone.
 __device__ __forceinline__ void philox_normal4(uint64_t seed, uint64_t ctr_lo, uint32_t ctr_hi, float (&r)[4]);
+__device__ __forceinline__ void step_noise_keyed4(const uint64_t* __restrict__ keys, int64_t Q, int64_t row_quads, int t, float (&z)[4]);
+template <bool kKeyed>
 __global__ __launch_bounds__(256) void ddpm_step_kernel(float* x, const float* __restrict__ eps, int M, int C, int T,
                                                         const float* __restrict__ table, const int32_t* __restrict__ t,
                                                         int clip, const float* __restrict__ noise, int64_t noise_row, int t_top,
-                                                        uint64_t seed) {
+                                                        uint64_t seed, const uint64_t* __restrict__ keys, int64_t quad0, int64_t row_quads) {
   const int64_t nquad = ((int64_t)M * C) >> 2;  // C is a multiple of 4: a quad stays inside one row
   for (int64_t q = blockIdx.x * 256 + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * 256) {
     const int64_t i = q << 2;
@@ -273,7 +277,9 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(float* x, const float* _
     const float* tb = table + (int64_t)tn * DN_GD_COLS;
     const float4 xv = *reinterpret_cast<const float4*>(x + i), ev = *reinterpret_cast<const float4*>(eps + i);
     float z[4];
-    if (noise) {
+    if (kKeyed) {
+      step_noise_keyed4(keys, quad0 + q, row_quads, tn, z);
+    } else if (noise) {
       const float4 nv = *reinterpret_cast<const float4*>(noise + (int64_t)(t_top - tn) * noise_row + i);
       z[0] = nv.x; z[1] = nv.y; z[2] = nv.z; z[3] = nv.w;
     } else {
@@ -308,8 +314,9 @@ __device__ __forceinline__ void philox_normal4(uint64_t seed, uint64_t ctr_lo, u
 // ------------------------------------------------------------------------------------------ keyed chain-start noise
 // One noise stream per utterance: Philox4x32-10 under key = keys[b] (low, high), counter = (q low, q high, stream_id, "STRT"),
 // q = frame * (Z / 4) + channel quad WITHIN the utterance -- a draw depends on the key, the frame and the channel only, not on the
-// row b, the batch size, the padded length or the launch.  stream_id 0: posterior noise, 1: chain-start noise.  The fourth word
-// keeps the stream apart from dn_randn's (0) and the update kernels' ("DPMP").
+// row b, the batch size, the padded length or the launch.  stream_id 0: posterior noise, 1: chain-start noise, 2 + t: the noise of the
+// update that leaves timestep t (the keyed update kernels: step_noise_keyed4).  The fourth word keeps the stream apart from dn_randn's
+// (0) and the seed-drawn update kernels' ("DPMP").
 __device__ __forceinline__ void philox_keyed4(uint64_t key, uint64_t q, uint32_t stream_id, float (&r)[4]) {
   uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), stream_id, 0x53545254u};
   uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
@@ -320,6 +327,15 @@ __device__ __forceinline__ void philox_keyed4(uint64_t key, uint64_t q, uint32_t
     k1 += 0xBB67AE85u;
   }
   box_muller4(c, r);
+}
+
+// The per-step noise of a keyed chain, shared by the three update kernels: quad Q of the WHOLE batch [B, T, Z] (row_quads = T Z / 4
+// quads per utterance) at timestep t -> keys[b]'s stream 2 + t at the quad within the utterance, which is what dn_randn_keyed
+// materialises for stream_id = 2 + t.  The timestep, not the step index, is the stream: a draw does not depend on the schedule's
+// other members.  One 64-bit division per quad, as chain_start_kernel pays.
+__device__ __forceinline__ void step_noise_keyed4(const uint64_t* __restrict__ keys, int64_t Q, int64_t row_quads, int t, float (&z)[4]) {
+  const int64_t b = Q / row_quads;
+  philox_keyed4(keys[b], (uint64_t)(Q - b * row_quads), 2u + (uint32_t)t, z);
 }
 
 // out [B, T, Z] dense; one thread per quad of channels (Z is a multiple of 4: a quad stays inside one frame)
@@ -375,6 +391,8 @@ __global__ __launch_bounds__(256) void chain_start_kernel(const float* __restric
 // statements of ddim_step_kernel, product for product (as compiled: see sched_update).  eta_on: + 1[e_i != 0] sigma z (diffusion/gaussian_diffusion.py:513-560), z
 // injected (row i of `noise`) or drawn here: Philox4x32-10, key = seed, counter = (element quad OF THE WHOLE BATCH, step index i) --
 // a half-batch launch passes its first quad (q0), so eager, graph replay and the two half-batch streams draw the same numbers.
+// kKeyed (dn_ddim_sched_loop_keyed, dn_ddim_sched_step_keyed, dn_guided_ddim_loop_keyed): drawn from the utterance's key under stream
+// 2 + steps[i] (step_noise_keyed4) -- the timestep, the frame and the channel, not the row, B, the padded T or the step index.
 // The three pieces below are the one definition of that update: dn_guided_ddim_loop's kernel applies them too, and the two chains are
 // tested bit-equal.
 struct SchedCoef {
@@ -385,10 +403,24 @@ __device__ __forceinline__ SchedCoef sched_coef(const float* __restrict__ coef, 
   const float* cf = coef + (int64_t)step * DN_DDIM_SCHED_COLS;
   return {cf[0], cf[1], cf[2], cf[3], (eta_on && steps[step] != 0) ? cf[4] : 0.0f};
 }
-// the four normals of quad q (elements i .. i+3) at `step`: the injected row, or Philox keyed by (q, step)
-__device__ __forceinline__ void sched_normal4(const float* __restrict__ noise, int64_t noise_row, uint64_t seed, int64_t q, int64_t i, int step,
-                                              float (&z)[4]) {
-  if (noise) {
+// where the scheduled updates take their normals from: the injected rows, else (kKeyed) the utterances' keys, else `seed`
+struct SchedNoise {
+  const float* noise;
+  int64_t noise_row;
+  uint64_t seed;
+  const uint64_t* keys;
+  int64_t row_quads;
+};
+// the four normals of quad q (elements i .. i+3) of the whole batch at `step` (timestep t): kKeyed: the utterance's stream 2 + t; else
+// the injected row, or Philox keyed by (q, step)
+template <bool kKeyed>
+__device__ __forceinline__ void sched_normal4(const SchedNoise& s, int64_t q, int64_t i, int step, int t, float (&z)[4]) {
+  const float* __restrict__ noise = s.noise;
+  const int64_t noise_row = s.noise_row;
+  const uint64_t seed = s.seed;
+  if (kKeyed) {
+    step_noise_keyed4(s.keys, q, s.row_quads, t, z);
+  } else if (noise) {
     const float4 nv = *reinterpret_cast<const float4*>(noise + (int64_t)step * noise_row + i);
     z[0] = nv.x; z[1] = nv.y; z[2] = nv.z; z[3] = nv.w;
   } else {
@@ -404,17 +436,18 @@ __device__ __forceinline__ float sched_update(const SchedCoef& c, float x, float
   return eta_on ? fmaf(c.sg, z, r) : r;
 }
 
+template <bool kKeyed>
 __global__ __launch_bounds__(256) void ddim_sched_step_kernel(float* x, const float* __restrict__ eps, int64_t q0, int64_t nquad,
                                                               const float* __restrict__ coef, const int32_t* __restrict__ steps,
-                                                              const int32_t* __restrict__ counter, int eta_on,
-                                                              const float* __restrict__ noise, int64_t noise_row, uint64_t seed) {
+                                                              const int32_t* __restrict__ counter, int eta_on, SchedNoise src) {
   const int step = *counter;
   const SchedCoef c = sched_coef(coef, steps, step, eta_on);
+  const int t = kKeyed ? steps[step] : 0;
   for (int64_t q = q0 + blockIdx.x * 256 + threadIdx.x; q < q0 + nquad; q += (int64_t)gridDim.x * 256) {
     const int64_t i = q << 2;
     const float4 xv = *reinterpret_cast<const float4*>(x + i), ev = *reinterpret_cast<const float4*>(eps + i);
     float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (eta_on) sched_normal4(noise, noise_row, seed, q, i, step, z);
+    if (eta_on) sched_normal4<kKeyed>(src, q, i, step, t, z);
     const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, es[4] = {ev.x, ev.y, ev.z, ev.w};
     float o[4];
 #pragma unroll
@@ -459,17 +492,18 @@ __global__ __launch_bounds__(256) void dpm2m_step_kernel(float* x, const float* 
 // One update of the prompted, guided chain over a timestep schedule (dn_guided_ddim_loop), per float4 quad of the B-row latent:
 // eps = the conditioned row of `both` (kGuided: combined with the null row, n elements further, by cfg_combine_kernel's three rounded
 // operations), then ddim_sched_step_kernel's update through the same three helpers: its coefficient row, noise mask and noise source
-// (the Philox counter is the quad of the B-row batch and the step index, so a scale-1 chain draws what dn_ddim_sched_loop draws).
+// (the Philox counter is the quad of the B-row batch and the step index, so a scale-1 chain draws what dn_ddim_sched_loop draws;
+// kKeyed: the utterance's stream 2 + steps[i], as ddim_sched_step_kernel<true>).
 // The result goes to x and to the model's next input: xin[0:n] and (kGuided) xin[n:2n] -- one pass where the host-driven chain
 // copies x twice, combines, updates and decrements.  !kGuided: nothing past n is touched, and xin may be x itself.
 // HBM-bound: (2 + kGuided) reads and (1 + 1 + kGuided) writes of n floats; 16-byte accesses, grid-stride, no LDS.
-template <bool kGuided, bool kEta>
+template <bool kGuided, bool kEta, bool kKeyed>
 __global__ __launch_bounds__(256) void guided_sched_step_kernel(float* x, float* xin, const float* __restrict__ both, int64_t nquad, float scale,
                                                                 const float* __restrict__ coef, const int32_t* __restrict__ steps,
-                                                                const int32_t* __restrict__ counter, const float* __restrict__ noise,
-                                                                int64_t noise_row, uint64_t seed) {
+                                                                const int32_t* __restrict__ counter, SchedNoise src) {
   const int step = *counter;
   const SchedCoef c = sched_coef(coef, steps, step, kEta);
+  const int t = kKeyed ? steps[step] : 0;
   const int64_t n = nquad << 2;
   for (int64_t q = blockIdx.x * 256 + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * 256) {
     const int64_t i = q << 2;
@@ -482,7 +516,7 @@ __global__ __launch_bounds__(256) void guided_sched_step_kernel(float* x, float*
       for (int j = 0; j < 4; ++j) es[j] = __fadd_rn(us[j], __fmul_rn(__fsub_rn(es[j], us[j]), scale));
     }
     float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (kEta) sched_normal4(noise, noise_row, seed, q, i, step, z);
+    if (kEta) sched_normal4<kKeyed>(src, q, i, step, t, z);
     const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
     float o[4];
 #pragma unroll
@@ -801,21 +835,35 @@ extern "C" int dn_cfg_combine(const float* both, float scale, int64_t n, float* 
 }
 
 // (engine.hip: the ancestral update of dn_ddpm_loop)
+// keys != NULL (dn_ddpm_loop_keyed): the whole batch's keys and the launch's first batch row b0; noise and seed are not read
 int dn_ddpm_step_launch(float* x, const float* eps, int M, int C, int T, const float* table, const int32_t* t, int clip, const float* noise,
-                        int64_t noise_row, int t_top, uint64_t seed, hipStream_t stream) {
+                        int64_t noise_row, int t_top, uint64_t seed, const uint64_t* keys, int b0, hipStream_t stream) {
   DN_CHECK_ARG(C % 4 == 0, "dn_ddpm_loop: the latent width must be a multiple of 4");
-  hipLaunchKernelGGL(ddpm_step_kernel, dim3(ew_grid(((int64_t)M * C) >> 2)), dim3(256), 0, stream, x, eps, M, C, T, table, t, clip, noise,
-                     noise_row, t_top, seed);
+  const dim3 grid(ew_grid(((int64_t)M * C) >> 2)), block(256);
+  const int64_t row_quads = (int64_t)T * (C >> 2);
+  if (keys)
+    hipLaunchKernelGGL(ddpm_step_kernel<true>, grid, block, 0, stream, x, eps, M, C, T, table, t, clip, nullptr, 0, t_top, 0, keys,
+                       (int64_t)b0 * row_quads, row_quads);
+  else
+    hipLaunchKernelGGL(ddpm_step_kernel<false>, grid, block, 0, stream, x, eps, M, C, T, table, t, clip, noise, noise_row, t_top, seed, nullptr,
+                       0, 0);
   DN_CHECK_LAUNCH("dn_ddpm_loop step");
   return DN_OK;
 }
 
 // (engine.hip: the update of dn_ddim_sched_loop; x, eps, noise: the whole batch's; [elem0, elem0 + n_elem): this launch's elements)
+// keys != NULL (the keyed entries; eta_on): the whole batch's keys, row_quads = T Z / 4 quads per utterance; noise and seed are not read
 int dn_ddim_sched_step_launch(float* x, const float* eps, int64_t elem0, int64_t n_elem, const float* coef, const int32_t* steps,
-                              const int32_t* counter, int eta_on, const float* noise, int64_t noise_row, uint64_t seed, hipStream_t stream) {
+                              const int32_t* counter, int eta_on, const float* noise, int64_t noise_row, uint64_t seed, const uint64_t* keys,
+                              int64_t row_quads, hipStream_t stream) {
   DN_CHECK_ARG(elem0 % 4 == 0 && n_elem % 4 == 0 && n_elem > 0, "dn_ddim_sched_loop: the latent width must be a multiple of 4");
-  hipLaunchKernelGGL(ddim_sched_step_kernel, dim3(ew_grid(n_elem >> 2)), dim3(256), 0, stream, x, eps, elem0 >> 2, n_elem >> 2, coef, steps,
-                     counter, eta_on, noise, noise_row, seed);
+  const dim3 grid(ew_grid(n_elem >> 2)), block(256);
+  if (keys)
+    hipLaunchKernelGGL(ddim_sched_step_kernel<true>, grid, block, 0, stream, x, eps, elem0 >> 2, n_elem >> 2, coef, steps, counter, 1,
+                       SchedNoise{nullptr, 0, 0, keys, row_quads});
+  else
+    hipLaunchKernelGGL(ddim_sched_step_kernel<false>, grid, block, 0, stream, x, eps, elem0 >> 2, n_elem >> 2, coef, steps, counter, eta_on,
+                       SchedNoise{noise, noise_row, seed, nullptr, 0});
   DN_CHECK_LAUNCH("dn_ddim_sched_loop step");
   return DN_OK;
 }
@@ -836,15 +884,44 @@ extern "C" int dn_dpm2m_step(float* x, const float* eps, float* hist, int64_t n,
   return dn_dpm2m_step_launch(x, eps, hist, 0, n, coef, step_index, (hipStream_t)stream);
 }
 
+extern "C" int dn_ddim_sched_step(float* x, const float* eps, int64_t n, const float* coef, const int32_t* steps, const int32_t* step_index,
+                                  int32_t eta_on, uint64_t seed, const float* noise, void* stream) {
+  DN_CHECK_ARG(x && eps && coef && steps && step_index, "dn_ddim_sched_step: null argument");
+  DN_CHECK_ARG(n > 0 && n % 4 == 0, "dn_ddim_sched_step: n=%lld must be a positive multiple of 4", (long long)n);
+  DN_CHECK_ARG((((uintptr_t)x | (uintptr_t)eps | (uintptr_t)noise) & 15) == 0, "dn_ddim_sched_step: x, eps and noise must be 16-byte aligned");
+  DN_CHECK_ARG(eta_on || !noise, "dn_ddim_sched_step: injected noise needs eta_on (eta = 0 draws none)");
+  // (row stride 0: `noise` is this step's row whatever the step index)
+  return dn_ddim_sched_step_launch(x, eps, 0, n, coef, steps, step_index, eta_on != 0, noise, 0, eta_on ? seed : 0, nullptr, 0, (hipStream_t)stream);
+}
+
+extern "C" int dn_ddim_sched_step_keyed(float* x, const float* eps, const uint64_t* keys, int32_t B, int32_t T, int32_t Z, const float* coef,
+                                        const int32_t* steps, const int32_t* step_index, void* stream) {
+  DN_CHECK_ARG(x && eps && keys && coef && steps && step_index, "dn_ddim_sched_step_keyed: null argument");
+  DN_CHECK_ARG(B > 0 && T > 0 && Z > 0 && Z % 4 == 0, "dn_ddim_sched_step_keyed: B=%d T=%d must be positive, Z=%d a positive multiple of 4", B, T,
+               Z);
+  DN_CHECK_ARG((((uintptr_t)x | (uintptr_t)eps) & 15) == 0 && ((uintptr_t)keys & 7) == 0,
+               "dn_ddim_sched_step_keyed: x and eps must be 16-byte, keys 8-byte aligned");
+  const int64_t row_quads = (int64_t)T * (Z >> 2);
+  return dn_ddim_sched_step_launch(x, eps, 0, (int64_t)B * row_quads * 4, coef, steps, step_index, 1, nullptr, 0, 0, keys, row_quads,
+                                   (hipStream_t)stream);
+}
+
 // (engine.hip: the update of dn_guided_ddim_loop; n_elem = B*T*latent of the B-row latent; both / xin hold 2 n_elem floats when guided)
+// keys != NULL (dn_guided_ddim_loop_keyed; eta on): the B keys, row_quads = T Z / 4 quads per utterance; noise and seed are not read
 int dn_guided_sched_step_launch(float* x, float* xin, const float* both, int64_t n_elem, int guided, float scale, const float* coef,
                                 const int32_t* steps, const int32_t* counter, int eta_on, const float* noise, int64_t noise_row, uint64_t seed,
-                                hipStream_t stream) {
+                                const uint64_t* keys, int64_t row_quads, hipStream_t stream) {
   DN_CHECK_ARG(n_elem % 4 == 0 && n_elem > 0, "dn_guided_ddim_loop: the latent width must be a multiple of 4");
   const dim3 grid(ew_grid(n_elem >> 2)), block(256);
+  const SchedNoise src = keys ? SchedNoise{nullptr, 0, 0, keys, row_quads} : SchedNoise{noise, noise_row, seed, nullptr, 0};
 #define DN_GUIDED_STEP(G, E) \
-  hipLaunchKernelGGL((guided_sched_step_kernel<G, E>), grid, block, 0, stream, x, xin, both, n_elem >> 2, scale, coef, steps, counter, noise, noise_row, seed)
-  if (guided) {
+  hipLaunchKernelGGL((guided_sched_step_kernel<G, E, false>), grid, block, 0, stream, x, xin, both, n_elem >> 2, scale, coef, steps, counter, src)
+  if (keys) {
+    if (guided)
+      hipLaunchKernelGGL((guided_sched_step_kernel<true, true, true>), grid, block, 0, stream, x, xin, both, n_elem >> 2, scale, coef, steps, counter, src);
+    else
+      hipLaunchKernelGGL((guided_sched_step_kernel<false, true, true>), grid, block, 0, stream, x, xin, both, n_elem >> 2, scale, coef, steps, counter, src);
+  } else if (guided) {
     if (eta_on) DN_GUIDED_STEP(true, true); else DN_GUIDED_STEP(true, false);
   } else {
     if (eta_on) DN_GUIDED_STEP(false, true); else DN_GUIDED_STEP(false, false);

@@ -377,6 +377,19 @@ class EpsEngine(_Engine):
         assert nz.shape == shape, (nz.shape, shape)
         return nz
 
+    def _loop_keys(self, keys, B: int, who: str, noise=None, seed: int = 0, eta: Optional[float] = None):
+        """`keys` of a keyed chain: int64 [B] (the uint64 bit patterns of sharding.utterance_keys) -> the same on the device.  A
+        tensor already there is passed as it is: the loops' graph caches are keyed by its address."""
+        if keys is None:
+            return None
+        if noise is not None or int(seed) != 0:
+            raise ValueError(f"{who}: keys draw the per-step noise: neither injected noise nor a non-zero seed can be given with them")
+        if eta is not None and not eta > 0:
+            raise ValueError(f"{who}: keys need eta > 0 (eta = 0 draws none)")
+        if not (torch.is_tensor(keys) and keys.dtype == torch.int64 and tuple(keys.shape) == (B,)):
+            raise ValueError(f"{who}: keys must be a torch.int64 tensor [{B}] (the uint64 bit patterns, one key per utterance)")
+        return self._on_device(keys, torch.int64, contiguous=True)
+
     def ddim_loop(self, x: torch.Tensor, lengths: torch.Tensor, start_step: int, coef: torch.Tensor,
                   use_graph: bool = True, max_evals: int = 0, split: bool = True, keep_table: bool = False) -> int:
         """In-place DDIM eta=0 chain on x [B,T,z] fp32 (reference latent_module.py:1411-1445).
@@ -396,19 +409,27 @@ class EpsEngine(_Engine):
 
     def ddpm_loop(self, x: torch.Tensor, lengths: torch.Tensor, start_step: int, table: torch.Tensor, seed: int = 0,
                   noise: Optional[torch.Tensor] = None, clip_denoised: bool = False, use_graph: bool = True, max_evals: int = 0,
-                  split: bool = True, keep_table: bool = False) -> int:
+                  split: bool = True, keep_table: bool = False, keys: Optional[torch.Tensor] = None) -> int:
         """In-place ancestral (DDPM) chain on x [B,T,z] fp32: GaussianDiffusion.p_sample (reference diffusion/gaussian_diffusion.py:
         376-417) for t = start_step-1 .. 0, x given at index start_step-1 (x_T ~ N(0, I) with start_step = timesteps: BASELINE
         configs[2] read literally).  table: fp32 [timesteps, 12] from `scheduler.gaussian_table`.  The noise of a step is drawn
         in the update kernel (Philox keyed by `seed` and the step) or injected: noise [start_step, B, T, z], row k for
-        t = start_step-1-k.  Returns the number of model evaluations."""
+        t = start_step-1-k.  `keys` (int64 [B], excludes `noise` and a non-zero `seed`): the noise of row b at step t is
+        `ops.randn_keyed`'s stream 2 + t of keys[b] (dn_ddpm_loop_keyed) -- it depends on the key, the timestep, the frame and the
+        channel only, and both half batches draw it, so the keyed chain is split-invariant.  Returns the number of model evaluations."""
         B, T, z = self._loop_x(x)
         assert table.dtype == torch.float32 and table.is_contiguous() and table.device == self.device and table.shape[1] == 12
         l32 = self._on_device(lengths, torch.int32)
         nz = self._loop_noise(noise, (start_step, B, T, z))
-        self._keep = (l32, table, nz)
+        k64 = self._loop_keys(keys, B, "ddpm_loop", noise, seed)
+        self._keep = (l32, table, nz, k64)
         wp, wn = self._aligned_workspace(self.lib.dn_ddim_workspace_bytes(self.handle, B, T, start_step))
         with torch.cuda.device(self.device):
+            if k64 is not None:
+                return _lib.check(self.lib.dn_ddpm_loop_keyed(self.handle, x.data_ptr(), l32.data_ptr(), B, T, start_step, max_evals,
+                                                              table.data_ptr(), table.shape[0], int(clip_denoised), k64.data_ptr(),
+                                                              _loop_flags(use_graph, split, keep_table), wp, wn,
+                                                              _lib.current_stream()), "dn_ddpm_loop_keyed")
             return _lib.check(self.lib.dn_ddpm_loop(self.handle, x.data_ptr(), l32.data_ptr(), B, T, start_step, max_evals, table.data_ptr(),
                                                     table.shape[0], int(clip_denoised), int(seed) & (2 ** 64 - 1), _lib.ptr(nz),
                                                     _loop_flags(use_graph, split, keep_table), wp, wn,
@@ -416,20 +437,29 @@ class EpsEngine(_Engine):
 
     def ddim_schedule_loop(self, x: torch.Tensor, lengths: torch.Tensor, steps: torch.Tensor, coef: torch.Tensor, eta: float = 0.0,
                            seed: int = 0, noise: Optional[torch.Tensor] = None, use_graph: bool = True, split: bool = True,
-                           timesteps: Optional[int] = None) -> int:
+                           timesteps: Optional[int] = None, keys: Optional[torch.Tensor] = None) -> int:
         """In-place DDIM chain on x [B,T,z] fp32 over a timestep schedule (dn_ddim_sched_loop): `steps` int32 [n] strictly descending,
         `coef` fp32 [n, 5], both from `scheduler.ddim_schedule` (built with the same `eta`).  One evaluation per step; the
         conditioning table and the workspace have n rows.  eta > 0 adds sigma z after every update but one at timestep 0: z drawn
         in the update kernel (Philox keyed by `seed`, the step index and the element's index in the whole batch -- eager, graph and
         split chains agree bit for bit) or injected, noise [n, B, T, z], row i for update i.  `timesteps`: the length of the noise
-        schedule the steps index (the entry refuses a list longer than that).  Returns the number of evaluations."""
+        schedule the steps index (the entry refuses a list longer than that).  `keys` (int64 [B], needs eta > 0, excludes `noise`
+        and a non-zero `seed`): z of row b at update i is `ops.randn_keyed`'s stream 2 + steps[i] of keys[b], drawn in the kernel
+        (dn_ddim_sched_loop_keyed) -- it depends on the key, the timestep, the frame and the channel only, not on the batch.
+        Returns the number of evaluations."""
         B, T, z = self._loop_x(x)
         n = self._loop_schedule(steps, coef, _lib.DDIM_SCHED_COLS)
         l32 = self._on_device(lengths, torch.int32)
         nz = self._loop_noise(noise, (n, B, T, z), "ddim_schedule_loop", eta)
-        self._keep = (l32, steps, coef, nz)
+        k64 = self._loop_keys(keys, B, "ddim_schedule_loop", noise, seed, eta)
+        self._keep = (l32, steps, coef, nz, k64)
         wp, wn = self._aligned_workspace(self.lib.dn_ddim_sched_workspace_bytes(self.handle, B, T, n))
         with torch.cuda.device(self.device):
+            if k64 is not None:
+                return _lib.check(self.lib.dn_ddim_sched_loop_keyed(self.handle, x.data_ptr(), l32.data_ptr(), B, T, steps.data_ptr(),
+                                                                    coef.data_ptr(), n, n if timesteps is None else int(timesteps),
+                                                                    k64.data_ptr(), _loop_flags(use_graph, split), wp, wn,
+                                                                    _lib.current_stream()), "dn_ddim_sched_loop_keyed")
             return _lib.check(self.lib.dn_ddim_sched_loop(self.handle, x.data_ptr(), l32.data_ptr(), B, T, steps.data_ptr(), coef.data_ptr(), n,
                                                           n if timesteps is None else int(timesteps), int(eta > 0), int(seed) & (2 ** 64 - 1), _lib.ptr(nz),
                                                           _loop_flags(use_graph, split), wp, wn, _lib.current_stream()),
@@ -477,13 +507,14 @@ class EpsEngine(_Engine):
 
     def guided_ddim_schedule_loop(self, x: torch.Tensor, lengths, prompt, prompt_lengths, steps: torch.Tensor, coef: torch.Tensor,
                                   cond_scale: float = 1.0, eta: float = 0.0, seed: int = 0, noise: Optional[torch.Tensor] = None,
-                                  use_graph: bool = True, timesteps: Optional[int] = None) -> int:
+                                  use_graph: bool = True, timesteps: Optional[int] = None, keys: Optional[torch.Tensor] = None) -> int:
         """In-place prompted, guided DDIM chain on x [B,T,z] fp32 over a timestep schedule (dn_guided_ddim_loop): `ddim_schedule_loop`'s
         chain -- `steps` int32 [n] strictly descending and `coef` fp32 [n, 5] from `scheduler.ddim_schedule` (built with the same
         `eta`), `seed`, injected `noise` [n, B, T, z], `timesteps` with its meaning -- with the guided prediction of
         `forward_with_cond_scale` (one pass over 2B rows, or B rows at scale 1).  The whole loop runs behind the C entry: time table
         of n rows, prompt-only work in the first step, one fused combination + update kernel per step, hipGraph replay.  On the
-        every-timestep schedule at eta = 0 it is `guided_ddim_chain` bit for bit.  Returns the number of evaluations."""
+        every-timestep schedule at eta = 0 it is `guided_ddim_chain` bit for bit.  `keys` as `ddim_schedule_loop` takes them
+        (dn_guided_ddim_loop_keyed).  Returns the number of evaluations."""
         B, T, z = self._loop_x(x)
         n = self._loop_schedule(steps, coef, _lib.DDIM_SCHED_COLS)
         l32 = self._on_device(lengths, torch.int32)
@@ -492,9 +523,16 @@ class EpsEngine(_Engine):
         assert p32.dim() == 3 and p32.shape[0] == B and p32.shape[2] == self.cfg.dim_prompt and l32.shape == (B,) and pl32.shape == (B,)
         Tp = int(p32.shape[1])
         nz = self._loop_noise(noise, (n, B, T, z), "guided_ddim_schedule_loop", eta)
-        self._keep = (l32, pl32, p32, steps, coef, nz)
+        k64 = self._loop_keys(keys, B, "guided_ddim_schedule_loop", noise, seed, eta)
+        self._keep = (l32, pl32, p32, steps, coef, nz, k64)
         wp, wn = self._aligned_workspace(self.lib.dn_guided_ddim_workspace_bytes(self.handle, B, T, Tp, n, int(float(cond_scale) != 1.0)))
         with torch.cuda.device(self.device):
+            if k64 is not None:
+                return _lib.check(self.lib.dn_guided_ddim_loop_keyed(self.handle, x.data_ptr(), l32.data_ptr(), p32.data_ptr(), pl32.data_ptr(), B,
+                                                                     T, Tp, float(cond_scale), steps.data_ptr(), coef.data_ptr(), n,
+                                                                     n if timesteps is None else int(timesteps), k64.data_ptr(),
+                                                                     _loop_flags(use_graph), wp, wn, _lib.current_stream()),
+                                  "dn_guided_ddim_loop_keyed")
             return _lib.check(self.lib.dn_guided_ddim_loop(self.handle, x.data_ptr(), l32.data_ptr(), p32.data_ptr(), pl32.data_ptr(), B, T, Tp,
                                                            float(cond_scale), steps.data_ptr(), coef.data_ptr(), n,
                                                            n if timesteps is None else int(timesteps), int(eta > 0), int(seed) & (2 ** 64 - 1),

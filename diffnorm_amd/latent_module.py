@@ -502,6 +502,19 @@ def _chain_start(self, tgt_feature, input_mask, t_index, post_noise, start_noise
     return dev, B, input_mask, lengths, x
 
 
+def _keyed_steps(who, dev, keyed_steps, noise_keys, step_noise, seed, draws=True):
+    """The `keyed_steps=` switch of the three samplers -> the keyword the engine's loop takes on top of its earlier ones: `keys`, the
+    keys the chain's update kernels draw from (on the device); or nothing: unset, or a chain that draws nothing (`draws` false: DDIM
+    at eta = 0, the DPM solver), which is then called exactly as before."""
+    if not keyed_steps:
+        return {}
+    if noise_keys is None:
+        raise ValueError(f"{who}: keyed_steps draws the per-step noise from the utterances' keys: it needs noise_keys")
+    if step_noise is not None or int(seed) != 0:
+        raise ValueError(f"{who}: keyed_steps draws the per-step noise from noise_keys: step_noise / a non-zero seed cannot be given with it")
+    return {"keys": noise_keys.to(dev).contiguous()} if draws else {}
+
+
 class LatentDiscreteModel(nn.Module):
     """reference latent_module.py:1300-1613.  `speech_decoder` is the fairseq model whose `.encoder` is the VAE."""
 
@@ -578,13 +591,17 @@ class LatentDiscreteModel(nn.Module):
     @torch.no_grad()
     def ddim_sample(self, tgt_feature, prompt=None, prompt_mask=None, input_mask=None, cond_scale=1., ref_units=None,
                     start_step=50, post_noise=None, start_noise=None, use_graph=True, sampling_steps=None, timestep_schedule=None,
-                    eta=0.0, seed=0, step_noise=None, solver=None, solver_order=2, noise_keys=None):
+                    eta=0.0, seed=0, step_noise=None, solver=None, solver_order=2, noise_keys=None, keyed_steps=False):
         """-> (list of unit tensors, match, total, recon_feature), as upstream (:1385-1471).
 
         `noise_keys` (int64 [B], sharding.utterance_keys): the posterior and the start noise of row b are drawn on the device from
         key b alone (dn_chain_start), so the result for an utterance does not depend on the batch it sits in; it excludes
-        `post_noise` / `start_noise`.  The per-step noise of `eta` > 0 stays indexed by position in the batch (keyed per-step noise
-        is not implemented): with eta > 0 results still depend on batch composition.
+        `post_noise` / `start_noise`.  On its own it leaves the per-step noise of `eta` > 0 where it was -- drawn from `seed`,
+        indexed by position in the batch, so those results still depend on batch composition.  `keyed_steps=True` (needs
+        `noise_keys`; excludes `step_noise` and a non-zero `seed`) draws that noise from the keys too: the update that leaves
+        timestep t adds stream 2 + t of the utterance's key (dn_ddim_sched_loop_keyed; `ops.randn_keyed` materialises it), which
+        depends on the key, the timestep, the frame and the channel only, so a stochastic chain is batch-independent as well.
+        With eta = 0 or a solver there is nothing to draw and the flag changes nothing.
 
         `sampling_steps` = N runs the chain on N of the timesteps start_step-1 .. 1 (scheduler.ddim_steps: uniformly spread, N =
         start_step-1 is every timestep), `timestep_schedule` on an explicit strictly descending list; `eta` > 0 adds the DDIM noise
@@ -610,6 +627,7 @@ class LatentDiscreteModel(nn.Module):
             raise ValueError("ddim_sample: sampling_steps / timestep_schedule / eta cover the unconditional model (the prompted, "
                              "guided chain walks every timestep)")
         coef = self._tables()[0]
+        step_keys = _keyed_steps("ddim_sample", self.device, keyed_steps, noise_keys, step_noise, seed, draws=solver is None and eta != 0.0)
         dev, B, input_mask, lengths, x = _chain_start(self, tgt_feature, input_mask, start_step, post_noise, start_noise, noise_keys)
         if self.use_cond:
             # prompted chain (f3): the reference's loop drops the prompt it was given (:1413-1417 -- with use_cond it cannot run at
@@ -625,7 +643,7 @@ class LatentDiscreteModel(nn.Module):
         elif scheduled:
             steps, rows = self.scheduler.ddim_schedule(start_step, sampling_steps, timestep_schedule, eta=eta, device=dev)
             self.model.engine().ddim_schedule_loop(x, lengths, steps, rows, eta=eta, seed=seed, noise=step_noise, use_graph=use_graph,
-                                                   timesteps=self.timesteps)
+                                                   timesteps=self.timesteps, **step_keys)
         else:
             self.model.engine().ddim_loop(x, lengths, start_step, coef, use_graph=use_graph)    # (:1411-1445)
         recon, _, units = self.speech_decoder.engine().decode(x, lengths, want_logits=False)     # (:1448-1451)
@@ -641,7 +659,7 @@ class LatentDiscreteModel(nn.Module):
     @torch.no_grad()
     def prompted_ddim_sample(self, tgt_feature, prompt, prompt_mask, input_mask=None, cond_scale=1., ref_units=None, start_step=50,
                              sampling_steps=None, timestep_schedule=None, eta=0.0, seed=0, step_noise=None, post_noise=None,
-                             start_noise=None, use_graph=True, solver=None, solver_order=2, noise_keys=None):
+                             start_noise=None, use_graph=True, solver=None, solver_order=2, noise_keys=None, keyed_steps=False):
         """`ddim_sample` for the prompted model (use_cond) over a timestep schedule -> the same (list of unit tensors, match, total,
         recon_feature).  Encode and q_sample as `ddim_sample`; the chain is the device loop dn_guided_ddim_loop
         (EpsEngine.guided_ddim_schedule_loop): the guided prediction forward_with_cond_scale (:813-826) at every step of the schedule
@@ -654,8 +672,9 @@ class LatentDiscreteModel(nn.Module):
         EpsEngine.guided_dpm_schedule_loop, dn_guided_dpm_loop; `solver_order` 1 or 2) in place of DDIM's, on the same guided
         prediction.  It is deterministic: `eta` and `step_noise` do not apply.  `solver=None` is the code above, unchanged.
 
-        `noise_keys` as `ddim_sample`: keyed posterior and start noise; the per-step noise of `eta` > 0 stays indexed by position
-        in the batch."""
+        `noise_keys` and `keyed_steps` as `ddim_sample`: keyed posterior and start noise, and with `keyed_steps=True` the per-step
+        noise of `eta` > 0 from the same keys (dn_guided_ddim_loop_keyed: stream 2 + t of the utterance's key at the update leaving
+        timestep t); without it that noise is drawn from `seed`, indexed by position in the batch."""
         if solver is not None:
             if solver != "dpmpp_2m":
                 raise ValueError(f"prompted_ddim_sample: unknown solver {solver!r} (None or 'dpmpp_2m')")
@@ -671,6 +690,8 @@ class LatentDiscreteModel(nn.Module):
             steps, rows = self.scheduler.dpm_schedule(start_step, sampling_steps, timestep_schedule, order=solver_order)  # (validates, on the host)
         else:
             steps, rows = self.scheduler.ddim_schedule(start_step, sampling_steps, timestep_schedule, eta=eta)  # (validates, on the host)
+        step_keys = _keyed_steps("prompted_ddim_sample", self.device, keyed_steps, noise_keys, step_noise, seed,
+                                 draws=solver is None and eta != 0.0)
         dev, B, input_mask, lengths, x = _chain_start(self, tgt_feature, input_mask, start_step, post_noise, start_noise, noise_keys)
         plens = _mask_to_lengths(prompt_mask.to(dev))
         if solver is not None:
@@ -678,7 +699,8 @@ class LatentDiscreteModel(nn.Module):
                                                          use_graph=use_graph, timesteps=self.timesteps)
         else:
             self.model.engine().guided_ddim_schedule_loop(x, lengths, prompt, plens, steps.to(dev), rows.to(dev), cond_scale=cond_scale, eta=eta,
-                                                          seed=seed, noise=step_noise, use_graph=use_graph, timesteps=self.timesteps)
+                                                          seed=seed, noise=step_noise, use_graph=use_graph, timesteps=self.timesteps,
+                                                          **step_keys)
         recon, _, units = self.speech_decoder.engine().decode(x, lengths, want_logits=False)     # (:1448-1451)
         pred_units = units.long()
         match = (pred_units[input_mask] == ref_units.to(dev)[input_mask]).sum().item() if ref_units is not None else 0
@@ -687,21 +709,25 @@ class LatentDiscreteModel(nn.Module):
 
     @torch.no_grad()
     def ddpm_sample(self, tgt_feature, input_mask=None, ref_units=None, start_step=50, post_noise=None, start_noise=None, seed=0,
-                    step_noise=None, fixed_large=False, clip_denoised=False, use_graph=True, noise_keys=None):
+                    step_noise=None, fixed_large=False, clip_denoised=False, use_graph=True, noise_keys=None, keyed_steps=False):
         """The chain of `ddim_sample` with the ancestral (DDPM) update -- GaussianDiffusion.p_sample (reference diffusion/
         gaussian_diffusion.py:376-417) on this model's cosine schedule: encode, noise to index start_step-1 (q_sample), then
         t = start_step-1 .. 0 on the device (dn_ddpm_loop; the per-step noise drawn in the kernel from `seed`, or `step_noise`
         [start_step, B, T, z] injected), decode, units.  BASELINE configs[2] read literally; the reference's LatentDiscreteModel
         itself only has the DDIM sampler.  -> (list of unit tensors, match, total, recon_feature).
 
-        `noise_keys` as `ddim_sample`: keyed posterior and start noise only.  The per-step noise of every ancestral update stays
-        indexed by position in the batch, so this sampler's results depend on batch composition with or without keys."""
+        `noise_keys` as `ddim_sample`: keyed posterior and start noise.  On its own the per-step noise of every ancestral update
+        stays drawn from `seed`, indexed by position in the batch (and by half batch), so the results depend on batch composition.
+        `keyed_steps=True` (needs `noise_keys`; excludes `step_noise` and a non-zero `seed`) draws it from the keys: the update that
+        leaves timestep t adds stream 2 + t of the utterance's key (dn_ddpm_loop_keyed), in both half batches, so an utterance's
+        result does not depend on the batch or on how the batch is split."""
+        step_keys = _keyed_steps("ddpm_sample", self.device, keyed_steps, noise_keys, step_noise, seed)
         dev, B, input_mask, lengths, x = _chain_start(self, tgt_feature, input_mask, start_step - 1, post_noise, start_noise, noise_keys)
         key = ("gd", bool(fixed_large))
         if getattr(self, "_gd_table", (None,))[0] != key or self._gd_table[1].device != dev:
             self._gd_table = (key, self.scheduler.gaussian_table(dev, fixed_large=fixed_large))
         self.model.engine().ddpm_loop(x, lengths, start_step, self._gd_table[1], seed=seed, noise=step_noise, clip_denoised=clip_denoised,
-                                      use_graph=use_graph)
+                                      use_graph=use_graph, **step_keys)
         recon, _, units = self.speech_decoder.engine().decode(x, lengths, want_logits=False)
         pred_units = units.long()
         match = (pred_units[input_mask] == ref_units.to(dev)[input_mask]).sum().item() if ref_units is not None else 0

@@ -76,7 +76,7 @@ def tsv_line(it: Utterance, pred_units: Sequence[int]) -> str:
 def normalize(ddim_sample: Callable, utterances: Sequence[Utterance], start_step: int = 50, batch_size: int = 100,
               device="cuda:0", group=None, sampling_steps: Optional[int] = None, eta: float = 0.0, seed: int = 0,
               solver: Optional[str] = None, noise_seed: Optional[int] = None, max_tokens: Optional[int] = None,
-              max_sentences: Optional[int] = None, pad_multiple: int = 1) -> Optional[List[str]]:
+              max_sentences: Optional[int] = None, pad_multiple: int = 1, keyed_steps: bool = False) -> Optional[List[str]]:
     """Runs `ddim_sample(feat, input_mask=..., ref_units=..., start_step=...)` (LatentDiscreteModel.ddim_sample) over this
     rank's batches and gathers the TSV lines of all ranks in utterance order (every rank returns the full list).
     `sampling_steps` (evaluations per chain instead of start_step-1), `eta`, `seed` and `solver` ("dpmpp_2m": the second-order
@@ -87,10 +87,13 @@ def normalize(ddim_sample: Callable, utterances: Sequence[Utterance], start_step
     it is in, on torch's generators or on the number of ranks.  `max_tokens` (needs `noise_seed`): batches are formed by a frame
     budget instead of `batch_size` consecutive utterances -- sharding.plan_batches over the de-duplicated lengths (length-sorted, at
     most `max_sentences` utterances, T rounded up to `pad_multiple`), spread over the ranks by cost (sharding.balanced_batches).
-    `pad_multiple` > 1 also rounds the consecutive batches' T up.  With the four unset this is the reference's batching and noise."""
-    if noise_seed is not None or max_tokens is not None or max_sentences is not None or pad_multiple != 1:
+    `pad_multiple` > 1 also rounds the consecutive batches' T up.  `keyed_steps` (needs `noise_seed`): a stochastic chain
+    (`eta` != 0) draws its per-step noise from the utterance's key as well (the sampler's `keyed_steps=True`; `seed` is not used),
+    so it keeps the same promises; without it `noise_seed` refuses `eta` != 0.  With the five unset this is the reference's batching
+    and noise."""
+    if noise_seed is not None or max_tokens is not None or max_sentences is not None or pad_multiple != 1 or keyed_steps:
         return _normalize_keyed(ddim_sample, utterances, start_step, batch_size, device, group, sampling_steps, eta, solver,
-                                noise_seed, max_tokens, max_sentences, pad_multiple)
+                                noise_seed, max_tokens, max_sentences, pad_multiple, keyed_steps)
     rank, world = sharding.rank_world(group)
     # A run must give the same results on any number of ranks (and whatever sizes the last batches have).  The 2-byte / f32
     # contractions' fast K order (taps of a causal conv innermost, one staged copy of the rows, on the two 256-row tiles) sums in a
@@ -126,14 +129,17 @@ def normalize(ddim_sample: Callable, utterances: Sequence[Utterance], start_step
 
 
 def _normalize_keyed(ddim_sample, utterances, start_step, batch_size, device, group, sampling_steps, eta, solver, noise_seed,
-                     max_tokens, max_sentences, pad_multiple) -> List[str]:
+                     max_tokens, max_sentences, pad_multiple, keyed_steps=False) -> List[str]:
     """normalize() with per-utterance noise keys and, under `max_tokens`, frame-budget batches (see normalize)."""
+    if noise_seed is None and keyed_steps:
+        raise ValueError("normalize: keyed_steps draws the per-step noise from the utterances' keys: set noise_seed")
     if noise_seed is None:
         raise ValueError("normalize: max_tokens / max_sentences / pad_multiple re-form the batches, which changes the results unless "
                          "every utterance has its own noise: set noise_seed")
-    if eta != 0.0:
-        raise ValueError("normalize: noise_seed keys the posterior and chain-start noise only; the per-step noise of eta != 0 is "
-                         "indexed by batch position, so the results would still depend on the batches")
+    if eta != 0.0 and not keyed_steps:
+        raise ValueError("normalize: noise_seed alone keys the posterior and chain-start noise; the per-step noise of eta != 0 would "
+                         "stay indexed by batch position, so the results would still depend on the batches: set keyed_steps=True to "
+                         "draw it from the utterances' keys too")
     if max_tokens is None and max_sentences is not None:
         raise ValueError("normalize: max_sentences caps the batches max_tokens forms; without max_tokens use batch_size")
     from . import _lib
@@ -154,6 +160,10 @@ def _normalize_keyed(ddim_sample, utterances, start_step, batch_size, device, gr
         extra["sampling_steps"] = sampling_steps
     if solver is not None:
         extra["solver"] = solver
+    if eta != 0.0:
+        extra["eta"] = eta
+    if keyed_steps:
+        extra["keyed_steps"] = True
     chosen = _lib.get_option("taps_inner")
     local = []
     with _lib.option("taps_inner", 2 if chosen is None else chosen):  # routing by shape, as normalize()

@@ -213,7 +213,8 @@ def _keys(keys, device):
 
 def randn_keyed(keys, T: int, Z: int, stream_id: int, device="cuda:0"):
     """-> fp32 [B, T, Z]: row b is the noise stream of keys[b] (dn_randn_keyed: element (t, c) depends on the key, t and c only).
-    stream_id 0 = the posterior noise, 1 = the chain-start noise of `chain_start`."""
+    stream_id 0 = the posterior noise, 1 = the chain-start noise of `chain_start`, 2 + t = the noise of the sampler update that
+    leaves timestep t (what a `keyed_steps` chain draws in its update kernels)."""
     lib = _lib.load()
     keys = _keys(keys, device)
     out = torch.empty(keys.numel(), T, Z, dtype=torch.float32, device=keys.device)
@@ -239,6 +240,47 @@ def chain_start(params, keys, coef_a, coef_b, t_i32, want_z=False):
         _lib.check(lib.dn_chain_start(params.data_ptr(), params.stride(1), keys.data_ptr(), B, T, Z, coef_a.data_ptr(), coef_b.data_ptr(),
                                       t_i32.data_ptr(), x.data_ptr(), _lib.ptr(z), _stream()), "dn_chain_start")
     return (x, z) if want_z else x
+
+
+def _sched_step_args(who, x, eps, coef, steps, step_index):
+    n = int(steps.numel())
+    for name, t, dtype in (("x", x, torch.float32), ("eps", eps, torch.float32), ("coef", coef, torch.float32), ("steps", steps, torch.int32),
+                           ("step_index", step_index, torch.int32)):
+        if not (torch.is_tensor(t) and t.dtype == dtype and t.is_contiguous() and t.device == x.device and t.is_cuda):
+            raise ValueError(f"{who}: {name} must be a contiguous {dtype} tensor on x's device")
+    if eps.shape != x.shape or tuple(coef.shape) != (n, _lib.DDIM_SCHED_COLS) or steps.dim() != 1 or n < 1 or step_index.numel() != 1:
+        raise ValueError(f"{who}: eps like x, steps [n], coef [n, {_lib.DDIM_SCHED_COLS}] and a one-element step_index are needed")
+
+
+def ddim_sched_step(x, eps, coef, steps, step_index, eta_on: bool = True, seed: int = 0, noise=None):
+    """One scheduled DDIM update in place on x (dn_ddim_sched_step: the update of `EpsEngine.ddim_schedule_loop` alone): row
+    step_index[0] (device int32) of `steps` int32 [n] / `coef` fp32 [n, 5] from `scheduler.ddim_schedule`; with eta_on, z is
+    drawn from `seed` or injected as `noise` (like x: the noise of this step).  -> x."""
+    _sched_step_args("ddim_sched_step", x, eps, coef, steps, step_index)
+    if noise is not None and not (noise.dtype == torch.float32 and noise.is_contiguous() and noise.device == x.device and noise.shape == x.shape):
+        raise ValueError("ddim_sched_step: noise must be a contiguous fp32 tensor like x")
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dn_ddim_sched_step(x.data_ptr(), eps.data_ptr(), x.numel(), coef.data_ptr(), steps.data_ptr(),
+                                                  step_index.data_ptr(), int(bool(eta_on)), int(seed) & (2 ** 64 - 1), _lib.ptr(noise),
+                                                  _stream()), "dn_ddim_sched_step")
+    return x
+
+
+def ddim_sched_step_keyed(x, eps, keys, coef, steps, step_index):
+    """One scheduled DDIM update with eta on and keyed noise, in place on x fp32 [B, T, Z] (dn_ddim_sched_step_keyed): row
+    step_index[0] (device int32) of `steps` / `coef` as `ddim_sched_step`; z of row b is `randn_keyed(keys, T, Z, 2 + steps[i])[b]`,
+    drawn in the kernel (none at timestep 0).  For host-stepped chains whose noise must not depend on the batch.  -> x."""
+    _sched_step_args("ddim_sched_step_keyed", x, eps, coef, steps, step_index)
+    if x.dim() != 3:
+        raise ValueError("ddim_sched_step_keyed: x must be [B, T, Z]")
+    B, T, Z = x.shape
+    keys = _keys(keys, x.device)
+    if keys.numel() != B:
+        raise ValueError(f"ddim_sched_step_keyed: {keys.numel()} keys for a batch of {B}")
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dn_ddim_sched_step_keyed(x.data_ptr(), eps.data_ptr(), keys.data_ptr(), B, T, Z, coef.data_ptr(), steps.data_ptr(),
+                                                        step_index.data_ptr(), _stream()), "dn_ddim_sched_step_keyed")
+    return x
 
 
 def convert_rows(src, dst, C_):

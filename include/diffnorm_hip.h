@@ -321,7 +321,8 @@ int dn_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream
  * fp32 [B, T, Z] tensor is normal c & 3 of the Philox4x32-10 call with key (keys[b] low, keys[b] high) and counter (q low, q high,
  * stream_id, 0x53545254), q = t * (Z / 4) + c / 4 as a 64-bit value; Box-Muller as dn_randn.  The draw depends on the key, the
  * frame and the channel only.  stream_id 0: posterior noise (distributions.py:24-41), 1: chain-start noise
- * (latent_module.py:1405-1409).  Z a multiple of 4, out 16-byte aligned.                                              */
+ * (latent_module.py:1405-1409), 2 + t: the noise of the sampler update that leaves timestep t (the *_keyed loops below draw it in
+ * their update kernels; this entry materialises the same numbers).  Z a multiple of 4, out 16-byte aligned.            */
 int dn_randn_keyed(float* out, const uint64_t* keys, int32_t B, int32_t T, int32_t Z, uint32_t stream_id, void* stream);
 
 /* Posterior sample + q_sample in one pass on those draws (distributions.py:24-41, latent_module.py:1405-1409): params fp32
@@ -693,6 +694,17 @@ int dn_ddpm_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t 
                  const float* table, int32_t timesteps, int32_t clip_denoised, uint64_t seed, const float* noise, int32_t flags,
                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* dn_ddpm_loop (diffusion/gaussian_diffusion.py:376-417, 459-511) with keyed per-step noise: z of element (b, frame, channel) at
+ * step t is dn_randn_keyed's stream 2 + t under keys[b] (device uint64 [B], 8-byte aligned) -- it depends on the key, the timestep,
+ * the frame and the channel only, not on the row, B, the padded T, graph or eager, or the half batch: BOTH halves of a
+ * DN_LOOP_SPLIT2 chain draw under the keys, so, unlike the seed-drawn chain, the keyed one is split-invariant.  At t = 0 no draw
+ * is applied.  The captured step bakes in the ADDRESS of keys (part of the graph key, with seed 0), never their contents.  Null or
+ * misaligned keys and a latent width that is no multiple of 4 are refused before anything is written; everything else as
+ * dn_ddpm_loop.                                                                                                              */
+int dn_ddpm_loop_keyed(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, int32_t start_step, int32_t max_evals,
+                       const float* table, int32_t timesteps, int32_t clip_denoised, const uint64_t* keys, int32_t flags,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* A DDIM chain over a timestep schedule: strided steps and eta (GaussianDiffusion.ddim_sample, diffusion/gaussian_diffusion.py:
  * 513-560, on a sub-sequence of the timesteps as SpacedDiffusion / space_timesteps select one, diffusion/respace.py:12-115; entered
  * like LatentDiscreteModel.ddim_sample's loop, latent_module.py:1405-1445).  The chain is a strictly descending list of evaluation
@@ -717,6 +729,25 @@ int dn_ddim_sched_check(const int32_t* steps_host, int32_t n_steps, int32_t time
 int dn_ddim_sched_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, const int32_t* steps, const float* coef,
                        int32_t n_steps, int32_t timesteps, int32_t eta_on, uint64_t seed, const float* noise, int32_t flags,
                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* dn_ddim_sched_loop (diffusion/gaussian_diffusion.py:513-560, diffusion/respace.py:12-115, latent_module.py:1405-1445) with eta on
+ * and keyed per-step noise: z of element (b, frame, channel) at update i is dn_randn_keyed's stream 2 + e_i under keys[b] (device
+ * uint64 [B], 8-byte aligned).  The stream is the TIMESTEP e_i = steps[i], not the index i: the draw depends on (key, timestep,
+ * frame, channel) only -- not on the row, B, the padded T, the half batch, the schedule's other members, graph or eager.  At
+ * e_i == 0 no draw is applied.  The captured step bakes in the ADDRESS of keys (part of the graph key, with seed 0), never their
+ * contents: new contents at that address give new draws, another address is a cache miss.  Null or misaligned keys and a latent
+ * width that is no multiple of 4 are refused before anything is written; flags, workspace (dn_ddim_sched_workspace_bytes) and
+ * everything else as dn_ddim_sched_loop.
+ * dn_ddim_sched_step is the update alone on n (a multiple of 4) contiguous fp32 elements, x / eps / noise 16-byte aligned: row
+ * *step_index (device int32) of coef and steps, z from `seed` (counter: element quad, step index) or the injected `noise` [n] of THIS
+ * step; dn_ddim_sched_step_keyed the keyed update alone on dense x / eps [B, T, Z] (Z a multiple of 4), for host-stepped chains.  */
+int dn_ddim_sched_loop_keyed(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, const int32_t* steps, const float* coef,
+                             int32_t n_steps, int32_t timesteps, const uint64_t* keys, int32_t flags, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int dn_ddim_sched_step(float* x, const float* eps, int64_t n, const float* coef, const int32_t* steps, const int32_t* step_index,
+                       int32_t eta_on, uint64_t seed, const float* noise, void* stream);
+int dn_ddim_sched_step_keyed(float* x, const float* eps, const uint64_t* keys, int32_t B, int32_t T, int32_t Z, const float* coef,
+                             const int32_t* steps, const int32_t* step_index, void* stream);
 
 /* DPM-Solver++(2M) over a timestep schedule, as a device loop (Lu et al. 2022, "DPM-Solver++", the data-prediction multistep solver,
  * eq. 11-12 / algorithm 2): dn_ddim_sched_loop's chain -- the strictly descending evaluation timesteps e_0 > ... > e_{n-1}, the level
@@ -768,6 +799,16 @@ int dn_guided_ddim_loop(DnEps* m, float* x, const int32_t* lengths, const float*
                         int32_t Tp, float cond_scale, const int32_t* steps, const float* coef, int32_t n_steps, int32_t timesteps,
                         int32_t eta_on, uint64_t seed, const float* noise, int32_t flags, void* workspace, size_t workspace_bytes,
                         void* stream);
+
+/* dn_guided_ddim_loop (latent_module.py:813-826, diffusion/gaussian_diffusion.py:513-560) with eta on and keyed per-step noise, as
+ * dn_ddim_sched_loop_keyed draws it: stream 2 + e_i of keys[b] (device uint64 [B], 8-byte aligned) for the B-row latent, so a
+ * scale-1 chain draws what dn_ddim_sched_loop_keyed draws.  `keys` stands where the twin takes eta_on, seed and noise; its address
+ * is part of the guided slot's graph key (seed 0).  Null or misaligned keys and a latent width that is no multiple of 4 are refused
+ * before anything is written; everything else as dn_guided_ddim_loop.                                                          */
+int dn_guided_ddim_loop_keyed(DnEps* m, float* x, const int32_t* lengths, const float* prompt, const int32_t* prompt_lengths, int32_t B,
+                              int32_t T, int32_t Tp, float cond_scale, const int32_t* steps, const float* coef, int32_t n_steps,
+                              int32_t timesteps, const uint64_t* keys, int32_t flags, void* workspace, size_t workspace_bytes,
+                              void* stream);
 
 /* DPM-Solver++(2M) for the prompted, classifier-free-guided chain, as a device loop (Lu et al. 2022, "DPM-Solver++", the
  * data-prediction multistep solver, eq. 11-12 / algorithm 2): dn_guided_ddim_loop's chain -- the same steps, the level x enters at,
