@@ -277,6 +277,13 @@ SYMBOLS = {
     "dn_last_error": (C.c_char_p, []),
     "dn_version": (C.c_int, []),
     "dn_cmlm_step_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "dn_nar_null_cross_bytes": (_sz, [_vp]),
+    "dn_nar_null_cross": (C.c_int, [_vp, _i32, _vp, _sz, _vp]),
+    "dn_nar_null_table": (_vp, [_vp]),
+    "dn_nar_guided_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
+    "dn_nar_decoder_forward_guided": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "dn_cmlm_guided_step": (C.c_int, [_vp, C.c_float, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "dn_cmlm_guided_step_dev": (C.c_int, [_vp, C.c_float, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "dn_set_option": (C.c_int, [C.c_char_p, _i32]),
     "dn_get_option": (C.c_int, [C.c_char_p, _vp, _vp]),
 }

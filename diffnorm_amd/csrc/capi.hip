@@ -44,6 +44,7 @@ const OptDef kOpts[dn::OPT_COUNT] = {
     {"wgrad_prio", "DN_WGRAD_PRIO", nullptr},              // 1: the weight-gradient stream at the lowest priority (read when the stream is created; measured level, default off)
     {"wgrad_tn_x3", "DN_WGRAD_TN_X3", nullptr},            // split-operand (bf16x3) weight gradients: 0 from transposed copies (default 1: straight from the row-major split rows) ("wgrad_tn" covers the 2-byte modes only)
     {"ffn_fold", "DN_FFN_FOLD", nullptr},                  // sampling engines: 0 = the FFN causal conv and its output projection as two contractions (default 1, in DN_BF16 0: one folded three-tap contraction; 2 / 3: the same forced to the 256 x 128 / 256 x 256 tile, A/B timing)
+    {"nar_cg_fold", "DN_NAR_CG_FOLD", nullptr},            // guided NAR decoder pass: 0 = the null half's encoder attention evaluated literally against S copies of the null key / value (default 1: the broadcast addition of the constant row c_l)
 };
 std::atomic<int> g_opt[dn::OPT_COUNT];
 std::atomic<int> g_opt_gen{0};

@@ -781,6 +781,92 @@ __global__ __launch_bounds__(256) void cmlm_step_kernel(const float* __restrict_
   }
 }
 
+// The guided update of research/TranSpeech/nat_gen.py:197-236 (classifier-free guidance, --cg_scale): as cmlm_step_kernel, but the
+// scores START FROM ZERO in every iteration (:197 -- forward_decoder keeps the earlier iterations' scores) and the masked positions
+// take arg-max / max of log_softmax(cond + scale * (cond - null)) (:223-226).  The combination, the log-softmax and the arg-max are
+// one pass over the two logit rows (running maximum and rescaled sum per lane, merged across the wave): each row is read once and
+// the scaled logits are never written.  The three roundings of the combination are torch's (no contraction into an FMA).
+__global__ __launch_bounds__(256) void cmlm_guided_step_kernel(const float* __restrict__ logits2, float scale, int32_t* __restrict__ tokens,
+                                                               float* __restrict__ scores, int32_t* __restrict__ predicted, int B, int T, int V,
+                                                               float p, int remask, int unk, int pad, const int32_t* __restrict__ step_dev,
+                                                               int max_step) {
+  if (step_dev) {
+    const int step = *step_dev;
+    remask = (step + 1) < max_step;
+    p = (float)(1.0 - (double)(step + 1) / (double)max_step);
+  }
+  __shared__ float s_sc[2048];
+  __shared__ int32_t s_tok[2048];
+  __shared__ int s_n;
+  const int b = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t half = (int64_t)B * T * V;
+  if (threadIdx.x == 0) s_n = 0;
+  for (int t = wave; t < T; t += 4) {
+    int32_t tok = tokens[(int64_t)b * T + t];
+    float sc = 0.f;  // output_scores = new_full(shape, 0.0) (:197)
+    if (tok == unk) {  // wave-uniform
+      const float* lc = logits2 + ((int64_t)b * T + t) * V;
+      const float* ln = lc + half;
+      float best = -INFINITY, se = 0.f;
+      int bi = 0x7fffffff;
+      for (int c = lane; c < V; c += 64) {
+        const float cv = lc[c];
+        const float v = __fadd_rn(cv, __fmul_rn(scale, __fsub_rn(cv, ln[c])));
+        if (v > best) {
+          se = se * expf(best - v) + 1.0f;  // (first element: 0 * exp(-inf) + 1)
+          best = v; bi = c;
+        } else {
+          se += expf(v - best);
+        }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64), os = __shfl_xor(se, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        const float mx = fmaxf(best, ov);
+        const float sa = best == -INFINITY ? 0.f : se * expf(best - mx), sb = ov == -INFINITY ? 0.f : os * expf(ov - mx);
+        se = sa + sb;  // (commutative: both lanes of a pair hold the same sum)
+        if (ov > best || (ov == best && oi < bi)) bi = oi;
+        best = mx;
+      }
+      tok = bi;
+      sc = -logf(se);  // max - logsumexp
+    }
+    if (lane == 0) {
+      s_tok[t] = tok;
+      s_sc[t] = sc;
+      predicted[(int64_t)b * T + t] = tok;
+    }
+  }
+  __syncthreads();
+  if (remask) {
+    int cnt = 0;
+    for (int t = threadIdx.x; t < T; t += 256) cnt += s_tok[t] != pad;
+    if (cnt) atomicAdd(&s_n, cnt);
+    __syncthreads();
+    const long long boundary = (long long)((float)(s_n - 2) * p);
+    for (int i = threadIdx.x; i < T; i += 256) {
+      const float si = s_sc[i];
+      int rank = 0;
+      for (int j = 0; j < T; ++j) {
+        const float sj = s_sc[j];
+        rank += (sj < si) || (sj == si && j < i);
+      }
+      int32_t tok = s_tok[i];
+      float sc = si;
+      if ((long long)rank < boundary) { tok = unk; sc = 0.f; }
+      tokens[(int64_t)b * T + i] = tok;
+      scores[(int64_t)b * T + i] = sc;
+    }
+  } else {
+    for (int i = threadIdx.x; i < T; i += 256) {
+      tokens[(int64_t)b * T + i] = s_tok[i];
+      scores[(int64_t)b * T + i] = s_sc[i];
+    }
+  }
+}
+
 static inline int ew_grid(int64_t n) {
   int64_t b = (n + 255) / 256;
   return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
@@ -1045,5 +1131,29 @@ extern "C" int dn_cmlm_step_dev(const float* logits, int32_t* tokens, float* sco
   hipLaunchKernelGGL(cmlm_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, tokens, scores, predicted, T, V, 0.f, 0, unk, pad,
                      step_dev, max_step);
   DN_CHECK_LAUNCH("dn_cmlm_step_dev");
+  return DN_OK;
+}
+
+extern "C" int dn_cmlm_guided_step(const float* logits2, float scale, int32_t* tokens, float* scores, int32_t* predicted, int32_t B, int32_t T,
+                                   int32_t V, int32_t step, int32_t max_step, int32_t unk, int32_t pad, void* stream) {
+  DN_CHECK_ARG(logits2 && tokens && scores && predicted && B > 0 && T > 0 && T <= 2048 && V > 1 && max_step > 0 && step >= 0,
+               "dn_cmlm_guided_step: bad args (T=%d must be <= 2048)", T);
+  DN_CHECK_ARG(scale > 0.f, "dn_cmlm_guided_step: guidance scale %g must be > 0 (nat_gen.py:180: without it the loop runs dn_cmlm_step on one pass)", (double)scale);
+  const int remask = (step + 1) < max_step;
+  const float p = (float)(1.0 - (double)(step + 1) / (double)max_step);
+  hipLaunchKernelGGL(cmlm_guided_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits2, scale, tokens, scores, predicted, B, T, V, p, remask,
+                     unk, pad, (const int32_t*)nullptr, max_step);
+  DN_CHECK_LAUNCH("dn_cmlm_guided_step");
+  return DN_OK;
+}
+
+extern "C" int dn_cmlm_guided_step_dev(const float* logits2, float scale, int32_t* tokens, float* scores, int32_t* predicted, int32_t B, int32_t T,
+                                       int32_t V, const int32_t* step_dev, int32_t max_step, int32_t unk, int32_t pad, void* stream) {
+  DN_CHECK_ARG(logits2 && tokens && scores && predicted && step_dev && B > 0 && T > 0 && T <= 2048 && V > 1 && max_step > 0,
+               "dn_cmlm_guided_step_dev: bad args (T=%d must be <= 2048)", T);
+  DN_CHECK_ARG(scale > 0.f, "dn_cmlm_guided_step_dev: guidance scale %g must be > 0", (double)scale);
+  hipLaunchKernelGGL(cmlm_guided_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits2, scale, tokens, scores, predicted, B, T, V, 0.f, 0,
+                     unk, pad, step_dev, max_step);
+  DN_CHECK_LAUNCH("dn_cmlm_guided_step_dev");
   return DN_OK;
 }

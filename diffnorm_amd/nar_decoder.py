@@ -10,6 +10,10 @@ attention / ReLU FFN layers, final LayerNorm, output projection), the length pre
 mask-predict update (:791-842, one kernel: dn_cmlm_step).  The speech ENCODER (conv subsampler + transformer over fbank frames) is
 out of scope: its output is a given tensor -- the `encoder` here only carries it and re-orders it.  Weights come from a state dict
 under the reference decoder's parameter names (`decoder.*` of the model's checkpoint).
+
+Classifier-free guidance (the reference's `nar_cg` evaluation: scripts/s2ut/eval_cg.sh -> research/TranSpeech/nat_gen.py --cg_scale):
+`NarDecoderEngine.forward_guided` is the two decoder passes of an iteration (TransformerUnitDecoder.forward and .cg_forward,
+nar_transformer.py:123-183) as one pass over 2 B rows, `NARS2UTDecoderModel.guided_mask_predict` the loop of nat_gen.py:192-236.
 """
 import ctypes as C
 import math
@@ -199,6 +203,51 @@ class NarDecoderEngine(_Engine):
         return logits
 
 
+    # ---- classifier-free guidance (nat_gen.py:196-236; cg_forward, nar_transformer.py:123-183)
+    null_generation = 0  # counts the tables formed: a captured pass holds the address of the one it was captured with
+    null_token = None  # the token whose embedding row stands in for the dropped source (None: dn_nar_null_cross has not run)
+
+    def null_cross(self, null_token: int = 0) -> torch.Tensor:
+        """dn_nar_null_cross: the fp32 [layers, dim] table of c_l = W_o (W_v emb[null_token] + b_v) + b_o, formed on the device in the
+        engine's arithmetic, once per engine and token.  -> a view of the table (it lives in a buffer this engine keeps)."""
+        if self.null_token != int(null_token):
+            n = int(self.lib.dn_nar_null_cross_bytes(self.handle))
+            buf = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
+            wp, wn = self._aligned(buf)
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.dn_nar_null_cross(self.handle, int(null_token), wp, wn, _lib.current_stream()), "dn_nar_null_cross")
+                torch.cuda.current_stream().synchronize()  # the previous buffer (another token's table) may go only after this
+            off = int(self.lib.dn_nar_null_table(self.handle)) - buf.data_ptr()
+            self._null_buf, self.null_token, self.null_generation = buf, int(null_token), self.null_generation + 1
+            self._null_tab = buf[off: off + self.layers * self.dim * 4].view(torch.float32).view(self.layers, self.dim)
+        return self._null_tab
+
+    def _guided_ws(self, B, T, S):
+        return self._aligned(self._workspace(int(self.lib.dn_nar_guided_workspace_bytes(self.handle, B, T, S))))
+
+    def forward_guided(self, tokens: torch.Tensor, ckv: torch.Tensor, src_lengths: torch.Tensor, out: Optional[torch.Tensor] = None,
+                       workspace=None) -> torch.Tensor:
+        """tokens int32 [B, T] -> logits fp32 [2, B, T, vocab]: [0] attends to the encoder (`ckv`), [1] to the null source.
+        `null_cross` must have run (the C entry refuses otherwise).  workspace: (aligned address, bytes) of the caller's, else the engine's."""
+        B, T = tokens.shape
+        S = ckv.shape[2]
+        assert tokens.dtype == torch.int32 and tokens.is_contiguous() and ckv.is_contiguous() and ckv.shape[1] == B
+        sl = src_lengths if (src_lengths.dtype == torch.int32 and src_lengths.device == self.device) else src_lengths.to(self.device, torch.int32)
+        logits = torch.empty(2, B, T, self.vocab, dtype=torch.float32, device=self.device) if out is None else out
+        assert logits.shape == (2, B, T, self.vocab) and logits.dtype == torch.float32 and logits.is_contiguous()
+        wp, wn = self._guided_ws(B, T, S) if workspace is None else workspace
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.dn_nar_decoder_forward_guided(self.handle, tokens.data_ptr(), ckv.data_ptr(), sl.contiguous().data_ptr(), B, T, S,
+                                                              logits.data_ptr(), wp, wn, _lib.current_stream()), "dn_nar_decoder_forward_guided")
+        return logits
+
+    def guided_logits(self, tokens: torch.Tensor, ckv: torch.Tensor, src_lengths: torch.Tensor, cg_scale: float) -> torch.Tensor:
+        """scaled_logits = cond + cg_scale * (cond - null) (nat_gen.py:223), fp32 [B, T, vocab] -- for callers and tests: the loop's
+        update kernel (dn_cmlm_guided_step) forms the same values in registers and never writes them."""
+        both = self.forward_guided(tokens, ckv, src_lengths)
+        return both[0] + float(cg_scale) * (both[0] - both[1])
+
+
 class _GivenEncoder:
     """The speech encoder is out of this row's scope: `__call__` hands back the encoder output it is given (the reference's dict:
     encoder_out [S,B,D], encoder_padding_mask [B,S]); `reorder_encoder_out` follows S2TTransformerEncoder's
@@ -270,6 +319,68 @@ class _RefineGraph:
                 self.graph.replay()
 
 
+class _GuidedGraph:
+    """ONE iteration of the guided loop (nat_gen.py:196-236) captured into a hipGraph and replayed: the score reset (:197 -- inside
+    the update kernel, which writes the scores and never reads them; a memset in the unguided form), the decoder pass over 2 B rows,
+    the guided update with the iteration index read from a device counter, the counter's increment.  scale None: the same loop
+    without the null half (:225) -- dn_nar_decoder_forward and dn_cmlm_step_dev on zeroed scores.  Keyed by the model on
+    (B, T, S, n_iters, scale, option nar_cg_fold).  The encoder-attention keys / values and the source lengths are COPIED into the
+    static buffers on every call: nothing here remembers a caller's addresses or tensor versions, so two encoder outputs that
+    happen to reuse one allocation cannot be confused.  The workspace is this graph's own (the engine's may be re-allocated by a
+    larger later call)."""
+
+    def __init__(self, model, B, T, S, n_iters, scale, ckv_like, slen_like):
+        eng, dev = model.engine, model.device
+        self.model, self.n_iters, self.scale, self.graph = model, int(n_iters), scale, None
+        self.tokens = torch.empty(B, T, dtype=torch.int32, device=dev)
+        self.scores = torch.zeros(B, T, dtype=torch.float32, device=dev)
+        self.predicted = torch.empty(B, T, dtype=torch.int32, device=dev)
+        self.logits = torch.empty(2 if scale is not None else 1, B, T, eng.vocab, dtype=torch.float32, device=dev)
+        self.step = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.ckv, self.slen = torch.empty_like(ckv_like), torch.empty_like(slen_like)
+        size = eng.lib.dn_nar_guided_workspace_bytes if scale is not None else eng.lib.dn_nar_workspace_bytes
+        self._ws = torch.empty(int(size(eng.handle, B, T, S)) + 256, dtype=torch.uint8, device=dev)
+
+    def _iteration(self):
+        m, eng = self.model, self.model.engine
+        _, B, T, V = self.logits.shape
+        ws = eng._aligned(self._ws)
+        args = (self.tokens.data_ptr(), self.scores.data_ptr(), self.predicted.data_ptr(), B, T, V, self.step.data_ptr(), self.n_iters, int(m.unk),
+                int(m.pad), _lib.current_stream())
+        if self.scale is not None:
+            eng.forward_guided(self.tokens, self.ckv, self.slen, out=self.logits, workspace=ws)
+            _lib.check(eng.lib.dn_cmlm_guided_step_dev(self.logits.data_ptr(), float(self.scale), *args), "dn_cmlm_guided_step_dev")
+        else:
+            self.scores.zero_()
+            _lib.check(eng.lib.dn_nar_decoder_forward(eng.handle, self.tokens.data_ptr(), self.ckv.data_ptr(), self.slen.data_ptr(), B, T, self.ckv.shape[2],
+                                                      self.logits.data_ptr(), ws[0], ws[1], _lib.current_stream()), "dn_nar_decoder_forward")
+            _lib.check(eng.lib.dn_cmlm_step_dev(self.logits.data_ptr(), *args), "dn_cmlm_step_dev")
+        self.step.add_(1)
+
+    def start(self, tokens, ckv, slen):
+        self.tokens.copy_(tokens)
+        self.ckv.copy_(ckv)
+        self.slen.copy_(slen)
+        self.step.zero_()
+
+    def run(self, n: int = 1):
+        with torch.cuda.device(self.model.device):
+            if self.graph is None:
+                self._iteration()  # eager first: kernel attributes settle outside capture
+                n -= 1
+                cur = torch.cuda.current_stream()
+                side = torch.cuda.Stream(device=self.model.device)
+                side.wait_stream(cur)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.stream(side):
+                    with torch.cuda.graph(g, stream=side):
+                        self._iteration()
+                cur.wait_stream(side)
+                self.graph = g
+            for _ in range(n):
+                self.graph.replay()
+
+
 class NARS2UTDecoderModel:
     """forward_decoder / initialize_output_tokens / regenerate_length_beam of NARS2UTTransformerModel (:791-912) over the HIP decoder.
     `use_graph` (default on): an iteration of `forward_decoder` runs as ONE captured hipGraph launch (_RefineGraph) instead of ~70
@@ -278,7 +389,7 @@ class NARS2UTDecoderModel:
     allow_length_beam = True
 
     def __init__(self, decoder_state_dict, dim=512, ffn=2048, layers=6, heads=8, vocab=1004, pad=1, unk=3, dtype="bf16", device="cuda:0",
-                 use_graph: bool = True, encoder_state_dict=None, encoder_kw=None):
+                 use_graph: bool = True, encoder_state_dict=None, encoder_kw=None, eos: int = 2):
         """encoder_state_dict (S2TTransformerEncoder.state_dict() names; encoder_kw = NarEncoderEngine's sizes): with it `forward_encoder`
         runs the speech encoder on the HIP engine from [B, L, 80] features, as NARS2UTTransformerModel.forward_encoder does (:566-567);
         without it the encoder output is a tensor the caller supplies."""
@@ -289,8 +400,8 @@ class NARS2UTDecoderModel:
             self.encoder = _HipEncoder(NarEncoderEngine(encoder_state_dict, **kw))
         else:
             self.encoder = _GivenEncoder()
-        self.pad, self.unk, self.device = pad, unk, self.engine.device
-        self.use_graph, self._graphs = use_graph, {}
+        self.pad, self.unk, self.eos, self.device = pad, unk, eos, self.engine.device
+        self.use_graph, self._graphs, self._guided_graphs = use_graph, {}, {}
 
     def _graph_for(self, B, T, ckv, slen, max_step) -> "_RefineGraph":
         key = (B, T, ckv.shape[2], int(max_step))
@@ -313,6 +424,57 @@ class NARS2UTDecoderModel:
         g.step.fill_(int(decoder_out.step))
         g.run(n_iters)
         return decoder_out._replace(output_tokens=g.tokens.long(), output_scores=g.scores.clone(), attn=None, step=decoder_out.step + n_iters)
+
+    def guided_mask_predict(self, encoder_out, lengths, n_iters: int, cg_scale, null_token: int = 0, history: Optional[list] = None):
+        """The decoding loop of research/TranSpeech/nat_gen.py:192-236 (scripts/s2ut/eval_cg.sh: the `nar_cg` model with --cg_scale):
+        rows of `unk` for lengths[b] positions, then `eos`, then `pad` (prepare_batch :109-113); n_iters iterations of decoder pass(es) +
+        update, the scores starting from zero in every iteration (:197); with guidance every iteration decodes the tokens against the
+        speech encoder's output and against the null source (cg_forward: embed_tokens.weight[null_token] at every source position, no
+        padding mask) and takes the arg-max of log_softmax(cond + cg_scale * (cond - null)).  cg_scale None or <= 0: the same loop
+        without the null half (use_cg = cg_scale > 0, :179-181, :225).  encoder_out: the reference's encoder dict (forward_encoder's).
+        -> tokens int64 [B, T], T = max(lengths) + 1.  history (a list) receives (tokens, scores, predicted) after every iteration."""
+        ckv, slen = self._prepared(encoder_out)
+        scale = float(cg_scale) if (cg_scale is not None and float(cg_scale) > 0) else None
+        lengths = torch.as_tensor(lengths).to(self.device).long()
+        B, T = lengths.numel(), int(lengths.max()) + 1
+        assert ckv.shape[1] == B and int(lengths.min()) >= 1 and int(n_iters) >= 1
+        idx = torch.arange(T, device=self.device)[None, :]
+        tok = torch.full((B, T), self.pad, dtype=torch.int32, device=self.device)
+        tok = tok.masked_fill(idx < lengths[:, None], self.unk).masked_fill(idx == lengths[:, None], self.eos)
+        eng = self.engine
+        if scale is not None:
+            eng.null_cross(null_token)
+        keep = lambda t, sc, pr: history.append((t.long().clone(), sc.clone(), pr.long().clone())) if history is not None else None
+        if self.use_graph:
+            key = (B, T, ckv.shape[2], int(n_iters), scale, _lib.get_option("nar_cg_fold"), eng.null_generation if scale is not None else None)
+            g = self._guided_graphs.get(key)
+            if g is None:
+                if len(self._guided_graphs) >= 8:
+                    self._guided_graphs.pop(next(iter(self._guided_graphs)))
+                g = self._guided_graphs[key] = _GuidedGraph(self, B, T, ckv.shape[2], n_iters, scale, ckv, slen)
+            g.start(tok, ckv, slen)
+            if history is None:
+                g.run(int(n_iters))
+            else:
+                for _ in range(int(n_iters)):
+                    g.run(1)
+                    keep(g.tokens, g.scores, g.predicted)
+            return g.tokens.long()
+        scores = torch.zeros(B, T, dtype=torch.float32, device=self.device)
+        predicted = torch.empty(B, T, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            for step in range(int(n_iters)):
+                args = (tok.data_ptr(), scores.data_ptr(), predicted.data_ptr(), B, T, eng.vocab, step, int(n_iters), int(self.unk), int(self.pad),
+                        _lib.current_stream())
+                if scale is not None:
+                    logits = eng.forward_guided(tok, ckv, slen)
+                    _lib.check(eng.lib.dn_cmlm_guided_step(logits.data_ptr(), scale, *args), "dn_cmlm_guided_step")
+                else:
+                    scores.zero_()
+                    logits = eng.forward(tok, ckv, slen)
+                    _lib.check(eng.lib.dn_cmlm_step(logits.data_ptr(), *args), "dn_cmlm_step")
+                keep(tok, scores, predicted)
+        return tok.long()
 
     def eval(self):
         return self

@@ -961,6 +961,8 @@ int dn_version(void);
  * "ffn_fold" (DN_FFN_FOLD: sampling engines with folded weights attached -- 0 the FFN's causal conv and output projection as two
  * contractions, 1 [default; DN_BF16 engines default to 0] one folded contraction on the routed tile, 2 / 3 the same forced to the 256 x 128 / 256 x 256
  * tile; like every option it is part of the captured-step cache keys through the option generation).
+ * "nar_cg_fold" (DN_NAR_CG_FOLD: the guided NAR decoder pass -- 1 [default] the null half's encoder attention as the addition of
+ * the constant row c_l, 0 evaluated literally; it changes the option generation like every option).
  * dn_get_option: *is_set = 0 when the option is neither set nor in the environment (the library's built-in choice applies). */
 #define DN_OPTION_DEFAULT (-2147483647 - 1)
 int dn_set_option(const char* name, int32_t value);
@@ -999,6 +1001,46 @@ int dn_nar_predict_lengths(DnNar* m, const float* enc_out, const int32_t* src_le
  * logits fp32 [B, T, vocab]; dn_cmlm_step turns them into the mask-predict update of forward_decoder (:791-842).            */
 int dn_nar_decoder_forward(DnNar* m, const int32_t* tokens, const void* ckv, const int32_t* src_lengths, int32_t B, int32_t T, int32_t S,
                            float* logits, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ classifier-free guidance of the same decoder (nar_cg) */
+/* The reference's `nar_cg` evaluation (scripts/s2ut/eval_cg.sh -> research/TranSpeech/nat_gen.py --cg_scale) runs the decoder twice
+ * in every iteration of its mask-predict loop (nat_gen.py:196-236): TransformerUnitDecoder.forward on the speech encoder's output and
+ * TransformerUnitDecoder.cg_forward (nar_transformer.py:123-183) on a "dropped" source -- every source position of every row replaced
+ * by e_null = embed_tokens.weight[bos] (:144-149, the raw row: no sqrt(D) scale, no position) and the padding mask cleared
+ * (:152-156).  All S keys / values of a layer are then equal, the softmax is uniform and the encoder attention of EVERY query is
+ *   c_l = W_o,l (W_v,l e_null + b_v,l) + b_o,l          l = 0 .. layers - 1,
+ * independent of the query, of S and of the batch: in the pre-norm layer (fairseq/modules/transformer_layer.py:447-470) the whole
+ * block -- encoder_attn_layer_norm, q_proj, attention, out_proj -- is the broadcast addition of c_l.  Not in the reference; against
+ * the literal evaluation it differs by the rounding of sum_S (1/S) v only.
+ *
+ * dn_nar_null_cross forms the fp32 [layers][dim] table of c_l on the device in the engine's arithmetic: emb[null_token] through the
+ * packed ckv_W (v rows) / ckv_b and co_W / co_b with the operand roundings of dn_nar_cross_kv and of the attention output.  `buffer`
+ * (256-byte aligned, dn_nar_null_cross_bytes) is the caller's, like the packed tensors: the engine keeps reading the table at its
+ * start, so it stays allocated and untouched while guided passes run; the rest is scratch of this call.  Once per engine and token,
+ * never per iteration.  dn_nar_null_table: the table's device address (NULL before the first call).                              */
+size_t dn_nar_null_cross_bytes(const DnNar* m);
+int dn_nar_null_cross(DnNar* m, int32_t null_token, void* buffer, size_t buffer_bytes, void* stream);
+const float* dn_nar_null_table(const DnNar* m);
+/* The two decoder passes of one iteration (nat_gen.py:209-222) as ONE pass over 2 B rows: embedding, self-attention, FFN, final
+ * LayerNorm and output projection on all 2 B T rows; encoder attention on the first B T rows; the rows of the second half receive
+ * + c_l.  tokens / ckv / src_lengths as dn_nar_decoder_forward -> logits2 fp32 [2, B, T, vocab], conditioned then null.  Refused
+ * before dn_nar_null_cross.  Option "nar_cg_fold" (DN_NAR_CG_FOLD, default 1): 0 evaluates the null half's encoder attention
+ * literally -- dn_nar_cross_kv on B S copies of e_null, every source length S, formed in the workspace by every pass -- the
+ * on-device check of the fold and the A/B leg of tools/nar_cg_bench.py, not a tuned path.  No allocation, no synchronisation.     */
+size_t dn_nar_guided_workspace_bytes(const DnNar* m, int32_t B, int32_t T, int32_t S);
+int dn_nar_decoder_forward_guided(DnNar* m, const int32_t* tokens, const void* ckv, const int32_t* src_lengths, int32_t B, int32_t T, int32_t S,
+                                  float* logits2, void* workspace, size_t workspace_bytes, void* stream);
+/* The update of nat_gen.py:197-236 on logits2 fp32 [2, B, T, V] in one kernel.  Unlike forward_decoder's (dn_cmlm_step), the scores
+ * START FROM ZERO in every iteration (:197; `scores` is written, never read); positions holding `unk` take arg-max / max of
+ * log_softmax(cond + scale * (cond - null)) (:223-229); `predicted` receives the tokens at that point; unless step + 1 == max_step
+ * the trunc((n_nonpad - 2) * (1 - (step + 1) / max_step)) lowest-scoring positions are re-masked and their scores zeroed (:230-236,
+ * _skeptical_unmasking; equal scores ordered by position, as dn_cmlm_step).  Each logit row is read once; the scaled logits are never
+ * written.  T <= 2048; scale <= 0 is refused (nat_gen.py:180,225: that loop is dn_cmlm_step over one pass, scores zeroed first).
+ * _dev: the iteration index is read from the device, for a captured iteration.                                                */
+int dn_cmlm_guided_step(const float* logits2, float scale, int32_t* tokens, float* scores, int32_t* predicted, int32_t B, int32_t T,
+                        int32_t V, int32_t step, int32_t max_step, int32_t unk, int32_t pad, void* stream);
+int dn_cmlm_guided_step_dev(const float* logits2, float scale, int32_t* tokens, float* scores, int32_t* predicted, int32_t B, int32_t T,
+                            int32_t V, const int32_t* step_dev, int32_t max_step, int32_t unk, int32_t pad, void* stream);
 
 /* ------------------------------------------------------------------ the speech encoder of the same model */
 /* S2STransformerEncoder (research/TranSpeech/nar_transformer.py:40-76; no speaker embedding) = S2TTransformerEncoder._forward
