@@ -119,6 +119,21 @@ class NarEncConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("input_dim", "conv_channels", "kernel", "dim", "ffn", "layers", "heads", "max_pos", "pad", "dtype")]
 
 
+class VocConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("embedding_dim", "num_embeddings", "initial_channel", "n_ups")] + \
+               [("up_rates", C.c_int32 * 8), ("up_kernels", C.c_int32 * 8), ("n_kernels", C.c_int32), ("res_kernels", C.c_int32 * 4),
+                ("res_dilations", (C.c_int32 * 3) * 4), ("dur_hidden", C.c_int32), ("dtype", C.c_int32)]
+
+
+class VocConvParams(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("x", "W", "bias", "res", "out", "lengths")] + \
+               [(n, C.c_int32) for n in ("B", "Lmax", "C_in", "C_out", "k", "d", "ldx", "ldo", "ldr", "dtype", "post")] + \
+               [("slope", C.c_float), ("div", C.c_float)]
+
+
+VOC_POST_NONE, VOC_POST_RES, VOC_POST_RES_ACC, VOC_POST_RELU, VOC_POST_TANH = range(5)
+
+
 class VaeTrainBatch(C.Structure):
     _fields_ = [("feat", C.c_void_p), ("units", C.c_void_p), ("lengths", C.c_void_p), ("noise", C.c_void_p), ("B", C.c_int32),
                 ("T", C.c_int32), ("ntokens", C.c_int32), ("w_lsce", C.c_float), ("w_mse", C.c_float), ("w_kl", C.c_float),
@@ -284,6 +299,17 @@ SYMBOLS = {
     "dn_nar_decoder_forward_guided": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "dn_cmlm_guided_step": (C.c_int, [_vp, C.c_float, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dn_cmlm_guided_step_dev": (C.c_int, [_vp, C.c_float, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "dn_voc_conv": (C.c_int, [C.POINTER(VocConvParams), _vp]),
+    "dn_voc_conv_tile": (C.c_int, [_i32, _i32, _i32, _i32]),
+    "dn_voc_conv_weight_elems": (_i64, [_i32, _i32, _i32, _i32]),
+    "dn_voc_create": (C.c_int, [C.POINTER(VocConfig), C.POINTER(_vp), _i32, C.POINTER(_vp)]),
+    "dn_voc_destroy": (None, [_vp]),
+    "dn_voc_upsample": (_i32, [_vp]),
+    "dn_voc_workspace_bytes": (_sz, [_vp, _i32, _i32]),
+    "dn_voc_durations": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "dn_voc_forward": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "dn_voc_set_profile": (C.c_int, [_vp, _i32]),
+    "dn_voc_stage_times": (C.c_int, [_vp, C.POINTER(C.c_float), _i32]),
     "dn_set_option": (C.c_int, [C.c_char_p, _i32]),
     "dn_get_option": (C.c_int, [C.c_char_p, _vp, _vp]),
 }

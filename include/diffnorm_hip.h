@@ -1066,6 +1066,70 @@ size_t dn_nar_encoder_workspace_bytes(const DnNarEnc* m, int32_t B, int32_t L);
 int dn_nar_encoder_forward(DnNarEnc* m, const float* feats, const int32_t* src_lengths, int32_t B, int32_t L, float* enc_out,
                            int32_t* out_lengths, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ CodeHiFiGAN unit vocoder: units -> waveform, batched */
+/* CodeHiFiGANVocoder.forward (fairseq/models/text_to_speech/vocoder.py:214-235) = CodeGenerator (codehifigan.py) over the HiFiGAN
+ * Generator (hifigan.py) with the duration predictor (fastspeech2.py:117-151), single-speaker, no f0.  Kernels: csrc/vocoder.hip.
+ *
+ * The conv operator.  Activations are channels-last fp32 [B, Lmax, C] with per-sequence lengths[B]:
+ *   out[b,t,co] = post(bias[co] + sum_{j<k} sum_ci pre(x[b, t + (j - (k-1)/2) d, ci]) W[co,j,ci])      for t < lengths[b],
+ * frames outside [0, lengths[b]) read as ZEROS (the reference's per-utterance zero padding), frames >= lengths[b] of `out` untouched.
+ * pre = leaky ReLU of slope `slope` (1 = none, 0 = ReLU), computed in fp32 and rounded once to the operand type.  k odd, C_in a
+ * multiple of 16 (of 128 beyond 128), (k - 1) / 2 * d <= 25 at 128 staged channels.  dtype DN_F32 or DN_F16 (half operands, fp32
+ * accumulation); DN_BF16 / DN_BF16X3 are refused.  W: [ceil16(C_out)][row] in the operand type, a row holding per pass of
+ * CK = min(C_in, 128) input channels the k * CK weights in (tap, channel) order, zero-padded to 32 elements in DN_F16
+ * (diffnorm_amd/vocoder.py::pack_conv_weight; dn_voc_conv_weight_elems = the element count).  Tiles are counted from frame 0 of each
+ * sequence: a frame's result does not depend on the batch, the row or Lmax.                                                     */
+enum { DN_VOC_POST_NONE = 0, DN_VOC_POST_RES = 1, DN_VOC_POST_RES_ACC = 2, DN_VOC_POST_RELU = 3, DN_VOC_POST_TANH = 4 };
+/* POST_RES: (acc + bias + res) / div.  POST_RES_ACC: (acc + bias + res + out's previous value) / div -- the sum over the ResBlocks
+ * of a stage, div = their number on the last one and 1 before.  res may alias out.                                              */
+typedef struct {
+  const float* x;
+  const void* W;
+  const float* bias; /* fp32 [C_out] or NULL */
+  const float* res;  /* fp32 [B, Lmax, ldr], POST_RES / POST_RES_ACC */
+  float* out;        /* fp32 [B, Lmax, ldo] */
+  const int32_t* lengths;
+  int32_t B, Lmax, C_in, C_out, k, d, ldx, ldo, ldr, dtype, post;
+  float slope, div;
+} DnVocConvParams;
+int dn_voc_conv(const DnVocConvParams* p, void* stream);
+int dn_voc_conv_tile(int32_t dtype, int32_t C_in, int32_t C_out, int32_t k); /* frames per time tile, or DN_EINVAL */
+int64_t dn_voc_conv_weight_elems(int32_t dtype, int32_t C_in, int32_t C_out, int32_t k); /* 0: unsupported shape */
+
+#define DN_VOC_MAX_UPS 8
+#define DN_VOC_MAX_KERNELS 4
+typedef struct DnVoc DnVoc;
+typedef struct {
+  int32_t embedding_dim, num_embeddings, initial_channel, n_ups;
+  int32_t up_rates[DN_VOC_MAX_UPS], up_kernels[DN_VOC_MAX_UPS];
+  int32_t n_kernels, res_kernels[DN_VOC_MAX_KERNELS], res_dilations[DN_VOC_MAX_KERNELS][3];
+  int32_t dur_hidden; /* var_pred_hidden_dim, 0 = no duration predictor */
+  int32_t dtype;
+} DnVocConfig;
+/* Packed tensors (diffnorm_amd/vocoder.py::pack_vocoder; conv weights as above, biases / norms fp32):
+ *   dict fp32 [V, E];  conv_pre W, b;  per stage: the transposed conv as a 3-tap conv C -> u * C / 2 (polyphase repack: output frame
+ *   s u + r reads input frames s - 1, s, s + 1; needs k - u even and k <= 3 u, refused otherwise) W, b (repeated per phase), then per
+ *   ResBlock and pair c1 W, b, c2 W, b;  conv_post W, b;  with a predictor (always DN_F32): conv1 W, b, ln1 g, b, conv2 W, b, ln2 g, b,
+ *   proj w [H], b [1].                                                                                                        */
+int dn_voc_create(const DnVocConfig* cfg, const void* const* weights, int32_t n_weights, DnVoc** out);
+void dn_voc_destroy(DnVoc* m);
+int32_t dn_voc_upsample(const DnVoc* m); /* samples per frame: the product of the rates */
+size_t dn_voc_workspace_bytes(const DnVoc* m, int32_t B, int32_t Lmax0);
+/* VariancePredictor in fp32 whatever the engine's dtype: codes int32 [B, Tmax] (valid: 0 <= code < V), lengths int32 [B] ->
+ * durations int32 [B, Tmax] = max(round_half_even(exp(logd) - 1), 1) (0 behind a row's units) and sums int32 [B].  Workspace:
+ * dn_voc_workspace_bytes(m, B, Tmax).                                                                                          */
+int dn_voc_durations(DnVoc* m, const int32_t* codes, const int32_t* lengths, int32_t B, int32_t Tmax, int32_t* durations, int32_t* sums,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* Units -> waveform.  durations NULL: one frame per unit.  Lmax0 = the longest row's frame count (the caller reads `sums` back once
+ * per batch to size `wav`: the only synchronisation; a row with more frames is cut at Lmax0).  wav fp32 [B, Lmax0 * upsample],
+ * wav_lengths int32 [B]; samples behind a row's length are not written.  Workspace: dn_voc_workspace_bytes(m, B, max(Lmax0, Tmax)). */
+int dn_voc_forward(DnVoc* m, const int32_t* codes, const int32_t* lengths, const int32_t* durations, int32_t B, int32_t Tmax, int32_t Lmax0,
+                   float* wav, int32_t* wav_lengths, void* workspace, size_t workspace_bytes, void* stream);
+/* Stage timing of dn_voc_forward (tools/vocoder_bench.py): events recorded between the stages while switched on; dn_voc_stage_times
+ * waits for the last profiled forward and returns n_ups + 2 values in ms: embedding + conv_pre, each stage, conv_post.            */
+int dn_voc_set_profile(DnVoc* m, int32_t on);
+int dn_voc_stage_times(DnVoc* m, float* ms, int32_t cap);
+
 #ifdef __cplusplus
 }
 #endif
