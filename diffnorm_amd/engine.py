@@ -48,6 +48,23 @@ def _loop_flags(use_graph: bool, split: bool = False, keep_table: bool = False) 
     return (1 if use_graph else 0) | (2 if split else 0) | (4 if keep_table else 0)  # DN_LOOP_GRAPH | DN_LOOP_SPLIT2 | DN_LOOP_KEEP_TABLE
 
 
+def capture_graph(device, step) -> torch.cuda.CUDAGraph:
+    """`step()` captured into a hipGraph (torch.cuda.CUDAGraph over this library's launches on the capture stream); nothing runs.
+    Capture happens on a side stream forked behind the current one (the null stream cannot capture) and joined back, so a replay on
+    the current stream is ordered behind everything issued before this call.  The caller runs `step` eagerly once before (workspaces
+    and kernel attributes settle outside capture) and keeps what it touches alive as long as the graph."""
+    with torch.cuda.device(device):
+        cur = torch.cuda.current_stream()
+        side = torch.cuda.Stream(device=device)
+        side.wait_stream(cur)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(side):
+            with torch.cuda.graph(g, stream=side):
+                step()
+        cur.wait_stream(side)
+    return g
+
+
 class _Engine:
     def __init__(self, device, tensors: List[torch.Tensor]):
         self.device = _require_cuda(device)
@@ -335,17 +352,9 @@ class EpsEngine(_Engine):
             one_step()  # eager first step: settles workspaces and kernel attributes outside capture
             done = 1
             if use_graph and n_eval > 2:
-                cur = torch.cuda.current_stream()
-                side = torch.cuda.Stream(device=self.device)
-                side.wait_stream(cur)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.stream(side):
-                    with torch.cuda.graph(g, stream=side):
-                        one_step()
-                    done += 0  # (capture does not execute)
-                    for _ in range(n_eval - done):
-                        g.replay()
-                cur.wait_stream(side)
+                g = capture_graph(self.device, one_step)  # (capture does not execute)
+                for _ in range(n_eval - done):
+                    g.replay()
                 done = n_eval
             for _ in range(n_eval - done):
                 one_step()

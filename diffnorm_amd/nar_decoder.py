@@ -16,14 +16,18 @@ Classifier-free guidance (the reference's `nar_cg` evaluation: scripts/s2ut/eval
 nar_transformer.py:123-183) as one pass over 2 B rows, `NARS2UTDecoderModel.guided_mask_predict` the loop of nat_gen.py:192-236.
 """
 import ctypes as C
+import itertools
 import math
 from typing import Dict, List, Optional
 
 import torch
 
 from . import _lib, packing
-from .engine import _Engine, _dtype_code
+from .engine import _Engine, _dtype_code, capture_graph
 from .iterative_refinement import DecoderOut, cmlm_update
+
+
+_src_ids = itertools.count(1)  # enc["_src_id"]: one per `_ckv` that comes into being; what a captured iteration's source copy is keyed by
 
 
 def sinusoidal_table(num: int, dim: int, padding_idx: int) -> torch.Tensor:
@@ -162,14 +166,18 @@ class NarDecoderEngine(_Engine):
             self.lib.dn_nar_destroy(self.handle)
             self.handle = None
 
-    def _ws_for(self, B, T, S):
-        return self._aligned(self._workspace(int(self.lib.dn_nar_workspace_bytes(self.handle, B, T, S))))
+    def _pass_bytes(self, B, T, S, guided: bool = False) -> int:
+        size = self.lib.dn_nar_guided_workspace_bytes if guided else self.lib.dn_nar_workspace_bytes
+        return int(size(self.handle, B, T, S))
+
+    def _ws_for(self, B, T, S, guided: bool = False):
+        return self._aligned(self._workspace(self._pass_bytes(B, T, S, guided)))
 
     def cross_kv(self, enc_out: torch.Tensor) -> torch.Tensor:
         """enc_out fp32 [B, S, D] -> the layers' encoder-attention keys / values [layers, B, S, 2 D] (engine dtype; fp32 for bf16x3)."""
         B, S, D = enc_out.shape
         assert D == self.dim and enc_out.is_contiguous() and enc_out.dtype == torch.float32 and enc_out.device == self.device
-        tdt = torch.bfloat16 if self.dtype == _lib.DN_BF16 else torch.float16 if self.dtype == _lib.DN_F16 else torch.float32
+        tdt = self._kv_dtype
         raw = torch.empty(int(self.lib.dn_nar_cross_kv_bytes(self.handle, B, S)) + 256, dtype=torch.uint8, device=self.device)
         off = (-raw.data_ptr()) % 256
         ckv = raw[off: off + self.layers * B * S * 2 * D * tdt.itemsize].view(tdt).view(self.layers, B, S, 2 * D)
@@ -188,19 +196,31 @@ class NarDecoderEngine(_Engine):
                        "dn_nar_predict_lengths")
         return out
 
-    def forward(self, tokens: torch.Tensor, ckv: torch.Tensor, src_lengths: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """tokens int32 [B, T] -> logits fp32 [B, T, vocab]."""
+    @property
+    def _kv_dtype(self) -> torch.dtype:
+        return torch.bfloat16 if self.dtype == _lib.DN_BF16 else torch.float16 if self.dtype == _lib.DN_F16 else torch.float32
+
+    def _pass(self, guided: bool, tokens, ckv, src_lengths, out, workspace) -> torch.Tensor:
+        """One decoder pass, plain ([B, T, vocab]) or guided ([2, B, T, vocab]).  workspace: (aligned address, bytes) of the caller's,
+        else the engine's (which a larger later call re-allocates: a captured pass brings its own)."""
         B, T = tokens.shape
         S = ckv.shape[2]
         assert tokens.dtype == torch.int32 and tokens.is_contiguous() and ckv.is_contiguous() and ckv.shape[1] == B
         sl = src_lengths if (src_lengths.dtype == torch.int32 and src_lengths.device == self.device) else src_lengths.to(self.device, torch.int32)
-        logits = torch.empty(B, T, self.vocab, dtype=torch.float32, device=self.device) if out is None else out
-        assert logits.shape == (B, T, self.vocab) and logits.dtype == torch.float32 and logits.is_contiguous()
-        wp, wn = self._ws_for(B, T, S)
+        shape = ((2,) if guided else ()) + (B, T, self.vocab)
+        logits = torch.empty(shape, dtype=torch.float32, device=self.device) if out is None else out
+        assert logits.shape == shape and logits.dtype == torch.float32 and logits.is_contiguous()
+        wp, wn = self._ws_for(B, T, S, guided) if workspace is None else workspace
+        name = "dn_nar_decoder_forward_guided" if guided else "dn_nar_decoder_forward"
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.dn_nar_decoder_forward(self.handle, tokens.data_ptr(), ckv.data_ptr(), sl.contiguous().data_ptr(), B, T, S, logits.data_ptr(),
-                                                       wp, wn, _lib.current_stream()), "dn_nar_decoder_forward")
+            _lib.check(getattr(self.lib, name)(self.handle, tokens.data_ptr(), ckv.data_ptr(), sl.contiguous().data_ptr(), B, T, S, logits.data_ptr(),
+                                               wp, wn, _lib.current_stream()), name)
         return logits
+
+    def forward(self, tokens: torch.Tensor, ckv: torch.Tensor, src_lengths: torch.Tensor, out: Optional[torch.Tensor] = None,
+                workspace=None) -> torch.Tensor:
+        """tokens int32 [B, T] -> logits fp32 [B, T, vocab]."""
+        return self._pass(False, tokens, ckv, src_lengths, out, workspace)
 
 
     # ---- classifier-free guidance (nat_gen.py:196-236; cg_forward, nar_transformer.py:123-183)
@@ -222,24 +242,11 @@ class NarDecoderEngine(_Engine):
             self._null_tab = buf[off: off + self.layers * self.dim * 4].view(torch.float32).view(self.layers, self.dim)
         return self._null_tab
 
-    def _guided_ws(self, B, T, S):
-        return self._aligned(self._workspace(int(self.lib.dn_nar_guided_workspace_bytes(self.handle, B, T, S))))
-
     def forward_guided(self, tokens: torch.Tensor, ckv: torch.Tensor, src_lengths: torch.Tensor, out: Optional[torch.Tensor] = None,
                        workspace=None) -> torch.Tensor:
         """tokens int32 [B, T] -> logits fp32 [2, B, T, vocab]: [0] attends to the encoder (`ckv`), [1] to the null source.
-        `null_cross` must have run (the C entry refuses otherwise).  workspace: (aligned address, bytes) of the caller's, else the engine's."""
-        B, T = tokens.shape
-        S = ckv.shape[2]
-        assert tokens.dtype == torch.int32 and tokens.is_contiguous() and ckv.is_contiguous() and ckv.shape[1] == B
-        sl = src_lengths if (src_lengths.dtype == torch.int32 and src_lengths.device == self.device) else src_lengths.to(self.device, torch.int32)
-        logits = torch.empty(2, B, T, self.vocab, dtype=torch.float32, device=self.device) if out is None else out
-        assert logits.shape == (2, B, T, self.vocab) and logits.dtype == torch.float32 and logits.is_contiguous()
-        wp, wn = self._guided_ws(B, T, S) if workspace is None else workspace
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.dn_nar_decoder_forward_guided(self.handle, tokens.data_ptr(), ckv.data_ptr(), sl.contiguous().data_ptr(), B, T, S,
-                                                              logits.data_ptr(), wp, wn, _lib.current_stream()), "dn_nar_decoder_forward_guided")
-        return logits
+        `null_cross` must have run (the C entry refuses otherwise)."""
+        return self._pass(True, tokens, ckv, src_lengths, out, workspace)
 
     def guided_logits(self, tokens: torch.Tensor, ckv: torch.Tensor, src_lengths: torch.Tensor, cg_scale: float) -> torch.Tensor:
         """scaled_logits = cond + cg_scale * (cond - null) (nat_gen.py:223), fp32 [B, T, vocab] -- for callers and tests: the loop's
@@ -261,89 +268,55 @@ class _GivenEncoder:
         out = {"encoder_out": [x.index_select(1, order) for x in enc["encoder_out"]],
                "encoder_padding_mask": [x.index_select(0, order) for x in enc["encoder_padding_mask"]],
                "encoder_embedding": [], "encoder_states": [], "src_tokens": [], "src_lengths": []}
-        for k in ("_ckv", "_src_len"):  # engine-side caches travel with the rows
-            if k in enc:
-                out[k] = enc[k].index_select(1 if k == "_ckv" else 0, order).contiguous()
+        if "_ckv" in enc:  # engine-side caches travel with the rows, as a NEW source: the id is never inherited
+            out["_ckv"], out["_src_len"] = enc["_ckv"].index_select(1, order).contiguous(), enc["_src_len"].index_select(0, order).contiguous()
+            out["_src_id"] = next(_src_ids)
         return out
 
 
-class _RefineGraph:
-    """ONE refinement iteration of the mask-predict loop -- the decoder pass (about 70 launches) and the CMLM update with the
-    iteration index read from a device counter, then the counter's increment -- captured into a hipGraph (torch.cuda.CUDAGraph over
-    this library's launches on the capture stream) over static buffers and replayed: an iteration is one graph launch instead of
-    70 host launches.  Keyed by (B, T, S, max_step); the encoder-attention keys / values and source lengths are copied into the
-    static buffers when the caller's tensors change (once per utterance batch, or after the generator re-ordered a shrunken batch)."""
+class _IterationGraph:
+    """ONE iteration of a mask-predict loop -- the decoder pass (about 70 launches), the CMLM update with the iteration index read
+    from a device counter, the counter's increment -- captured into a hipGraph over static buffers and replayed: an iteration is one
+    graph launch.  Three forms:
+      scale set             the guided loop (nat_gen.py:196-236): the pass over 2 B rows, dn_cmlm_guided_step_dev (which writes the
+                            scores and never reads them: the reset of :197 is inside the kernel)
+      scale None, reset     the same loop without the null half (:225): the scores zeroed, the plain pass, dn_cmlm_step_dev
+      scale None, no reset  forward_decoder / refine: the plain pass, dn_cmlm_step_dev on the scores of the earlier iterations
+    Everything a captured launch touches is held here -- tokens, scores, predicted, step, logits, a copy of the encoder-attention
+    keys / values and source lengths, a workspace of its own (the engine's is re-allocated by a larger later call) -- except the
+    engine's packed weights and null table.  The source is copied when its id (`_src_id`, stamped where a `_ckv` comes into being)
+    differs from the one copied last: once per utterance batch or re-ordering, whatever addresses the allocator hands out."""
 
-    def __init__(self, model, B, T, S, max_step, ckv_like, slen_like):
+    def __init__(self, model, B, T, S, n_iters, scale, reset_scores):
         eng, dev = model.engine, model.device
-        self.tokens = torch.empty(B, T, dtype=torch.int32, device=dev)
-        self.scores = torch.empty(B, T, dtype=torch.float32, device=dev)
-        self.predicted = torch.empty(B, T, dtype=torch.int32, device=dev)
-        self.logits = torch.empty(B, T, eng.vocab, dtype=torch.float32, device=dev)
-        self.step = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.ckv, self.slen = torch.empty_like(ckv_like), torch.empty_like(slen_like)
-        self._src = (None, None)
-        self.max_step, self.model, self.graph = max_step, model, None
-
-    def bind(self, ckv, slen):
-        key = (ckv.data_ptr(), slen.data_ptr(), ckv._version, slen._version)
-        if key != self._src:
-            self.ckv.copy_(ckv)
-            self.slen.copy_(slen)
-            self._src = key
-
-    def _iteration(self):
-        m, eng = self.model, self.model.engine
-        eng.forward(self.tokens, self.ckv, self.slen, out=self.logits)
-        B, T, V = self.logits.shape
-        _lib.check(eng.lib.dn_cmlm_step_dev(self.logits.data_ptr(), self.tokens.data_ptr(), self.scores.data_ptr(), self.predicted.data_ptr(), B, T, V,
-                                            self.step.data_ptr(), int(self.max_step), int(m.unk), int(m.pad), _lib.current_stream()), "dn_cmlm_step_dev")
-        self.step.add_(1)
-
-    def run(self, n: int = 1):
-        """n iterations from the state in the static buffers (tokens, scores, step)."""
-        with torch.cuda.device(self.model.device):
-            if self.graph is None:
-                self._iteration()  # eager first: workspaces and kernel attributes settle outside capture
-                n -= 1
-                cur = torch.cuda.current_stream()
-                side = torch.cuda.Stream(device=self.model.device)
-                side.wait_stream(cur)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.stream(side):
-                    with torch.cuda.graph(g, stream=side):
-                        self._iteration()
-                cur.wait_stream(side)
-                self.graph = g
-            for _ in range(n):
-                self.graph.replay()
-
-
-class _GuidedGraph:
-    """ONE iteration of the guided loop (nat_gen.py:196-236) captured into a hipGraph and replayed: the score reset (:197 -- inside
-    the update kernel, which writes the scores and never reads them; a memset in the unguided form), the decoder pass over 2 B rows,
-    the guided update with the iteration index read from a device counter, the counter's increment.  scale None: the same loop
-    without the null half (:225) -- dn_nar_decoder_forward and dn_cmlm_step_dev on zeroed scores.  Keyed by the model on
-    (B, T, S, n_iters, scale, option nar_cg_fold).  The encoder-attention keys / values and the source lengths are COPIED into the
-    static buffers on every call: nothing here remembers a caller's addresses or tensor versions, so two encoder outputs that
-    happen to reuse one allocation cannot be confused.  The workspace is this graph's own (the engine's may be re-allocated by a
-    larger later call)."""
-
-    def __init__(self, model, B, T, S, n_iters, scale, ckv_like, slen_like):
-        eng, dev = model.engine, model.device
-        self.model, self.n_iters, self.scale, self.graph = model, int(n_iters), scale, None
+        self.model, self.n_iters, self.scale, self.reset_scores, self.graph = model, int(n_iters), scale, reset_scores, None
         self.tokens = torch.empty(B, T, dtype=torch.int32, device=dev)
         self.scores = torch.zeros(B, T, dtype=torch.float32, device=dev)
         self.predicted = torch.empty(B, T, dtype=torch.int32, device=dev)
-        self.logits = torch.empty(2 if scale is not None else 1, B, T, eng.vocab, dtype=torch.float32, device=dev)
         self.step = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.ckv, self.slen = torch.empty_like(ckv_like), torch.empty_like(slen_like)
-        size = eng.lib.dn_nar_guided_workspace_bytes if scale is not None else eng.lib.dn_nar_workspace_bytes
-        self._ws = torch.empty(int(size(eng.handle, B, T, S)) + 256, dtype=torch.uint8, device=dev)
+        self.logits = torch.empty(((2,) if scale is not None else ()) + (B, T, eng.vocab), dtype=torch.float32, device=dev)
+        self.ckv = torch.empty(eng.layers, B, S, 2 * eng.dim, dtype=eng._kv_dtype, device=dev)
+        self.slen = torch.empty(B, dtype=torch.int32, device=dev)
+        self._src_id = None
+        self._ws = torch.empty(eng._pass_bytes(B, T, S, scale is not None) + 256, dtype=torch.uint8, device=dev)
+
+    def load(self, enc, tokens, scores=None, step=None):
+        """The state the next run() starts from; `enc` has been through the model's _prepared()."""
+        if enc["_src_id"] != self._src_id:
+            self.ckv.copy_(enc["_ckv"])
+            self.slen.copy_(enc["_src_len"])
+            self._src_id = enc["_src_id"]
+        self.tokens.copy_(tokens)
+        if scores is not None:
+            self.scores.copy_(scores)
+        if step is None:
+            self.step.zero_()
+        else:
+            self.step.fill_(int(step))
 
     def _iteration(self):
         m, eng = self.model, self.model.engine
-        _, B, T, V = self.logits.shape
+        B, T, V = self.logits.shape[-3:]
         ws = eng._aligned(self._ws)
         args = (self.tokens.data_ptr(), self.scores.data_ptr(), self.predicted.data_ptr(), B, T, V, self.step.data_ptr(), self.n_iters, int(m.unk),
                 int(m.pad), _lib.current_stream())
@@ -351,41 +324,30 @@ class _GuidedGraph:
             eng.forward_guided(self.tokens, self.ckv, self.slen, out=self.logits, workspace=ws)
             _lib.check(eng.lib.dn_cmlm_guided_step_dev(self.logits.data_ptr(), float(self.scale), *args), "dn_cmlm_guided_step_dev")
         else:
-            self.scores.zero_()
-            _lib.check(eng.lib.dn_nar_decoder_forward(eng.handle, self.tokens.data_ptr(), self.ckv.data_ptr(), self.slen.data_ptr(), B, T, self.ckv.shape[2],
-                                                      self.logits.data_ptr(), ws[0], ws[1], _lib.current_stream()), "dn_nar_decoder_forward")
+            if self.reset_scores:
+                self.scores.zero_()
+            eng.forward(self.tokens, self.ckv, self.slen, out=self.logits, workspace=ws)
             _lib.check(eng.lib.dn_cmlm_step_dev(self.logits.data_ptr(), *args), "dn_cmlm_step_dev")
         self.step.add_(1)
 
-    def start(self, tokens, ckv, slen):
-        self.tokens.copy_(tokens)
-        self.ckv.copy_(ckv)
-        self.slen.copy_(slen)
-        self.step.zero_()
-
     def run(self, n: int = 1):
+        """n iterations from the state in the static buffers (tokens, scores, step)."""
         with torch.cuda.device(self.model.device):
             if self.graph is None:
                 self._iteration()  # eager first: kernel attributes settle outside capture
                 n -= 1
-                cur = torch.cuda.current_stream()
-                side = torch.cuda.Stream(device=self.model.device)
-                side.wait_stream(cur)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.stream(side):
-                    with torch.cuda.graph(g, stream=side):
-                        self._iteration()
-                cur.wait_stream(side)
-                self.graph = g
+                self.graph = capture_graph(self.model.device, self._iteration)
             for _ in range(n):
                 self.graph.replay()
 
 
 class NARS2UTDecoderModel:
     """forward_decoder / initialize_output_tokens / regenerate_length_beam of NARS2UTTransformerModel (:791-912) over the HIP decoder.
-    `use_graph` (default on): an iteration of `forward_decoder` runs as ONE captured hipGraph launch (_RefineGraph) instead of ~70
-    host launches -- same kernels on the same inputs, bit-identical results; `refine(state, enc, n)` runs n iterations back to back
-    with no host work in between (a generator without the adaptive early stop, and the benchmark)."""
+    `use_graph` (default on): an iteration of `forward_decoder` and of `guided_mask_predict` runs as ONE captured hipGraph launch
+    (_IterationGraph, one bounded cache for both loops) instead of ~70 host launches -- same kernels on the same inputs,
+    bit-identical results; `refine(state, enc, n)` runs n iterations back to back with no host work in between (a generator without
+    the adaptive early stop, and the benchmark).  The captured iteration decodes against its own copy of the encoder-attention keys /
+    values, refreshed whenever the encoder dict it is handed carries another `_src_id`."""
     allow_length_beam = True
 
     def __init__(self, decoder_state_dict, dim=512, ffn=2048, layers=6, heads=8, vocab=1004, pad=1, unk=3, dtype="bf16", device="cuda:0",
@@ -401,16 +363,18 @@ class NARS2UTDecoderModel:
         else:
             self.encoder = _GivenEncoder()
         self.pad, self.unk, self.eos, self.device = pad, unk, eos, self.engine.device
-        self.use_graph, self._graphs, self._guided_graphs = use_graph, {}, {}
+        self.use_graph, self._graphs = use_graph, {}
 
-    def _graph_for(self, B, T, ckv, slen, max_step) -> "_RefineGraph":
-        key = (B, T, ckv.shape[2], int(max_step))
+    def _graph_for(self, reset_scores: bool, B, T, S, n_iters, scale=None) -> "_IterationGraph":
+        """The captured iteration for everything a capture bakes in: (reset_scores, B, T, S, n_iters, scale[, nar_cg_fold, null table])."""
+        key = (bool(reset_scores), B, T, S, int(n_iters), scale)
+        if scale is not None:
+            key += (_lib.get_option("nar_cg_fold"), self.engine.null_generation)
         g = self._graphs.get(key)
         if g is None:
-            if len(self._graphs) >= 8:  # a generator whose batch keeps shrinking: keep the cache bounded
+            if len(self._graphs) >= 16:  # a generator whose batch keeps shrinking: keep the cache bounded, oldest out
                 self._graphs.pop(next(iter(self._graphs)))
-            g = self._graphs[key] = _RefineGraph(self, B, T, ckv.shape[2], max_step, ckv, slen)
-        g.bind(ckv, slen)
+            g = self._graphs[key] = _IterationGraph(self, B, T, S, n_iters, scale, reset_scores)
         return g
 
     def refine(self, decoder_out, encoder_out, n_iters: int):
@@ -418,10 +382,8 @@ class NARS2UTDecoderModel:
         in between: the captured iteration replayed while the device step counter advances.  -> the DecoderOut after them."""
         ckv, slen = self._prepared(encoder_out)
         B, T = decoder_out.output_tokens.shape
-        g = self._graph_for(B, T, ckv, slen, decoder_out.max_step)
-        g.tokens.copy_(decoder_out.output_tokens)
-        g.scores.copy_(decoder_out.output_scores)
-        g.step.fill_(int(decoder_out.step))
+        g = self._graph_for(False, B, T, ckv.shape[2], decoder_out.max_step)
+        g.load(encoder_out, decoder_out.output_tokens, decoder_out.output_scores, decoder_out.step)
         g.run(n_iters)
         return decoder_out._replace(output_tokens=g.tokens.long(), output_scores=g.scores.clone(), attn=None, step=decoder_out.step + n_iters)
 
@@ -446,13 +408,8 @@ class NARS2UTDecoderModel:
             eng.null_cross(null_token)
         keep = lambda t, sc, pr: history.append((t.long().clone(), sc.clone(), pr.long().clone())) if history is not None else None
         if self.use_graph:
-            key = (B, T, ckv.shape[2], int(n_iters), scale, _lib.get_option("nar_cg_fold"), eng.null_generation if scale is not None else None)
-            g = self._guided_graphs.get(key)
-            if g is None:
-                if len(self._guided_graphs) >= 8:
-                    self._guided_graphs.pop(next(iter(self._guided_graphs)))
-                g = self._guided_graphs[key] = _GuidedGraph(self, B, T, ckv.shape[2], n_iters, scale, ckv, slen)
-            g.start(tok, ckv, slen)
+            g = self._graph_for(True, B, T, ckv.shape[2], n_iters, scale)
+            g.load(encoder_out, tok)
             if history is None:
                 g.run(int(n_iters))
             else:
@@ -491,6 +448,7 @@ class NARS2UTDecoderModel:
             enc["_src_len"] = ((~pad).sum(1) if pad is not None else torch.full((B,), S)).to(self.device, torch.int32)
             enc["_ckv"] = self.engine.cross_kv(x)
             enc["_bsd"] = x
+            enc["_src_id"] = next(_src_ids)
         return enc["_ckv"], enc["_src_len"]
 
     def initialize_output_tokens(self, encoder_out, src_lengths, true_length=None):
@@ -523,10 +481,8 @@ class NARS2UTDecoderModel:
         step, max_step, history = decoder_out.step, decoder_out.max_step, decoder_out.history
         if self.use_graph:
             B, T = decoder_out.output_tokens.shape
-            g = self._graph_for(B, T, ckv, slen, max_step)
-            g.tokens.copy_(decoder_out.output_tokens)
-            g.scores.copy_(decoder_out.output_scores)
-            g.step.fill_(int(step))
+            g = self._graph_for(False, B, T, ckv.shape[2], max_step)
+            g.load(encoder_out, decoder_out.output_tokens, decoder_out.output_scores, step)
             g.run(1)
             if history is not None:
                 history.append(g.predicted.long())

@@ -225,7 +225,7 @@ def test_graph_copies_the_source_on_every_call(golden):
         for i in range(len(eager)):
             for a, b in zip(eager[i], graph[i]):
                 assert torch.equal(a, b), i
-    assert sum(1 for k in model("f32", True)._guided_graphs if k[4] == 3.0) == 1  # one capture served the three sources
+    assert sum(1 for k in model("f32", True)._graphs if k[5] == 3.0) == 1  # one capture served the three sources
 
 
 @pytest.mark.parametrize("use_graph", [False, True])
