@@ -119,6 +119,20 @@ class NarEncConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("input_dim", "conv_channels", "kernel", "dim", "ffn", "layers", "heads", "max_pos", "pad", "dtype")]
 
 
+class ConformerEncConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("input_dim", "conv_channels", "kernel", "dim", "ffn", "layers", "heads", "depthwise_kernel", "max_frames",
+                                         "dtype")]
+
+
+class RelAttnParams(C.Structure):
+    _fields_ = [("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("out", C.c_void_p),
+                ("ldq", C.c_int32), ("ldk", C.c_int32), ("ldv", C.c_int32), ("ldo", C.c_int32),
+                ("B", C.c_int32), ("T", C.c_int32), ("heads", C.c_int32), ("dim_head", C.c_int32),
+                ("dtype", C.c_int32), ("ldp", C.c_int32), ("lengths", C.c_void_p),
+                ("scale", C.c_float), ("pos_zero_row", C.c_int32), ("pos", C.c_void_p), ("bias_u", C.c_void_p), ("bias_v", C.c_void_p),
+                ("pos_rows", C.c_int32), ("pad_", C.c_int32)]
+
+
 class VocConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("embedding_dim", "num_embeddings", "initial_channel", "n_ups")] + \
                [("up_rates", C.c_int32 * 8), ("up_kernels", C.c_int32 * 8), ("n_kernels", C.c_int32), ("res_kernels", C.c_int32 * 4),
@@ -289,6 +303,12 @@ SYMBOLS = {
     "dn_nar_encoder_out_frames": (_i32, [_i32]),
     "dn_nar_encoder_workspace_bytes": (_sz, [_vp, _i32, _i32]),
     "dn_nar_encoder_forward": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "dn_rel_attention": (C.c_int, [C.POINTER(RelAttnParams), _vp]),
+    "dn_glu_dwconv": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "dn_conformer_encoder_create": (C.c_int, [_vp, _vp, _i32, _vp]),
+    "dn_conformer_encoder_destroy": (None, [_vp]),
+    "dn_conformer_encoder_workspace_bytes": (_sz, [_vp, _i32, _i32]),
+    "dn_conformer_encoder_forward": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "dn_last_error": (C.c_char_p, []),
     "dn_version": (C.c_int, []),
     "dn_cmlm_step_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),

@@ -19,41 +19,6 @@ using namespace dn;
 
 namespace dn {
 
-__device__ __forceinline__ void store_act(void* p, int64_t off, int dtype, float v) {
-  if (dtype == DN_BF16X3) store1_split(p, off, v);
-  else if (dn_is16(dtype)) reinterpret_cast<uint16_t*>(p)[off] = to_h16(dtype, v);
-  else reinterpret_cast<float*>(p)[off] = v;
-}
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// Rows of the contraction that IS a Conv1d(k, stride 2, padding k / 2) over [B, Lin, C]: cols[b * Lout + t][j * C + c] = in[b][2 t + j - k / 2][c]
-// (zero outside [0, Lin); columns >= k * C zero: the K padding).  GLU: `in` is the previous conv's output [B, Lin, 2 C] and the gathered
-// value is a * sigmoid(g) with a = in[..][c], g = in[..][C + c] (F.glu over the channels, convolution.py:56).  The whole PADDED batch is
-// convolved, frames behind an utterance's end included, as upstream.
-template <bool GLU>
-__global__ __launch_bounds__(256) void strided_rows_kernel(const float* __restrict__ in, int B, int Lin, int Lout, int C, int k, int Kp,
-                                                           void* __restrict__ cols, int dtype) {
-  const int64_t n = (int64_t)B * Lout * Kp;
-  const int ld_in = GLU ? 2 * C : C;
-  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const int col = (int)(i % Kp);
-    const int64_t row = i / Kp;
-    const int t = (int)(row % Lout), b = (int)(row / Lout);
-    float v = 0.f;
-    if (col < k * C) {
-      const int j = col / C, c = col - j * C;
-      const int src = 2 * t + j - k / 2;
-      if (src >= 0 && src < Lin) {
-        const float* r = in + ((int64_t)b * Lin + src) * ld_in;
-        v = GLU ? r[c] * sigmoidf_(r[C + c]) : r[c];
-      }
-    }
-    store_act(cols, i, dtype, v);
-  }
-}
-
-__device__ __forceinline__ int subsampled_len(int len) { return len <= 0 ? 0 : (len - 1) / 2 + 1; }  // floor((len - 1) / 2 + 1), convolution.py:45-49
-
 // x[b, t, :] = sqrt(D) * glu(y[b, t, :]) + P[pos], pos = pad + 1 + t for t < len2[b] and `pad` (the zero row) behind it: make_positions on the
 // padding mask itself (s2t_transformer.py:347-351; fairseq/utils.py:256-266).  Also writes the subsampled lengths.
 __global__ __launch_bounds__(256) void enc_embed_kernel(const float* __restrict__ y, const int32_t* __restrict__ src_len, int n_conv, int B, int S, int D,

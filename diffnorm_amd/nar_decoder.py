@@ -132,12 +132,146 @@ class NarEncoderEngine(_Engine):
         return out, lens
 
 
+def rel_pos_table(max_frames: int, dim: int) -> torch.Tensor:
+    """RelPositionalEncoding's table (fairseq/modules/positional_encoding.py:94-112) for the offsets d = -(max_frames - 1) ..
+    max_frames - 1, offset d at row max_frames - 1 + d: pe(d)[2m] = sin(d w_m), pe(d)[2m+1] = cos(d w_m), w_m = exp(-2m ln(1e4) / dim),
+    built in FLOAT32 like upstream (`position * div_term` in float32 included; -1 * position * div_term = (-position) * div_term exactly)."""
+    d = torch.arange(-(max_frames - 1), max_frames, dtype=torch.float32).unsqueeze(1)
+    div = torch.exp(torch.arange(0, dim, 2, dtype=torch.float32) * -(math.log(10000.0) / dim))
+    pe = torch.zeros(2 * max_frames - 1, dim)
+    pe[:, 0::2] = torch.sin(d * div)
+    pe[:, 1::2] = torch.cos(d * div)
+    return pe
+
+
+def fold_batch_norm(w: torch.Tensor, gamma, beta, mean, var, eps: float = 1e-5):
+    """Depthwise Conv1d weight [C, 1, k] (no bias) followed by BatchNorm1d in eval mode -> (w' [C, k], shift [C]) with
+    BatchNorm(conv_w(x)) = conv_w'(x) + shift: w' = w gamma / sqrt(var + eps), shift = beta - mean gamma / sqrt(var + eps)."""
+    s = gamma / torch.sqrt(var + eps)
+    return (w[:, 0, :] * s[:, None]).contiguous(), (beta - mean * s).contiguous()
+
+
+def check_conformer_args(attn_type="espnet", pos_enc_type="rel_pos", conv_version="s2t_transformer", depthwise_kernel=31):
+    """What of S2TConformerEncoder's variants the engine runs; the rest is refused here, on the host."""
+    if attn_type != "espnet":
+        raise ValueError(f"conformer encoder: attn_type {attn_type!r} (the fairseq MultiheadAttention variant) is not supported, only 'espnet'")
+    if pos_enc_type != "rel_pos":
+        raise ValueError(f"conformer encoder: pos_enc_type {pos_enc_type!r} is not supported, only 'rel_pos'")
+    if conv_version != "s2t_transformer":
+        raise ValueError(f"conformer encoder: conv_version {conv_version!r} (Conv2dSubsampler) is not supported, only 's2t_transformer'")
+    if depthwise_kernel % 2 != 1 or not 1 <= depthwise_kernel <= 63:
+        raise ValueError(f"conformer encoder: depthwise kernel {depthwise_kernel} must be odd ('same' padding) and <= 63")
+
+
+def pack_conformer_encoder(sd: Dict[str, torch.Tensor], input_dim: int, conv_channels: int, kernel: int, dim: int, ffn: int, layers: int, heads: int,
+                           depthwise_kernel: int, max_frames: int, dtype: int, attn_type: str = "espnet", pos_enc_type: str = "rel_pos",
+                           conv_version: str = "s2t_transformer") -> List[torch.Tensor]:
+    """Reference-named encoder state dict (S2TConformerEncoder.state_dict(), attn_type espnet + pos_enc_type rel_pos) -> the tensor
+    table of dn_conformer_encoder_create (include/diffnorm_hip.h).  The BatchNorm of the convolution module is folded into the
+    depthwise weights, the half step of the two FFNs into w_2 (a factor 0.5: exact in every arithmetic)."""
+    check_conformer_args(attn_type, pos_enc_type, conv_version, depthwise_kernel)
+    if any("spk_emb_proj" in k for k in sd):
+        raise ValueError("conformer encoder: the target-speaker projection (spk_emb_proj) is not supported")
+    if any(".self_attn.q_proj." in k for k in sd):
+        raise ValueError("conformer encoder: this state dict holds fairseq MultiheadAttention layers; only attn_type 'espnet' is supported")
+    if "subsample.conv_layers.0.weight" not in sd:
+        raise ValueError("conformer encoder: no Conv1dSubsampler in the state dict (conv_version 'convtransformer' is not supported)")
+    if "conformer_layers.0.self_attn.linear_pos.weight" not in sd:
+        raise ValueError("conformer encoder: no linear_pos in the state dict: only pos_enc_type 'rel_pos' is supported")
+    g = lambda k: sd[k].float()
+    mat = lambda w: packing._mat(w, dtype, cols=w.shape[1])
+    stack = lambda items: torch.stack(items).contiguous()
+
+    def conv_mat(w, cols=None):  # as pack_nar_encoder
+        w2 = w.permute(0, 2, 1).reshape(w.shape[0], -1)
+        return packing._mat(w2, dtype, cols=cols or w2.shape[1])
+
+    c0, c1 = g("subsample.conv_layers.0.weight"), g("subsample.conv_layers.1.weight")
+    assert c0.shape == (conv_channels, input_dim, kernel) and c1.shape == (2 * dim, conv_channels // 2, kernel), (c0.shape, c1.shape)
+    names = ("f1w1", "f1b1", "f1w2", "f1b2", "f2w1", "f2b1", "f2w2", "f2b2", "qkvW", "qkvb", "posW", "outW", "outb", "u", "v", "pw1", "dww", "dws",
+             "pw2", "lng", "lnb")
+    t = {n: [] for n in names}
+    for l in range(layers):
+        p = f"conformer_layers.{l}."
+        for tag, ff in (("f1", "ffn1."), ("f2", "ffn2.")):
+            t[tag + "w1"].append(mat(g(p + ff + "w_1.weight"))); t[tag + "b1"].append(g(p + ff + "w_1.bias"))
+            t[tag + "w2"].append(mat(0.5 * g(p + ff + "w_2.weight"))); t[tag + "b2"].append(0.5 * g(p + ff + "w_2.bias"))
+        sa, cm = p + "self_attn.", p + "conv_module."
+        t["qkvW"].append(mat(torch.cat([g(sa + "linear_q.weight"), g(sa + "linear_k.weight"), g(sa + "linear_v.weight")])))
+        t["qkvb"].append(torch.cat([g(sa + "linear_q.bias"), g(sa + "linear_k.bias"), g(sa + "linear_v.bias")]))
+        t["posW"].append(mat(g(sa + "linear_pos.weight")))
+        t["outW"].append(mat(g(sa + "linear_out.weight"))); t["outb"].append(g(sa + "linear_out.bias"))
+        u, v = g(sa + "pos_bias_u"), g(sa + "pos_bias_v")
+        assert u.shape == v.shape == (heads, dim // heads), u.shape
+        t["u"].append(u.reshape(-1)); t["v"].append(v.reshape(-1))
+        dw = g(cm + "depthwise_conv.weight")
+        if dw.shape != (dim, 1, depthwise_kernel) or (cm + "depthwise_conv.bias") in sd or (cm + "pointwise_conv1.bias") in sd:
+            raise ValueError(f"conformer encoder: depthwise conv {tuple(dw.shape)} (expected {(dim, 1, depthwise_kernel)}, no conv biases)")
+        w, shift = fold_batch_norm(dw, g(cm + "batch_norm.weight"), g(cm + "batch_norm.bias"), g(cm + "batch_norm.running_mean"),
+                                   g(cm + "batch_norm.running_var"))
+        t["pw1"].append(mat(g(cm + "pointwise_conv1.weight")[:, :, 0])); t["dww"].append(w); t["dws"].append(shift)
+        t["pw2"].append(mat(g(cm + "pointwise_conv2.weight")[:, :, 0]))
+        order = ("ffn1.layer_norm", "self_attn_layer_norm", "conv_module.layer_norm", "ffn2.layer_norm", "final_layer_norm")
+        t["lng"].append(torch.stack([g(p + n + ".weight") for n in order])); t["lnb"].append(torch.stack([g(p + n + ".bias") for n in order]))
+    pe = packing._arith(rel_pos_table(max_frames, dim), dtype, weight=False)
+    return [conv_mat(c0, cols=packing.padk(kernel * input_dim)), g("subsample.conv_layers.0.bias").contiguous(), conv_mat(c1),
+            g("subsample.conv_layers.1.bias").contiguous(), mat(g("linear.weight")), g("linear.bias").contiguous(), pe] + \
+           [stack(t[n]) for n in names] + [torch.zeros(2 * dim)]
+
+
+class ConformerEncoderEngine(_Engine):
+    """dn_conformer_encoder_* of libdiffnorm_hip.so: the Conformer speech encoder of the recipe's NAR S2UT model (S2SConformerEncoder,
+    research/TranSpeech/nar_conformer.py:42-74, attn_type espnet + pos_enc_type rel_pos, no speaker embedding), eval mode."""
+
+    def __init__(self, state_dict, input_dim=80, conv_channels=1024, kernel=5, dim=512, ffn=2048, layers=12, heads=8, depthwise_kernel=31,
+                 max_source_positions=6000, dtype="bf16", device="cuda:0", attn_type="espnet", pos_enc_type="rel_pos",
+                 conv_version="s2t_transformer"):
+        self.dim, self.input_dim = dim, input_dim
+        self.dtype = _dtype_code(dtype)
+        max_frames = ((max_source_positions - 1) // 2 + 1 - 1) // 2 + 1  # frames of the longest source behind the two stride-2 layers
+        super().__init__(device, pack_conformer_encoder(state_dict, input_dim, conv_channels, kernel, dim, ffn, layers, heads, depthwise_kernel,
+                                                        max_frames, self.dtype, attn_type, pos_enc_type, conv_version))
+        cfg = _lib.ConformerEncConfig(input_dim, conv_channels, kernel, dim, ffn, layers, heads, depthwise_kernel, max_frames, self.dtype)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.dn_conformer_encoder_create(C.byref(cfg), self._table, len(self.tensors), C.byref(self.handle)),
+                       "dn_conformer_encoder_create")
+
+    def __del__(self):
+        if getattr(self, "handle", None) is not None and self.handle.value:
+            self.lib.dn_conformer_encoder_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def workspace_bytes(self, B: int, L: int) -> int:
+        return int(self.lib.dn_conformer_encoder_workspace_bytes(self.handle, B, L))
+
+    def forward(self, feats: torch.Tensor, src_lengths: torch.Tensor):
+        """feats [B, L, input_dim], src_lengths [B] (each >= 1) -> (enc_out fp32 [B, S, dim] batch-major, lengths int32 [B]).
+        Lengths on the host are checked here; lengths already on the device are not read back (no synchronisation, as
+        NarEncoderEngine.forward): an empty utterance there is the caller's to exclude -- the kernels stay inside their tensors (the
+        attention treats it as one key) but its rows mean nothing."""
+        B, L, Fd = feats.shape
+        assert Fd == self.input_dim
+        src_lengths = torch.as_tensor(src_lengths)
+        if src_lengths.device.type == "cpu" and int(src_lengths.min()) < 1:
+            raise ValueError("ConformerEncoderEngine.forward: an empty utterance has no attention softmax")
+        feats = feats.to(self.device, torch.float32).contiguous()
+        sl = src_lengths.to(self.device, torch.int32).contiguous()
+        S = int(self.lib.dn_nar_encoder_out_frames(L))
+        out = torch.empty(B, S, self.dim, dtype=torch.float32, device=self.device)
+        lens = torch.empty(B, dtype=torch.int32, device=self.device)
+        wp, wn = self._aligned(self._workspace(self.workspace_bytes(B, L)))
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.dn_conformer_encoder_forward(self.handle, feats.data_ptr(), sl.data_ptr(), B, L, out.data_ptr(), lens.data_ptr(), wp,
+                                                             wn, _lib.current_stream()), "dn_conformer_encoder_forward")
+        return out, lens
+
+
 class _HipEncoder:
     """`model.encoder` of the NAR S2UT model on the HIP engine: __call__(src_tokens [B, L, 80], src_lengths) -> the reference's encoder
     dict (encoder_out [S, B, D], encoder_padding_mask [B, S] -- an empty list when nothing is padded, s2t_transformer.py:364-373), with
     the batch-major copy and the subsampled lengths the decoder engine wants riding along; reorder_encoder_out as upstream (:387-420)."""
 
-    def __init__(self, engine: "NarEncoderEngine"):
+    def __init__(self, engine):  # a NarEncoderEngine or a ConformerEncoderEngine
         self.engine = engine
 
     def __call__(self, src_tokens, src_lengths=None):
@@ -351,15 +485,18 @@ class NARS2UTDecoderModel:
     allow_length_beam = True
 
     def __init__(self, decoder_state_dict, dim=512, ffn=2048, layers=6, heads=8, vocab=1004, pad=1, unk=3, dtype="bf16", device="cuda:0",
-                 use_graph: bool = True, encoder_state_dict=None, encoder_kw=None, eos: int = 2):
+                 use_graph: bool = True, encoder_state_dict=None, encoder_kw=None, eos: int = 2, encoder_arch: str = "transformer"):
         """encoder_state_dict (S2TTransformerEncoder.state_dict() names; encoder_kw = NarEncoderEngine's sizes): with it `forward_encoder`
         runs the speech encoder on the HIP engine from [B, L, 80] features, as NARS2UTTransformerModel.forward_encoder does (:566-567);
-        without it the encoder output is a tensor the caller supplies."""
+        without it the encoder output is a tensor the caller supplies.  encoder_arch "conformer": the state dict is
+        S2TConformerEncoder.state_dict()'s and encoder_kw ConformerEncoderEngine's sizes (the recipe's --arch nar_s2ut_conformer)."""
+        if encoder_arch not in ("transformer", "conformer"):
+            raise ValueError(f"encoder_arch {encoder_arch!r}: 'transformer' or 'conformer'")
         self.engine = NarDecoderEngine(decoder_state_dict, dim, ffn, layers, heads, vocab, pad=pad, dtype=dtype, device=device)
         if encoder_state_dict is not None:
             kw = dict(dim=dim, heads=heads, dtype=dtype, device=device)
             kw.update(encoder_kw or {})
-            self.encoder = _HipEncoder(NarEncoderEngine(encoder_state_dict, **kw))
+            self.encoder = _HipEncoder((ConformerEncoderEngine if encoder_arch == "conformer" else NarEncoderEngine)(encoder_state_dict, **kw))
         else:
             self.encoder = _GivenEncoder()
         self.pad, self.unk, self.eos, self.device = pad, unk, eos, self.engine.device

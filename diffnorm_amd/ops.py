@@ -136,6 +136,48 @@ def attention(q, k, v, out, B, T, heads, dim_head, lengths: Optional[torch.Tenso
     return out
 
 
+def rel_attention(q, k, v, pos, bias_u, bias_v, lengths, heads: int, pos_zero_row: int, x3: bool = False):
+    """dn_rel_attention: q, k, v [B, T, heads * dk] and pos [rows, heads * dk] (offset d at row pos_zero_row + d) in one element type
+    (fp32, bf16 or fp16; x3: fp32 tensors, DN_BF16X3 mode), bias_u / bias_v fp32 [heads, dk], lengths int32 [B] (each in [1, T]) or
+    None -> out [B, T, heads * dk] in that type (x3: fp32, read back from the split rows)."""
+    from . import packing
+
+    B, T, hd = q.shape
+    if T < 1 or (lengths is not None and (int(lengths.min()) < 1 or int(lengths.max()) > T)):
+        raise ValueError("rel_attention: every sequence needs between 1 and T keys")
+    if pos_zero_row < T - 1 or pos_zero_row + T > pos.shape[0]:
+        raise ValueError(f"rel_attention: the position table ({pos.shape[0]} rows, offset 0 at {pos_zero_row}) does not hold offsets -{T - 1} .. {T - 1}")
+    q, k, v, pos = (t.contiguous() for t in (q, k, v, pos))
+    a = _lib.RelAttnParams()
+    a.dtype = _lib.DN_BF16X3 if x3 else _code(q)
+    out = torch.empty((B, T, 2 * hd), dtype=torch.bfloat16, device=q.device) if x3 else torch.empty_like(q)
+    a.q, a.k, a.v, a.out, a.pos = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), pos.data_ptr()
+    a.ldq = a.ldk = a.ldv = a.ldo = a.ldp = hd
+    a.B, a.T, a.heads, a.dim_head = B, T, heads, hd // heads
+    a.lengths = _lib.ptr(None if lengths is None else lengths.to(q.device, torch.int32).contiguous())
+    a.scale, a.pos_zero_row, a.pos_rows = (hd // heads) ** -0.5, pos_zero_row, pos.shape[0]
+    bu, bv = bias_u.to(q.device, torch.float32).contiguous(), bias_v.to(q.device, torch.float32).contiguous()
+    a.bias_u, a.bias_v = bu.data_ptr(), bv.data_ptr()
+    _lib.check(_lib.load().dn_rel_attention(C.byref(a), _stream()), "dn_rel_attention")
+    return packing.unsplit_rows(out) if x3 else out
+
+
+def glu_dwconv(x, w, shift, dtype: Optional[int] = None):
+    """dn_glu_dwconv: x [B, S, 2 C] (fp32 in DN_BF16X3), w fp32 [C, k], shift fp32 [C] -> swish(depthwise_conv(glu(x)) + shift)
+    [B, S, C] in x's type (DN_BF16X3: fp32, read back from the split rows)."""
+    from . import packing
+
+    B, S, C2 = x.shape
+    Cc, k = w.shape
+    assert C2 == 2 * Cc and w.dtype == shift.dtype == torch.float32
+    code = _code(x) if dtype is None else dtype
+    x3 = code == _lib.DN_BF16X3
+    out = torch.empty((B, S, 2 * Cc), dtype=torch.bfloat16, device=x.device) if x3 else torch.empty((B, S, Cc), dtype=x.dtype, device=x.device)
+    x, w, shift = x.contiguous(), w.contiguous(), shift.contiguous()
+    _lib.check(_lib.load().dn_glu_dwconv(x.data_ptr(), w.data_ptr(), shift.data_ptr(), out.data_ptr(), B, S, Cc, k, code, _stream()), "dn_glu_dwconv")
+    return packing.unsplit_rows(out) if x3 else out
+
+
 def rmsnorm(x, out, T, D=None, gamma=None, gamma_beta=None, gb_shared=False, gb_half=0):
     lib = _lib.load()
     M = x.numel() // x.shape[-1]

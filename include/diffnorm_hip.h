@@ -1066,6 +1066,73 @@ size_t dn_nar_encoder_workspace_bytes(const DnNarEnc* m, int32_t B, int32_t L);
 int dn_nar_encoder_forward(DnNarEnc* m, const float* feats, const int32_t* src_lengths, int32_t B, int32_t L, float* enc_out,
                            int32_t* out_lengths, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ the Conformer speech encoder of the recipe's model */
+/* Key-masked multi-head self-attention with Transformer-XL relative positions, flash-style (csrc/rel_attention.hip).  Replaces
+ * RelPositionMultiHeadedAttention.forward (fairseq/modules/espnet_multihead_attention.py:109-196; rel_shift :120-145, zero_triu False)
+ * between linear_q / linear_k / linear_v / linear_pos and linear_out, and the [B, H, T, 2T - 1] matrix_bd it builds:
+ *   score[i, j] = ((q_i + u_h) . k_j + (q_i + v_h) . pos[pos_zero_row + i - j]_h) * scale,  keys j >= lengths[b] masked,  out = softmax V.
+ * q, k, v, out as DnAttnParams' (row m = b*T + t, head h at columns [h*dh, (h+1)*dh)); dtype is the element type of q, k, v, pos and
+ * out, except DN_BF16X3: q, k, v, pos plain fp32 (what dn_conv_gemm stores beside its split rows), out in split rows, arithmetic
+ * the fp32 form.  DN_F16 / DN_BF16: 2-byte MFMA operands, fp32 accumulation and softmax, q + u and q + v formed in fp32 and rounded
+ * once.  dim_head 16, 32 or 64; T >= 1; every lengths[b] in [1, T] (an empty sequence has no softmax: callers refuse it).  No
+ * buffer of size O(T^2) exists in any mode.  A sequence's result depends on nothing but its own rows, lengths[b] and T.        */
+typedef struct {
+  const void* q; const void* k; const void* v; void* out;
+  int32_t ldq, ldk, ldv, ldo;
+  int32_t B, T, heads, dim_head;
+  int32_t dtype;
+  int32_t ldp;             /* row stride of pos */
+  const int32_t* lengths;  /* [B] or NULL (no mask) */
+  float scale;             /* dim_head ** -0.5 */
+  int32_t pos_zero_row;    /* the row of pos that holds offset 0: offset d = i - j is row pos_zero_row + d, so one table built for the
+                              longest T serves every shorter batch; rows pos_zero_row - (T-1) .. pos_zero_row + (T-1) must exist
+                              (refused otherwise, see pos_rows)                                                                   */
+  const void* pos;         /* linear_pos(pe): one row per offset, head h at columns [h*dh, (h+1)*dh) */
+  const float* bias_u;     /* pos_bias_u fp32 [heads, dim_head] */
+  const float* bias_v;     /* pos_bias_v fp32 [heads, dim_head] */
+  int32_t pos_rows;        /* rows of pos: pos_zero_row - (T-1) >= 0 and pos_zero_row + (T-1) < pos_rows are checked on the host */
+  int32_t pad_;
+} DnRelAttnParams;
+int dn_rel_attention(const DnRelAttnParams* p, void* stream);
+
+/* The middle of the Conformer convolution module in one pass (ConvolutionModule.forward, fairseq/modules/conformer_layer.py:77-99: glu,
+ * depthwise_conv, batch_norm in eval mode, activation):
+ *   out[b,t,c] = swish(sum_j w[c][j] * glu(x)[b, t + j - k/2, c] + shift[c]),   glu(x)[..,c] = x[..,c] * sigmoid(x[.., C + c]),
+ * taps outside [0, S) zero; NO length mask, as upstream.  x [B*S, 2C] in `dtype` (fp32 in DN_BF16X3), w fp32 [C, k] and shift fp32 [C]
+ * with the BatchNorm folded in by the host (w * gamma / sqrt(var + eps), beta - mean * gamma / sqrt(var + eps)); fp32 accumulation;
+ * out [B*S, C] in `dtype` (split rows in DN_BF16X3).  k odd, <= 63; C a multiple of 64.                                          */
+int dn_glu_dwconv(const void* x, const float* w, const float* shift, void* out, int32_t B, int32_t S, int32_t C, int32_t k, int32_t dtype,
+                  void* stream);
+
+/* S2SConformerEncoder (research/TranSpeech/nar_conformer.py:42-74; no speaker embedding) = S2TConformerEncoder._forward
+ * (fairseq/models/speech_to_text/s2t_conformer.py:91-137), eval mode, attn_type espnet + pos_enc_type rel_pos: Conv1dSubsampler ->
+ * sqrt(dim) scaling -> linear -> `layers` ConformerEncoderLayers (fairseq/modules/conformer_layer.py:229-284); no final LayerNorm.
+ * Packed tensors (diffnorm_amd/nar_decoder.py::pack_conformer_encoder; matrices [rows -> 128][K] in cfg.dtype, the rest fp32):
+ *   0 conv0_W  1 conv0_b  2 conv1_W  3 conv1_b (as dn_nar_encoder_create)   4 linear_W [dim][dim]  5 linear_b
+ *   6 pe [2 max_frames - 1][dim] in cfg.dtype as an A operand (split rows in DN_BF16X3): RelPositionalEncoding's table
+ *     (fairseq/modules/positional_encoding.py:94-112), offset d at row max_frames - 1 + d
+ *   7 ffn1.w_1 [layers][ffn][dim]  8 its bias  9 0.5 * ffn1.w_2 [layers][dim][ffn]  10 0.5 * its bias   11-14 ffn2 likewise
+ *   15 qkv_W [layers][3 dim][dim] (linear_q ; linear_k ; linear_v)  16 qkv_b  17 linear_pos_W [layers][dim][dim]
+ *   18 linear_out_W  19 linear_out_b  20 pos_bias_u [layers][dim]  21 pos_bias_v
+ *   22 pointwise_conv1_W [layers][2 dim][dim]  23 depthwise w [layers][dim][depthwise_kernel] and 24 shift [layers][dim], BatchNorm folded
+ *   25 pointwise_conv2_W [layers][dim][dim]  26 ln_g [layers][5][dim] (ffn1 ; self_attn ; conv_module ; ffn2 ; final)  27 ln_b
+ *   28 zeros [2 dim] (the bias of the bias-free projections)
+ * linear_pos(pe) of a layer is formed inside the forward, in front of that layer's attention, into one workspace buffer.           */
+typedef struct DnConformerEnc DnConformerEnc;
+typedef struct {
+  int32_t input_dim, conv_channels, kernel, dim, ffn, layers, heads, depthwise_kernel;
+  int32_t max_frames; /* the longest S (frames after the subsampler) the packed position table serves */
+  int32_t dtype;
+} DnConformerEncConfig;
+int dn_conformer_encoder_create(const DnConformerEncConfig* cfg, const void* const* weights, int32_t n_weights, DnConformerEnc** out);
+void dn_conformer_encoder_destroy(DnConformerEnc* m);
+size_t dn_conformer_encoder_workspace_bytes(const DnConformerEnc* m, int32_t B, int32_t L);
+/* As dn_nar_encoder_forward: feats fp32 [B, L, input_dim], src_lengths int32 [B] -> enc_out fp32 [B, S, dim] batch-major (S =
+ * dn_nar_encoder_out_frames(L)), out_lengths int32 [B].  Every one of the B * S rows is computed: the convolution module is not
+ * masked upstream, so an utterance's output depends on how far its batch is padded, here as there; only attention keys are masked. */
+int dn_conformer_encoder_forward(DnConformerEnc* m, const float* feats, const int32_t* src_lengths, int32_t B, int32_t L, float* enc_out,
+                                 int32_t* out_lengths, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ CodeHiFiGAN unit vocoder: units -> waveform, batched */
 /* CodeHiFiGANVocoder.forward (fairseq/models/text_to_speech/vocoder.py:214-235) = CodeGenerator (codehifigan.py) over the HiFiGAN
  * Generator (hifigan.py) with the duration predictor (fastspeech2.py:117-151), single-speaker, no f0.  Kernels: csrc/vocoder.hip.
