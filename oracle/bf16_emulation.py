@@ -36,9 +36,9 @@ class Rounder:
 
     F16_MAX, F16_MIN_NORMAL, F16_MIN_SUB = 65504.0, 2.0 ** -14, 2.0 ** -24
 
-    def __init__(self, skip: Optional[Set[str]] = None, kind: str = "bf16"):
+    def __init__(self, skip: Optional[Set[str]] = None, kind: str = "bf16", count: bool = True):
         assert kind in ("bf16", "f16")
-        self.skip, self.kind = set(skip or ()), kind
+        self.skip, self.kind, self.count = set(skip or ()), kind, count
         self.stats = {}  # point -> [elements, overflow, subnormal, flushed to zero, max |x|]
 
     def __call__(self, t: Tensor, point: str) -> Tensor:
@@ -46,6 +46,8 @@ class Rounder:
             return t
         if self.kind == "bf16":
             return t.to(torch.bfloat16).float()
+        if not self.count:  # (long sequences: the five passes of the counting cost more than the model)
+            return t.to(torch.float16).float()
         a = t.detach().abs()
         s = self.stats.setdefault(point, [0, 0, 0, 0, 0.0])
         s[0] += a.numel()

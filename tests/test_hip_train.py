@@ -416,16 +416,19 @@ def test_cascaded_vae_gradients_vs_oracle_autograd():
         assert err <= 1e-3 * float(want[k].double().norm()) + 1e-6 * tot, (k, err)
 
 
-def _eps_setup(dtype):
+def _eps_setup(dtype, ecfg=None, tag="train", vae_tag="train"):
+    """The diffusion training engine over the frozen CHAIN_VAE; `ecfg` / the tags: another eps-predictor config and other seeded
+    weights (tests/test_hip_long_sequences.py)."""
     from diffnorm_amd import training
     from gen_golden_configs import CHAIN_EPS
 
-    vsd = O.make_vae_state_dict(CFG, "train")
-    esd = O.make_eps_state_dict(CHAIN_EPS, "train")
+    ecfg = CHAIN_EPS if ecfg is None else ecfg
+    vsd = O.make_vae_state_dict(CFG, vae_tag)
+    esd = O.make_eps_state_dict(ecfg, tag)
     vae = training.VaeTrainEngine(vsd, dim=CFG.dim, latent_dim=CFG.latent_dim, dtype=dtype, device=DEV, depth=CFG.depth, heads=CFG.heads,
                                   dim_head=CFG.dim_head, stacks=CFG.stacks, layers=CFG.layers)
-    eps = training.EpsTrainEngine(esd, CHAIN_EPS, vae, timesteps=200, dtype=dtype, device=DEV)
-    return eps, vae, esd, vsd, CHAIN_EPS
+    eps = training.EpsTrainEngine(esd, ecfg, vae, timesteps=200, dtype=dtype, device=DEV)
+    return eps, vae, esd, vsd, ecfg
 
 
 def test_diffusion_loss_and_gradients_match_reference_f32(golden):
