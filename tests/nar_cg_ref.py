@@ -52,6 +52,61 @@ def guided_update(logits, tokens, step, n_iters, unk, pad):
     return tokens, scores, predicted
 
 
+def _boundary(n_nonpad, step, n_iters):
+    """trunc(fp32(n_nonpad - 2) p), p the Python float cast to the scores' fp32 (cmlm_transformer.py:19-25)."""
+    return int((torch.tensor(float(n_nonpad - 2), dtype=torch.float32) * (1 - (step + 1) / n_iters)).long())
+
+
+def kept_update(logits, tokens, scores, step, n_iters, unk, pad):
+    """forward_decoder's update (nar_transformer.py:791-842), the one that does NOT reset: the positions that are not masked keep
+    the scores of the earlier iterations, and the re-mask ranking runs over old scores, new scores and the zeros of pad / bos / eos.
+    The sort is stable: equal scores are ordered by position.  -> (tokens, scores, predicted)."""
+    masks = tokens.eq(unk)
+    sc, tk = torch.log_softmax(logits.float(), -1).max(-1)
+    tokens = torch.where(masks, tk.to(tokens.dtype), tokens)
+    scores = torch.where(masks, sc, scores.float())
+    predicted = tokens.clone()
+    if step < n_iters - 1:
+        order = torch.sort(scores, dim=-1, stable=True)[1]
+        boundary = torch.tensor([[_boundary(int(n), step, n_iters)] for n in tokens.ne(pad).sum(1)])
+        cut = torch.arange(scores.size(1))[None, :] < boundary
+        sk = torch.zeros_like(cut).scatter(1, order, cut)
+        tokens = tokens.masked_fill(sk, unk)
+        scores = scores.masked_fill(sk, 0.0)
+    return tokens, scores, predicted
+
+
+def kept_margins(logits, tokens, scores, step, n_iters, unk, pad):
+    """`margins` for `kept_update`.  -> (arg-max margin, boundary gap, new scores equal to 0.0, rows whose boundary falls inside a
+    group of equal scores).  Equal scores may straddle a boundary only if every one of them is an INPUT (a kept position's score
+    or a pad / bos / eos zero: the same fp32 value on both sides, the position order decides); the gap of such a row is the distance
+    from the group to the nearest other score.  Any other pair across a boundary counts with its own difference."""
+    masks = tokens.eq(unk)
+    lp = torch.log_softmax(logits.double(), -1)
+    top = lp.topk(2, -1)[0]
+    m_arg = float((top[..., 0] - top[..., 1])[masks].min()) if bool(masks.any()) else float("inf")
+    sc = torch.where(masks, top[..., 0], scores.double())
+    zeros = int((sc[masks] == 0).sum())
+    gap, straddled = float("inf"), 0
+    if step < n_iters - 1:
+        nonpad = torch.where(masks, lp.argmax(-1), tokens).ne(pad)
+        for b in range(tokens.size(0)):
+            k = _boundary(int(nonpad[b].sum()), step, n_iters)
+            s = sc[b].sort()[0]
+            if not 0 < k < s.numel():
+                continue
+            if s[k] != s[k - 1]:
+                gap = min(gap, float(s[k] - s[k - 1]))
+                continue
+            group = sc[b] == s[k]
+            if bool((group & masks[b]).any()):
+                gap = 0.0  # a computed score inside the group: not reproducible
+                continue
+            straddled += 1
+            gap = min(gap, float((sc[b][~group] - s[k]).abs().min()) if bool((~group).any()) else float("inf"))
+    return m_arg, gap, zeros, straddled
+
+
 def margins(logits, tokens, step, n_iters, unk, pad):
     """The three conditions a fixture / a kernel input must meet for its decisions to be reproducible across arithmetic:
     -> (smallest top-2 margin of an arg-max at a masked position, smallest score gap across a re-mask boundary, number of new
