@@ -24,7 +24,25 @@ FULL_CFG = {
     "resblock_kernel_sizes": [3, 7, 11], "resblock_dilation_sizes": [[1, 3, 5], [1, 3, 5], [1, 3, 5]],
     "dur_predictor_params": {"encoder_embed_dim": 128, "var_pred_hidden_dim": 128, "var_pred_kernel_size": 3, "var_pred_dropout": 0.5},
 }
+# the edge tests' configuration: every wave arrangement of the conv operator (C_out 128 ... 16 and 1) at a size where float64 on
+# the CPU stays under a second for an utterance of 300 units
+EDGE_CFG = {
+    "embedding_dim": 32, "model_in_dim": 32, "num_embeddings": 60, "upsample_initial_channel": 128,
+    "upsample_rates": [4, 2, 2], "upsample_kernel_sizes": [8, 4, 4],
+    "resblock_kernel_sizes": [3, 7], "resblock_dilation_sizes": [[1, 3, 5], [1, 3, 5]],
+    "dur_predictor_params": {"encoder_embed_dim": 32, "var_pred_hidden_dim": 32, "var_pred_kernel_size": 3, "var_pred_dropout": 0.5},
+}
 TINY_SEED, FULL_SEED = 3, 11
+
+
+def predictor_cfg(hidden: int) -> dict:
+    """The smallest generator the engine accepts (no activation wider than 32 floats per unit) under a duration predictor of the
+    given hidden width: for tests that run the predictor alone."""
+    return {
+        "embedding_dim": 32, "model_in_dim": 32, "num_embeddings": 60, "upsample_initial_channel": 32,
+        "upsample_rates": [2], "upsample_kernel_sizes": [4], "resblock_kernel_sizes": [3], "resblock_dilation_sizes": [[1, 3, 5]],
+        "dur_predictor_params": {"encoder_embed_dim": 32, "var_pred_hidden_dim": hidden, "var_pred_kernel_size": 3, "var_pred_dropout": 0.5},
+    }
 # the golden file's utterances: 13, 1, 7 and 12 units (one -1 among the 14 codes of the first)
 TINY_UNITS = [[7, 41, 41, 3, -1, 58, 12, 12, 29, 0, 33, 17, 59, 21], [26], [5, 5, 48, 19, 36, 2, 50], [44, 9, 31, 31, 14, 55, 23, 6, 38, 1, 47, 20]]
 
@@ -41,10 +59,12 @@ def _unit(n: int, key: int) -> torch.Tensor:
     return torch.from_numpy((2.0 * u - 1.0) * math.sqrt(3.0))
 
 
-def make_state_dict(cfg: dict, seed: int, weight_norm: bool = True) -> dict:
+def make_state_dict(cfg: dict, seed: int, weight_norm: bool = True, proj_scale: float = 1.0, proj_bias: float = 0.85) -> dict:
     """Float64 generator state dict under the reference's parameter names.  Not init_weights' std 0.01 (every signal would vanish):
     each conv keeps its input's scale (gain over fan-in, leaky ReLU's loss made up), the second conv of a ResBlock pair is a quarter
-    of that so the residual stream stays O(1) through three pairs, and conv_post lands the pre-tanh signal at RMS ~ 0.7."""
+    of that so the residual stream stays O(1) through three pairs, and conv_post lands the pre-tanh signal at RMS ~ 0.7.
+    `proj_scale` multiplies the duration predictor's proj.weight (0: every log duration is exactly `proj_bias`), `proj_bias` is its
+    bias; the defaults are the fixtures' values."""
     sd, key = {}, [seed * 1000]
 
     def rnd(*shape, std=1.0):
@@ -83,8 +103,8 @@ def make_state_dict(cfg: dict, seed: int, weight_norm: bool = True) -> dict:
         for ln in ("ln1", "ln2"):
             sd[p + ln + ".weight"] = 1.0 + rnd(H, std=0.1)
             sd[p + ln + ".bias"] = rnd(H, std=0.05)
-        sd[p + "proj.weight"] = rnd(1, H, std=0.75 / math.sqrt(H))
-        sd[p + "proj.bias"] = torch.full((1,), 0.85, dtype=torch.float64)
+        sd[p + "proj.weight"] = rnd(1, H, std=0.75 / math.sqrt(H)) * proj_scale
+        sd[p + "proj.bias"] = torch.full((1,), proj_bias, dtype=torch.float64)
     return sd
 
 
@@ -149,9 +169,11 @@ def generator(sd, cfg, x, operand_dtype=None, return_pre_tanh=False):
     return pre if return_pre_tanh else torch.tanh(pre)
 
 
-def vocode(sd, cfg, code, dur_prediction, dtype=torch.float64, operand_dtype=None, device="cpu", folded=None, return_pre_tanh=False, durations=None):
+def vocode(sd, cfg, code, dur_prediction, dtype=torch.float64, operand_dtype=None, device="cpu", folded=None, return_pre_tanh=False, durations=None,
+           max_frames=None):
     """CodeHiFiGANVocoder.forward on one utterance -> (waveform [n], durations [T] or None).  `sd` in either form; `folded` a
-    cached fold(sd, dtype) on `device`.  The duration predictor never rounds its operands; `durations` overrides it."""
+    cached fold(sd, dtype) on `device`.  The duration predictor never rounds its operands; `durations` overrides it (an entry of 0
+    drops its unit).  `max_frames` keeps the first so many frames of the generator's input: the engine's frames = min(total, Lmax0)."""
     if folded is None:
         folded = {k: v.to(device) for k, v in fold(sd, dtype).items()}
     code = torch.as_tensor(code).reshape(-1).long()
@@ -161,5 +183,7 @@ def vocode(sd, cfg, code, dur_prediction, dtype=torch.float64, operand_dtype=Non
     if dur_prediction:
         dur = durations_from_log(log_durations(folded, cfg, x)) if durations is None else torch.as_tensor(durations).to(device).long()
         x = torch.repeat_interleave(x, dur, dim=1)
+    if max_frames is not None:
+        x = x[:, :max_frames]
     y = generator(folded, cfg, x.transpose(1, 2), operand_dtype, return_pre_tanh)
     return y.reshape(-1), dur
