@@ -285,6 +285,12 @@ SYMBOLS = {
                                             _vp]),
     "dn_dpm_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
     "dn_dpm_loop": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "dn_gaussian_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
+    "dn_gaussian_loop": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, C.c_uint64, _vp, _i32, _vp, _sz,
+                                   _vp]),
+    "dn_gaussian_loop_keyed": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, _vp, _i32, _vp, _sz, _vp]),
+    "dn_gaussian_sched_step": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, C.c_float, C.c_uint64, _vp, _vp]),
+    "dn_gaussian_sched_step_keyed": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _vp]),
     "dn_guided_ddim_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32, _i32]),
     "dn_guided_ddim_loop": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _vp, _vp, _i32, _i32, _i32, C.c_uint64, _vp, _i32,
                                       _vp, _sz, _vp]),

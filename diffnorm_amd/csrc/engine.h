@@ -114,10 +114,13 @@ struct StepKey {
   int32_t flags;                    // DN_LOOP_* without DN_LOOP_KEEP_TABLE
   int32_t opt_gen;                  // dn::option_generation() at capture: the run-time options its routes were chosen under
   uint32_t scale_bits;              // guided loop: cond_scale
+  uint32_t eta_bits;                // dn_gaussian_loop's DDIM update: the bits of eta, a kernel argument there (0 elsewhere)
   uint16_t ancestral, clip, scheduled, eta, dpm;  // which update the step applies
+  uint16_t generic;                 // dn_gaussian_loop: the respaced GaussianDiffusion update (ancestral: p_sample, else ddim_sample)
   uint16_t injected;                // injected noise bakes its row base into the step: stored (it evicts), never served
+  uint16_t reserved;                // zero
 };
-static_assert(sizeof(StepKey) == 7 * sizeof(void*) + 8 + 7 * 4 + 6 * 2, "StepKey has no padding: copies of a key compare equal too");
+static_assert(sizeof(StepKey) == 7 * sizeof(void*) + 8 + 8 * 4 + 8 * 2, "StepKey has no padding: copies of a key compare equal too");
 struct StepGraph {
   void* exec;  // hipGraphExec_t, null while empty
   StepKey key;

@@ -675,6 +675,10 @@ int dn_ddim_sched_step_launch(float* x, const float* eps, int64_t elem0, int64_t
                               int64_t row_quads, hipStream_t stream);  // pointwise.hip
 int dn_dpm2m_step_launch(float* x, const float* eps, float* hist, int64_t elem0, int64_t n_elem, const float* coef, const int32_t* counter,
                          hipStream_t stream);  // pointwise.hip
+int dn_gaussian_sched_step_launch(float* x, const float* eps, int64_t elem0, int64_t n_elem, const float* table, const int32_t* steps,
+                                  const int32_t* counter, int n_steps, int sampler, int clip, float eta, const float* noise, int64_t noise_row,
+                                  uint64_t seed, const uint64_t* keys, int64_t row_quads, hipStream_t stream);  // pointwise.hip
+int dn_gaussian_sched_args(const char* who, int32_t n_steps, int32_t sampler, float eta);                      // pointwise.hip
 
 namespace {
 // Runs n steps of a chain on `s` as replays of one captured step.  A hit of `slot` replays all n.  A miss evicts the slot, captures
@@ -759,7 +763,7 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
   if (sched) {  // (a strictly descending list inside [0, timesteps-1] has at most `timesteps` entries)
     DN_CHECK_ARG(d.n_steps >= 1 && d.n_steps <= timesteps, "%s: n_steps=%d must be in [1, %d]", d.name, d.n_steps, timesteps);
     DN_CHECK_ARG(B > 0 && T > 0 && T <= m->cfg.max_pos, "%s: B=%d T=%d (positional table: %d)", d.name, B, T, m->cfg.max_pos);
-    DN_CHECK_ARG(d.kind.eta || !d.kind.injected, "dn_ddim_sched_loop: injected noise needs eta_on (eta = 0 draws none)");
+    DN_CHECK_ARG(d.kind.eta || d.kind.generic || !d.kind.injected, "dn_ddim_sched_loop: injected noise needs eta_on (eta = 0 draws none)");
   } else
     DN_CHECK_ARG(start_step >= 1 && start_step <= timesteps - (ancestral ? 0 : 1), "dn_ddim_loop: start_step=%d must be in [1, %d]", start_step,
                  timesteps - (ancestral ? 0 : 1));
@@ -813,7 +817,7 @@ static int sampler_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, i
     // row i of the table belongs to steps[i].  The schedule and its coefficient rows move into the workspace, so a captured step
     // holds workspace addresses only: the steps where the other loops keep 0..start_step-1, the coefficients over `cond_all`
     // (dn_ddim_sched_workspace_bytes: dead once the table is built, and C >= 64 floats a row against DN_DDIM_SCHED_COLS).
-    static_assert(DN_DDIM_SCHED_COLS <= 64 && DN_DPM_COLS <= 64, "the coefficient rows live in cond_all");
+    static_assert(DN_DDIM_SCHED_COLS <= 64 && DN_DPM_COLS <= 64 && DN_GD_COLS <= 64, "the coefficient rows live in cond_all");
     if (hipMemcpyAsync(tall, d.steps, (size_t)start_step * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
       dn_set_error("%s: copying the schedule failed", d.name);
       return DN_ELAUNCH;
@@ -1012,6 +1016,58 @@ extern "C" int dn_dpm_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B
     return dn_dpm2m_step_launch(b.x, b.eps, b.hist, (int64_t)b0 * b.T * b.z, (int64_t)nb * b.T * b.z, b.coef, b.counter, st);
   };
   return sampler_loop(m, x, lengths, B, T, 0, 0, coef, timesteps, flags, workspace, workspace_bytes, stream, d);
+}
+
+// dn_ddim_sched_loop's layout: the DN_GD_COLS coefficients of a row fit where its DN_DDIM_SCHED_COLS do
+extern "C" size_t dn_gaussian_workspace_bytes(const DnEps* m, int32_t B, int32_t T, int32_t n_steps) {
+  return dn_ddim_sched_workspace_bytes(m, B, T, n_steps);
+}
+
+// dn_gaussian_loop (keys == NULL) and dn_gaussian_loop_keyed
+static int gaussian_loop(const char* who, DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, const int32_t* steps,
+                         const float* table, int32_t n_steps, int32_t timesteps, int32_t sampler, int32_t clip_denoised, float eta,
+                         uint64_t seed, const float* noise, const uint64_t* keys, int32_t flags, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  DN_CHECK_ARG(m, "%s: null engine", who);
+  DN_CHECK_ARG(m->cfg.dim_prompt == 0, "%s: the loop covers the unconditional model (the prompted, guided chain is dn_guided_ddim_loop)", who);
+  DN_CHECK_ARG(steps, "%s: null schedule", who);
+  DN_CHECK_ARG(!(flags & ~(DN_LOOP_GRAPH | DN_LOOP_SPLIT2)), "%s: flags=%d (DN_LOOP_GRAPH | DN_LOOP_SPLIT2 only)", who, flags);
+  DN_CHECK_ARG(x && lengths && table && workspace, "%s: null argument", who);
+  DN_TRY(dn_gaussian_sched_args(who, n_steps, sampler, eta));
+  DN_CHECK_ARG(m->cfg.latent % 4 == 0, "%s: the latent width %d must be a multiple of 4", who, m->cfg.latent);
+  DN_CHECK_ARG(((uintptr_t)noise & 15) == 0, "%s: noise must be 16-byte aligned", who);
+  const int clip = clip_denoised != 0;
+  const bool ddim = sampler == 1;
+  if (ddim && eta == 0.0f) seed = 0;  // (nothing is drawn: one graph serves every seed)
+  // the generic update on the half's element range of the whole batch: the whole batch's element index keys the draw (or finds the
+  // utterance's key), so the halves share one stream of numbers
+  LoopDesc d = {who, "dn_gaussian_workspace_bytes", dn_gaussian_workspace_bytes, steps, n_steps, DN_GD_COLS, false, step_kind(seed, noise, keys),
+                nullptr};
+  d.kind.scheduled = d.kind.generic = 1;
+  d.kind.ancestral = !ddim;
+  d.kind.clip = (uint16_t)clip;
+  d.kind.eta = ddim && eta != 0.0f;
+  if (ddim) memcpy(&d.kind.eta_bits, &eta, 4);
+  d.update = [=](const StepBufs& b, int, int b0, int nb, hipStream_t st) {
+    return dn_gaussian_sched_step_launch(b.x, b.eps, (int64_t)b0 * b.T * b.z, (int64_t)nb * b.T * b.z, b.coef, b.steps, b.counter, n_steps, sampler,
+                                         clip, eta, noise, b.all, seed, keys, (int64_t)b.T * (b.z >> 2), st);
+  };
+  return sampler_loop(m, x, lengths, B, T, 0, 0, table, timesteps, flags, workspace, workspace_bytes, stream, d);
+}
+
+extern "C" int dn_gaussian_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, const int32_t* steps, const float* table,
+                                int32_t n_steps, int32_t timesteps, int32_t sampler, int32_t clip_denoised, float eta, uint64_t seed,
+                                const float* noise, int32_t flags, void* workspace, size_t workspace_bytes, void* stream) {
+  return gaussian_loop("dn_gaussian_loop", m, x, lengths, B, T, steps, table, n_steps, timesteps, sampler, clip_denoised, eta, seed, noise, nullptr,
+                       flags, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dn_gaussian_loop_keyed(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, const int32_t* steps, const float* table,
+                                      int32_t n_steps, int32_t timesteps, int32_t sampler, int32_t clip_denoised, float eta,
+                                      const uint64_t* keys, int32_t flags, void* workspace, size_t workspace_bytes, void* stream) {
+  DN_TRY(check_keys("dn_gaussian_loop_keyed", m, keys));
+  return gaussian_loop("dn_gaussian_loop_keyed", m, x, lengths, B, T, steps, table, n_steps, timesteps, sampler, clip_denoised, eta, 0, nullptr, keys,
+                       flags, workspace, workspace_bytes, stream);
 }
 
 

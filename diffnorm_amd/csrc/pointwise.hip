@@ -257,7 +257,10 @@ __global__ __launch_bounds__(256) void randn_kernel(float* __restrict__ out, int
 }
 
 // ------------------------------------------------------------------------------------------ ancestral (DDPM) step of the device loop
-// p_sample (diffusion/gaussian_diffusion.py:376-417) with a fixed variance, the arithmetic of gaussian_step_kernel's sampler 0;
+// p_sample (diffusion/gaussian_diffusion.py:376-417) with a fixed variance, the arithmetic of gaussian_step_kernel's sampler 0 as
+// compiled -- every product of x0 and of the posterior mean rounded before its sum, the final + sd z fused -- written under
+// contract(off) so that the compiler cannot fuse it otherwise (it used to: one product of each sum went unrounded into an fma, a
+// last-bit difference from dn_gaussian_step; dn_gaussian_loop's p_sample over the same table is tested bit-equal to this loop);
 // the noise is injected (`noise`, the row of this step) or drawn here: Philox4x32-10, key = seed, counter = (element quad, t) --
 // t comes from the per-sample step vector the loop fills from its device counter, so graph replays draw fresh noise.
 // kKeyed (dn_ddpm_loop_keyed): drawn from the utterance's key instead (step_noise_keyed4 below) -- x, eps and t are the launch's (a
@@ -290,10 +293,11 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(float* x, const float* _
     float o[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float x0 = __fsub_rn(__fmul_rn(tb[0], xs[j]), __fmul_rn(tb[1], es[j]));
+#pragma clang fp contract(off)
+      float x0 = tb[0] * xs[j] - tb[1] * es[j];
       if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-      const float mean = __fadd_rn(__fmul_rn(tb[2], x0), __fmul_rn(tb[3], xs[j]));
-      o[j] = __fadd_rn(mean, __fmul_rn(sd, z[j]));
+      const float mean = tb[2] * x0 + tb[3] * xs[j];
+      o[j] = fmaf(sd, z[j], mean);
     }
     *reinterpret_cast<float4*>(x + i) = make_float4(o[0], o[1], o[2], o[3]);
   }
@@ -648,6 +652,76 @@ __global__ __launch_bounds__(256) void gaussian_step_kernel(const DnGaussianStep
   }
 }
 
+// ------------------------------------------------------------------------------------------ generic Gaussian step of the device loop
+// One update of a respaced p_sample / ddim_sample chain (dn_gaussian_loop, dn_gaussian_sched_step): gaussian_step_kernel's eps-predicting,
+// fixed-variance branch in place on quads [q0, q0 + nquad) of the whole batch.  Row i = *counter of `table` [n_steps, DN_GD_COLS], given
+// in chain order, is uniform over the launch, so what depends on the row alone (the standard deviation, DDIM's sigma and its two square
+// roots) is formed once per thread.  The noise switch is the RESPACED index, n_steps-1-i: the last row adds none, whatever original
+// timestep steps[i] it has.  z: the injected row i, or Philox4x32-10 keyed by (seed; element quad of the whole batch, i), or (kKeyed)
+// the utterance's stream 2 + steps[i] -- sched_normal4, as ddim_sched_step_kernel draws.  Nothing is drawn where nothing is added (the
+// last row; DDIM at eta == 0).
+// The arithmetic is gaussian_step_kernel's AS COMPILED, spelled out under contract(off) so that this kernel cannot be contracted
+// differently (as sched_update does for ddim_step_kernel): there the products of x0, of the posterior mean and of DDIM's mean are
+// rounded (packed multiplies) before their sums, DDIM's numerator is the rounded c0 x minus x0, and two sums take their product
+// unrounded: 1 - abar_prev - sigma^2 and the final + sdev z.  A host-stepped chain over dn_gaussian_step is tested bit-equal.
+// HBM-bound: two reads (three with injected noise) and one write of 16 bytes per quad; grid-stride, no LDS.
+struct GdRow {
+  float c0, c1, c2, c3;  // sqrt_recip_abar, sqrt_recipm1_abar, posterior_mean_coef1, posterior_mean_coef2
+  float sdev;            // the factor of z: 1[not the last row] exp(0.5 log_var) (p_sample) or sigma (ddim_sample)
+  float sq_abp, sq_dir;  // ddim_sample: sqrt(abar_prev), sqrt(1 - abar_prev - sigma^2)
+};
+__device__ __forceinline__ GdRow gd_row(const float* __restrict__ tb, float nz, int sampler, float eta) {
+#pragma clang fp contract(off)
+  GdRow r = {tb[0], tb[1], tb[2], tb[3], 0.0f, 0.0f, 0.0f};
+  if (sampler == 0) {
+    r.sdev = nz * expf(0.5f * tb[4]);
+  } else {
+    const float ab = tb[7], abp = tb[8];
+    const float sigma = (eta * sqrtf((1.0f - abp) / (1.0f - ab))) * sqrtf(1.0f - ab / abp);
+    r.sq_abp = sqrtf(abp);
+    r.sq_dir = sqrtf(fmaf(-sigma, sigma, 1.0f - abp));
+    r.sdev = nz * sigma;
+  }
+  return r;
+}
+__device__ __forceinline__ float gd_update(const GdRow& r, float x, float e, float z, int sampler, int clip) {
+#pragma clang fp contract(off)
+  const float cx = r.c0 * x;
+  float x0 = cx - r.c1 * e;
+  if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+  float mean;
+  if (sampler == 0) {
+    mean = r.c2 * x0 + r.c3 * x;
+  } else {  // eps re-derived from the (clipped) x_0 prediction (:539)
+    const float e2 = (cx - x0) / r.c1;
+    mean = x0 * r.sq_abp + r.sq_dir * e2;
+  }
+  return fmaf(r.sdev, z, mean);
+}
+
+template <bool kKeyed>
+__global__ __launch_bounds__(256) void gaussian_sched_step_kernel(float* x, const float* __restrict__ eps, int64_t q0, int64_t nquad,
+                                                                  const float* __restrict__ table, const int32_t* __restrict__ steps,
+                                                                  const int32_t* __restrict__ counter, int n_steps, int sampler, int clip,
+                                                                  float eta, SchedNoise src) {
+  const int step = *counter;
+  const float nz = step != n_steps - 1 ? 1.0f : 0.0f;
+  const GdRow r = gd_row(table + (int64_t)step * DN_GD_COLS, nz, sampler, eta);
+  const int t = kKeyed ? steps[step] : 0;
+  const bool draws = nz != 0.0f && (sampler == 0 || eta != 0.0f);
+  for (int64_t q = q0 + blockIdx.x * 256 + threadIdx.x; q < q0 + nquad; q += (int64_t)gridDim.x * 256) {
+    const int64_t i = q << 2;
+    const float4 xv = *reinterpret_cast<const float4*>(x + i), ev = *reinterpret_cast<const float4*>(eps + i);
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (draws || (!kKeyed && src.noise)) sched_normal4<kKeyed>(src, q, i, step, t, z);  // (an injected row is read as the host chain reads it)
+    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, es[4] = {ev.x, ev.y, ev.z, ev.w};
+    float o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = gd_update(r, xs[j], es[j], z[j], sampler, clip);
+    *reinterpret_cast<float4*>(x + i) = make_float4(o[0], o[1], o[2], o[3]);
+  }
+}
+
 // p_mean_variance / q_posterior_mean_variance / ddim_reverse_sample / the VB term, one thread per element (header: DnGaussianMoments)
 __global__ __launch_bounds__(256) void gaussian_moments_kernel(const DnGaussianMoments p) {
   const int64_t total = (int64_t)p.N * p.inner;
@@ -990,6 +1064,56 @@ extern "C" int dn_ddim_sched_step_keyed(float* x, const float* eps, const uint64
   const int64_t row_quads = (int64_t)T * (Z >> 2);
   return dn_ddim_sched_step_launch(x, eps, 0, (int64_t)B * row_quads * 4, coef, steps, step_index, 1, nullptr, 0, 0, keys, row_quads,
                                    (hipStream_t)stream);
+}
+
+// (engine.hip: the update of dn_gaussian_loop; x, eps, noise: the whole batch's; [elem0, elem0 + n_elem): this launch's elements)
+// keys != NULL (the keyed entries): the whole batch's keys, row_quads = T Z / 4 quads per utterance; noise and seed are not read
+int dn_gaussian_sched_step_launch(float* x, const float* eps, int64_t elem0, int64_t n_elem, const float* table, const int32_t* steps,
+                                  const int32_t* counter, int n_steps, int sampler, int clip, float eta, const float* noise, int64_t noise_row,
+                                  uint64_t seed, const uint64_t* keys, int64_t row_quads, hipStream_t stream) {
+  DN_CHECK_ARG(elem0 % 4 == 0 && n_elem % 4 == 0 && n_elem > 0, "dn_gaussian_loop: the latent width must be a multiple of 4");
+  const dim3 grid(ew_grid(n_elem >> 2)), block(256);
+  if (keys)
+    hipLaunchKernelGGL(gaussian_sched_step_kernel<true>, grid, block, 0, stream, x, eps, elem0 >> 2, n_elem >> 2, table, steps, counter, n_steps,
+                       sampler, clip, eta, SchedNoise{nullptr, 0, 0, keys, row_quads});
+  else
+    hipLaunchKernelGGL(gaussian_sched_step_kernel<false>, grid, block, 0, stream, x, eps, elem0 >> 2, n_elem >> 2, table, steps, counter, n_steps,
+                       sampler, clip, eta, SchedNoise{noise, noise_row, seed, nullptr, 0});
+  DN_CHECK_LAUNCH("dn_gaussian_loop step");
+  return DN_OK;
+}
+
+// what the four dn_gaussian_* entries check of the update's own arguments
+int dn_gaussian_sched_args(const char* who, int32_t n_steps, int32_t sampler, float eta) {
+  DN_CHECK_ARG(n_steps >= 1, "%s: n_steps=%d must be positive", who, n_steps);
+  DN_CHECK_ARG(sampler == 0 || sampler == 1, "%s: sampler=%d (0 = p_sample, 1 = ddim_sample)", who, sampler);
+  DN_CHECK_ARG(eta >= 0.0f && eta <= 1e30f, "%s: eta=%g must be finite and not negative", who, (double)eta);
+  return DN_OK;
+}
+
+extern "C" int dn_gaussian_sched_step(float* x, const float* eps, int64_t n, const float* table, const int32_t* step_index, int32_t n_steps,
+                                      int32_t sampler, int32_t clip_denoised, float eta, uint64_t seed, const float* noise, void* stream) {
+  DN_CHECK_ARG(x && eps && table && step_index, "dn_gaussian_sched_step: null argument");
+  DN_CHECK_ARG(n > 0 && n % 4 == 0, "dn_gaussian_sched_step: n=%lld must be a positive multiple of 4", (long long)n);
+  DN_CHECK_ARG((((uintptr_t)x | (uintptr_t)eps | (uintptr_t)noise) & 15) == 0, "dn_gaussian_sched_step: x, eps and noise must be 16-byte aligned");
+  if (const int rc = dn_gaussian_sched_args("dn_gaussian_sched_step", n_steps, sampler, eta)) return rc;
+  // (row stride 0: `noise` is this step's row whatever the step index)
+  return dn_gaussian_sched_step_launch(x, eps, 0, n, table, nullptr, step_index, n_steps, sampler, clip_denoised != 0, eta, noise, 0, seed, nullptr,
+                                       0, (hipStream_t)stream);
+}
+
+extern "C" int dn_gaussian_sched_step_keyed(float* x, const float* eps, const uint64_t* keys, int32_t B, int32_t T, int32_t Z, const float* table,
+                                            const int32_t* steps, const int32_t* step_index, int32_t n_steps, int32_t sampler,
+                                            int32_t clip_denoised, float eta, void* stream) {
+  DN_CHECK_ARG(x && eps && keys && table && steps && step_index, "dn_gaussian_sched_step_keyed: null argument");
+  DN_CHECK_ARG(B > 0 && T > 0 && Z > 0 && Z % 4 == 0, "dn_gaussian_sched_step_keyed: B=%d T=%d must be positive, Z=%d a positive multiple of 4", B,
+               T, Z);
+  DN_CHECK_ARG((((uintptr_t)x | (uintptr_t)eps) & 15) == 0 && ((uintptr_t)keys & 7) == 0,
+               "dn_gaussian_sched_step_keyed: x and eps must be 16-byte, keys 8-byte aligned");
+  if (const int rc = dn_gaussian_sched_args("dn_gaussian_sched_step_keyed", n_steps, sampler, eta)) return rc;
+  const int64_t row_quads = (int64_t)T * (Z >> 2);
+  return dn_gaussian_sched_step_launch(x, eps, 0, (int64_t)B * row_quads * 4, table, steps, step_index, n_steps, sampler, clip_denoised != 0, eta,
+                                       nullptr, 0, 0, keys, row_quads, (hipStream_t)stream);
 }
 
 // (engine.hip: the update of dn_guided_ddim_loop; n_elem = B*T*latent of the B-row latent; both / xin hold 2 n_elem floats when guided)

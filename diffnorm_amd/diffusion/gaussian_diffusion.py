@@ -187,6 +187,61 @@ class GaussianDiffusion(ScheduleTables):
             final = sample
         return final["sample"]
 
+    # ---- the same two loops on the device (dn_gaussian_loop): explicit entries, nothing above dispatches to them
+    def _model_timesteps(self):
+        """The timestep the model sees at each index of this diffusion (SpacedDiffusion: its timestep_map)."""
+        return list(range(self.num_timesteps))
+
+    def _model_num_timesteps(self):
+        return self.num_timesteps
+
+    def device_schedule(self, start_index=None, device=None):
+        """-> (steps, table) of a device chain: `steps` int32 [n], the ORIGINAL timesteps the model sees in chain order -- a
+        SpacedDiffusion's `timestep_map` reversed, else num_timesteps-1 .. 0 -- and `table` fp32 [n, 12], this diffusion's
+        `gaussian_table` rows in the same order, so the last row is respaced index 0.  `start_index` = s keeps the respaced indices
+        s-1 .. 0, the tail of both."""
+        n = self.num_timesteps
+        s = n if start_index is None else int(start_index)
+        if not 1 <= s <= n:
+            raise ValueError(f"start_index={start_index} must be in [1, {n}] (the chain runs the respaced indices start_index-1 .. 0)")
+        steps = torch.tensor(self._model_timesteps()[:s][::-1], dtype=torch.int32)
+        tab = self.gaussian_table(fixed_large=self.model_var_type == ModelVarType.FIXED_LARGE)
+        table = tab[:s].flip(0).contiguous()
+        return (steps.to(device), table.to(device)) if device is not None else (steps, table)
+
+    def _check_device_loop(self, who, engine):
+        if self.model_var_type == ModelVarType.LEARNED_RANGE:
+            raise ValueError(f"{who}: the engine predicts eps with z channels, a learned-range variance needs 2z: build the diffusion "
+                             f"with learn_sigma=False, or step {who[:-len('_device')]} from the host")
+        if self.model_mean_type != ModelMeanType.EPSILON:
+            raise ValueError(f"{who}: the engine predicts eps, this diffusion reads its model as x_0 (START_X): build it with "
+                             f"predict_xstart=False, or step {who[:-len('_device')]} from the host")
+        if getattr(engine, "conditional", False):
+            raise ValueError(f"{who}: the device loop covers the unconditional model; a prompted engine steps through "
+                             f"LatentDiscreteModel.prompted_ddim_sample (dn_guided_ddim_loop)")
+
+    def _sample_loop_device(self, who, sampler, engine, x_T, lengths, clip_denoised, start_index, noise, seed, keys, eta=0.0):
+        self._check_device_loop(who, engine)
+        steps, table = self.device_schedule(start_index, engine.device)
+        x = x_T.to(device=engine.device, dtype=torch.float32).contiguous().clone()
+        engine.gaussian_loop(x, lengths, steps, table, sampler=sampler, clip_denoised=clip_denoised, eta=eta, seed=seed, noise=noise,
+                             keys=keys, timesteps=self._model_num_timesteps())
+        return x
+
+    def p_sample_loop_device(self, engine, x_T, lengths, *, clip_denoised=True, start_index=None, noise=None, seed=0, keys=None):
+        """`p_sample_loop` (:419-511) for an `EpsEngine` as one device loop (EpsEngine.gaussian_loop): x_T fp32 [B, T, z], the
+        sample at respaced index start_index-1 (default: the last one), `lengths` [B] -> x_0 [B, T, z].  The model is evaluated at
+        the ORIGINAL timesteps (`timestep_map`), the coefficients are this diffusion's own rows.  Per-step noise: drawn in the
+        update kernel from `seed`, injected (`noise` [n, B, T, z], row k for the k-th update), or keyed (`keys` int64 [B]: stream
+        2 + original timestep of the utterance's key).  The update at respaced index 0 adds none.  Covers an eps-predicting,
+        fixed-variance diffusion and the unconditional engine; cond_fn / denoised_fn stay with the host loop."""
+        return self._sample_loop_device("p_sample_loop_device", "p_sample", engine, x_T, lengths, clip_denoised, start_index, noise, seed, keys)
+
+    def ddim_sample_loop_device(self, engine, x_T, lengths, *, clip_denoised=True, start_index=None, noise=None, seed=0, keys=None, eta=0.0):
+        """`ddim_sample_loop` (:600-680) as one device loop; arguments as `p_sample_loop_device`, with `eta` (:513-560)."""
+        return self._sample_loop_device("ddim_sample_loop_device", "ddim", engine, x_T, lengths, clip_denoised, start_index, noise, seed, keys,
+                                        eta=eta)
+
     # ---- moments (dn_gaussian_moments)
     def _moments(self, x, t, model_out=None, x_start=None, clip_denoised=True, want=(), learned=None, start_x=None):
         lib = _lib.load()

@@ -60,6 +60,12 @@ class SpacedDiffusion(GaussianDiffusion):
     def _wrap_model(self, model):
         return model if isinstance(model, _WrappedModel) else _WrappedModel(model, self.timestep_map, self.original_num_steps)
 
+    def _model_timesteps(self):  # the device loops (p_sample_loop_device / ddim_sample_loop_device) evaluate the model at these
+        return list(self.timestep_map)
+
+    def _model_num_timesteps(self):
+        return self.original_num_steps
+
     def _step(self, model, *args, cond_fn=None, **kwargs):  # the samplers: model and cond_fn both see the ORIGINAL step indices (:102-106)
         return super()._step(self._wrap_model(model), *args, cond_fn=None if cond_fn is None else self._wrap_model(cond_fn), **kwargs)
 

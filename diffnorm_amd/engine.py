@@ -499,6 +499,43 @@ class EpsEngine(_Engine):
                                                    n if nt is None else nt, _loop_flags(use_graph, split), wp, wn,
                                                    _lib.current_stream()), "dn_dpm_loop")
 
+    def gaussian_loop(self, x: torch.Tensor, lengths: torch.Tensor, steps: torch.Tensor, table: torch.Tensor, sampler: str = "p_sample",
+                      clip_denoised: bool = True, eta: float = 0.0, seed: int = 0, noise: Optional[torch.Tensor] = None,
+                      keys: Optional[torch.Tensor] = None, graph: bool = True, split: bool = True, timesteps: Optional[int] = None) -> int:
+        """In-place chain of the generic Gaussian scheduler on x [B,T,z] fp32 (dn_gaussian_loop): GaussianDiffusion.p_sample_loop
+        (`sampler="p_sample"`) or ddim_sample_loop (`"ddim"`, with `eta`) of a respaced or plain diffusion.  `steps` int32 [n]: the
+        ORIGINAL timesteps, strictly descending; `table` fp32 [n, 12]: the respaced diffusion's `gaussian_table` rows in the same
+        order, so the last row is respaced index 0 and adds no noise.  The noise of update i is drawn in the kernel (Philox keyed by
+        `seed`, i and the element's index in the whole batch -- eager, graph and split chains agree bit for bit), injected (`noise`
+        [n, B, T, z], row i), or keyed (`keys` int64 [B]; excludes `noise` and a non-zero `seed`): `ops.randn_keyed`'s stream
+        2 + steps[i] of keys[b], which depends on the key, the original timestep, the frame and the channel only.  `steps` may also
+        be a list or a host tensor: it is then validated by dn_ddim_sched_check against `timesteps` and uploaded.  `timesteps`: the
+        length of the original noise schedule.  Returns the number of evaluations."""
+        if sampler not in ("p_sample", "ddim"):
+            raise ValueError(f"gaussian_loop: unknown sampler {sampler!r} ('p_sample' or 'ddim')")
+        B, T, z = self._loop_x(x)
+        nt = None if timesteps is None else int(timesteps)
+        if not (isinstance(steps, torch.Tensor) and steps.device == self.device):
+            host = torch.as_tensor(steps, dtype=torch.int32).contiguous().view(-1)
+            limit = nt if nt is not None else (int(host.max()) + 1 if host.numel() else 0)  # (unset: only the order is checked)
+            if self.lib.dn_ddim_sched_check(host.data_ptr() if host.numel() else None, int(host.numel()), limit) != 0:
+                raise ValueError("gaussian_loop: " + (self.lib.dn_last_error() or b"").decode())
+            steps = host.to(self.device)
+        n = self._loop_schedule(steps, table, _lib.GD_COLS)
+        l32 = self._on_device(lengths, torch.int32)
+        nz = self._loop_noise(noise, (n, B, T, z))
+        k64 = self._loop_keys(keys, B, "gaussian_loop", noise, seed)
+        self._keep = (l32, steps, table, nz, k64)
+        wp, wn = self._aligned_workspace(self.lib.dn_gaussian_workspace_bytes(self.handle, B, T, n))
+        head = (self.handle, x.data_ptr(), l32.data_ptr(), B, T, steps.data_ptr(), table.data_ptr(), n, n if nt is None else nt,
+                int(sampler == "ddim"), int(bool(clip_denoised)), float(eta))
+        with torch.cuda.device(self.device):
+            if k64 is not None:
+                return _lib.check(self.lib.dn_gaussian_loop_keyed(*head, k64.data_ptr(), _loop_flags(graph, split), wp, wn,
+                                                                  _lib.current_stream()), "dn_gaussian_loop_keyed")
+            return _lib.check(self.lib.dn_gaussian_loop(*head, int(seed) & (2 ** 64 - 1), _lib.ptr(nz), _loop_flags(graph, split), wp, wn,
+                                                        _lib.current_stream()), "dn_gaussian_loop")
+
     def cond_time_table_steps(self, steps) -> torch.Tensor:
         """The time half of the conditioning rows of the timesteps `steps` (any list or int tensor; dn_eps_cond_time_table_steps):
         fp32 [n, n_cond], row i for steps[i]."""

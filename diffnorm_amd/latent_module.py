@@ -471,15 +471,16 @@ class SpeechVAEEncoderDecoder(_ParamTree):
         return mse, logits, kl.mean()
 
 
-def _chain_start(self, tgt_feature, input_mask, t_index, post_noise, start_noise, noise_keys):
-    """The prologue of LatentDiscreteModel's three samplers (`self`: the model -- a plain function, so it needs only the model's
+def _chain_start(self, tgt_feature, input_mask, t_index, post_noise, start_noise, noise_keys, tables=None):
+    """The prologue of LatentDiscreteModel's samplers (`self`: the model -- a plain function, so it needs only the model's
     device, tables and VAE): mask and lengths, VAE posterior sample, noise to index `t_index` (:1405-1409)
     -> (dev, B, input_mask, lengths, x).  noise_keys=None: the posterior noise from torch's CPU generator and the start noise
     from its device generator (or both injected), indexed by position in the padded batch.  noise_keys (int64 [B], the uint64 bit
     patterns of sharding.utterance_keys): both drawn on the device from the utterance's own key (ops.chain_start), so an
-    utterance's start latent does not depend on the batch it is in."""
+    utterance's start latent does not depend on the batch it is in.  `tables` = (sqrt abar, sqrt(1 - abar)) fp32 on the device: the
+    schedule `t_index` indexes when it is not the model's own (gaussian_sample: the diffusion's)."""
     dev = self.device
-    _, sa, s1 = self._tables()
+    sa, s1 = self._tables()[1:] if tables is None else tables
     B, T, _ = tgt_feature.shape
     if noise_keys is not None:
         if post_noise is not None or start_noise is not None:
@@ -728,6 +729,40 @@ class LatentDiscreteModel(nn.Module):
             self._gd_table = (key, self.scheduler.gaussian_table(dev, fixed_large=fixed_large))
         self.model.engine().ddpm_loop(x, lengths, start_step, self._gd_table[1], seed=seed, noise=step_noise, clip_denoised=clip_denoised,
                                       use_graph=use_graph, **step_keys)
+        recon, _, units = self.speech_decoder.engine().decode(x, lengths, want_logits=False)
+        pred_units = units.long()
+        match = (pred_units[input_mask] == ref_units.to(dev)[input_mask]).sum().item() if ref_units is not None else 0
+        lens = lengths.tolist()
+        return [pred_units[i, : lens[i]] for i in range(B)], match, int(input_mask.sum().item()), recon
+
+    @torch.no_grad()
+    def gaussian_sample(self, tgt_feature, diffusion, sampler="p_sample", start_index=None, eta=0.0, clip_denoised=False, input_mask=None,
+                        ref_units=None, post_noise=None, start_noise=None, step_noise=None, seed=0, noise_keys=None, keyed_steps=False):
+        """The chain of `ddim_sample` under a generic Gaussian scheduler: `diffusion` is a GaussianDiffusion / SpacedDiffusion
+        (`create_diffusion`; eps-predicting, fixed variance), `sampler` its p_sample_loop ("p_sample") or ddim_sample_loop ("ddim",
+        with `eta`).  Encode, noise to respaced index start_index-1 with the DIFFUSION's tables (q_sample; default: its last
+        index), then the respaced indices start_index-1 .. 0 as one device loop (GaussianDiffusion.p_sample_loop_device /
+        ddim_sample_loop_device, dn_gaussian_loop), decode, units -> (list of unit tensors, match, total, recon_feature), as
+        `ddim_sample`.  Per-step noise: drawn in the kernel from `seed`, or `step_noise` [n, B, T, z] injected.  `noise_keys` /
+        `keyed_steps` as `ddpm_sample`: keyed posterior and start noise (dn_chain_start), and with `keyed_steps=True` the per-step
+        noise from the same keys -- stream 2 + ORIGINAL timestep of the utterance's key (dn_gaussian_loop_keyed)."""
+        if sampler not in ("p_sample", "ddim"):
+            raise ValueError(f"gaussian_sample: unknown sampler {sampler!r} ('p_sample' or 'ddim')")
+        if self.use_cond:
+            raise ValueError("gaussian_sample: covers the unconditional model (the prompted, guided chain is prompted_ddim_sample)")
+        step_keys = _keyed_steps("gaussian_sample", self.device, keyed_steps, noise_keys, step_noise, seed)
+        n = diffusion.num_timesteps
+        s = n if start_index is None else int(start_index)
+        if not 1 <= s <= n:
+            raise ValueError(f"gaussian_sample: start_index={start_index} must be in [1, {n}]")
+        dev = self.device
+        tables = (diffusion.f32("sqrt_alphas_cumprod", dev), diffusion.f32("sqrt_one_minus_alphas_cumprod", dev))
+        dev, B, input_mask, lengths, x = _chain_start(self, tgt_feature, input_mask, s - 1, post_noise, start_noise, noise_keys, tables)
+        kw = dict(clip_denoised=clip_denoised, start_index=s, noise=step_noise, seed=seed, **step_keys)
+        if sampler == "ddim":
+            x = diffusion.ddim_sample_loop_device(self.model.engine(), x, lengths, eta=eta, **kw)
+        else:
+            x = diffusion.p_sample_loop_device(self.model.engine(), x, lengths, **kw)
         recon, _, units = self.speech_decoder.engine().decode(x, lengths, want_logits=False)
         pred_units = units.long()
         match = (pred_units[input_mask] == ref_units.to(dev)[input_mask]).sum().item() if ref_units is not None else 0

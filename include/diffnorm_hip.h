@@ -774,6 +774,48 @@ size_t dn_dpm_workspace_bytes(const DnEps* m, int32_t B, int32_t T, int32_t n_st
 int dn_dpm_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, const int32_t* steps, const float* coef, int32_t n_steps,
                 int32_t timesteps, int32_t flags, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The generic Gaussian scheduler as a device loop: GaussianDiffusion.p_sample_loop / ddim_sample_loop (diffusion/gaussian_diffusion.py:
+ * 419-511, 600-680) of a diffusion create_diffusion builds for an eps-predicting model with a fixed variance, respaced or not
+ * (SpacedDiffusion, diffusion/respace.py:63-129: the model sees timestep_map[i], the coefficients are row i of the RESPACED tables) --
+ * in place of a host loop that builds a timestep tensor, evaluates the model, draws randn_like and launches dn_gaussian_step per step.
+ * steps: device int32 [n_steps], the ORIGINAL timesteps the model is evaluated at, strictly descending (dn_ddim_sched_check validates
+ * a host copy).  table: device fp32 [n_steps, DN_GD_COLS], the rows of the respaced diffusion's dn_gaussian_step table IN CHAIN ORDER:
+ * row i belongs to steps[i], i.e. to respaced index n_steps-1-i, so the LAST row is respaced index 0.  A chain that starts part-way
+ * passes the tail of both.  The update of row i is dn_gaussian_step's on eps = Model(x, steps[i]), bit for bit:
+ *   x0 = sqrt_recip_abar x - sqrt_recipm1_abar eps [clamped to +-1 when clip_denoised]
+ *   sampler 0, p_sample (:376-417):     x <- coef1 x0 + coef2 x + 1[i != n_steps-1] exp(0.5 log_var) z
+ *   sampler 1, ddim_sample (:513-560):  e = (sqrt_recip_abar x - x0) / sqrt_recipm1_abar,
+ *       sigma = eta sqrt((1-abar_prev)/(1-abar)) sqrt(1-abar/abar_prev),
+ *       x <- x0 sqrt(abar_prev) + sqrt(1-abar_prev-sigma^2) e + 1[i != n_steps-1] sigma z
+ * The noise switch is the respaced index (t != 0 of :404-407, :551-554), not the timestep's value: the last row adds none even where
+ * steps[n_steps-1] != 0 (a use_timesteps without 0).
+ * z: injected -- noise fp32 [n_steps, B*T*latent], row i for update i, 16-byte aligned -- or, noise == NULL, Philox4x32-10 keyed by
+ * `seed` with the counter (element quad of the whole batch, i), as dn_ddim_sched_loop draws: eager, graph replay and the two
+ * half-batch streams agree bit for bit.  dn_gaussian_loop_keyed: z of element (b, frame, channel) at update i is dn_randn_keyed's
+ * stream 2 + steps[i] under keys[b] (device uint64 [B], 8-byte aligned) -- the ORIGINAL timestep, so a draw depends on (key, timestep,
+ * frame, channel) only: not on the respacing's other members, the row, B, the padded T, the half batch, graph or eager.
+ * Chain state, conditioning table (n_steps rows), hipGraph replay and the two half-batch streams as dn_ddim_sched_loop; flags:
+ * DN_LOOP_GRAPH | DN_LOOP_SPLIT2.  The captured step is cached under the sampler, clip_denoised and the bits of eta besides what
+ * every loop keys: it never serves the other sampler, another eta or another clip, nor another loop.  Workspace:
+ * dn_gaussian_workspace_bytes (= dn_ddim_sched_workspace_bytes).  Unconditional model only; eta finite and >= 0; the latent width a
+ * multiple of 4.  Every argument check precedes the first HIP call.  Returns the number of model evaluations (= n_steps) or a
+ * negative error.
+ * dn_gaussian_sched_step is the update alone on n (a multiple of 4) contiguous fp32 elements, x / eps / noise 16-byte aligned: row
+ * *step_index (device int32) of table, z from `seed` (counter: element quad, step index) or the injected `noise` [n] of THIS step;
+ * dn_gaussian_sched_step_keyed the keyed update alone on dense x / eps [B, T, Z] (Z a multiple of 4), for host-stepped chains.     */
+size_t dn_gaussian_workspace_bytes(const DnEps* m, int32_t B, int32_t T, int32_t n_steps);
+int dn_gaussian_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, const int32_t* steps, const float* table,
+                     int32_t n_steps, int32_t timesteps, int32_t sampler, int32_t clip_denoised, float eta, uint64_t seed,
+                     const float* noise, int32_t flags, void* workspace, size_t workspace_bytes, void* stream);
+int dn_gaussian_loop_keyed(DnEps* m, float* x, const int32_t* lengths, int32_t B, int32_t T, const int32_t* steps, const float* table,
+                           int32_t n_steps, int32_t timesteps, int32_t sampler, int32_t clip_denoised, float eta, const uint64_t* keys,
+                           int32_t flags, void* workspace, size_t workspace_bytes, void* stream);
+int dn_gaussian_sched_step(float* x, const float* eps, int64_t n, const float* table, const int32_t* step_index, int32_t n_steps,
+                           int32_t sampler, int32_t clip_denoised, float eta, uint64_t seed, const float* noise, void* stream);
+int dn_gaussian_sched_step_keyed(float* x, const float* eps, const uint64_t* keys, int32_t B, int32_t T, int32_t Z, const float* table,
+                                 const int32_t* steps, const int32_t* step_index, int32_t n_steps, int32_t sampler, int32_t clip_denoised,
+                                 float eta, void* stream);
+
 /* The prompted, classifier-free-guided chain over a timestep schedule, as a device loop: dn_ddim_sched_loop's chain -- steps, coef,
  * the level x enters at, the target of every update, eta_on / seed / noise [n_steps, B*T*latent] and the Philox key (seed, step
  * index, element quad of the B-row batch) are its arguments with its meaning, dn_ddim_sched_check validates the schedule's host
