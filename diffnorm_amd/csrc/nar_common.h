@@ -1,7 +1,10 @@
-// Kernels shared by the NAR decoder and encoder engines (nar_decoder.hip, nar_encoder.hip, conformer_encoder.hip): internal linkage,
-// one copy per unit.
+// What the NAR decoder and the two speech encoders share (nar_decoder.hip, nar_encoder.hip, conformer_encoder.hip): the LayerNorm
+// kernel, the Conv1dSubsampler, and the few host helpers their passes are written in.  Internal linkage, one copy per unit.
 #pragma once
+#include <algorithm>
+
 #include "common.h"
+#include "engine.h"
 
 namespace dn {
 namespace {
@@ -86,7 +89,137 @@ __global__ __launch_bounds__(256) void strided_rows_kernel(const float* __restri
   }
 }
 
-__device__ __forceinline__ int subsampled_len(int len) { return len <= 0 ? 0 : (len - 1) / 2 + 1; }  // floor((len - 1) / 2 + 1), convolution.py:45-49
+// Frames behind n_conv stride-2 convolutions with padding k / 2 (any odd k): floor((len - 1) / 2 + 1) each (convolution.py:45-49)
+__host__ __device__ __forceinline__ int subsampled_len(int len, int n_conv) {
+  for (int l = 0; l < n_conv; ++l) len = len <= 0 ? 0 : (len - 1) / 2 + 1;
+  return len;
+}
+
+// ---------------------------------------------------------------------------------------------- host helpers of the passes
+inline int side_dt(int dtype) { return dtype == DN_BF16X3 ? DN_F32 : dtype; }  // q / k / v are read by the attention kernel, not staged
+inline int ew_grid(int64_t n) { return (int)std::min<int64_t>((n + 255) / 256, 4096); }  // blocks of a grid-stride elementwise kernel
+// layer l of a stacked packed weight [layers][padn(N)][K]
+inline const void* layer_mat(const void* W, int l, int N, int K, int es) { return eoff(W, (size_t)l * padn(N) * K, es); }
+
+// What the launches of a pass share: the arithmetic, M rows of T per sequence, the width D of the fp32 residual stream, the stream.
+struct Rows { int dtype, M, T, D; hipStream_t s; };
+
+inline void layernorm(const Rows& r, const float* x, const float* gamma, const float* beta, void* y, int out_dtype) {
+  hipLaunchKernelGGL(layernorm_kernel, dim3((r.M + 3) / 4), dim3(256), 0, r.s, x, r.D, y, r.D, out_dtype, r.M, r.D, gamma, beta);
+}
+
+// out[M, N] = epilogue(A[M, K] W^T + bias) in out_dtype; A and out dense
+inline int linear(const Rows& r, const void* A, int K, const void* W, const float* bias, int N, int epilogue, void* out, int out_dtype) {
+  DnGemmParams p = gemm_base(r.dtype, r.M, N, K, r.T);
+  p.terms[0].A = A; p.terms[0].lda = K; p.terms[0].W = W;
+  p.bias = bias; p.epilogue = epilogue; p.out = out; p.ldo = N; p.out_dtype = out_dtype;
+  return dn_conv_gemm(&p, r.s);
+}
+
+// x[M, D] += A[M, K] W^T + bias on the fp32 residual stream
+inline int linear_resadd(const Rows& r, const void* A, int K, const void* W, const float* bias, float* x) {
+  DnGemmParams p = gemm_base(r.dtype, r.M, r.D, K, r.T);
+  p.terms[0].A = A; p.terms[0].lda = K; p.terms[0].W = W;
+  p.bias = bias; p.epilogue = DN_EPI_RESADD; p.res = x; p.ldr = r.D; p.out = x; p.ldo = r.D; p.out_dtype = DN_F32;
+  return dn_conv_gemm(&p, r.s);
+}
+
+// x += W2 act(W1 LayerNorm(x) + b1) + b2 through xn [M, D] and h [M, F]: the FFN of a fairseq layer (act = DN_EPI_RELU,
+// transformer_layer.py:210-215 and :495-508) and of a Conformer layer (DN_EPI_SILU; FeedForwardModule.forward, conformer_layer.py:132-144)
+inline int ffn_block(const Rows& r, float* x, void* xn, void* h, int F, const float* gamma, const float* beta, const void* W1, const float* b1,
+                     const void* W2, const float* b2, int act) {
+  layernorm(r, x, gamma, beta, xn, r.dtype);
+  DN_TRY(linear(r, xn, r.D, W1, b1, F, act, h, r.dtype));
+  return linear_resadd(r, h, F, W2, b2, x);
+}
+
+// The fields DnAttnParams and DnRelAttnParams share: B sequences of T queries, `heads` heads of width dh, k and v with one leading
+// dimension, out [B * T, heads * dh]; scale = head_dim^-0.5 (multihead_attention.py)
+template <class P>
+inline P attn_params(int dtype, int heads, int dh, const void* q, int ldq, const void* k, const void* v, int ldkv, int B, int T, const int32_t* lengths,
+                     void* out) {
+  P a;
+  memset(&a, 0, sizeof(a));
+  a.q = q; a.k = k; a.v = v; a.out = out;
+  a.ldq = ldq; a.ldk = a.ldv = ldkv; a.ldo = heads * dh;
+  a.B = B; a.T = T; a.heads = heads; a.dim_head = dh; a.dtype = dtype; a.lengths = lengths;
+  a.scale = 1.0f / sqrtf((float)dh);
+  return a;
+}
+// Tk keys per sequence, `lengths` of them valid; Tk = 0: the keys are the queries' own frames
+inline int attention(int dtype, int heads, int dh, const void* q, int ldq, const void* k, const void* v, int ldkv, int B, int T, int Tk,
+                     const int32_t* lengths, void* out, hipStream_t s) {
+  DnAttnParams a = attn_params<DnAttnParams>(dtype, heads, dh, q, ldq, k, v, ldkv, B, T, lengths, out);
+  a.Tk = Tk;
+  return dn_attention(&a, s);
+}
+
+// After the plan: the caller's workspace is aligned and holds what the plan took
+inline int check_workspace(const char* who, const void* workspace, size_t bytes, size_t required) {
+  DN_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", who);
+  if (required > bytes) {
+    dn_set_error("%s: workspace %zu < required %zu", who, bytes, required);
+    return DN_EWORKSPACE;
+  }
+  return DN_OK;
+}
+
+// What every *_create here asks of its arguments and of the fields the three configs share
+template <class Cfg>
+inline int check_create(const char* who, const Cfg* cfg, const void* const* w, int n, int expected, const void* out) {
+  DN_CHECK_ARG(cfg && w && out, "%s: null argument", who);
+  DN_CHECK_ARG(n == expected, "%s: expected %d packed tensors, got %d", who, expected, n);
+  DN_CHECK_ARG(cfg->dtype == DN_F32 || cfg->dtype == DN_BF16 || cfg->dtype == DN_BF16X3 || cfg->dtype == DN_F16, "%s: bad dtype", who);
+  DN_CHECK_ARG(cfg->dim > 0 && cfg->dim % 64 == 0 && cfg->dim <= 1024 && cfg->heads > 0 && cfg->dim % cfg->heads == 0 && (cfg->dim / cfg->heads) % 4 == 0,
+               "%s: embed dim %d must be a multiple of 64 (<= 1024) and of the head count", who, cfg->dim);
+  DN_CHECK_ARG(cfg->ffn > 0 && cfg->ffn % 64 == 0 && cfg->layers >= 1, "%s: ffn %% 64, at least one layer", who);
+  for (int i = 0; i < n; ++i) DN_CHECK_ARG(w[i] != nullptr, "%s: packed tensor %d is null", who, i);
+  return DN_OK;
+}
+
+struct TableCursor {  // over a packed tensor table, in table order
+  const void* const* w;
+  int i;
+  const void* next_mat() { return w[i++]; }                 // a contraction operand, in the engine's arithmetic
+  const float* next_vec() { return (const float*)w[i++]; }  // fp32
+};
+
+// Conv1dSubsampler (convolution.py:13-57): two Conv1d(k, stride 2, padding k / 2), a GLU behind each.  A strided conv is a contraction over
+// gathered rows; the first GLU is applied by the second gather, the second is left to the caller's embedding kernel.
+struct Subsampler {
+  int input_dim, conv_channels, kernel, dim;
+  const void* conv0_W;  // (members in table order: both encoders' tables open with these four)
+  const float* conv0_b;
+  const void* conv1_W;
+  const float* conv1_b;
+  struct Bufs { void *cols0, *cols1; float *y0, *y1; };
+
+  int K0() const { return padk(kernel * input_dim); }
+  int K1() const { return kernel * (conv_channels / 2); }
+  int check(const char* who) const {
+    DN_CHECK_ARG(input_dim > 0 && conv_channels > 0 && conv_channels % 8 == 0 && K1() % 64 == 0 && kernel >= 1 && kernel % 2 == 1,
+                 "%s: conv_channels %% 8, odd kernel, kernel * conv_channels / 2 a multiple of 64", who);
+    return DN_OK;
+  }
+  Bufs plan(int dtype, int B, int L, Arena& ar) const {
+    const int es = esize(dtype), S1 = subsampled_len(L, 1), S = subsampled_len(L, 2);
+    Bufs b;
+    b.cols0 = ar.take((size_t)B * S1 * K0() * es);
+    b.y0 = (float*)ar.take((size_t)B * S1 * conv_channels * 4);
+    b.cols1 = ar.take((size_t)B * S * K1() * es);
+    b.y1 = (float*)ar.take((size_t)B * S * 2 * dim * 4);
+    return b;
+  }
+  // feats fp32 [B, L, input_dim] -> b.y1 fp32 [B, S, 2 dim]: the second conv's output, its GLU not yet applied
+  int run(int dtype, const float* feats, int B, int L, const Bufs& b, hipStream_t s) const {
+    const int S1 = subsampled_len(L, 1), S = subsampled_len(L, 2), Ch = conv_channels / 2;
+    hipLaunchKernelGGL((strided_rows_kernel<false>), dim3(ew_grid((int64_t)B * S1 * K0())), dim3(256), 0, s, feats, B, L, S1, input_dim, kernel, K0(), b.cols0,
+                       dtype);
+    DN_TRY(linear(Rows{dtype, B * S1, S1, 0, s}, b.cols0, K0(), conv0_W, conv0_b, conv_channels, DN_EPI_BIAS, b.y0, DN_F32));
+    hipLaunchKernelGGL((strided_rows_kernel<true>), dim3(ew_grid((int64_t)B * S * K1())), dim3(256), 0, s, b.y0, B, S1, S, Ch, kernel, K1(), b.cols1, dtype);
+    return linear(Rows{dtype, B * S, S, 0, s}, b.cols1, K1(), conv1_W, conv1_b, 2 * dim, DN_EPI_BIAS, b.y1, DN_F32);
+  }
+};
 
 }  // namespace
 }  // namespace dn

@@ -41,6 +41,26 @@ def sinusoidal_table(num: int, dim: int, padding_idx: int) -> torch.Tensor:
     return tab.contiguous()
 
 
+def _cat_proj(sd, prefix, names):
+    """(weight, bias) of the projections `names` under `prefix` as one: q ; k ; v or k ; v along the output rows."""
+    return tuple(torch.cat([sd[prefix + n + "." + part].float() for n in names]) for part in ("weight", "bias"))
+
+
+def _conv_mat(w, dtype, cols=None):
+    """Conv1d weight [out, in, k] -> [out, k * in], column j * in + c (the gathered rows' order)."""
+    w2 = w.permute(0, 2, 1).reshape(w.shape[0], -1)
+    return packing._mat(w2, dtype, cols=cols or w2.shape[1])
+
+
+def _subsampler_tensors(sd, input_dim, conv_channels, kernel, dim, dtype) -> List[torch.Tensor]:
+    """The Conv1dSubsampler's two convs: the four tensors both speech encoders' tables open with."""
+    g = lambda k: sd[k].float()
+    c0, c1 = g("subsample.conv_layers.0.weight"), g("subsample.conv_layers.1.weight")
+    assert c0.shape == (conv_channels, input_dim, kernel) and c1.shape == (2 * dim, conv_channels // 2, kernel), (c0.shape, c1.shape)
+    return [_conv_mat(c0, dtype, cols=packing.padk(kernel * input_dim)), g("subsample.conv_layers.0.bias").contiguous(), _conv_mat(c1, dtype),
+            g("subsample.conv_layers.1.bias").contiguous()]
+
+
 def pack_nar(sd: Dict[str, torch.Tensor], dim: int, ffn: int, layers: int, vocab: int, max_pos: int, pad: int, dtype: int) -> List[torch.Tensor]:
     """Reference-named decoder state dict -> the tensor table of dn_nar_create (include/diffnorm_hip.h)."""
     g = lambda k: sd[k].float()
@@ -50,12 +70,12 @@ def pack_nar(sd: Dict[str, torch.Tensor], dim: int, ffn: int, layers: int, vocab
     for l in range(layers):
         p = f"layers.{l}."
         sa, ea = p + "self_attn.", p + "encoder_attn."
-        qkv_W.append(mat(torch.cat([g(sa + "q_proj.weight"), g(sa + "k_proj.weight"), g(sa + "v_proj.weight")])))
-        qkv_b.append(torch.cat([g(sa + "q_proj.bias"), g(sa + "k_proj.bias"), g(sa + "v_proj.bias")]))
+        W, b = _cat_proj(sd, sa, ("q_proj", "k_proj", "v_proj"))
+        qkv_W.append(mat(W)); qkv_b.append(b)
         so_W.append(mat(g(sa + "out_proj.weight"))); so_b.append(g(sa + "out_proj.bias"))
         cq_W.append(mat(g(ea + "q_proj.weight"))); cq_b.append(g(ea + "q_proj.bias"))
-        ckv_W.append(mat(torch.cat([g(ea + "k_proj.weight"), g(ea + "v_proj.weight")])))
-        ckv_b.append(torch.cat([g(ea + "k_proj.bias"), g(ea + "v_proj.bias")]))
+        W, b = _cat_proj(sd, ea, ("k_proj", "v_proj"))
+        ckv_W.append(mat(W)); ckv_b.append(b)
         co_W.append(mat(g(ea + "out_proj.weight"))); co_b.append(g(ea + "out_proj.bias"))
         f1W.append(mat(g(p + "fc1.weight"))); f1b.append(g(p + "fc1.bias"))
         f2W.append(mat(g(p + "fc2.weight"))); f2b.append(g(p + "fc2.bias"))
@@ -75,46 +95,43 @@ def pack_nar_encoder(sd: Dict[str, torch.Tensor], input_dim: int, conv_channels:
     g = lambda k: sd[k].float()
     mat = lambda w: packing._mat(w, dtype, cols=w.shape[1])
     stack = lambda items: torch.stack(items).contiguous()
-
-    def conv_mat(w, cols=None):  # Conv1d weight [out, in, k] -> [out, k * in], column j * in + c (the gathered rows' order)
-        w2 = w.permute(0, 2, 1).reshape(w.shape[0], -1)
-        return packing._mat(w2, dtype, cols=cols or w2.shape[1])
-
-    c0, c1 = g("subsample.conv_layers.0.weight"), g("subsample.conv_layers.1.weight")
-    assert c0.shape == (conv_channels, input_dim, kernel) and c1.shape == (2 * dim, conv_channels // 2, kernel), (c0.shape, c1.shape)
+    sub = _subsampler_tensors(sd, input_dim, conv_channels, kernel, dim, dtype)
     qkv_W, qkv_b, so_W, so_b, f1W, f1b, f2W, f2b, lng, lnb = ([] for _ in range(10))
     for l in range(layers):
         p = f"transformer_layers.{l}."
         sa = p + "self_attn."
-        qkv_W.append(mat(torch.cat([g(sa + "q_proj.weight"), g(sa + "k_proj.weight"), g(sa + "v_proj.weight")])))
-        qkv_b.append(torch.cat([g(sa + "q_proj.bias"), g(sa + "k_proj.bias"), g(sa + "v_proj.bias")]))
+        W, b = _cat_proj(sd, sa, ("q_proj", "k_proj", "v_proj"))
+        qkv_W.append(mat(W)); qkv_b.append(b)
         so_W.append(mat(g(sa + "out_proj.weight"))); so_b.append(g(sa + "out_proj.bias"))
         f1W.append(mat(g(p + "fc1.weight"))); f1b.append(g(p + "fc1.bias"))
         f2W.append(mat(g(p + "fc2.weight"))); f2b.append(g(p + "fc2.bias"))
         lng.append(torch.stack([g(p + "self_attn_layer_norm.weight"), g(p + "final_layer_norm.weight")]))
         lnb.append(torch.stack([g(p + "self_attn_layer_norm.bias"), g(p + "final_layer_norm.bias")]))
-    return [conv_mat(c0, cols=packing.padk(kernel * input_dim)), g("subsample.conv_layers.0.bias").contiguous(), conv_mat(c1),
-            g("subsample.conv_layers.1.bias").contiguous(), sinusoidal_table(max_pos, dim, pad), stack(qkv_W), stack(qkv_b), stack(so_W), stack(so_b),
-            stack(f1W), stack(f1b), stack(f2W), stack(f2b), stack(lng), stack(lnb), g("layer_norm.weight").contiguous(), g("layer_norm.bias").contiguous()]
+    return sub + [sinusoidal_table(max_pos, dim, pad), stack(qkv_W), stack(qkv_b), stack(so_W), stack(so_b),
+                  stack(f1W), stack(f1b), stack(f2W), stack(f2b), stack(lng), stack(lnb), g("layer_norm.weight").contiguous(), g("layer_norm.bias").contiguous()]
 
 
-class NarEncoderEngine(_Engine):
-    """dn_nar_encoder_* of libdiffnorm_hip.so: the speech encoder of the NAR S2UT model (S2STransformerEncoder,
-    research/TranSpeech/nar_transformer.py:40-76): one pass per utterance batch, in front of the refinement loop."""
+class _NarEngine(_Engine):
+    """An engine behind dn_<_sym>_create / dn_<_sym>_destroy: a subclass names `_sym` and hands `_create` its packed table and config."""
+    _sym = None
 
-    def __init__(self, state_dict, input_dim=80, conv_channels=1024, kernel=5, dim=512, ffn=2048, layers=12, heads=8, max_pos=6002, pad=1,
-                 dtype="bf16", device="cuda:0"):
-        self.dim, self.input_dim = dim, input_dim
-        self.dtype = _dtype_code(dtype)
-        super().__init__(device, pack_nar_encoder(state_dict, input_dim, conv_channels, kernel, dim, ffn, layers, max_pos, pad, self.dtype))
-        cfg = _lib.NarEncConfig(input_dim, conv_channels, kernel, dim, ffn, layers, heads, max_pos, pad, self.dtype)
+    def _create(self, device, tensors, cfg):
+        super().__init__(device, tensors)
+        name = f"dn_{self._sym}_create"
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.dn_nar_encoder_create(C.byref(cfg), self._table, len(self.tensors), C.byref(self.handle)), "dn_nar_encoder_create")
+            _lib.check(getattr(self.lib, name)(C.byref(cfg), self._table, len(self.tensors), C.byref(self.handle)), name)
 
     def __del__(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
-            self.lib.dn_nar_encoder_destroy(self.handle)
+            getattr(self.lib, f"dn_{self._sym}_destroy")(self.handle)
             self.handle = C.c_void_p()
+
+
+class _SpeechEncoderEngine(_NarEngine):
+    """The pass of a speech encoder, dn_<_sym>_workspace_bytes / dn_<_sym>_forward: once per utterance batch, in front of the refinement loop."""
+
+    def workspace_bytes(self, B: int, L: int) -> int:
+        return int(getattr(self.lib, f"dn_{self._sym}_workspace_bytes")(self.handle, B, L))
 
     def forward(self, feats: torch.Tensor, src_lengths: torch.Tensor):
         """feats [B, L, input_dim], src_lengths [B] -> (enc_out fp32 [B, S, dim] batch-major, lengths int32 [B])."""
@@ -122,14 +139,28 @@ class NarEncoderEngine(_Engine):
         assert Fd == self.input_dim
         feats = feats.to(self.device, torch.float32).contiguous()
         sl = src_lengths.to(self.device, torch.int32).contiguous()
-        S = int(self.lib.dn_nar_encoder_out_frames(L))
+        S = int(self.lib.dn_nar_encoder_out_frames(L))  # (the one Conv1dSubsampler in front of both encoders)
         out = torch.empty(B, S, self.dim, dtype=torch.float32, device=self.device)
         lens = torch.empty(B, dtype=torch.int32, device=self.device)
-        wp, wn = self._aligned(self._workspace(int(self.lib.dn_nar_encoder_workspace_bytes(self.handle, B, L))))
+        wp, wn = self._aligned(self._workspace(self.workspace_bytes(B, L)))
+        name = f"dn_{self._sym}_forward"
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.dn_nar_encoder_forward(self.handle, feats.data_ptr(), sl.data_ptr(), B, L, out.data_ptr(), lens.data_ptr(), wp, wn,
-                                                       _lib.current_stream()), "dn_nar_encoder_forward")
+            _lib.check(getattr(self.lib, name)(self.handle, feats.data_ptr(), sl.data_ptr(), B, L, out.data_ptr(), lens.data_ptr(), wp, wn,
+                                               _lib.current_stream()), name)
         return out, lens
+
+
+class NarEncoderEngine(_SpeechEncoderEngine):
+    """dn_nar_encoder_* of libdiffnorm_hip.so: the speech encoder of the NAR S2UT model (S2STransformerEncoder,
+    research/TranSpeech/nar_transformer.py:40-76)."""
+    _sym = "nar_encoder"
+
+    def __init__(self, state_dict, input_dim=80, conv_channels=1024, kernel=5, dim=512, ffn=2048, layers=12, heads=8, max_pos=6002, pad=1,
+                 dtype="bf16", device="cuda:0"):
+        self.dim, self.input_dim = dim, input_dim
+        self.dtype = _dtype_code(dtype)
+        self._create(device, pack_nar_encoder(state_dict, input_dim, conv_channels, kernel, dim, ffn, layers, max_pos, pad, self.dtype),
+                     _lib.NarEncConfig(input_dim, conv_channels, kernel, dim, ffn, layers, heads, max_pos, pad, self.dtype))
 
 
 def rel_pos_table(max_frames: int, dim: int) -> torch.Tensor:
@@ -181,13 +212,7 @@ def pack_conformer_encoder(sd: Dict[str, torch.Tensor], input_dim: int, conv_cha
     g = lambda k: sd[k].float()
     mat = lambda w: packing._mat(w, dtype, cols=w.shape[1])
     stack = lambda items: torch.stack(items).contiguous()
-
-    def conv_mat(w, cols=None):  # as pack_nar_encoder
-        w2 = w.permute(0, 2, 1).reshape(w.shape[0], -1)
-        return packing._mat(w2, dtype, cols=cols or w2.shape[1])
-
-    c0, c1 = g("subsample.conv_layers.0.weight"), g("subsample.conv_layers.1.weight")
-    assert c0.shape == (conv_channels, input_dim, kernel) and c1.shape == (2 * dim, conv_channels // 2, kernel), (c0.shape, c1.shape)
+    sub = _subsampler_tensors(sd, input_dim, conv_channels, kernel, dim, dtype)
     names = ("f1w1", "f1b1", "f1w2", "f1b2", "f2w1", "f2b1", "f2w2", "f2b2", "qkvW", "qkvb", "posW", "outW", "outb", "u", "v", "pw1", "dww", "dws",
              "pw2", "lng", "lnb")
     t = {n: [] for n in names}
@@ -197,8 +222,8 @@ def pack_conformer_encoder(sd: Dict[str, torch.Tensor], input_dim: int, conv_cha
             t[tag + "w1"].append(mat(g(p + ff + "w_1.weight"))); t[tag + "b1"].append(g(p + ff + "w_1.bias"))
             t[tag + "w2"].append(mat(0.5 * g(p + ff + "w_2.weight"))); t[tag + "b2"].append(0.5 * g(p + ff + "w_2.bias"))
         sa, cm = p + "self_attn.", p + "conv_module."
-        t["qkvW"].append(mat(torch.cat([g(sa + "linear_q.weight"), g(sa + "linear_k.weight"), g(sa + "linear_v.weight")])))
-        t["qkvb"].append(torch.cat([g(sa + "linear_q.bias"), g(sa + "linear_k.bias"), g(sa + "linear_v.bias")]))
+        W, b = _cat_proj(sd, sa, ("linear_q", "linear_k", "linear_v"))
+        t["qkvW"].append(mat(W)); t["qkvb"].append(b)
         t["posW"].append(mat(g(sa + "linear_pos.weight")))
         t["outW"].append(mat(g(sa + "linear_out.weight"))); t["outb"].append(g(sa + "linear_out.bias"))
         u, v = g(sa + "pos_bias_u"), g(sa + "pos_bias_v")
@@ -214,56 +239,33 @@ def pack_conformer_encoder(sd: Dict[str, torch.Tensor], input_dim: int, conv_cha
         order = ("ffn1.layer_norm", "self_attn_layer_norm", "conv_module.layer_norm", "ffn2.layer_norm", "final_layer_norm")
         t["lng"].append(torch.stack([g(p + n + ".weight") for n in order])); t["lnb"].append(torch.stack([g(p + n + ".bias") for n in order]))
     pe = packing._arith(rel_pos_table(max_frames, dim), dtype, weight=False)
-    return [conv_mat(c0, cols=packing.padk(kernel * input_dim)), g("subsample.conv_layers.0.bias").contiguous(), conv_mat(c1),
-            g("subsample.conv_layers.1.bias").contiguous(), mat(g("linear.weight")), g("linear.bias").contiguous(), pe] + \
-           [stack(t[n]) for n in names] + [torch.zeros(2 * dim)]
+    return sub + [mat(g("linear.weight")), g("linear.bias").contiguous(), pe] + [stack(t[n]) for n in names] + [torch.zeros(2 * dim)]
 
 
-class ConformerEncoderEngine(_Engine):
+class ConformerEncoderEngine(_SpeechEncoderEngine):
     """dn_conformer_encoder_* of libdiffnorm_hip.so: the Conformer speech encoder of the recipe's NAR S2UT model (S2SConformerEncoder,
     research/TranSpeech/nar_conformer.py:42-74, attn_type espnet + pos_enc_type rel_pos, no speaker embedding), eval mode."""
+    _sym = "conformer_encoder"
 
     def __init__(self, state_dict, input_dim=80, conv_channels=1024, kernel=5, dim=512, ffn=2048, layers=12, heads=8, depthwise_kernel=31,
                  max_source_positions=6000, dtype="bf16", device="cuda:0", attn_type="espnet", pos_enc_type="rel_pos",
                  conv_version="s2t_transformer"):
         self.dim, self.input_dim = dim, input_dim
         self.dtype = _dtype_code(dtype)
-        max_frames = ((max_source_positions - 1) // 2 + 1 - 1) // 2 + 1  # frames of the longest source behind the two stride-2 layers
-        super().__init__(device, pack_conformer_encoder(state_dict, input_dim, conv_channels, kernel, dim, ffn, layers, heads, depthwise_kernel,
-                                                        max_frames, self.dtype, attn_type, pos_enc_type, conv_version))
-        cfg = _lib.ConformerEncConfig(input_dim, conv_channels, kernel, dim, ffn, layers, heads, depthwise_kernel, max_frames, self.dtype)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.dn_conformer_encoder_create(C.byref(cfg), self._table, len(self.tensors), C.byref(self.handle)),
-                       "dn_conformer_encoder_create")
-
-    def __del__(self):
-        if getattr(self, "handle", None) is not None and self.handle.value:
-            self.lib.dn_conformer_encoder_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def workspace_bytes(self, B: int, L: int) -> int:
-        return int(self.lib.dn_conformer_encoder_workspace_bytes(self.handle, B, L))
+        max_frames = int(_lib.load().dn_nar_encoder_out_frames(max_source_positions))  # frames of the longest source behind the subsampler
+        self._create(device, pack_conformer_encoder(state_dict, input_dim, conv_channels, kernel, dim, ffn, layers, heads, depthwise_kernel,
+                                                    max_frames, self.dtype, attn_type, pos_enc_type, conv_version),
+                     _lib.ConformerEncConfig(input_dim, conv_channels, kernel, dim, ffn, layers, heads, depthwise_kernel, max_frames, self.dtype))
 
     def forward(self, feats: torch.Tensor, src_lengths: torch.Tensor):
         """feats [B, L, input_dim], src_lengths [B] (each >= 1) -> (enc_out fp32 [B, S, dim] batch-major, lengths int32 [B]).
         Lengths on the host are checked here; lengths already on the device are not read back (no synchronisation, as
         NarEncoderEngine.forward): an empty utterance there is the caller's to exclude -- the kernels stay inside their tensors (the
         attention treats it as one key) but its rows mean nothing."""
-        B, L, Fd = feats.shape
-        assert Fd == self.input_dim
         src_lengths = torch.as_tensor(src_lengths)
         if src_lengths.device.type == "cpu" and int(src_lengths.min()) < 1:
             raise ValueError("ConformerEncoderEngine.forward: an empty utterance has no attention softmax")
-        feats = feats.to(self.device, torch.float32).contiguous()
-        sl = src_lengths.to(self.device, torch.int32).contiguous()
-        S = int(self.lib.dn_nar_encoder_out_frames(L))
-        out = torch.empty(B, S, self.dim, dtype=torch.float32, device=self.device)
-        lens = torch.empty(B, dtype=torch.int32, device=self.device)
-        wp, wn = self._aligned(self._workspace(self.workspace_bytes(B, L)))
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.dn_conformer_encoder_forward(self.handle, feats.data_ptr(), sl.data_ptr(), B, L, out.data_ptr(), lens.data_ptr(), wp,
-                                                             wn, _lib.current_stream()), "dn_conformer_encoder_forward")
-        return out, lens
+        return super().forward(feats, src_lengths)
 
 
 class _HipEncoder:
@@ -285,20 +287,15 @@ class _HipEncoder:
         return _GivenEncoder.reorder_encoder_out(self, enc, order)
 
 
-class NarDecoderEngine(_Engine):
+class NarDecoderEngine(_NarEngine):
     """dn_nar_* of libdiffnorm_hip.so: cross-attention keys / values once per batch, length prediction, one decoder pass."""
+    _sym = "nar"
 
     def __init__(self, state_dict, dim=512, ffn=2048, layers=6, heads=8, vocab=1004, max_pos=1026, pad=1, dtype="bf16", device="cuda:0"):
         self.dim, self.ffn, self.layers, self.heads, self.vocab, self.pad = dim, ffn, layers, heads, vocab, pad
         self.dtype = _dtype_code(dtype)
-        super().__init__(device, pack_nar(state_dict, dim, ffn, layers, vocab, max_pos, pad, self.dtype))
-        cfg = _lib.NarConfig(dim, ffn, layers, heads, vocab, max_pos, pad, self.dtype)
-        _lib.check(self.lib.dn_nar_create(C.byref(cfg), self._table, len(self.tensors), C.byref(self.handle)), "dn_nar_create")
-
-    def __del__(self):
-        if getattr(self, "handle", None) and self.handle.value:
-            self.lib.dn_nar_destroy(self.handle)
-            self.handle = None
+        self._create(device, pack_nar(state_dict, dim, ffn, layers, vocab, max_pos, pad, self.dtype),
+                     _lib.NarConfig(dim, ffn, layers, heads, vocab, max_pos, pad, self.dtype))
 
     def _pass_bytes(self, B, T, S, guided: bool = False) -> int:
         size = self.lib.dn_nar_guided_workspace_bytes if guided else self.lib.dn_nar_workspace_bytes
