@@ -99,7 +99,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_tn_kernel(const WgTnParams p) {
     const int kq = kq0 + cs * 8;
     int tap = kq / p.rows_w;
     const int k = kq - tap * p.rows_w;
-    const bool ok = kq < p.n_total && k < p.cin && cs * 8 < KW;  // (a chunk that straddles cin relies on the buffer's zero pad columns)
+    const bool ok = kq < p.n_total && k < p.cin && cs * 8 < KW;  // (a chunk that straddles cin reads pad columns: masked in the epilogue)
     tap = tap < p.n_taps ? tap : 0;
     x_shift[i] = p.shift_by_group ? p.shift[tap] << g : p.shift[tap];
     x_col_ok[i] = ok;

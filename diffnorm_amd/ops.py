@@ -336,7 +336,8 @@ def convert_rows(src, dst, C_):
 def conv_weight_grad_tn(x: torch.Tensor, dy: torch.Tensor, T: int, cin: int, cout: int, shifts: Sequence[int],
                         slices: int = 1, dtype: str = "bf16", grad: torch.Tensor = None) -> torch.Tensor:
     """conv_weight_grad without transposed operand copies (dn_conv_weight_grad_tn, bf16): the contraction over frames reads the
-    row-major x / dy through transposing LDS reads.  x [B*T, ldx], dy [B*T, lddy] with zero pad columns.  -> fp32 [taps, cout, cin].
+    row-major x / dy through transposing LDS reads.  x [B*T, ldx], dy [B*T, lddy]; the pad columns may hold anything (the epilogue masks
+    them: tests/test_hip_wgrad_grid.py).  -> fp32 [taps, cout, cin].
 
     dtype "bf16x3" (dn_conv_weight_grad_tn_x3): x and dy are split rows in activation order (packing.split_rows of fp32 [B*T, ld],
     ld a multiple of 32: bf16 tensors of 2 ld entries per row).  grad: a packed fp32 [taps, padn(cout), padk(cin)] gradient to
