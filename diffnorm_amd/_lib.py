@@ -124,6 +124,11 @@ class ConformerEncConfig(C.Structure):
                                          "dtype")]
 
 
+class HubertConfig(C.Structure):
+    _fields_ = [("n_conv", C.c_int32), ("conv_dim", C.c_int32), ("conv_kernel", C.c_int32 * 8), ("conv_stride", C.c_int32 * 8)] + \
+               [(n, C.c_int32) for n in ("dim", "ffn", "layers", "heads", "conv_pos", "conv_pos_groups", "dtype", "has_proj")]
+
+
 class RelAttnParams(C.Structure):
     _fields_ = [("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("out", C.c_void_p),
                 ("ldq", C.c_int32), ("ldk", C.c_int32), ("ldv", C.c_int32), ("ldo", C.c_int32),
@@ -336,6 +341,16 @@ SYMBOLS = {
     "dn_voc_forward": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "dn_voc_set_profile": (C.c_int, [_vp, _i32]),
     "dn_voc_stage_times": (C.c_int, [_vp, C.POINTER(C.c_float), _i32]),
+    "dn_grouped_conv1d": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "dn_kmeans_workspace_bytes": (_sz, [_i32, _i32]),
+    "dn_kmeans_assign": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "dn_hubert_create": (C.c_int, [_vp, _vp, _i32, _vp]),
+    "dn_hubert_destroy": (None, [_vp]),
+    "dn_hubert_out_frames": (_i32, [_vp, _i32]),
+    "dn_hubert_workspace_bytes": (_sz, [_vp, _i32, _i32]),
+    "dn_hubert_forward": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "dn_hubert_set_profile": (C.c_int, [_vp, _i32]),
+    "dn_hubert_stage_times": (C.c_int, [_vp, C.POINTER(C.c_float), _i32]),
     "dn_set_option": (C.c_int, [C.c_char_p, _i32]),
     "dn_get_option": (C.c_int, [C.c_char_p, _vp, _vp]),
 }

@@ -1,0 +1,470 @@
+// The mHuBERT front end of the recipe (scripts/prepare/feature_dump.sh -> examples/textless_nlp/gslm/speech2unit/pretrained/
+// hubert_feature_reader.py; scripts/prepare/quantize_unit.sh -> quantize_with_kmeans.py): HubertModel.extract_features(source,
+// padding_mask=None, mask=False, output_layer=k) (fairseq/models/hubert/hubert.py:429-476, 529-545), eval mode, and the k-means
+// assignment behind it.  ConvFeatureExtractionModel (fairseq/models/wav2vec/wav2vec2.py:819-896, mode "default", no conv bias) ->
+// LayerNorm -> post_extract_proj -> pos_conv + residual -> LayerNorm (TransformerEncoder.extract_features, :1009-1076,
+// layer_norm_first False) -> post-norm TransformerSentenceEncoderLayers (:1258-1283).  The reader runs one utterance at a time, so a
+// batch here gives every utterance what it gets alone: per-utterance GroupNorm statistics, zeros outside [0, len) in the positional
+// conv, key lengths in the attention; every other stage is row-wise.
+//   first conv + GroupNorm + GELU   conv0_stats_kernel / conv0_combine_kernel / conv0_apply_kernel (two passes over the waveform)
+//   conv layers 1..                 a stride-s k-tap conv without padding as a contraction over gathered rows (strided_taps_kernel,
+//                                   the subsampler's form in nar_common.h) on dn_conv_gemm; the GELU behind layer i is applied by the
+//                                   gather of layer i + 1 (as the subsampler's GLU is), the last one by gelu_rows_kernel
+//   positional conv                 dn_grouped_conv1d below
+//   layers                          dn_conv_gemm / dn_attention launches, nar_common.h's LayerNorm
+#include <new>
+
+#include "common.h"
+#include "engine.h"
+#include "nar_common.h"
+
+using namespace dn;
+
+namespace dn {
+namespace {
+
+constexpr int C0_KMAX = 16;   // taps of the first conv held in registers (zero weights behind the kernel)
+constexpr int C0_SMAX = 8;    // its largest stride
+constexpr int C0_TF = 256;    // frames per tile, counted from frame 0 of each utterance
+
+// nn.GELU() (erf form) in fp32
+__device__ __forceinline__ float gelu_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
+
+__host__ __device__ __forceinline__ int conv_frames(int len, int k, int s) { return len >= k ? (len - k) / s + 1 : 0; }
+
+// len1[b] = frames of utterance b behind the first conv; out_len[b] = behind the whole stack (at most S)
+struct ConvGeom { int n, k[DN_HUBERT_MAX_CONV], s[DN_HUBERT_MAX_CONV]; };
+__global__ void hubert_lengths_kernel(const int32_t* __restrict__ lengths, int B, int L, ConvGeom g, int S, int32_t* __restrict__ len1,
+                                      int32_t* __restrict__ out_len) {
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    int l = lengths[b] < L ? lengths[b] : L;
+    for (int i = 0; i < g.n; ++i) {
+      l = conv_frames(l, g.k[i], g.s[i]);
+      if (i == 0) len1[b] = l;
+    }
+    out_len[b] = l < S ? l : S;
+  }
+}
+
+// The samples of a frame tile in LDS: ws[i] = wave[b][t0 * s + i], zeros at and behind the utterance's own length (whatever the
+// caller left there never reaches a valid frame, not even through a zero weight)
+__device__ __forceinline__ void stage_wave(float* ws, const float* __restrict__ wave, int64_t L, int b, int len, int t0, int s) {
+  const int n = C0_TF * s + C0_KMAX;
+  const int64_t base = (int64_t)t0 * s;
+  for (int i = threadIdx.x; i < n; i += 256) ws[i] = base + i < len ? wave[(int64_t)b * L + base + i] : 0.f;
+}
+__device__ __forceinline__ float conv0_at(const float* ws, const float (&w)[C0_KMAX]) {
+  float a = 0.f;
+#pragma unroll
+  for (int j = 0; j < C0_KMAX; ++j) a = fmaf(w[j], ws[j], a);
+  return a;
+}
+
+// Pass 1 of Fp32GroupNorm(C, C) behind Conv1d(1 -> C) (wav2vec2.py:860-866): per (utterance, tile, channel) the mean and the sum of
+// squared deviations FROM THAT MEAN of the tile's valid frames (two sweeps over the staged samples: no E[x^2] - mean^2).
+__global__ __launch_bounds__(256) void conv0_stats_kernel(const float* __restrict__ wave, const int32_t* __restrict__ lengths, const int32_t* __restrict__ len1,
+                                                          int L, int C, int s, const float* __restrict__ w0, float2* __restrict__ part) {
+  __shared__ float ws[C0_TF * C0_SMAX + C0_KMAX];
+  const int tile = blockIdx.x, b = blockIdx.y, t0 = tile * C0_TF;
+  int nv = len1[b] - t0;
+  nv = nv < 0 ? 0 : nv > C0_TF ? C0_TF : nv;
+  stage_wave(ws, wave, L, b, lengths[b] < L ? lengths[b] : L, t0, s);
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256) {
+    float w[C0_KMAX];
+#pragma unroll
+    for (int j = 0; j < C0_KMAX; ++j) w[j] = w0[j * C + c];
+    float sum = 0.f;
+    for (int f = 0; f < nv; ++f) sum += conv0_at(ws + f * s, w);
+    const float mean = nv ? sum / (float)nv : 0.f;
+    float m2 = 0.f;
+    for (int f = 0; f < nv; ++f) {
+      const float d = conv0_at(ws + f * s, w) - mean;
+      m2 = fmaf(d, d, m2);
+    }
+    part[((int64_t)b * gridDim.x + tile) * C + c] = make_float2(mean, m2);
+  }
+}
+
+// The tiles' (count, mean, M2) combined in tile order in double precision (Chan et al.): stat[b][c] = (mean hi, mean lo, rstd, 0)
+__global__ __launch_bounds__(256) void conv0_combine_kernel(const float2* __restrict__ part, const int32_t* __restrict__ len1, int B, int C, int tiles,
+                                                            float4* __restrict__ stat) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= B * C) return;
+  const int b = i / C, c = i - b * C;
+  double n = 0, mean = 0, m2 = 0;
+  for (int t = 0; t < tiles; ++t) {
+    int nb = len1[b] - t * C0_TF;
+    if (nb <= 0) break;
+    nb = nb > C0_TF ? C0_TF : nb;
+    const float2 p = part[((int64_t)b * tiles + t) * C + c];
+    const double d = (double)p.x - mean, tot = n + nb;
+    mean += d * nb / tot;
+    m2 += (double)p.y + d * d * n * nb / tot;
+    n = tot;
+  }
+  float4 o = make_float4(0, 0, 0, 0);
+  if (n > 0) {
+    o.x = (float)mean;
+    o.y = (float)(mean - (double)o.x);
+    o.z = (float)(1.0 / sqrt(m2 / n + 1e-5));
+  }
+  stat[i] = o;
+}
+
+// Pass 2: the conv again, normalised, affine, GELU, stored once in the operand type: y[b][t][c], channels last
+__global__ __launch_bounds__(256) void conv0_apply_kernel(const float* __restrict__ wave, const int32_t* __restrict__ lengths, int L, int T1, int C, int s,
+                                                          const float* __restrict__ w0, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                          const float4* __restrict__ stat, void* __restrict__ y, int dtype) {
+  __shared__ float ws[C0_TF * C0_SMAX + C0_KMAX];
+  const int b = blockIdx.y, t0 = blockIdx.x * C0_TF;
+  const int nf = T1 - t0 < C0_TF ? T1 - t0 : C0_TF;
+  stage_wave(ws, wave, L, b, lengths[b] < L ? lengths[b] : L, t0, s);
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256) {
+    float w[C0_KMAX];
+#pragma unroll
+    for (int j = 0; j < C0_KMAX; ++j) w[j] = w0[j * C + c];
+    const float4 st = stat[b * C + c];
+    const float sc = st.z * gamma[c], sh = beta[c];
+    for (int f = 0; f < nf; ++f) {
+      const float v = (conv0_at(ws + f * s, w) - st.x) - st.y;
+      store_act(y, ((int64_t)b * T1 + t0 + f) * C + c, dtype, gelu_exact(fmaf(v, sc, sh)));
+    }
+  }
+}
+
+// Rows of the contraction that IS a Conv1d(k, stride s, no padding) over channels-last [B, Tin, C]:
+// cols[b * Tout + t][j * C + c] = act(in[b][s t + j][c]); every source row exists (s (Tout - 1) + k - 1 <= Tin - 1).  GELU: `in` is the
+// previous conv's fp32 pre-activation and the gathered value gelu(in); else `in` is in the operand type already.
+template <bool GELU>
+__global__ __launch_bounds__(256) void strided_taps_kernel(const void* __restrict__ in, int in_dtype, int B, int Tin, int Tout, int C, int k, int s,
+                                                           void* __restrict__ cols, int dtype) {
+  const int Kq = k * C / 4, Cq = C / 4;
+  const int64_t n = (int64_t)B * Tout * Kq;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int q = (int)(i % Kq);
+    const int64_t row = i / Kq;
+    const int t = (int)(row % Tout), b = (int)(row / Tout), j = q / Cq, c = (q - j * Cq) * 4;
+    float4 v = load4(in, ((int64_t)b * Tin + (int64_t)s * t + j) * C + c, in_dtype);
+    if (GELU) v = make_float4(gelu_exact(v.x), gelu_exact(v.y), gelu_exact(v.z), gelu_exact(v.w));
+    store4(cols, i * 4, dtype, v.x, v.y, v.z, v.w);
+  }
+}
+
+// out = gelu(in) element-wise, fp32 -> out_dtype (in place when out_dtype is DN_F32 and out == in)
+__global__ __launch_bounds__(256) void gelu_rows_kernel(const float* in, void* out, int out_dtype, int64_t nquad) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nquad; i += (int64_t)gridDim.x * 256) {
+    const float4 v = *reinterpret_cast<const float4*>(in + i * 4);
+    store4(out, i * 4, out_dtype, gelu_exact(v.x), gelu_exact(v.y), gelu_exact(v.z), gelu_exact(v.w));
+  }
+}
+
+// out[b][t][:] = x[b][t][:] for t < len[b], zeros behind
+__global__ __launch_bounds__(256) void masked_copy_kernel(const float* __restrict__ x, const int32_t* __restrict__ len, int B, int S, int D,
+                                                          float* __restrict__ out) {
+  const int Dq = D / 4;
+  const int64_t n = (int64_t)B * S * Dq;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int64_t row = i / Dq;
+    const int t = (int)(row % S), b = (int)(row / S);
+    reinterpret_cast<float4*>(out)[i] = t < len[b] ? reinterpret_cast<const float4*>(x)[i] : make_float4(0, 0, 0, 0);
+  }
+}
+
+// dn_grouped_conv1d.  A workgroup: GC_NF * (256 / Cg) frames of one group of one sequence; thread -> (output channel co, frame
+// slot fr), GC_NF frames fr + FR i each.  The tile's rows and the k - 1 halo rows lie in LDS once for all taps; the weights stream
+// from [g][tap][ci][co] (co fastest: one coalesced load per (tap, ci), reused for the GC_NF frames).
+constexpr int GC_NF = 8, GC_CGMAX = 64, GC_KMAX = 128;
+__global__ __launch_bounds__(256) void grouped_conv1d_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                             float* __restrict__ out, const int32_t* __restrict__ lengths, int T, int C, int Cg, int k) {
+  extern __shared__ __attribute__((aligned(16))) float xs[];  // [TT + k - 1][Cg]
+  const int tid = threadIdx.x, g = blockIdx.y, b = blockIdx.z, FR = 256 / Cg, TT = FR * GC_NF, t0 = blockIdx.x * TT, half = k / 2;
+  const int len = lengths[b] < T ? lengths[b] : T;
+  const int co = tid % Cg, fr = tid / Cg;
+  const int64_t row0 = (int64_t)b * T;
+  if (t0 >= len) {  // a tile behind the sequence: zeros
+    if (fr < FR)
+      for (int i = 0; i < GC_NF; ++i) {
+        const int t = t0 + fr + FR * i;
+        if (t < T) out[(row0 + t) * C + g * Cg + co] = 0.f;
+      }
+    return;
+  }
+  const int rows = TT + k - 1, Cq = Cg / 4;
+  for (int i = tid; i < rows * Cq; i += 256) {
+    const int r = i / Cq, c = (i - r * Cq) * 4, t = t0 + r - half;
+    float4 v = make_float4(0, 0, 0, 0);
+    if (t >= 0 && t < len) v = *reinterpret_cast<const float4*>(x + (row0 + t) * C + g * Cg + c);
+    *reinterpret_cast<float4*>(xs + r * Cg + c) = v;
+  }
+  __syncthreads();
+  if (fr >= FR) return;
+  float acc[GC_NF];
+#pragma unroll
+  for (int i = 0; i < GC_NF; ++i) acc[i] = 0.f;
+  const float* wg = w + (int64_t)g * k * Cg * Cg + co;
+  for (int j = 0; j < k; ++j) {
+    const float* wj = wg + (int64_t)j * Cg * Cg;
+    const float* xj = xs + (fr + j) * Cg;
+    for (int ci = 0; ci < Cg; ci += 4) {
+      const float w0 = wj[ci * Cg], w1 = wj[(ci + 1) * Cg], w2 = wj[(ci + 2) * Cg], w3 = wj[(ci + 3) * Cg];
+#pragma unroll
+      for (int i = 0; i < GC_NF; ++i) {
+        const float4 v = *reinterpret_cast<const float4*>(xj + FR * i * Cg + ci);
+        acc[i] = fmaf(w0, v.x, acc[i]);
+        acc[i] = fmaf(w1, v.y, acc[i]);
+        acc[i] = fmaf(w2, v.z, acc[i]);
+        acc[i] = fmaf(w3, v.w, acc[i]);
+      }
+    }
+  }
+  const float bc = bias[g * Cg + co];
+#pragma unroll
+  for (int i = 0; i < GC_NF; ++i) {
+    const int f = fr + FR * i, t = t0 + f;
+    if (t >= T) continue;
+    out[(row0 + t) * C + g * Cg + co] = t < len ? xs[(f + half) * Cg + co] + gelu_exact(acc[i] + bc) : 0.f;
+  }
+}
+
+}  // namespace
+}  // namespace dn
+
+extern "C" int dn_grouped_conv1d(const float* x, const float* w, const float* bias, float* out, const int32_t* lengths, int32_t B, int32_t T, int32_t C,
+                                 int32_t groups, int32_t k, void* stream) {
+  DN_CHECK_ARG(x && w && bias && out && lengths && x != out, "dn_grouped_conv1d: null argument (or out aliases x)");
+  DN_CHECK_ARG(B > 0 && B <= 65535 && T > 0 && C > 0 && groups > 0 && groups <= 65535 && C % groups == 0, "dn_grouped_conv1d: B=%d T=%d C=%d groups=%d", B, T, C, groups);
+  const int Cg = C / groups;
+  DN_CHECK_ARG(Cg % 4 == 0 && Cg <= GC_CGMAX && k >= 1 && k <= GC_KMAX, "dn_grouped_conv1d: %d channels per group (a multiple of 4, <= %d), kernel %d (<= %d)", Cg,
+               GC_CGMAX, k, GC_KMAX);
+  DN_CHECK_ARG((int64_t)B * T * C < (int64_t)1 << 31, "dn_grouped_conv1d: B * T * C exceeds 2^31 elements");
+  DN_CHECK_ARG((((uintptr_t)x | (uintptr_t)out) & 15) == 0, "dn_grouped_conv1d: x and out must be 16-byte aligned");
+  const int TT = (256 / Cg) * GC_NF;
+  const size_t lds = (size_t)(TT + k - 1) * Cg * sizeof(float);
+  hipLaunchKernelGGL(grouped_conv1d_kernel, dim3((T + TT - 1) / TT, groups, B), dim3(256), lds, (hipStream_t)stream, x, w, bias, out, lengths, T, C, Cg, k);
+  DN_CHECK_LAUNCH("dn_grouped_conv1d");
+  return DN_OK;
+}
+
+extern "C" size_t dn_kmeans_workspace_bytes(int32_t M, int32_t n_centroids) {
+  if (M <= 0 || n_centroids <= 0) return 0;
+  return (size_t)M * round_up(n_centroids, 4) * sizeof(float) + 512;
+}
+
+extern "C" int dn_kmeans_assign(const float* feats, const float* centroids, const float* half_norm, int32_t M, int32_t D, int32_t n_centroids,
+                                int32_t* units, void* workspace, size_t workspace_bytes, void* stream) {
+  DN_CHECK_ARG(feats && centroids && half_norm && units && workspace, "dn_kmeans_assign: null argument");
+  DN_CHECK_ARG(M > 0 && D > 0 && D % 32 == 0 && n_centroids > 0, "dn_kmeans_assign: M=%d D=%d (a multiple of 32) centroids=%d", M, D, n_centroids);
+  const int N = round_up(n_centroids, 4);
+  DN_CHECK_ARG((int64_t)M * std::max(N, D) < (int64_t)1 << 31, "dn_kmeans_assign: M=%d: a buffer exceeds 2^31 elements", M);
+  DN_TRY(check_workspace("dn_kmeans_assign", workspace, workspace_bytes, (size_t)M * N * sizeof(float)));
+  hipStream_t s = (hipStream_t)stream;
+  float* scores = (float*)workspace;
+  DN_TRY(linear(Rows{DN_F32, M, M, 0, s}, feats, D, centroids, half_norm, N, DN_EPI_BIAS, scores, DN_F32));  // x . c_j - |c_j|^2 / 2
+  return dn_argmax_units(scores, N, M, n_centroids, 0, units, stream);  // the first maximum wins: ties go to the lowest index
+}
+
+struct DnHubert {
+  DnHubertConfig cfg;
+  const float *conv0_w, *gn_g, *gn_b, *ln_g, *ln_b, *proj_b, *pos_w, *pos_b, *enc_g, *enc_b, *qkv_b, *out_b, *fc1_b, *fc2_b, *lng, *lnb, *zeros;
+  const void *conv_W[DN_HUBERT_MAX_CONV], *proj_W, *qkv_W, *out_W, *fc1_W, *fc2_W;
+  hipEvent_t ev[DN_HUBERT_STAGES + 1];  // dn_hubert_set_profile: stage boundaries of the last profiled forward
+  int n_ev, profile;
+};
+
+extern "C" int dn_hubert_create(const DnHubertConfig* cfg, const void* const* w, int32_t n, DnHubert** out) {
+  DN_CHECK_ARG(cfg && cfg->n_conv >= 2 && cfg->n_conv <= DN_HUBERT_MAX_CONV, "dn_hubert_create: 2 .. %d conv layers", DN_HUBERT_MAX_CONV);
+  DN_TRY(check_create("dn_hubert_create", cfg, w, n, 21 + cfg->n_conv, out));
+  const int C = cfg->conv_dim, dh = cfg->dim / cfg->heads;
+  DN_CHECK_ARG(C > 0 && C % 64 == 0 && C <= 1024, "dn_hubert_create: conv width %d must be a multiple of 64, <= 1024", C);
+  DN_CHECK_ARG(cfg->conv_kernel[0] >= 1 && cfg->conv_kernel[0] <= C0_KMAX && cfg->conv_stride[0] >= 1 && cfg->conv_stride[0] <= C0_SMAX,
+               "dn_hubert_create: first conv kernel %d (<= %d), stride %d (<= %d)", cfg->conv_kernel[0], C0_KMAX, cfg->conv_stride[0], C0_SMAX);
+  for (int i = 1; i < cfg->n_conv; ++i)
+    DN_CHECK_ARG(cfg->conv_kernel[i] >= 1 && cfg->conv_kernel[i] <= 8 && cfg->conv_stride[i] >= 1, "dn_hubert_create: conv layer %d: kernel %d stride %d", i,
+                 cfg->conv_kernel[i], cfg->conv_stride[i]);
+  DN_CHECK_ARG(cfg->has_proj || C == cfg->dim, "dn_hubert_create: no post_extract_proj needs conv width %d == embed width %d", C, cfg->dim);
+  DN_CHECK_ARG(dh == 16 || dh == 32 || dh == 64, "dn_hubert_create: head width %d (16, 32 or 64)", dh);
+  const int G = cfg->conv_pos_groups;
+  DN_CHECK_ARG(G > 0 && cfg->dim % G == 0 && (cfg->dim / G) % 4 == 0 && cfg->dim / G <= GC_CGMAX && cfg->conv_pos >= 1 && cfg->conv_pos <= GC_KMAX,
+               "dn_hubert_create: conv_pos %d (<= %d) with %d groups (channels per group a multiple of 4, <= %d)", cfg->conv_pos, GC_KMAX, G, GC_CGMAX);
+  DnHubert* m = new (std::nothrow) DnHubert();
+  DN_CHECK_ARG(m != nullptr, "dn_hubert_create: out of host memory");
+  m->cfg = *cfg;
+  m->n_ev = m->profile = 0;
+  TableCursor t{w, 0};
+  m->conv0_w = t.next_vec(); m->gn_g = t.next_vec(); m->gn_b = t.next_vec();
+  for (int i = 1; i < cfg->n_conv; ++i) m->conv_W[i] = t.next_mat();
+  m->ln_g = t.next_vec(); m->ln_b = t.next_vec(); m->proj_W = t.next_mat(); m->proj_b = t.next_vec();
+  m->pos_w = t.next_vec(); m->pos_b = t.next_vec(); m->enc_g = t.next_vec(); m->enc_b = t.next_vec();
+  m->qkv_W = t.next_mat(); m->qkv_b = t.next_vec(); m->out_W = t.next_mat(); m->out_b = t.next_vec();
+  m->fc1_W = t.next_mat(); m->fc1_b = t.next_vec(); m->fc2_W = t.next_mat(); m->fc2_b = t.next_vec();
+  m->lng = t.next_vec(); m->lnb = t.next_vec(); m->zeros = t.next_vec();
+  *out = m;
+  return DN_OK;
+}
+
+extern "C" void dn_hubert_destroy(DnHubert* m) {
+  if (!m) return;
+  for (int i = 0; i < m->n_ev; ++i) (void)hipEventDestroy(m->ev[i]);
+  delete m;
+}
+
+extern "C" int dn_hubert_set_profile(DnHubert* m, int32_t on) {
+  DN_CHECK_ARG(m, "dn_hubert_set_profile: null engine");
+  if (on && !m->n_ev)
+    for (int i = 0; i <= DN_HUBERT_STAGES; ++i) {
+      if (hipEventCreate(&m->ev[i]) != hipSuccess) {
+        dn_set_error("dn_hubert_set_profile: hipEventCreate failed");
+        return DN_ELAUNCH;
+      }
+      m->n_ev = i + 1;
+    }
+  m->profile = on ? 1 : 0;
+  return DN_OK;
+}
+
+extern "C" int dn_hubert_stage_times(DnHubert* m, float* ms, int32_t cap) {
+  DN_CHECK_ARG(m && ms && m->n_ev == DN_HUBERT_STAGES + 1, "dn_hubert_stage_times: profiling was not switched on (dn_hubert_set_profile)");
+  DN_CHECK_ARG(cap >= DN_HUBERT_STAGES, "dn_hubert_stage_times: room for %d values needed", DN_HUBERT_STAGES);
+  bool ok = hipEventSynchronize(m->ev[DN_HUBERT_STAGES]) == hipSuccess;
+  for (int i = 0; i < DN_HUBERT_STAGES && ok; ++i) ok = hipEventElapsedTime(&ms[i], m->ev[i], m->ev[i + 1]) == hipSuccess;
+  if (!ok) {
+    dn_set_error("dn_hubert_stage_times: no profiled forward has run");
+    return DN_ELAUNCH;
+  }
+  return DN_OK;
+}
+
+extern "C" int32_t dn_hubert_out_frames(const DnHubert* m, int32_t L) {
+  if (!m) return 0;
+  for (int i = 0; i < m->cfg.n_conv; ++i) L = conv_frames(L, m->cfg.conv_kernel[i], m->cfg.conv_stride[i]);
+  return L;
+}
+
+namespace {
+struct HubertBufs {
+  int T[DN_HUBERT_MAX_CONV], tiles;
+  int64_t max_elems;  // the largest buffer, in elements
+  float2* part; float4* stat; int32_t* len1;
+  void *y0, *cols, *xn, *qkv, *ao, *h;
+  float *y, *x0, *xa, *xb, *hf;
+};
+HubertBufs plan_hubert(const DnHubert* m, int B, int L, Arena& ar) {
+  const DnHubertConfig& c = m->cfg;
+  const int es = esize(c.dtype), C = c.conv_dim, D = c.dim;
+  HubertBufs b;
+  int len = L;
+  for (int i = 0; i < c.n_conv; ++i) b.T[i] = len = conv_frames(len, c.conv_kernel[i], c.conv_stride[i]);
+  const int S = b.T[c.n_conv - 1];
+  b.tiles = (b.T[0] + C0_TF - 1) / C0_TF;
+  size_t cols = 0;
+  for (int i = 1; i < c.n_conv; ++i) cols = std::max(cols, (size_t)b.T[i] * c.conv_kernel[i] * C);
+  b.max_elems = (int64_t)B * std::max<int64_t>({(int64_t)b.T[0] * C, (int64_t)cols, (int64_t)S * c.ffn, (int64_t)S * 3 * D});
+  b.part = (float2*)ar.take((size_t)B * b.tiles * C * sizeof(float2));
+  b.stat = (float4*)ar.take((size_t)B * C * sizeof(float4));
+  b.len1 = (int32_t*)ar.take((size_t)B * sizeof(int32_t));
+  b.y0 = ar.take((size_t)B * b.T[0] * C * es);
+  b.cols = ar.take((size_t)B * cols * es);
+  b.y = (float*)ar.take((size_t)B * b.T[1] * C * 4);
+  b.x0 = (float*)ar.take((size_t)B * S * D * 4);
+  b.xa = (float*)ar.take((size_t)B * S * D * 4);
+  b.xb = (float*)ar.take((size_t)B * S * D * 4);
+  b.xn = ar.take((size_t)B * S * std::max(C, D) * es);
+  b.qkv = ar.take((size_t)B * S * 3 * D * es);
+  b.ao = ar.take((size_t)B * S * D * es);
+  b.hf = (float*)ar.take((size_t)B * S * c.ffn * 4);
+  b.h = ar.take((size_t)B * S * c.ffn * es);
+  return b;
+}
+}  // namespace
+
+extern "C" size_t dn_hubert_workspace_bytes(const DnHubert* m, int32_t B, int32_t L) {
+  if (!m || B <= 0 || dn_hubert_out_frames(m, L) < 1) return 0;
+  Arena a{nullptr, 0, 0};
+  (void)plan_hubert(m, B, L, a);
+  return a.off + 512;
+}
+
+extern "C" int dn_hubert_forward(DnHubert* m, const float* wave, const int32_t* lengths, int32_t B, int32_t L, int32_t n_layers_run, float* out,
+                                 int32_t* out_lengths, void* workspace, size_t workspace_bytes, void* stream) {
+  DN_CHECK_ARG(m && wave && lengths && out && out_lengths && workspace, "dn_hubert_forward: null argument");
+  const DnHubertConfig& c = m->cfg;
+  const int S = dn_hubert_out_frames(m, L);
+  DN_CHECK_ARG(B > 0 && B <= 65535 && L > 0 && S >= 1, "dn_hubert_forward: B=%d L=%d: the waveform is shorter than one frame of the conv stack", B, L);
+  DN_CHECK_ARG(n_layers_run >= 1 && n_layers_run <= c.layers, "dn_hubert_forward: output layer %d outside 1 .. %d", n_layers_run, c.layers);
+  hipStream_t s = (hipStream_t)stream;
+  Arena ar{(char*)workspace, 0, workspace_bytes};
+  const HubertBufs b = plan_hubert(m, B, L, ar);
+  DN_CHECK_ARG(b.max_elems < (int64_t)1 << 31, "dn_hubert_forward: B=%d L=%d: a buffer of %lld elements exceeds 2^31 (rows are indexed in 32 bits): split the batch", B,
+               L, (long long)b.max_elems);
+  DN_TRY(check_workspace("dn_hubert_forward", workspace, workspace_bytes, ar.off));
+  const int dtype = c.dtype, es = esize(dtype), C = c.conv_dim, D = c.dim, F = c.ffn, H = c.heads, dh = D / H;
+  const int sdt = side_dt(dtype), ses = esize(sdt);
+  ConvGeom g;
+  g.n = c.n_conv;
+  for (int i = 0; i < DN_HUBERT_MAX_CONV; ++i) { g.k[i] = c.conv_kernel[i]; g.s[i] = c.conv_stride[i]; }
+  int ei = 0;
+  auto mark = [&]() { if (m->profile && ei < m->n_ev) (void)hipEventRecord(m->ev[ei++], s); };
+  // LayerNorm of x into the fp32 stream `y32` and, as the next contraction's A operand, into xn; in DN_F32 the two are one
+  const void* xn = b.xn;
+  auto norm_both = [&](const Rows& rr, const float* x, const float* gm, const float* bt, float* y32) {
+    layernorm(rr, x, gm, bt, y32, DN_F32);
+    if (dtype == DN_F32) xn = y32;
+    else { layernorm(rr, x, gm, bt, b.xn, dtype); xn = b.xn; }
+  };
+  mark();
+  // (out_lengths is written first; a failed launch anywhere in the pass is reported by the DN_CHECK_LAUNCH at its end)
+  hipLaunchKernelGGL(hubert_lengths_kernel, dim3(1), dim3(256), 0, s, lengths, B, L, g, S, b.len1, out_lengths);
+  // ---- conv layer 0 + Fp32GroupNorm + GELU (wav2vec2.py:860-866), statistics per utterance over its own frames
+  const int T1 = b.T[0], s0 = c.conv_stride[0];
+  hipLaunchKernelGGL(conv0_stats_kernel, dim3(b.tiles, B), dim3(256), 0, s, wave, lengths, b.len1, L, C, s0, m->conv0_w, b.part);
+  hipLaunchKernelGGL(conv0_combine_kernel, dim3((B * C + 255) / 256), dim3(256), 0, s, b.part, b.len1, B, C, b.tiles, b.stat);
+  hipLaunchKernelGGL(conv0_apply_kernel, dim3(b.tiles, B), dim3(256), 0, s, wave, lengths, L, T1, C, s0, m->conv0_w, m->gn_g, m->gn_b, b.stat, b.y0, dtype);
+  mark();
+  // ---- conv layers 1.. + GELU (:867-868): gathered rows, one contraction each; y holds layer i's pre-activation
+  for (int i = 1; i < c.n_conv; ++i) {
+    const int k = c.conv_kernel[i], st = c.conv_stride[i], Tin = b.T[i - 1], Tout = b.T[i];
+    const int grid = ew_grid((int64_t)B * Tout * k * C / 4);
+    if (i == 1)
+      hipLaunchKernelGGL((strided_taps_kernel<false>), dim3(grid), dim3(256), 0, s, b.y0, dtype, B, Tin, Tout, C, k, st, b.cols, dtype);
+    else
+      hipLaunchKernelGGL((strided_taps_kernel<true>), dim3(grid), dim3(256), 0, s, b.y, DN_F32, B, Tin, Tout, C, k, st, b.cols, dtype);
+    DN_TRY(linear(Rows{dtype, B * Tout, Tout, 0, s}, b.cols, k * C, m->conv_W[i], m->zeros, C, DN_EPI_BIAS, b.y, DN_F32));
+  }
+  const Rows rc{dtype, B * S, S, C, s}, r{dtype, B * S, S, D, s};
+  hipLaunchKernelGGL(gelu_rows_kernel, dim3(ew_grid((int64_t)rc.M * C / 4)), dim3(256), 0, s, b.y, b.y, DN_F32, (int64_t)rc.M * C / 4);
+  mark();
+  // ---- layer_norm, post_extract_proj (hubert.py:445-453)
+  if (c.has_proj) {
+    layernorm(rc, b.y, m->ln_g, m->ln_b, b.xn, dtype);
+    DN_TRY(linear(rc, b.xn, C, m->proj_W, m->proj_b, D, DN_EPI_BIAS, b.x0, DN_F32));
+  } else {
+    layernorm(rc, b.y, m->ln_g, m->ln_b, b.x0, DN_F32);
+  }
+  // ---- x + gelu(SamePad(pos_conv(x))), encoder.layer_norm (wav2vec2.py:1020-1025); frames outside the utterance are zeros
+  DN_TRY(dn_grouped_conv1d(b.x0, m->pos_w, m->pos_b, b.xa, out_lengths, B, S, D, c.conv_pos_groups, c.conv_pos, s));
+  mark();
+  float *cur = b.xb, *other = b.xa;
+  norm_both(r, b.xa, m->enc_g, m->enc_b, cur);
+  for (int l = 0; l < n_layers_run; ++l) {  // TransformerSentenceEncoderLayer.forward, layer_norm_first False (:1258-1283)
+    const float* lg = m->lng + (size_t)l * 2 * D;
+    const float* lb = m->lnb + (size_t)l * 2 * D;
+    DN_TRY(linear(r, xn, D, layer_mat(m->qkv_W, l, 3 * D, D, es), m->qkv_b + (size_t)l * 3 * D, 3 * D, DN_EPI_BIAS, b.qkv, sdt));
+    DN_TRY(attention(dtype, H, dh, b.qkv, 3 * D, eoff(b.qkv, D, ses), eoff(b.qkv, 2 * D, ses), 3 * D, B, S, 0, out_lengths, b.ao, s));
+    DN_TRY(linear_resadd(r, b.ao, D, layer_mat(m->out_W, l, D, D, es), m->out_b + (size_t)l * D, cur));
+    norm_both(r, cur, lg, lb, other);  // self_attn_layer_norm BEHIND the residual
+    std::swap(cur, other);
+    DN_TRY(linear(r, xn, D, layer_mat(m->fc1_W, l, F, D, es), m->fc1_b + (size_t)l * F, F, DN_EPI_BIAS, b.hf, DN_F32));
+    hipLaunchKernelGGL(gelu_rows_kernel, dim3(ew_grid((int64_t)r.M * F / 4)), dim3(256), 0, s, b.hf, b.h, dtype, (int64_t)r.M * F / 4);
+    DN_TRY(linear_resadd(r, b.h, F, layer_mat(m->fc2_W, l, D, F, es), m->fc2_b + (size_t)l * D, cur));
+    if (l + 1 < n_layers_run) norm_both(r, cur, lg + D, lb + D, other);  // final_layer_norm
+    else layernorm(r, cur, lg + D, lb + D, other, DN_F32);
+    std::swap(cur, other);
+  }
+  mark();
+  hipLaunchKernelGGL(masked_copy_kernel, dim3(ew_grid((int64_t)r.M * D / 4)), dim3(256), 0, s, cur, out_lengths, B, S, D, out);
+  mark();
+  DN_CHECK_LAUNCH("dn_hubert_forward");
+  return DN_OK;
+}

@@ -166,3 +166,35 @@ def random_nar_encoder_state_dict(input_dim=80, conv_channels=1024, kernel=5, di
         sd[p + "final_layer_norm.weight"], sd[p + "final_layer_norm.bias"] = torch.ones(dim), torch.zeros(dim)
     sd["layer_norm.weight"], sd["layer_norm.bias"] = torch.ones(dim), torch.zeros(dim)
     return sd
+
+
+def random_hubert_state_dict(cfg, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """A seeded HubertModel state dict under the reference's key names (fairseq/models/hubert/hubert.py:242-323 without label
+    dictionaries) for `cfg` (diffnorm_amd.hubert.MHUBERT_BASE's fields): fan-in scaled weights, unit norms, weight-norm gain = |v|."""
+    from .hubert import conv_layers
+
+    layers = conv_layers(cfg)
+    Cw, D, Fd, G, kp = layers[0][0], cfg.encoder_embed_dim, cfg.encoder_ffn_embed_dim, cfg.conv_pos_groups, cfg.conv_pos
+    it = _Init(seed)
+    for i, (_, k, _) in enumerate(layers):
+        it.lin(f"feature_extractor.conv_layers.{i}.0", Cw, 1 if i == 0 else Cw, bias=False, k=k)
+        it.sd[f"feature_extractor.conv_layers.{i}.0.weight"] *= 3.0 ** 0.5 * 1.6  # unit-variance fan-in init times the GELU's loss
+    for name, width in (("feature_extractor.conv_layers.0.2", Cw), ("layer_norm", Cw), ("encoder.layer_norm", D)):
+        it.sd[name + ".weight"], it.sd[name + ".bias"] = torch.ones(width), torch.zeros(width)
+    if Cw != D:
+        it.lin("post_extract_proj", D, Cw)
+    v = torch.randn(D, D // G, kp, generator=it.g) * (4.0 / (kp * D)) ** 0.5
+    it.sd["encoder.pos_conv.0.weight_v"] = v
+    it.sd["encoder.pos_conv.0.weight_g"] = v.pow(2).sum(dim=(0, 1), keepdim=True).sqrt()
+    it.sd["encoder.pos_conv.0.bias"] = torch.zeros(D)
+    for l in range(cfg.encoder_layers):
+        p = f"encoder.layers.{l}."
+        for proj in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            it.lin(p + "self_attn." + proj, D, D)
+        it.lin(p + "fc1", Fd, D)
+        it.lin(p + "fc2", D, Fd)
+        for name in ("self_attn_layer_norm", "final_layer_norm"):
+            it.sd[p + name + ".weight"], it.sd[p + name + ".bias"] = torch.ones(D), torch.zeros(D)
+    it.sd["mask_emb"] = torch.rand(D, generator=it.g)
+    it.lin("final_proj", D, D)
+    return it.sd

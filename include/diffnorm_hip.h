@@ -1239,6 +1239,74 @@ int dn_voc_forward(DnVoc* m, const int32_t* codes, const int32_t* lengths, const
 int dn_voc_set_profile(DnVoc* m, int32_t on);
 int dn_voc_stage_times(DnVoc* m, float* ms, int32_t cap);
 
+/* ------------------------------------------------------------------ mHuBERT front end: waveform -> layer features -> k-means units */
+/* The reader of the recipe's feature dump (scripts/prepare/feature_dump.sh -> examples/textless_nlp/gslm/speech2unit/pretrained/
+ * hubert_feature_reader.py): HubertModel.extract_features(source, padding_mask=None, mask=False, output_layer=k)
+ * (fairseq/models/hubert/hubert.py:429-476, 529-545), eval mode, one utterance at a time.  A batch here gives every utterance what it
+ * would get ALONE (the reader never batches; the reference's batched padding-mask path is not what this reproduces): a result depends
+ * on the utterance's own samples and length only, not on B, the row or L.  Kernels and the pass: csrc/hubert.hip.  Supported form
+ * (mHuBERT-base): extractor_mode "default", conv_bias False, layer_norm_first False, layer_type "transformer",
+ * required_seq_len_multiple 1, task normalize False; every conv layer of the same width.
+ *
+ * Grouped Conv1d with 'same' zero padding of k / 2 frames in front and SamePad's trim behind (an even k drops the last frame;
+ * make_conv_pos, fairseq/models/wav2vec/wav2vec2.py:899-915), then GELU and the residual add (TransformerEncoder.extract_features,
+ * wav2vec2.py:1020-1022):
+ *   out[b,t,g Cg + co] = x[b,t,g Cg + co] + gelu_erf(bias[g Cg + co] + sum_{j<k} sum_{ci<Cg} w[g][j][ci][co] x[b, t + j - k/2, g Cg + ci])
+ * for t < lengths[b]; frames outside [0, lengths[b]) read as ZEROS (what a lone utterance's padding gives) and rows t >= lengths[b] of
+ * out are written as zeros.  x, out fp32 [B, T, C]; w fp32 [groups][k][Cg][Cg] with the weight-norm folded in by the host; fp32 FMA
+ * accumulation over (tap, channel) in that order whatever the engine's dtype.  One workgroup owns a frame tile of one group and stages
+ * the tile's rows plus the k - 1 halo once in LDS for all taps; tiles are counted from frame 0 of each sequence.  Cg a multiple of 4,
+ * <= 64; k <= 128.                                                                                                             */
+int dn_grouped_conv1d(const float* x, const float* w, const float* bias, float* out, const int32_t* lengths, int32_t B, int32_t T, int32_t C,
+                      int32_t groups, int32_t k, void* stream);
+
+/* units[m] = argmax_j (x_m . c_j - |c_j|^2 / 2): the arg-min of |x|^2 - 2 x . c + |c|^2 of
+ * examples/hubert/simple_kmeans/dump_km_label.py:38-53 (ApplyKmeans) and of the recipe's quantize_with_kmeans.py (sklearn predict);
+ * ties go to the lowest index.  feats fp32 [M, D]; centroids: the packed fp32 matrix [n -> multiple of 128][D] (zero rows behind the
+ * table) and half_norm fp32 [n -> multiple of 4] = -|c_j|^2 / 2 computed by the host in float64 (any value in the pad entries: they
+ * are not compared).  Always the DN_F32 contraction (fp32 MFMA), whatever arithmetic the engine in front runs in: a unit is a
+ * decision.  One contraction with half_norm as the bias, then dn_argmax_units' row arg-max.  D a multiple of 32; workspace:
+ * dn_kmeans_workspace_bytes(M, n).                                                                                           */
+size_t dn_kmeans_workspace_bytes(int32_t M, int32_t n_centroids);
+int dn_kmeans_assign(const float* feats, const float* centroids, const float* half_norm, int32_t M, int32_t D, int32_t n_centroids,
+                     int32_t* units, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Packed tensors (diffnorm_amd/hubert.py::pack_hubert; matrices [rows -> 128][K] in cfg.dtype, everything else fp32):
+ *   0 conv0_w fp32 [16][C] (tap j of channel c at [j][c], zero rows behind the kernel)   1 GroupNorm gamma [C]   2 beta [C]
+ *   3 .. n_conv + 1: conv layer i >= 1 as [C][k_i C], column j C + c = weight[o][c][j]
+ *   then: layer_norm g, b [C] (HubertModel.layer_norm)   post_extract_proj W [dim][C], b
+ *   pos_conv w fp32 [groups][k][Cg][Cg] (weight-norm folded: g v / |v| over dim 2, float64 on the host), bias [dim]
+ *   encoder.layer_norm g, b   qkv_W [layers][3 dim][dim] (q ; k ; v), qkv_b   out_W, out_b   fc1_W, fc1_b   fc2_W, fc2_b
+ *   ln_g [layers][2][dim] (self_attn_layer_norm ; final_layer_norm), ln_b   zeros [C] (the bias of the bias-free convs)        */
+#define DN_HUBERT_MAX_CONV 8
+typedef struct DnHubert DnHubert;
+typedef struct {
+  int32_t n_conv, conv_dim;
+  int32_t conv_kernel[DN_HUBERT_MAX_CONV], conv_stride[DN_HUBERT_MAX_CONV];
+  int32_t dim, ffn, layers, heads, conv_pos, conv_pos_groups, dtype;
+  int32_t has_proj; /* 0: no post_extract_proj (conv_dim == dim, hubert.py:264-268); its two table entries are then not read */
+} DnHubertConfig;
+int dn_hubert_create(const DnHubertConfig* cfg, const void* const* weights, int32_t n_weights, DnHubert** out);
+void dn_hubert_destroy(DnHubert* m);
+/* frames of L samples behind the conv stack: floor((len - k) / stride) + 1 per layer (Wav2Vec2Model._get_feat_extract_output_lengths,
+ * wav2vec2.py:564-579); 0 when L is too short for one frame                                                                  */
+int32_t dn_hubert_out_frames(const DnHubert* m, int32_t L);
+size_t dn_hubert_workspace_bytes(const DnHubert* m, int32_t B, int32_t L);
+/* wave fp32 [B, L] (any finite values behind an utterance's samples), lengths int32 [B] (each long enough for one frame: the caller
+ * checks; a shorter one yields no valid row) -> out fp32 [B, S, dim], S = dn_hubert_out_frames(m, L), the output of transformer layer
+ * n_layers_run - 1 (output_layer = n_layers_run: TransformerEncoder.extract_features breaks at tgt_layer, wav2vec2.py:1045-1055);
+ * rows at or past out_lengths[b] are written as zeros.  Refused before anything is launched: L shorter than one frame, n_layers_run
+ * outside [1, layers], and any (B, L) for which a buffer would pass 2^31 - 1 elements (the kernels index rows in 32 bits).  No
+ * allocation and no synchronisation inside.                                                                                  */
+int dn_hubert_forward(DnHubert* m, const float* wave, const int32_t* lengths, int32_t B, int32_t L, int32_t n_layers_run, float* out,
+                      int32_t* out_lengths, void* workspace, size_t workspace_bytes, void* stream);
+/* Stage timing of dn_hubert_forward (tools/hubert_bench.py): events recorded between the stages while switched on;
+ * dn_hubert_stage_times waits for the last profiled forward and returns DN_HUBERT_STAGES values in ms: first conv + GroupNorm,
+ * conv layers 1.., layer_norm + post_extract_proj + positional conv, the transformer layers, the masked copy of the output.    */
+#define DN_HUBERT_STAGES 5
+int dn_hubert_set_profile(DnHubert* m, int32_t on);
+int dn_hubert_stage_times(DnHubert* m, float* ms, int32_t cap);
+
 #ifdef __cplusplus
 }
 #endif
