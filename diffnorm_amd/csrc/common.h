@@ -166,6 +166,23 @@ __device__ __forceinline__ float4 load4(const void* base, int64_t elem_off, int 
   return *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(base) + elem_off);
 }
 
+// one element as `dtype` at element offset `off`
+__device__ __forceinline__ void store_act(void* p, int64_t off, int dtype, float v) {
+  if (dtype == DN_BF16X3)
+    store1_split(p, off, v);
+  else if (dn_is16(dtype))
+    reinterpret_cast<uint16_t*>(p)[off] = to_h16(dtype, v);
+  else
+    reinterpret_cast<float*>(p)[off] = v;
+}
+
+// sum over the 64 lanes of a wave, left in every lane
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 // Reductions over the four lanes {l, l^16, l^32, l^48} with the gfx950 half/row swaps instead of ds_bpermute:
 // v_permlane32_swap(a, b) exchanges lanes 32-63 of a with lanes 0-31 of b, v_permlane16_swap the odd 16-lane rows of a
 // with the even rows of b; fed the same value twice they leave {x[l], x[l^32]} resp. {x[l], x[l^16]} in the two results.

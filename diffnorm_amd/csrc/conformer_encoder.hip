@@ -168,7 +168,7 @@ extern "C" int dn_conformer_encoder_forward(DnConformerEnc* m, const float* feat
   const ConfBufs b = plan_conf(m, B, L, ar);
   DN_TRY(check_workspace("dn_conformer_encoder_forward", workspace, workspace_bytes, ar.off));
   const int dtype = c.dtype, es = esize(dtype), D = c.dim, F = c.ffn, H = c.heads, dh = D / H, P = 2 * S - 1;
-  const int sdt = side_dt(dtype), ses = esize(sdt);
+  const int sdt = side_dtype(dtype), ses = esize(sdt);
   const Rows r{dtype, B * S, S, D, s};
   DN_TRY(m->sub.run(dtype, feats, B, L, b.sub, s));
   // ---- x = linear(sqrt(D) * glu(conv))  (s2t_conformer.py:108-120)

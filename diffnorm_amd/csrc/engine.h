@@ -17,6 +17,14 @@ inline int padn(int c) { return round_up(c, 128); }   // packed weight rows
 inline const void* eoff(const void* p, size_t elems, int es) { return static_cast<const char*>(p) + elems * es; }
 inline void* eoff(void* p, size_t elems, int es) { return static_cast<char*>(p) + elems * es; }
 inline int esize(int dtype) { return dtype == DN_BF16 || dtype == DN_F16 ? 2 : 4; }
+// DN_BF16X3: tensors that are read by an epilogue or by the attention kernel rather than staged as a contraction operand stay
+// plain fp32 (the WaveNet block's residual branch, q / k / v)
+inline int side_dtype(int dtype) { return dtype == DN_BF16X3 ? DN_F32 : dtype; }
+// blocks of 256 threads of a grid-stride element-wise kernel over n > 0 items
+inline int ew_grid(int64_t n) {
+  const int64_t b = (n + 255) / 256;
+  return (int)(b > 4096 ? 4096 : b);
+}
 
 #define DN_TRY(expr)          \
   do {                        \
@@ -126,7 +134,50 @@ struct StepGraph {
   StepKey key;
 };
 
+// ---- The update kernels of the device loops (pointwise.hip).
+// Where a scheduled update takes its normals from: the utterances' keys (row_quads = T Z / 4 quads per utterance; noise and seed are
+// not read), else the injected rows (noise_row floats apart; 0: `noise` is the row whatever the step index), else `seed`.
+struct SchedNoise {
+  const float* noise;
+  int64_t noise_row;
+  uint64_t seed;
+  const uint64_t* keys;
+  int64_t row_quads;
+};
+inline SchedNoise sched_noise(const float* noise, int64_t noise_row, uint64_t seed, const uint64_t* keys, int64_t row_quads) {
+  return keys ? SchedNoise{nullptr, 0, 0, keys, row_quads} : SchedNoise{noise, noise_row, seed, nullptr, 0};
+}
+// One update of a chain over a timestep schedule, in place on elements [elem0, elem0 + n_elem) of the whole batch's x (both multiples
+// of 4): row *counter of the rule's coefficients.  The descriptor is the kernel's argument as it stands.
+enum SchedRule { SCHED_DDIM, SCHED_DPM2M, SCHED_GAUSSIAN };
+struct SchedStep {
+  int rule;
+  float* x;
+  int64_t elem0, n_elem;
+  // eps source: `eps` at the element, or (guided; elem0 = 0) the conditioned rows eps[0:n_elem] combined at `scale` with the null rows
+  // eps[n_elem:2 n_elem].  Sink: x, and xin[0:n_elem] (+ xin[n_elem:2 n_elem] when guided) unless xin is null or x itself.
+  const float* eps;
+  int guided;
+  float scale;
+  float* xin;
+  // rule: coef [n_steps, DN_DDIM_SCHED_COLS | DN_DPM_COLS | DN_GD_COLS], steps (the rows' timesteps: DDIM always, else keyed only)
+  const float* coef;
+  const int32_t *steps, *counter;
+  int eta_on;                      // SCHED_DDIM (keys imply it)
+  float* hist;                     // SCHED_DPM2M: the previous data prediction, the whole batch's
+  int n_steps, sampler, clip;      // SCHED_GAUSSIAN
+  float eta;
+  SchedNoise src;
+};
+// `who` names the loop in the messages ("<who>: the latent width must be a multiple of 4", "<who> step: <HIP error>")
+int sched_step_launch(const char* who, const SchedStep& d, void* stream);
+
 }  // namespace dn
+
+// the ancestral update of dn_ddpm_loop[_keyed], and what the dn_gaussian_* entries check of the update's own arguments (pointwise.hip)
+int dn_ddpm_step_launch(float* x, const float* eps, int M, int C, int T, const float* table, const int32_t* t, int clip, const float* noise,
+                        int64_t noise_row, int t_top, uint64_t seed, const uint64_t* keys, int b0, void* stream);
+int dn_gaussian_sched_args(const char* who, int32_t n_steps, int32_t sampler, float eta);
 
 struct DnEps {
   DnEpsConfig cfg;

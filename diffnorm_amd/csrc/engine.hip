@@ -30,9 +30,6 @@ inline bool fuse_norm_enabled(int Dp, int dtype) {
 inline bool split_norm_enabled(int Dp, int dtype) {
   return option_or(OPT_NO_SPLIT_NORM, 0) == 0 && Dp % 64 == 0 && !fuse_norm_enabled(Dp, dtype);
 }
-// DN_BF16X3: tensors that are read by an epilogue or by the attention kernel rather than staged as a contraction operand stay
-// plain fp32 (the WaveNet block's residual branch, q / k / v)
-inline int side_dtype(int dtype) { return dtype == DN_BF16X3 ? DN_F32 : dtype; }
 
 // DN_KBLOCK: unset = K-blocked buffers where the consuming contraction lands on a tile that gains from them, 0 = never,
 // 1 = always (the contraction then runs on a tile that takes them; tests).  Read per call (host side, once per capture).
@@ -668,18 +665,6 @@ extern "C" size_t dn_ddim_workspace_bytes(const DnEps* m, int32_t B, int32_t T, 
   return (whole > halves ? whole : halves) + ddim_extra_bytes(m, B, T, start_step);
 }
 
-int dn_ddpm_step_launch(float* x, const float* eps, int M, int C, int T, const float* table, const int32_t* t, int clip, const float* noise,
-                        int64_t noise_row, int t_top, uint64_t seed, const uint64_t* keys, int b0, hipStream_t stream);  // pointwise.hip
-int dn_ddim_sched_step_launch(float* x, const float* eps, int64_t elem0, int64_t n_elem, const float* coef, const int32_t* steps,
-                              const int32_t* counter, int eta_on, const float* noise, int64_t noise_row, uint64_t seed, const uint64_t* keys,
-                              int64_t row_quads, hipStream_t stream);  // pointwise.hip
-int dn_dpm2m_step_launch(float* x, const float* eps, float* hist, int64_t elem0, int64_t n_elem, const float* coef, const int32_t* counter,
-                         hipStream_t stream);  // pointwise.hip
-int dn_gaussian_sched_step_launch(float* x, const float* eps, int64_t elem0, int64_t n_elem, const float* table, const int32_t* steps,
-                                  const int32_t* counter, int n_steps, int sampler, int clip, float eta, const float* noise, int64_t noise_row,
-                                  uint64_t seed, const uint64_t* keys, int64_t row_quads, hipStream_t stream);  // pointwise.hip
-int dn_gaussian_sched_args(const char* who, int32_t n_steps, int32_t sampler, float eta);                      // pointwise.hip
-
 namespace {
 // Runs n steps of a chain on `s` as replays of one captured step.  A hit of `slot` replays all n.  A miss evicts the slot, captures
 // `step` (recorded, not run), instantiates, stores the graph under `key` and replays it; with eager_first it runs one step eagerly
@@ -974,8 +959,10 @@ static int ddim_sched_loop(const char* who, DnEps* m, float* x, const int32_t* l
   d.kind.scheduled = 1;
   d.kind.eta = (uint16_t)eta_on;
   d.update = [=](const StepBufs& b, int, int b0, int nb, hipStream_t st) {
-    return dn_ddim_sched_step_launch(b.x, b.eps, (int64_t)b0 * b.T * b.z, (int64_t)nb * b.T * b.z, b.coef, b.steps, b.counter, eta_on, noise, b.all,
-                                     seed, keys, (int64_t)b.T * (b.z >> 2), st);
+    SchedStep u = {SCHED_DDIM, b.x, (int64_t)b0 * b.T * b.z, (int64_t)nb * b.T * b.z, b.eps};
+    u.coef = b.coef; u.steps = b.steps; u.counter = b.counter; u.eta_on = eta_on;
+    u.src = sched_noise(noise, b.all, seed, keys, (int64_t)b.T * (b.z >> 2));
+    return sched_step_launch("dn_ddim_sched_loop", u, st);
   };
   return sampler_loop(m, x, lengths, B, T, 0, 0, coef, timesteps, flags, workspace, workspace_bytes, stream, d);
 }
@@ -1013,7 +1000,9 @@ extern "C" int dn_dpm_loop(DnEps* m, float* x, const int32_t* lengths, int32_t B
   LoopDesc d = {"dn_dpm_loop", "dn_dpm_workspace_bytes", dn_dpm_workspace_bytes, steps, n_steps, DN_DPM_COLS, true, step_kind(0, nullptr), nullptr};
   d.kind.scheduled = d.kind.dpm = 1;
   d.update = [](const StepBufs& b, int, int b0, int nb, hipStream_t st) {
-    return dn_dpm2m_step_launch(b.x, b.eps, b.hist, (int64_t)b0 * b.T * b.z, (int64_t)nb * b.T * b.z, b.coef, b.counter, st);
+    SchedStep u = {SCHED_DPM2M, b.x, (int64_t)b0 * b.T * b.z, (int64_t)nb * b.T * b.z, b.eps};
+    u.coef = b.coef; u.counter = b.counter; u.hist = b.hist;
+    return sched_step_launch("dn_dpm_loop", u, st);
   };
   return sampler_loop(m, x, lengths, B, T, 0, 0, coef, timesteps, flags, workspace, workspace_bytes, stream, d);
 }
@@ -1049,8 +1038,11 @@ static int gaussian_loop(const char* who, DnEps* m, float* x, const int32_t* len
   d.kind.eta = ddim && eta != 0.0f;
   if (ddim) memcpy(&d.kind.eta_bits, &eta, 4);
   d.update = [=](const StepBufs& b, int, int b0, int nb, hipStream_t st) {
-    return dn_gaussian_sched_step_launch(b.x, b.eps, (int64_t)b0 * b.T * b.z, (int64_t)nb * b.T * b.z, b.coef, b.steps, b.counter, n_steps, sampler,
-                                         clip, eta, noise, b.all, seed, keys, (int64_t)b.T * (b.z >> 2), st);
+    SchedStep u = {SCHED_GAUSSIAN, b.x, (int64_t)b0 * b.T * b.z, (int64_t)nb * b.T * b.z, b.eps};
+    u.coef = b.coef; u.steps = b.steps; u.counter = b.counter;
+    u.n_steps = n_steps; u.sampler = sampler; u.clip = clip; u.eta = eta;
+    u.src = sched_noise(noise, b.all, seed, keys, (int64_t)b.T * (b.z >> 2));
+    return sched_step_launch("dn_gaussian_loop", u, st);
   };
   return sampler_loop(m, x, lengths, B, T, 0, 0, table, timesteps, flags, workspace, workspace_bytes, stream, d);
 }
@@ -1188,8 +1180,6 @@ int attn_call(int dtype, const void* q, int ldq, const void* k, const void* v, i
   return dn_attention(&a, s);
 }
 
-inline int ew(int64_t n) { return (int)std::min<int64_t>((n + 255) / 256, 4096); }
-
 }  // namespace
 
 extern "C" size_t dn_eps_cond_workspace_bytes(const DnEps* m, int32_t B, int32_t T, int32_t Tp) {
@@ -1281,7 +1271,7 @@ extern "C" int dn_eps_forward_cond_ex(DnEps* m, const float* x, const int32_t* t
     p.bias = m->tpc_b; p.epilogue = DN_EPI_SILU; p.out = b.pc; p.ldo = C; p.out_dtype = DN_F32;
     DN_TRY(dn_conv_gemm(&p, s));
   }
-  hipLaunchKernelGGL(dn::assemble_cond2_kernel, dim3(ew((int64_t)B * 2 * C)), dim3(256), 0, s, b.pc, b.pc, m->null_pc, drop, B, C, b.cond2);  // (second half: pc or null_pc by drop)
+  hipLaunchKernelGGL(dn::assemble_cond2_kernel, dim3(ew_grid((int64_t)B * 2 * C)), dim3(256), 0, s, b.pc, b.pc, m->null_pc, drop, B, C, b.cond2);  // (second half: pc or null_pc by drop)
   {  // prompt half + bias
     DnGemmParams p = gemm_base(DN_F32, B, m->n_cond, C, 1);
     p.terms[0].A = b.cond2 + C; p.terms[0].lda = 2 * C; p.terms[0].W = reinterpret_cast<const float*>(m->cond_W) + C; p.terms[0].ldw = 2 * C;
@@ -1297,14 +1287,14 @@ extern "C" int dn_eps_forward_cond_ex(DnEps* m, const float* x, const int32_t* t
     DN_TRY(dn_conv_gemm(&p, s));
   }
   // keys/values of every resampler layer = [latents ; projected prompt]: the prompt rows are placed once
-  hipLaunchKernelGGL(dn::place_rows_kernel, dim3(ew((int64_t)B * Tp * Dp)), dim3(256), 0, s, b.ctx, dtype, (int64_t)Tp * Dp, nullptr, nullptr, b.kvsrc,
+  hipLaunchKernelGGL(dn::place_rows_kernel, dim3(ew_grid((int64_t)B * Tp * Dp)), dim3(256), 0, s, b.ctx, dtype, (int64_t)Tp * Dp, nullptr, nullptr, b.kvsrc,
                      dtype, B, Tp, Dp, Lk, ml);
-  hipLaunchKernelGGL(dn::place_rows_kernel, dim3(ew((int64_t)B * ml * Dp)), dim3(256), 0, s, m->lat_pos, DN_F32, (int64_t)0, nullptr, nullptr, b.lat,
+  hipLaunchKernelGGL(dn::place_rows_kernel, dim3(ew_grid((int64_t)B * ml * Dp)), dim3(256), 0, s, m->lat_pos, DN_F32, (int64_t)0, nullptr, nullptr, b.lat,
                      DN_F32, B, ml, Dp, ml, 0);
   hipLaunchKernelGGL(dn::add_const_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, s, prompt_lengths, ml, Tp, b.klen, B);  // mask = [ones(ml) ; prompt_mask]
   for (int l = 0; l < R; ++l) {
     DN_TRY(dn_convert_rows(b.lat, DN_F32, Dp, b.lat_act, dtype, Dp, B * ml, Dp, s));
-    hipLaunchKernelGGL(dn::place_rows_kernel, dim3(ew((int64_t)B * ml * Dp)), dim3(256), 0, s, b.lat_act, dtype, (int64_t)ml * Dp, nullptr, nullptr,
+    hipLaunchKernelGGL(dn::place_rows_kernel, dim3(ew_grid((int64_t)B * ml * Dp)), dim3(256), 0, s, b.lat_act, dtype, (int64_t)ml * Dp, nullptr, nullptr,
                        b.kvsrc, dtype, B, ml, Dp, Lk, 0);
     {
       DnGemmParams p = gemm_base(dtype, B * ml, hd, Dp, ml);
@@ -1342,7 +1332,7 @@ extern "C" int dn_eps_forward_cond_ex(DnEps* m, const float* x, const int32_t* t
   }
   DN_TRY(dn_rmsnorm(b.lat, Dp, b.lat_act, Dp, dtype, B * ml, D, ml, m->rnorm_g, nullptr, 0, 0, s));
   // c = where(drop, null_prompt_tokens, resampled) (:855-859)
-  hipLaunchKernelGGL(dn::place_rows_kernel, dim3(ew((int64_t)B * ml * Dp)), dim3(256), 0, s, b.lat_act, dtype, (int64_t)ml * Dp, m->null_tok, drop, b.c_act,
+  hipLaunchKernelGGL(dn::place_rows_kernel, dim3(ew_grid((int64_t)B * ml * Dp)), dim3(256), 0, s, b.lat_act, dtype, (int64_t)ml * Dp, m->null_tok, drop, b.c_act,
                      dtype, B, ml, Dp, ml, 0);
   {  // keys / values of all cross-attention layers at once (they depend on the prompt only)
     DnGemmParams p = gemm_base(dtype, B * ml, 2 * hd, Dp, ml);
@@ -1355,7 +1345,7 @@ extern "C" int dn_eps_forward_cond_ex(DnEps* m, const float* x, const int32_t* t
   }  // !reuse_prompt
   // ---- the step's conditioning rows: time half (from the chain's table, or contracted here) + prompt half
   if (time_table) {
-    hipLaunchKernelGGL(dn::cond_rows_from_table_kernel, dim3(ew((int64_t)B * m->n_cond / 4)), dim3(256), 0, s, time_table, t, table_t0, table_n, b.gbp, B,
+    hipLaunchKernelGGL(dn::cond_rows_from_table_kernel, dim3(ew_grid((int64_t)B * m->n_cond / 4)), dim3(256), 0, s, time_table, t, table_t0, table_n, b.gbp, B,
                        m->n_cond, b.gb);
   } else {
     DnGemmParams p = gemm_base(DN_F32, B, m->n_cond, C, 1);
@@ -1397,12 +1387,6 @@ extern "C" int dn_eps_forward_cond_ex(DnEps* m, const float* x, const int32_t* t
 }
 
 // ------------------------------------------------------------------------------------------ guided chain over a timestep schedule
-int dn_guided_sched_step_launch(float* x, float* xin, const float* both, int64_t n_elem, int guided, float scale, const float* coef,
-                                const int32_t* steps, const int32_t* counter, int eta_on, const float* noise, int64_t noise_row, uint64_t seed,
-                                const uint64_t* keys, int64_t row_quads, hipStream_t stream);  // pointwise.hip
-int dn_guided_dpm_step_launch(float* x, float* xin, const float* both, float* hist, int64_t n_elem, int guided, float scale, const float* coef,
-                              const int32_t* counter, hipStream_t stream);  // pointwise.hip
-
 namespace {
 // drop mask of the guided pass over n rows = [conditioned (first B) ; null]
 __global__ void drop_mask_kernel(int32_t* drop, int n, int B) {
@@ -1556,8 +1540,10 @@ static int guided_ddim_loop(const char* who, DnEps* m, float* x, const int32_t* 
   GuidedDesc d = {who, "dn_guided_ddim_workspace_bytes", "dn_ddim_sched_loop", DN_DDIM_SCHED_COLS, false, step_kind(seed, noise, keys), nullptr};
   d.kind.eta = (uint16_t)eta_on;
   d.update = [=](const GuidedBufs& g, float* xb, float* xin, int64_t n_elem, int guided, float scale, hipStream_t st) {
-    return dn_guided_sched_step_launch(xb, xin, g.both, n_elem, guided, scale, g.coef, g.steps, g.counter, eta_on, noise, n_elem, seed, keys,
-                                       n_elem / B / 4, st);
+    SchedStep u = {SCHED_DDIM, xb, 0, n_elem, g.both, guided, scale, xin};
+    u.coef = g.coef; u.steps = g.steps; u.counter = g.counter; u.eta_on = eta_on;
+    u.src = sched_noise(noise, n_elem, seed, keys, n_elem / B / 4);
+    return sched_step_launch("dn_guided_ddim_loop", u, st);
   };
   return guided_loop(m, x, lengths, prompt, prompt_lengths, B, T, Tp, cond_scale, steps, coef, n_steps, timesteps, flags, workspace,
                      workspace_bytes, stream, d);
@@ -1594,7 +1580,9 @@ extern "C" int dn_guided_dpm_loop(DnEps* m, float* x, const int32_t* lengths, co
   GuidedDesc d = {"dn_guided_dpm_loop", "dn_guided_dpm_workspace_bytes", "dn_dpm_loop", DN_DPM_COLS, true, step_kind(0, nullptr), nullptr};
   d.kind.dpm = 1;
   d.update = [](const GuidedBufs& g, float* xb, float* xin, int64_t n_elem, int guided, float scale, hipStream_t st) {
-    return dn_guided_dpm_step_launch(xb, xin, g.both, g.hist, n_elem, guided, scale, g.coef, g.counter, st);
+    SchedStep u = {SCHED_DPM2M, xb, 0, n_elem, g.both, guided, scale, xin};
+    u.coef = g.coef; u.counter = g.counter; u.hist = g.hist;
+    return sched_step_launch("dn_guided_dpm_loop", u, st);
   };
   return guided_loop(m, x, lengths, prompt, prompt_lengths, B, T, Tp, cond_scale, steps, coef, n_steps, timesteps, flags, workspace,
                      workspace_bytes, stream, d);

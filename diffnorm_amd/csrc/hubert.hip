@@ -400,7 +400,7 @@ extern "C" int dn_hubert_forward(DnHubert* m, const float* wave, const int32_t* 
                L, (long long)b.max_elems);
   DN_TRY(check_workspace("dn_hubert_forward", workspace, workspace_bytes, ar.off));
   const int dtype = c.dtype, es = esize(dtype), C = c.conv_dim, D = c.dim, F = c.ffn, H = c.heads, dh = D / H;
-  const int sdt = side_dt(dtype), ses = esize(sdt);
+  const int sdt = side_dtype(dtype), ses = esize(sdt);
   ConvGeom g;
   g.n = c.n_conv;
   for (int i = 0; i < DN_HUBERT_MAX_CONV; ++i) { g.k[i] = c.conv_kernel[i]; g.s[i] = c.conv_stride[i]; }

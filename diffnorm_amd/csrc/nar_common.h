@@ -9,12 +9,6 @@
 namespace dn {
 namespace {
 
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // LayerNorm (eps 1e-5, biased variance, affine): x fp32 [M, ldx] -> y [M, ldy] in out_dtype (pad columns zeroed).  One wave per
 // row, D <= 1024 in registers.
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int ldx, void* __restrict__ y, int ldy, int out_dtype, int M,
@@ -30,7 +24,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     v[i] = c < D ? *reinterpret_cast<const float4*>(xr + c) : make_float4(0, 0, 0, 0);
     s += v[i].x + v[i].y + v[i].z + v[i].w;
   }
-  const float mean = wave_sum64(s) / (float)D;
+  const float mean = wave_sum(s) / (float)D;
   float q = 0.f;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -40,7 +34,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
       q += a * a + b * b + cc * cc + d * d;
     }
   }
-  const float rstd = rsqrtf(wave_sum64(q) / (float)D + 1e-5f);
+  const float rstd = rsqrtf(wave_sum(q) / (float)D + 1e-5f);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int c = (i * 64 + lane) * 4;
@@ -56,11 +50,6 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 }
 
 // ---- the Conv1dSubsampler's gathers, shared by the two speech encoders (nar_encoder.hip, conformer_encoder.hip)
-__device__ __forceinline__ void store_act(void* p, int64_t off, int dtype, float v) {
-  if (dtype == DN_BF16X3) store1_split(p, off, v);
-  else if (dn_is16(dtype)) reinterpret_cast<uint16_t*>(p)[off] = to_h16(dtype, v);
-  else reinterpret_cast<float*>(p)[off] = v;
-}
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // Rows of the contraction that IS a Conv1d(k, stride 2, padding k / 2) over [B, Lin, C]: cols[b * Lout + t][j * C + c] = in[b][2 t + j - k / 2][c]
@@ -96,8 +85,6 @@ __host__ __device__ __forceinline__ int subsampled_len(int len, int n_conv) {
 }
 
 // ---------------------------------------------------------------------------------------------- host helpers of the passes
-inline int side_dt(int dtype) { return dtype == DN_BF16X3 ? DN_F32 : dtype; }  // q / k / v are read by the attention kernel, not staged
-inline int ew_grid(int64_t n) { return (int)std::min<int64_t>((n + 255) / 256, 4096); }  // blocks of a grid-stride elementwise kernel
 // layer l of a stacked packed weight [layers][padn(N)][K]
 inline const void* layer_mat(const void* W, int l, int N, int K, int es) { return eoff(W, (size_t)l * padn(N) * K, es); }
 

@@ -141,7 +141,7 @@ int cross_kv_proj(const DnNar* m, const void* src, int rows, int T, void* out, h
   p.terms[0].A = src; p.terms[0].lda = D; p.terms[0].a_gstride = 0;
   p.terms[0].W = m->ckv_W; p.terms[0].w_gstride = (int64_t)padn(2 * D) * D;
   p.bias = m->ckv_b; p.bias_gstride = 2 * D;
-  p.out = out; p.ldo = 2 * D; p.out_gstride = (int64_t)rows * 2 * D; p.out_dtype = side_dt(dtype);
+  p.out = out; p.ldo = 2 * D; p.out_gstride = (int64_t)rows * 2 * D; p.out_dtype = side_dtype(dtype);
   return dn_conv_gemm(&p, s);
 }
 }  // namespace
@@ -223,7 +223,7 @@ extern "C" int dn_nar_null_cross(DnNar* m, int32_t null_token, void* workspace, 
   DN_CHECK_ARG(m && workspace, "dn_nar_null_cross: null argument");
   DN_CHECK_ARG(null_token >= 0 && null_token < m->cfg.vocab, "dn_nar_null_cross: null token %d outside the vocabulary of %d", null_token, m->cfg.vocab);
   const int dtype = m->cfg.dtype, D = m->cfg.dim, L = m->cfg.layers;
-  const int sdt = side_dt(dtype), ses = esize(sdt);
+  const int sdt = side_dtype(dtype), ses = esize(sdt);
   Arena ar{(char*)workspace, 0, workspace_bytes};
   const NarNullBufs b = plan_null(m, ar);
   DN_TRY(check_workspace("dn_nar_null_cross", workspace, workspace_bytes, ar.off));
@@ -273,7 +273,7 @@ static int decoder_pass(const char* who, DnNar* m, int halves, const int32_t* to
   NarLiteralBufs lit{nullptr, nullptr, nullptr, nullptr};
   if (literal) lit = plan_literal(m, B, S, ar);
   DN_TRY(check_workspace(who, workspace, workspace_bytes, ar.off));
-  const int sdt = side_dt(dtype), ses = esize(sdt);
+  const int sdt = side_dtype(dtype), ses = esize(sdt);
   const Rows all{dtype, halves * M, T, D, s};
   const Rows cross = fold ? Rows{dtype, M, T, D, s} : all;  // the rows that run the encoder attention
   for (int h = 0; h < halves; ++h)

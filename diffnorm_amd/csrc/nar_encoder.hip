@@ -105,7 +105,7 @@ extern "C" int dn_nar_encoder_forward(DnNarEnc* m, const float* feats, const int
   hipLaunchKernelGGL(enc_embed_kernel, dim3(ew_grid((int64_t)r.M * D)), dim3(256), 0, s, b.sub.y1, src_lengths, 2, B, S, D, m->pos, c.pad, sqrtf((float)D), b.x,
                      out_lengths);
   // ---- pre-norm encoder layers
-  const int sdt = side_dt(dtype), ses = esize(sdt);
+  const int sdt = side_dtype(dtype), ses = esize(sdt);
   for (int l = 0; l < c.layers; ++l) {
     const float* g = m->ln_g + (size_t)l * 2 * D;
     const float* be = m->ln_b + (size_t)l * 2 * D;

@@ -2,14 +2,9 @@
 // argmax, Philox normal fill, row conversion.  All are one pass over their operands with 16-byte
 // accesses where the layout allows; reductions are wave-level (64 lanes) with DPP-free shuffles.
 #include "common.h"
+#include "engine.h"
 
 namespace dn {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // ------------------------------------------------------------------------------------------ RMSNorm
 // one wave per row; D <= 1024 keeps the row in registers (4 float4 per lane), larger D re-reads.
@@ -108,15 +103,6 @@ __global__ __launch_bounds__(256) void time_cond_kernel(const int32_t* __restric
 }
 
 // ------------------------------------------------------------------------------------------ scheduler
-__device__ __forceinline__ void store_act1(void* p, int64_t off, int dtype, float v) {
-  if (dtype == DN_BF16X3)
-    store1_split(p, off, v);
-  else if (dn_is16(dtype))
-    reinterpret_cast<uint16_t*>(p)[off] = to_h16(dtype, v);
-  else
-    reinterpret_cast<float*>(p)[off] = v;
-}
-
 __global__ __launch_bounds__(256) void ddim_step_kernel(const float* x, const float* __restrict__ eps, float* xo,
                                                         void* __restrict__ xact, int act_dtype, int ld_act, int M, int C, int ld,
                                                         int T, const float* __restrict__ coef, const int32_t* __restrict__ t) {
@@ -132,7 +118,7 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const float* x, const fl
     const float pn = __fdiv_rn(__fsub_rn(xv, __fmul_rn(sa, x1)), fmaxf(s1, 1e-10f));
     const float r = __fadd_rn(__fmul_rn(x1, cf[2]), __fmul_rn(cf[3], pn));
     xo[o] = r;
-    if (xact) store_act1(xact, (int64_t)m * ld_act + c, act_dtype, r);
+    if (xact) store_act(xact, (int64_t)m * ld_act + c, act_dtype, r);
   }
 }
 
@@ -147,7 +133,7 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__
     const int64_t o = (int64_t)m * ld + c;
     const float r = __fadd_rn(__fmul_rn(ca[tb], x[o]), __fmul_rn(cb[tb], noise[o]));
     out[o] = r;
-    if (oact) store_act1(oact, (int64_t)m * ld_act + c, act_dtype, r);
+    if (oact) store_act(oact, (int64_t)m * ld_act + c, act_dtype, r);
   }
 }
 
@@ -166,12 +152,12 @@ __global__ __launch_bounds__(256) void posterior_kernel(const float* __restrict_
     const float sd = expf(0.5f * lv);
     const float v = __fadd_rn(mean, __fmul_rn(sd, noise[(int64_t)row * ldn + c]));
     z[(int64_t)row * ldz + c] = v;
-    if (zact) store_act1(zact, (int64_t)row * ldz + c, act_dtype, v);
+    if (zact) store_act(zact, (int64_t)row * ldz + c, act_dtype, v);
     kl += mean * mean + expf(lv) - 1.0f - lv;
   }
   for (int c = Z + lane; c < ldz; c += 64) {
     z[(int64_t)row * ldz + c] = 0.f;
-    if (zact) store_act1(zact, (int64_t)row * ldz + c, act_dtype, 0.f);
+    if (zact) store_act(zact, (int64_t)row * ldz + c, act_dtype, 0.f);
   }
   if (kl_rows) {
     kl = wave_sum(kl);
@@ -389,203 +375,6 @@ __global__ __launch_bounds__(256) void chain_start_kernel(const float* __restric
   }
 }
 
-// ------------------------------------------------------------------------------------------ scheduled DDIM step of the device loop
-// One update of a DDIM chain over a timestep schedule (dn_ddim_sched_loop): row i = *counter of `coef` [n, DN_DDIM_SCHED_COLS] =
-// {sqrt abar_e, sqrt(1-abar_e), sqrt abar_tgt, sqrt(1-abar_tgt-sigma^2), sigma}, uniform over the batch.  eta_on == 0: the
-// statements of ddim_step_kernel, product for product (as compiled: see sched_update).  eta_on: + 1[e_i != 0] sigma z (diffusion/gaussian_diffusion.py:513-560), z
-// injected (row i of `noise`) or drawn here: Philox4x32-10, key = seed, counter = (element quad OF THE WHOLE BATCH, step index i) --
-// a half-batch launch passes its first quad (q0), so eager, graph replay and the two half-batch streams draw the same numbers.
-// kKeyed (dn_ddim_sched_loop_keyed, dn_ddim_sched_step_keyed, dn_guided_ddim_loop_keyed): drawn from the utterance's key under stream
-// 2 + steps[i] (step_noise_keyed4) -- the timestep, the frame and the channel, not the row, B, the padded T or the step index.
-// The three pieces below are the one definition of that update: dn_guided_ddim_loop's kernel applies them too, and the two chains are
-// tested bit-equal.
-struct SchedCoef {
-  float sa, s1, ct, cd, sg;
-};
-// row `step` of `coef`, with sigma masked to 0 without eta and at timestep 0
-__device__ __forceinline__ SchedCoef sched_coef(const float* __restrict__ coef, const int32_t* __restrict__ steps, int step, bool eta_on) {
-  const float* cf = coef + (int64_t)step * DN_DDIM_SCHED_COLS;
-  return {cf[0], cf[1], cf[2], cf[3], (eta_on && steps[step] != 0) ? cf[4] : 0.0f};
-}
-// where the scheduled updates take their normals from: the injected rows, else (kKeyed) the utterances' keys, else `seed`
-struct SchedNoise {
-  const float* noise;
-  int64_t noise_row;
-  uint64_t seed;
-  const uint64_t* keys;
-  int64_t row_quads;
-};
-// the four normals of quad q (elements i .. i+3) of the whole batch at `step` (timestep t): kKeyed: the utterance's stream 2 + t; else
-// the injected row, or Philox keyed by (q, step)
-template <bool kKeyed>
-__device__ __forceinline__ void sched_normal4(const SchedNoise& s, int64_t q, int64_t i, int step, int t, float (&z)[4]) {
-  const float* __restrict__ noise = s.noise;
-  const int64_t noise_row = s.noise_row;
-  const uint64_t seed = s.seed;
-  if (kKeyed) {
-    step_noise_keyed4(s.keys, q, s.row_quads, t, z);
-  } else if (noise) {
-    const float4 nv = *reinterpret_cast<const float4*>(noise + (int64_t)step * noise_row + i);
-    z[0] = nv.x; z[1] = nv.y; z[2] = nv.z; z[3] = nv.w;
-  } else {
-    philox_normal4(seed, (uint64_t)q, (uint32_t)step, z);
-  }
-}
-// ddim_step_kernel's statements as the compiler builds them (products contracted into the sums that take them: x - s1 eps,
-// x - sa x1, and x1 c2 onto the rounded c3 pn), spelled out so that no two kernels can be contracted differently
-__device__ __forceinline__ float sched_update(const SchedCoef& c, float x, float e, float z, bool eta_on) {
-  const float x1 = __fdiv_rn(fmaf(-c.s1, e, x), fmaxf(c.sa, 1e-10f));
-  const float pn = __fdiv_rn(fmaf(-c.sa, x1, x), fmaxf(c.s1, 1e-10f));
-  const float r = fmaf(c.ct, x1, __fmul_rn(c.cd, pn));
-  return eta_on ? fmaf(c.sg, z, r) : r;
-}
-
-template <bool kKeyed>
-__global__ __launch_bounds__(256) void ddim_sched_step_kernel(float* x, const float* __restrict__ eps, int64_t q0, int64_t nquad,
-                                                              const float* __restrict__ coef, const int32_t* __restrict__ steps,
-                                                              const int32_t* __restrict__ counter, int eta_on, SchedNoise src) {
-  const int step = *counter;
-  const SchedCoef c = sched_coef(coef, steps, step, eta_on);
-  const int t = kKeyed ? steps[step] : 0;
-  for (int64_t q = q0 + blockIdx.x * 256 + threadIdx.x; q < q0 + nquad; q += (int64_t)gridDim.x * 256) {
-    const int64_t i = q << 2;
-    const float4 xv = *reinterpret_cast<const float4*>(x + i), ev = *reinterpret_cast<const float4*>(eps + i);
-    float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (eta_on) sched_normal4<kKeyed>(src, q, i, step, t, z);
-    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, es[4] = {ev.x, ev.y, ev.z, ev.w};
-    float o[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = sched_update(c, xs[j], es[j], z[j], eta_on);
-    *reinterpret_cast<float4*>(x + i) = make_float4(o[0], o[1], o[2], o[3]);
-  }
-}
-
-// ------------------------------------------------------------------------------------------ DPM-Solver++(2M) step of the device loop
-// One update of a DPM-Solver++(2M) chain over a timestep schedule (dn_dpm_loop; Lu et al. 2022, data-prediction multistep form): row
-// i = *counter of `coef` [n, DN_DPM_COLS] = {alpha_s, sigma_s, a, b, c1, c0}, uniform over the batch:
-//   x0_i = (x - sigma_s eps) / max(alpha_s, 1e-10);  x <- a x + b (c1 x0_i + c0 x0_{i-1});  hist <- x0_i.
-// hist holds x0_{i-1} of the whole batch and is read only by a second-order row (c0 != 0: uniform over the launch), so the first row of
-// a chain never reads what an earlier chain left there.  Deterministic: no draws.  A half-batch launch passes its first quad (q0).
-// Every product and sum is spelled out, so eager, graph replay and the two half-batch streams cannot be contracted differently.
-// HBM-bound: 2 (+1) reads and 2 writes of 16 bytes per quad; grid-stride, no LDS.
-__global__ __launch_bounds__(256) void dpm2m_step_kernel(float* x, const float* __restrict__ eps, float* hist, int64_t q0, int64_t nquad,
-                                                         const float* __restrict__ coef, const int32_t* __restrict__ counter) {
-  const float* cf = coef + (int64_t)(*counter) * DN_DPM_COLS;
-  const float as = fmaxf(cf[0], 1e-10f), ss = cf[1], a = cf[2], b = cf[3], c1 = cf[4], c0 = cf[5];
-  const bool two = c0 != 0.0f;
-  for (int64_t q = q0 + blockIdx.x * 256 + threadIdx.x; q < q0 + nquad; q += (int64_t)gridDim.x * 256) {
-    const int64_t i = q << 2;
-    const float4 xv = *reinterpret_cast<const float4*>(x + i), ev = *reinterpret_cast<const float4*>(eps + i);
-    float4 hv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (two) hv = *reinterpret_cast<const float4*>(hist + i);
-    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, es[4] = {ev.x, ev.y, ev.z, ev.w}, hs[4] = {hv.x, hv.y, hv.z, hv.w};
-    float o[4], p[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      p[j] = __fdiv_rn(fmaf(-ss, es[j], xs[j]), as);
-      float d = __fmul_rn(c1, p[j]);
-      if (two) d = fmaf(c0, hs[j], d);
-      o[j] = fmaf(a, xs[j], __fmul_rn(b, d));
-    }
-    *reinterpret_cast<float4*>(x + i) = make_float4(o[0], o[1], o[2], o[3]);
-    *reinterpret_cast<float4*>(hist + i) = make_float4(p[0], p[1], p[2], p[3]);
-  }
-}
-
-// ------------------------------------------------------------------------------------------ guided scheduled DDIM step of the device loop
-// One update of the prompted, guided chain over a timestep schedule (dn_guided_ddim_loop), per float4 quad of the B-row latent:
-// eps = the conditioned row of `both` (kGuided: combined with the null row, n elements further, by cfg_combine_kernel's three rounded
-// operations), then ddim_sched_step_kernel's update through the same three helpers: its coefficient row, noise mask and noise source
-// (the Philox counter is the quad of the B-row batch and the step index, so a scale-1 chain draws what dn_ddim_sched_loop draws;
-// kKeyed: the utterance's stream 2 + steps[i], as ddim_sched_step_kernel<true>).
-// The result goes to x and to the model's next input: xin[0:n] and (kGuided) xin[n:2n] -- one pass where the host-driven chain
-// copies x twice, combines, updates and decrements.  !kGuided: nothing past n is touched, and xin may be x itself.
-// HBM-bound: (2 + kGuided) reads and (1 + 1 + kGuided) writes of n floats; 16-byte accesses, grid-stride, no LDS.
-template <bool kGuided, bool kEta, bool kKeyed>
-__global__ __launch_bounds__(256) void guided_sched_step_kernel(float* x, float* xin, const float* __restrict__ both, int64_t nquad, float scale,
-                                                                const float* __restrict__ coef, const int32_t* __restrict__ steps,
-                                                                const int32_t* __restrict__ counter, SchedNoise src) {
-  const int step = *counter;
-  const SchedCoef c = sched_coef(coef, steps, step, kEta);
-  const int t = kKeyed ? steps[step] : 0;
-  const int64_t n = nquad << 2;
-  for (int64_t q = blockIdx.x * 256 + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * 256) {
-    const int64_t i = q << 2;
-    const float4 xv = *reinterpret_cast<const float4*>(x + i), cv = *reinterpret_cast<const float4*>(both + i);
-    float es[4] = {cv.x, cv.y, cv.z, cv.w};
-    if (kGuided) {
-      const float4 uv = *reinterpret_cast<const float4*>(both + n + i);
-      const float us[4] = {uv.x, uv.y, uv.z, uv.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) es[j] = __fadd_rn(us[j], __fmul_rn(__fsub_rn(es[j], us[j]), scale));
-    }
-    float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (kEta) sched_normal4<kKeyed>(src, q, i, step, t, z);
-    const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
-    float o[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = sched_update(c, xs[j], es[j], z[j], kEta);
-    const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
-    *reinterpret_cast<float4*>(x + i) = ov;
-    if (kGuided) {
-      *reinterpret_cast<float4*>(xin + i) = ov;
-      *reinterpret_cast<float4*>(xin + n + i) = ov;
-    } else if (xin != x) {
-      *reinterpret_cast<float4*>(xin + i) = ov;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------ guided DPM-Solver++(2M) step of the device loop
-// One update of the prompted, guided DPM-Solver++(2M) chain (dn_guided_dpm_loop), per float4 quad of the B-row latent: eps formed as
-// guided_sched_step_kernel forms it (the conditioned row of `both`; kGuided: combined with the null row, n elements further, by
-// cfg_combine_kernel's three rounded operations), then dpm2m_step_kernel's update statement for statement: row *counter of `coef`
-// [n_steps, DN_DPM_COLS], x0 = (x - sigma_s eps) / max(alpha_s, 1e-10), x <- a x + b (c1 x0 + c0 hist), hist <- x0.  hist is read only
-// by a second-order row (c0 != 0: uniform over the launch), so a chain's first row never reads what an earlier chain left there.
-// Deterministic: no draws.  The result goes to x and to the model's next input: xin[0:n] and (kGuided) xin[n:2n]; !kGuided: nothing
-// past n is touched, and xin may be x itself.
-// HBM-bound: (2 + kGuided + second-order) reads and (2 + 1 + kGuided) writes of 16 bytes per quad; grid-stride, no LDS.
-template <bool kGuided>
-__global__ __launch_bounds__(256) void guided_dpm_step_kernel(float* x, float* xin, const float* __restrict__ both, float* hist, int64_t nquad,
-                                                              float scale, const float* __restrict__ coef,
-                                                              const int32_t* __restrict__ counter) {
-  const float* cf = coef + (int64_t)(*counter) * DN_DPM_COLS;
-  const float as = fmaxf(cf[0], 1e-10f), ss = cf[1], a = cf[2], b = cf[3], c1 = cf[4], c0 = cf[5];
-  const bool two = c0 != 0.0f;
-  const int64_t n = nquad << 2;
-  for (int64_t q = blockIdx.x * 256 + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * 256) {
-    const int64_t i = q << 2;
-    const float4 xv = *reinterpret_cast<const float4*>(x + i), cv = *reinterpret_cast<const float4*>(both + i);
-    float es[4] = {cv.x, cv.y, cv.z, cv.w};
-    if (kGuided) {
-      const float4 uv = *reinterpret_cast<const float4*>(both + n + i);
-      const float us[4] = {uv.x, uv.y, uv.z, uv.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) es[j] = __fadd_rn(us[j], __fmul_rn(__fsub_rn(es[j], us[j]), scale));
-    }
-    float4 hv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (two) hv = *reinterpret_cast<const float4*>(hist + i);
-    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, hs[4] = {hv.x, hv.y, hv.z, hv.w};
-    float o[4], p[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      p[j] = __fdiv_rn(fmaf(-ss, es[j], xs[j]), as);
-      float d = __fmul_rn(c1, p[j]);
-      if (two) d = fmaf(c0, hs[j], d);
-      o[j] = fmaf(a, xs[j], __fmul_rn(b, d));
-    }
-    const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
-    *reinterpret_cast<float4*>(x + i) = ov;
-    *reinterpret_cast<float4*>(hist + i) = make_float4(p[0], p[1], p[2], p[3]);
-    if (kGuided) {
-      *reinterpret_cast<float4*>(xin + i) = ov;
-      *reinterpret_cast<float4*>(xin + n + i) = ov;
-    } else if (xin != x) {
-      *reinterpret_cast<float4*>(xin + i) = ov;
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------ convert rows
 __global__ __launch_bounds__(256) void convert_rows_kernel(const void* __restrict__ src, int sdt, int lds, void* __restrict__ dst, int ddt,
                                                            int ldd, int M, int C) {
@@ -597,7 +386,7 @@ __global__ __launch_bounds__(256) void convert_rows_kernel(const void* __restric
       const int64_t so = (int64_t)m * lds + c;
       v = sdt == DN_BF16X3 ? load1_split(src, so) : dn_is16(sdt) ? from_h16(sdt, reinterpret_cast<const uint16_t*>(src)[so]) : reinterpret_cast<const float*>(src)[so];
     }
-    store_act1(dst, i, ddt, v);
+    store_act(dst, i, ddt, v);
   }
 }
 
@@ -652,19 +441,121 @@ __global__ __launch_bounds__(256) void gaussian_step_kernel(const DnGaussianStep
   }
 }
 
-// ------------------------------------------------------------------------------------------ generic Gaussian step of the device loop
-// One update of a respaced p_sample / ddim_sample chain (dn_gaussian_loop, dn_gaussian_sched_step): gaussian_step_kernel's eps-predicting,
-// fixed-variance branch in place on quads [q0, q0 + nquad) of the whole batch.  Row i = *counter of `table` [n_steps, DN_GD_COLS], given
-// in chain order, is uniform over the launch, so what depends on the row alone (the standard deviation, DDIM's sigma and its two square
-// roots) is formed once per thread.  The noise switch is the RESPACED index, n_steps-1-i: the last row adds none, whatever original
-// timestep steps[i] it has.  z: the injected row i, or Philox4x32-10 keyed by (seed; element quad of the whole batch, i), or (kKeyed)
-// the utterance's stream 2 + steps[i] -- sched_normal4, as ddim_sched_step_kernel draws.  Nothing is drawn where nothing is added (the
-// last row; DDIM at eta == 0).
+// ------------------------------------------------------------------------------------------ scheduled updates of the device loops
+// One update of a chain over a timestep schedule, in place on the float4 quads [q0, q0 + nquad) of the whole batch (engine.h: SchedStep),
+// under row i = *counter of the rule's coefficients, uniform over the launch.  sched_step_kernel assembles it from an eps source, a
+// rule and a sink, and every scheduled loop runs that one kernel: seeded, injected or keyed, whole batch or half, unconditional or
+// guided.  So eager, graph replay, the two half-batch streams and the guided chain at scale 1 apply the same statements, each of
+// which exists once below with every product and sum spelled out (or under contract(off)): no two chains can be contracted differently.
+// HBM-bound: 2 reads (+ the null row, the history, an injected noise row) and 1 write (+ the history, one or two model inputs) of 16
+// bytes per quad; grid-stride, no LDS.
+
+// ---- eps source: the buffer's quad, or (kCfg) its conditioned row combined with the null row n elements further on.
+// forward_with_cond_scale's combination (latent_module.py:813-826), three rounded operations; cfg_combine_kernel applies it too
+__device__ __forceinline__ float cfg_combine(float c, float u, float scale) { return __fadd_rn(u, __fmul_rn(__fsub_rn(c, u), scale)); }
+template <bool kCfg>
+__device__ __forceinline__ void eps_quad(const float* __restrict__ eps, int64_t i, int64_t n, float scale, float (&es)[4]) {
+  const float4 cv = *reinterpret_cast<const float4*>(eps + i);
+  es[0] = cv.x; es[1] = cv.y; es[2] = cv.z; es[3] = cv.w;
+  if (kCfg) {
+    const float4 uv = *reinterpret_cast<const float4*>(eps + n + i);
+    const float us[4] = {uv.x, uv.y, uv.z, uv.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) es[j] = cfg_combine(es[j], us[j], scale);
+  }
+}
+
+// ---- noise (engine.h: SchedNoise): the Philox counter is the element quad OF THE WHOLE BATCH and the step index -- a half-batch
+// launch starts at its first quad, and the guided chain's B-row latent is the whole batch -- so eager, graph replay, the two half-batch
+// streams and a scale-1 guided chain draw the same numbers.  kKeyed: the utterance's stream 2 + steps[i] (step_noise_keyed4): the
+// timestep, the frame and the channel, not the row, B, the padded T or the step index.
+// the four normals of quad q (elements i .. i+3) of the whole batch at `step` (timestep t): kKeyed: the utterance's stream 2 + t; else
+// the injected row, or Philox keyed by (q, step)
+template <bool kKeyed>
+__device__ __forceinline__ void sched_normal4(const SchedNoise& s, int64_t q, int64_t i, int step, int t, float (&z)[4]) {
+  const float* __restrict__ noise = s.noise;
+  const int64_t noise_row = s.noise_row;
+  const uint64_t seed = s.seed;
+  if (kKeyed) {
+    step_noise_keyed4(s.keys, q, s.row_quads, t, z);
+  } else if (noise) {
+    const float4 nv = *reinterpret_cast<const float4*>(noise + (int64_t)step * noise_row + i);
+    z[0] = nv.x; z[1] = nv.y; z[2] = nv.z; z[3] = nv.w;
+  } else {
+    philox_normal4(seed, (uint64_t)q, (uint32_t)step, z);
+  }
+}
+
+// ---- rules.  A rule reads row `step` of its coefficients once per thread, says whether the row draws, and maps a quad (x, eps, z) to
+// the new x.
+// DDIM (dn_ddim_sched_loop, dn_guided_ddim_loop): coef [n, DN_DDIM_SCHED_COLS] = {sqrt abar_e, sqrt(1-abar_e), sqrt abar_tgt,
+// sqrt(1-abar_tgt-sigma^2), sigma}.  !kEta: the statements of ddim_step_kernel, product for product (as compiled: see sched_update).
+// kEta: + 1[e_i != 0] sigma z (diffusion/gaussian_diffusion.py:513-560).
+struct SchedCoef {
+  float sa, s1, ct, cd, sg;
+};
+// row `step` of `coef`, with sigma masked to 0 without eta and at timestep 0
+__device__ __forceinline__ SchedCoef sched_coef(const float* __restrict__ coef, const int32_t* __restrict__ steps, int step, bool eta_on) {
+  const float* cf = coef + (int64_t)step * DN_DDIM_SCHED_COLS;
+  return {cf[0], cf[1], cf[2], cf[3], (eta_on && steps[step] != 0) ? cf[4] : 0.0f};
+}
+// ddim_step_kernel's statements as the compiler builds them (products contracted into the sums that take them: x - s1 eps,
+// x - sa x1, and x1 c2 onto the rounded c3 pn), spelled out so that no two kernels can be contracted differently
+__device__ __forceinline__ float sched_update(const SchedCoef& c, float x, float e, float z, bool eta_on) {
+  const float x1 = __fdiv_rn(fmaf(-c.s1, e, x), fmaxf(c.sa, 1e-10f));
+  const float pn = __fdiv_rn(fmaf(-c.sa, x1, x), fmaxf(c.s1, 1e-10f));
+  const float r = fmaf(c.ct, x1, __fmul_rn(c.cd, pn));
+  return eta_on ? fmaf(c.sg, z, r) : r;
+}
+template <bool kEta>
+struct DdimRule {
+  SchedCoef c;
+  __device__ DdimRule(const SchedStep& d, int step, bool) : c(sched_coef(d.coef, d.steps, step, kEta)) {}
+  __device__ bool draws() const { return kEta; }
+  __device__ void quad(const SchedStep&, int64_t, const float (&xs)[4], const float (&es)[4], const float (&z)[4], float (&o)[4]) const {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = sched_update(c, xs[j], es[j], z[j], kEta);
+  }
+};
+
+// DPM-Solver++(2M) (dn_dpm_loop, dn_guided_dpm_loop; Lu et al. 2022, data-prediction multistep form): coef [n, DN_DPM_COLS] =
+// {alpha_s, sigma_s, a, b, c1, c0}:
+//   x0_i = (x - sigma_s eps) / max(alpha_s, 1e-10);  x <- a x + b (c1 x0_i + c0 x0_{i-1});  hist <- x0_i.
+// hist holds x0_{i-1} of the whole batch and is read only by a second-order row (c0 != 0: uniform over the launch), so the first row of
+// a chain never reads what an earlier chain left there.  Deterministic: no draws.
+struct Dpm2mRule {
+  float as, ss, a, b, c1, c0;
+  __device__ Dpm2mRule(const SchedStep& d, int step, bool) {
+    const float* cf = d.coef + (int64_t)step * DN_DPM_COLS;
+    as = fmaxf(cf[0], 1e-10f), ss = cf[1], a = cf[2], b = cf[3], c1 = cf[4], c0 = cf[5];
+  }
+  __device__ bool draws() const { return false; }
+  __device__ void quad(const SchedStep& s, int64_t i, const float (&xs)[4], const float (&es)[4], const float (&)[4], float (&o)[4]) const {
+    const bool two = c0 != 0.0f;
+    float4 hv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (two) hv = *reinterpret_cast<const float4*>(s.hist + i);
+    const float hs[4] = {hv.x, hv.y, hv.z, hv.w};
+    float p[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      p[j] = __fdiv_rn(fmaf(-ss, es[j], xs[j]), as);
+      float d = __fmul_rn(c1, p[j]);
+      if (two) d = fmaf(c0, hs[j], d);
+      o[j] = fmaf(a, xs[j], __fmul_rn(b, d));
+    }
+    *reinterpret_cast<float4*>(s.hist + i) = make_float4(p[0], p[1], p[2], p[3]);
+  }
+};
+
+// Generic Gaussian (dn_gaussian_loop, dn_gaussian_sched_step): a respaced p_sample / ddim_sample chain, gaussian_step_kernel's
+// eps-predicting, fixed-variance branch under table [n_steps, DN_GD_COLS] given in chain order.  What depends on the row alone (the
+// standard deviation, DDIM's sigma and its two square roots) is formed once per thread.  The noise switch is the RESPACED index,
+// n_steps-1-i: the last row adds none, whatever original timestep steps[i] it has.  Nothing is drawn where nothing is added (the last
+// row; DDIM at eta == 0), but an injected row is read as the host chain reads it.
 // The arithmetic is gaussian_step_kernel's AS COMPILED, spelled out under contract(off) so that this kernel cannot be contracted
 // differently (as sched_update does for ddim_step_kernel): there the products of x0, of the posterior mean and of DDIM's mean are
 // rounded (packed multiplies) before their sums, DDIM's numerator is the rounded c0 x minus x0, and two sums take their product
 // unrounded: 1 - abar_prev - sigma^2 and the final + sdev z.  A host-stepped chain over dn_gaussian_step is tested bit-equal.
-// HBM-bound: two reads (three with injected noise) and one write of 16 bytes per quad; grid-stride, no LDS.
 struct GdRow {
   float c0, c1, c2, c3;  // sqrt_recip_abar, sqrt_recipm1_abar, posterior_mean_coef1, posterior_mean_coef2
   float sdev;            // the factor of z: 1[not the last row] exp(0.5 log_var) (p_sample) or sigma (ddim_sample)
@@ -698,27 +589,46 @@ __device__ __forceinline__ float gd_update(const GdRow& r, float x, float e, flo
   }
   return fmaf(r.sdev, z, mean);
 }
+struct GaussRule {
+  GdRow r;
+  bool noisy;
+  __device__ GaussRule(const SchedStep& d, int step, bool keyed) {
+    const float nz = step != d.n_steps - 1 ? 1.0f : 0.0f;
+    r = gd_row(d.coef + (int64_t)step * DN_GD_COLS, nz, d.sampler, d.eta);
+    noisy = (nz != 0.0f && (d.sampler == 0 || d.eta != 0.0f)) || (!keyed && d.src.noise);
+  }
+  __device__ bool draws() const { return noisy; }
+  __device__ void quad(const SchedStep& d, int64_t, const float (&xs)[4], const float (&es)[4], const float (&z)[4], float (&o)[4]) const {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = gd_update(r, xs[j], es[j], z[j], d.sampler, d.clip);
+  }
+};
 
-template <bool kKeyed>
-__global__ __launch_bounds__(256) void gaussian_sched_step_kernel(float* x, const float* __restrict__ eps, int64_t q0, int64_t nquad,
-                                                                  const float* __restrict__ table, const int32_t* __restrict__ steps,
-                                                                  const int32_t* __restrict__ counter, int n_steps, int sampler, int clip,
-                                                                  float eta, SchedNoise src) {
-  const int step = *counter;
-  const float nz = step != n_steps - 1 ? 1.0f : 0.0f;
-  const GdRow r = gd_row(table + (int64_t)step * DN_GD_COLS, nz, sampler, eta);
-  const int t = kKeyed ? steps[step] : 0;
-  const bool draws = nz != 0.0f && (sampler == 0 || eta != 0.0f);
+// ---- the kernel.  Sink: x, and the model's next input where it is another buffer -- xin[0:n] and (kCfg: the 2B-row pass) xin[n:2n],
+// one pass where a host-driven guided chain copies x twice, combines, updates and decrements.  !kCfg: nothing past n is touched.
+template <class Rule, bool kCfg, bool kKeyed>
+__global__ __launch_bounds__(256) void sched_step_kernel(const SchedStep d) {
+  const int step = *d.counter;
+  const Rule rule(d, step, kKeyed);
+  const int t = kKeyed ? d.steps[step] : 0;
+  const bool draws = rule.draws();
+  const int64_t q0 = d.elem0 >> 2, nquad = d.n_elem >> 2, n = d.n_elem;
   for (int64_t q = q0 + blockIdx.x * 256 + threadIdx.x; q < q0 + nquad; q += (int64_t)gridDim.x * 256) {
     const int64_t i = q << 2;
-    const float4 xv = *reinterpret_cast<const float4*>(x + i), ev = *reinterpret_cast<const float4*>(eps + i);
-    float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (draws || (!kKeyed && src.noise)) sched_normal4<kKeyed>(src, q, i, step, t, z);  // (an injected row is read as the host chain reads it)
-    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, es[4] = {ev.x, ev.y, ev.z, ev.w};
-    float o[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = gd_update(r, xs[j], es[j], z[j], sampler, clip);
-    *reinterpret_cast<float4*>(x + i) = make_float4(o[0], o[1], o[2], o[3]);
+    const float4 xv = *reinterpret_cast<const float4*>(d.x + i);
+    const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+    float es[4], z[4] = {0.f, 0.f, 0.f, 0.f}, o[4];
+    if (draws) sched_normal4<kKeyed>(d.src, q, i, step, t, z);  // (before eps is loaded: four registers fewer live across the Philox rounds)
+    eps_quad<kCfg>(d.eps, i, n, d.scale, es);
+    rule.quad(d, i, xs, es, z, o);
+    const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<float4*>(d.x + i) = ov;
+    if (kCfg) {
+      *reinterpret_cast<float4*>(d.xin + i) = ov;
+      *reinterpret_cast<float4*>(d.xin + n + i) = ov;
+    } else if (d.xin != d.x) {
+      *reinterpret_cast<float4*>(d.xin + i) = ov;
+    }
   }
 }
 
@@ -779,14 +689,72 @@ __global__ __launch_bounds__(256) void gaussian_moments_kernel(const DnGaussianM
 }
 
 // ------------------------------------------------------------------------------------------ CMLM mask-predict update (f4)
-// One workgroup per sequence (T <= 2048).  Phase 1: every position holding `unk` (the mask symbol) takes argmax / max of
-// log_softmax(logits[b, t, :]) (one wave per position).  Phase 2 (not on the last iteration): the boundary lowest-scoring
-// positions -- boundary = trunc((n_nonpad - 2) * p), scores ascending, ties by position -- are re-masked (token = unk, score = 0).
+// One workgroup per sequence (T <= 2048).  Phase 1: every position holding `unk` (the mask symbol) takes argmax / max of the
+// log-softmax of its logit row (one wave per position; the two scorings below).  Phase 2 (not on the last iteration): the boundary
+// lowest-scoring positions -- boundary = trunc((n_nonpad - 2) * p), scores ascending, ties by position -- are re-masked (token = unk,
+// score = 0).
 // step_dev != nullptr: the iteration index is read from the device (a captured refinement iteration is replayed while a device
 // counter advances: nothing of the iteration is baked into the graph) and p / remask are derived here exactly as the host derives them.
-__global__ __launch_bounds__(256) void cmlm_step_kernel(const float* __restrict__ logits, int32_t* __restrict__ tokens, float* __restrict__ scores,
-                                                        int32_t* __restrict__ predicted, int T, int V, float p, int remask, int unk, int pad,
-                                                        const int32_t* __restrict__ step_dev, int max_step) {
+
+// Unguided scoring (forward_decoder): arg-max / max of log_softmax(lr[0:V]), the maximum first and the sum in a second pass.
+__device__ __forceinline__ void cmlm_score(const float* __restrict__ lr, int V, int lane, int32_t& tok, float& sc) {
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int c = lane; c < V; c += 64) {
+    const float v = lr[c];
+    if (v > best) { best = v; bi = c; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+  }
+  float se = 0.f;
+  for (int c = lane; c < V; c += 64) se += expf(lr[c] - best);
+  se = wave_sum(se);
+  tok = bi;
+  sc = -logf(se);  // max - logsumexp = -(log sum exp(x - max))
+}
+
+// Guided scoring (research/TranSpeech/nat_gen.py:223-226; classifier-free guidance, --cg_scale): arg-max / max of
+// log_softmax(cond + scale * (cond - null)).  The combination, the log-softmax and the arg-max are one pass over the two logit rows
+// (running maximum and rescaled sum per lane, merged across the wave): each row is read once and the scaled logits are never written.
+// The three roundings of the combination are torch's (no contraction into an FMA).
+__device__ __forceinline__ void cmlm_score_guided(const float* __restrict__ lc, const float* __restrict__ ln, float scale, int V, int lane,
+                                                  int32_t& tok, float& sc) {
+  float best = -INFINITY, se = 0.f;
+  int bi = 0x7fffffff;
+  for (int c = lane; c < V; c += 64) {
+    const float cv = lc[c];
+    const float v = __fadd_rn(cv, __fmul_rn(scale, __fsub_rn(cv, ln[c])));
+    if (v > best) {
+      se = se * expf(best - v) + 1.0f;  // (first element: 0 * exp(-inf) + 1)
+      best = v; bi = c;
+    } else {
+      se += expf(v - best);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64), os = __shfl_xor(se, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    const float mx = fmaxf(best, ov);
+    const float sa = best == -INFINITY ? 0.f : se * expf(best - mx), sb = ov == -INFINITY ? 0.f : os * expf(ov - mx);
+    se = sa + sb;  // (commutative: both lanes of a pair hold the same sum)
+    if (ov > best || (ov == best && oi < bi)) bi = oi;
+    best = mx;
+  }
+  tok = bi;
+  sc = -logf(se);  // max - logsumexp
+}
+
+// kGuided: logits = [cond rows ; null rows] of one 2B-row pass (the grid is the B sequences), and the scores START FROM ZERO in every
+// iteration (nat_gen.py:197, output_scores = new_full(shape, 0.0)); else a kept position keeps its earlier score (forward_decoder).
+template <bool kGuided>
+__global__ __launch_bounds__(256) void cmlm_step_kernel(const float* __restrict__ logits, float scale, int32_t* __restrict__ tokens,
+                                                        float* __restrict__ scores, int32_t* __restrict__ predicted, int T, int V, float p,
+                                                        int remask, int unk, int pad, const int32_t* __restrict__ step_dev, int max_step) {
   if (step_dev) {
     const int step = *step_dev;
     remask = (step + 1) < max_step;
@@ -797,29 +765,17 @@ __global__ __launch_bounds__(256) void cmlm_step_kernel(const float* __restrict_
   __shared__ int s_n;
   const int b = blockIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t half = (int64_t)gridDim.x * T * V;
   if (threadIdx.x == 0) s_n = 0;
   for (int t = wave; t < T; t += 4) {
     int32_t tok = tokens[(int64_t)b * T + t];
-    float sc = scores[(int64_t)b * T + t];
+    float sc = kGuided ? 0.f : scores[(int64_t)b * T + t];
     if (tok == unk) {  // wave-uniform
       const float* lr = logits + ((int64_t)b * T + t) * V;
-      float best = -INFINITY;
-      int bi = 0x7fffffff;
-      for (int c = lane; c < V; c += 64) {
-        const float v = lr[c];
-        if (v > best) { best = v; bi = c; }
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-      }
-      float se = 0.f;
-      for (int c = lane; c < V; c += 64) se += expf(lr[c] - best);
-      se = wave_sum(se);
-      tok = bi;
-      sc = -logf(se);  // max - logsumexp = -(log sum exp(x - max))
+      if (kGuided)
+        cmlm_score_guided(lr, lr + half, scale, V, lane, tok, sc);
+      else
+        cmlm_score(lr, V, lane, tok, sc);
     }
     if (lane == 0) {
       s_tok[t] = tok;
@@ -855,95 +811,11 @@ __global__ __launch_bounds__(256) void cmlm_step_kernel(const float* __restrict_
   }
 }
 
-// The guided update of research/TranSpeech/nat_gen.py:197-236 (classifier-free guidance, --cg_scale): as cmlm_step_kernel, but the
-// scores START FROM ZERO in every iteration (:197 -- forward_decoder keeps the earlier iterations' scores) and the masked positions
-// take arg-max / max of log_softmax(cond + scale * (cond - null)) (:223-226).  The combination, the log-softmax and the arg-max are
-// one pass over the two logit rows (running maximum and rescaled sum per lane, merged across the wave): each row is read once and
-// the scaled logits are never written.  The three roundings of the combination are torch's (no contraction into an FMA).
-__global__ __launch_bounds__(256) void cmlm_guided_step_kernel(const float* __restrict__ logits2, float scale, int32_t* __restrict__ tokens,
-                                                               float* __restrict__ scores, int32_t* __restrict__ predicted, int B, int T, int V,
-                                                               float p, int remask, int unk, int pad, const int32_t* __restrict__ step_dev,
-                                                               int max_step) {
-  if (step_dev) {
-    const int step = *step_dev;
-    remask = (step + 1) < max_step;
-    p = (float)(1.0 - (double)(step + 1) / (double)max_step);
-  }
-  __shared__ float s_sc[2048];
-  __shared__ int32_t s_tok[2048];
-  __shared__ int s_n;
-  const int b = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t half = (int64_t)B * T * V;
-  if (threadIdx.x == 0) s_n = 0;
-  for (int t = wave; t < T; t += 4) {
-    int32_t tok = tokens[(int64_t)b * T + t];
-    float sc = 0.f;  // output_scores = new_full(shape, 0.0) (:197)
-    if (tok == unk) {  // wave-uniform
-      const float* lc = logits2 + ((int64_t)b * T + t) * V;
-      const float* ln = lc + half;
-      float best = -INFINITY, se = 0.f;
-      int bi = 0x7fffffff;
-      for (int c = lane; c < V; c += 64) {
-        const float cv = lc[c];
-        const float v = __fadd_rn(cv, __fmul_rn(scale, __fsub_rn(cv, ln[c])));
-        if (v > best) {
-          se = se * expf(best - v) + 1.0f;  // (first element: 0 * exp(-inf) + 1)
-          best = v; bi = c;
-        } else {
-          se += expf(v - best);
-        }
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64), os = __shfl_xor(se, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        const float mx = fmaxf(best, ov);
-        const float sa = best == -INFINITY ? 0.f : se * expf(best - mx), sb = ov == -INFINITY ? 0.f : os * expf(ov - mx);
-        se = sa + sb;  // (commutative: both lanes of a pair hold the same sum)
-        if (ov > best || (ov == best && oi < bi)) bi = oi;
-        best = mx;
-      }
-      tok = bi;
-      sc = -logf(se);  // max - logsumexp
-    }
-    if (lane == 0) {
-      s_tok[t] = tok;
-      s_sc[t] = sc;
-      predicted[(int64_t)b * T + t] = tok;
-    }
-  }
-  __syncthreads();
-  if (remask) {
-    int cnt = 0;
-    for (int t = threadIdx.x; t < T; t += 256) cnt += s_tok[t] != pad;
-    if (cnt) atomicAdd(&s_n, cnt);
-    __syncthreads();
-    const long long boundary = (long long)((float)(s_n - 2) * p);
-    for (int i = threadIdx.x; i < T; i += 256) {
-      const float si = s_sc[i];
-      int rank = 0;
-      for (int j = 0; j < T; ++j) {
-        const float sj = s_sc[j];
-        rank += (sj < si) || (sj == si && j < i);
-      }
-      int32_t tok = s_tok[i];
-      float sc = si;
-      if ((long long)rank < boundary) { tok = unk; sc = 0.f; }
-      tokens[(int64_t)b * T + i] = tok;
-      scores[(int64_t)b * T + i] = sc;
-    }
-  } else {
-    for (int i = threadIdx.x; i < T; i += 256) {
-      tokens[(int64_t)b * T + i] = s_tok[i];
-      scores[(int64_t)b * T + i] = s_sc[i];
-    }
-  }
-}
-
-static inline int ew_grid(int64_t n) {
+// blocks of this file's grid-stride kernels: at least one, at most kPointwiseGridCap (engine.h's ew_grid stops at 4096)
+constexpr int kPointwiseGridCap = 2048;
+static inline int pw_grid(int64_t n) {
   int64_t b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
+  return (int)(b < 1 ? 1 : (b > kPointwiseGridCap ? kPointwiseGridCap : b));
 }
 
 }  // namespace dn
@@ -973,7 +845,7 @@ extern "C" int dn_time_cond(const int32_t* times, int32_t B, const float* w_freq
 extern "C" int dn_ddim_step(const float* x, const float* eps, float* x_out, void* x_act, int32_t act_dtype, int32_t ld_act, int32_t M,
                             int32_t C, int32_t ld, int32_t T, const float* coef, const int32_t* t, void* stream) {
   DN_CHECK_ARG(x && eps && x_out && coef && t && M > 0 && C > 0 && ld >= C && T > 0, "dn_ddim_step: bad args");
-  hipLaunchKernelGGL(ddim_step_kernel, dim3(ew_grid((int64_t)M * C)), dim3(256), 0, (hipStream_t)stream, x, eps, x_out, x_act, act_dtype,
+  hipLaunchKernelGGL(ddim_step_kernel, dim3(pw_grid((int64_t)M * C)), dim3(256), 0, (hipStream_t)stream, x, eps, x_out, x_act, act_dtype,
                      ld_act, M, C, ld, T, coef, t);
   DN_CHECK_LAUNCH("dn_ddim_step");
   return DN_OK;
@@ -983,23 +855,23 @@ extern "C" int dn_ddim_step(const float* x, const float* eps, float* x_out, void
 // 2B-batch pass ([cond rows ; null rows])
 __global__ __launch_bounds__(256) void cfg_combine_kernel(const float* __restrict__ both, float scale, int64_t n, float* __restrict__ out) {
   for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const float c = both[i], u = both[n + i];
-    out[i] = __fadd_rn(u, __fmul_rn(__fsub_rn(c, u), scale));
+    out[i] = cfg_combine(both[i], both[n + i], scale);
   }
 }
 extern "C" int dn_cfg_combine(const float* both, float scale, int64_t n, float* out, void* stream) {
   DN_CHECK_ARG(both && out && n > 0, "dn_cfg_combine: bad argument");
-  hipLaunchKernelGGL(cfg_combine_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, both, scale, n, out);
+  hipLaunchKernelGGL(cfg_combine_kernel, dim3(pw_grid(n)), dim3(256), 0, (hipStream_t)stream, both, scale, n, out);
   DN_CHECK_LAUNCH("dn_cfg_combine");
   return DN_OK;
 }
 
-// (engine.hip: the ancestral update of dn_ddpm_loop)
+// (engine.h: the ancestral update of dn_ddpm_loop)
 // keys != NULL (dn_ddpm_loop_keyed): the whole batch's keys and the launch's first batch row b0; noise and seed are not read
 int dn_ddpm_step_launch(float* x, const float* eps, int M, int C, int T, const float* table, const int32_t* t, int clip, const float* noise,
-                        int64_t noise_row, int t_top, uint64_t seed, const uint64_t* keys, int b0, hipStream_t stream) {
+                        int64_t noise_row, int t_top, uint64_t seed, const uint64_t* keys, int b0, void* stream_) {
   DN_CHECK_ARG(C % 4 == 0, "dn_ddpm_loop: the latent width must be a multiple of 4");
-  const dim3 grid(ew_grid(((int64_t)M * C) >> 2)), block(256);
+  hipStream_t stream = (hipStream_t)stream_;
+  const dim3 grid(pw_grid(((int64_t)M * C) >> 2)), block(256);
   const int64_t row_quads = (int64_t)T * (C >> 2);
   if (keys)
     hipLaunchKernelGGL(ddpm_step_kernel<true>, grid, block, 0, stream, x, eps, M, C, T, table, t, clip, nullptr, 0, t_top, 0, keys,
@@ -1011,29 +883,35 @@ int dn_ddpm_step_launch(float* x, const float* eps, int M, int C, int T, const f
   return DN_OK;
 }
 
-// (engine.hip: the update of dn_ddim_sched_loop; x, eps, noise: the whole batch's; [elem0, elem0 + n_elem): this launch's elements)
-// keys != NULL (the keyed entries; eta_on): the whole batch's keys, row_quads = T Z / 4 quads per utterance; noise and seed are not read
-int dn_ddim_sched_step_launch(float* x, const float* eps, int64_t elem0, int64_t n_elem, const float* coef, const int32_t* steps,
-                              const int32_t* counter, int eta_on, const float* noise, int64_t noise_row, uint64_t seed, const uint64_t* keys,
-                              int64_t row_quads, hipStream_t stream) {
-  DN_CHECK_ARG(elem0 % 4 == 0 && n_elem % 4 == 0 && n_elem > 0, "dn_ddim_sched_loop: the latent width must be a multiple of 4");
-  const dim3 grid(ew_grid(n_elem >> 2)), block(256);
-  if (keys)
-    hipLaunchKernelGGL(ddim_sched_step_kernel<true>, grid, block, 0, stream, x, eps, elem0 >> 2, n_elem >> 2, coef, steps, counter, 1,
-                       SchedNoise{nullptr, 0, 0, keys, row_quads});
-  else
-    hipLaunchKernelGGL(ddim_sched_step_kernel<false>, grid, block, 0, stream, x, eps, elem0 >> 2, n_elem >> 2, coef, steps, counter, eta_on,
-                       SchedNoise{noise, noise_row, seed, nullptr, 0});
-  DN_CHECK_LAUNCH("dn_ddim_sched_loop step");
-  return DN_OK;
+// (engine.h) the one launcher of the scheduled updates: the instantiation a descriptor names
+template <class Rule, bool kCfg, bool kKeyed>
+static void sched_launch(const SchedStep& d, hipStream_t stream) {
+  hipLaunchKernelGGL((sched_step_kernel<Rule, kCfg, kKeyed>), dim3(pw_grid(d.n_elem >> 2)), dim3(256), 0, stream, d);
 }
-
-// (engine.hip: the update of dn_dpm_loop; x, eps, hist: the whole batch's; [elem0, elem0 + n_elem): this launch's elements)
-int dn_dpm2m_step_launch(float* x, const float* eps, float* hist, int64_t elem0, int64_t n_elem, const float* coef, const int32_t* counter,
-                         hipStream_t stream) {
-  DN_CHECK_ARG(elem0 % 4 == 0 && n_elem % 4 == 0 && n_elem > 0, "dn_dpm_loop: the latent width must be a multiple of 4");
-  hipLaunchKernelGGL(dpm2m_step_kernel, dim3(ew_grid(n_elem >> 2)), dim3(256), 0, stream, x, eps, hist, elem0 >> 2, n_elem >> 2, coef, counter);
-  DN_CHECK_LAUNCH("dn_dpm_loop step");
+template <class Rule, bool kKeyed>
+static void sched_launch_source(const SchedStep& d, hipStream_t stream) {
+  d.guided ? sched_launch<Rule, true, kKeyed>(d, stream) : sched_launch<Rule, false, kKeyed>(d, stream);
+}
+int dn::sched_step_launch(const char* who, const SchedStep& desc, void* stream_) {
+  DN_CHECK_ARG(desc.elem0 % 4 == 0 && desc.n_elem % 4 == 0 && desc.n_elem > 0, "%s: the latent width must be a multiple of 4", who);
+  DN_CHECK_ARG(!desc.guided || (desc.rule != SCHED_GAUSSIAN && desc.elem0 == 0), "%s: no guided form of this update", who);
+  SchedStep d = desc;
+  if (!d.xin) d.xin = d.x;  // (the kernel writes xin where it is not x)
+  hipStream_t stream = (hipStream_t)stream_;
+  const bool keyed = d.src.keys != nullptr;
+  if (d.rule == SCHED_DPM2M)
+    sched_launch_source<Dpm2mRule, false>(d, stream);
+  else if (d.rule == SCHED_GAUSSIAN)
+    keyed ? sched_launch<GaussRule, false, true>(d, stream) : sched_launch<GaussRule, false, false>(d, stream);
+  else if (keyed)
+    sched_launch_source<DdimRule<true>, true>(d, stream);
+  else
+    d.eta_on ? sched_launch_source<DdimRule<true>, false>(d, stream) : sched_launch_source<DdimRule<false>, false>(d, stream);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    dn_set_error("%s step: %s", who, hipGetErrorString(e));
+    return DN_ELAUNCH;
+  }
   return DN_OK;
 }
 
@@ -1041,7 +919,9 @@ extern "C" int dn_dpm2m_step(float* x, const float* eps, float* hist, int64_t n,
   DN_CHECK_ARG(x && eps && hist && coef && step_index, "dn_dpm2m_step: null argument");
   DN_CHECK_ARG(n > 0 && n % 4 == 0, "dn_dpm2m_step: n=%lld must be a positive multiple of 4", (long long)n);
   DN_CHECK_ARG((((uintptr_t)x | (uintptr_t)eps | (uintptr_t)hist) & 15) == 0, "dn_dpm2m_step: x, eps and hist must be 16-byte aligned");
-  return dn_dpm2m_step_launch(x, eps, hist, 0, n, coef, step_index, (hipStream_t)stream);
+  SchedStep u = {SCHED_DPM2M, x, 0, n, eps};
+  u.coef = coef; u.counter = step_index; u.hist = hist;
+  return sched_step_launch("dn_dpm_loop", u, stream);
 }
 
 extern "C" int dn_ddim_sched_step(float* x, const float* eps, int64_t n, const float* coef, const int32_t* steps, const int32_t* step_index,
@@ -1050,8 +930,10 @@ extern "C" int dn_ddim_sched_step(float* x, const float* eps, int64_t n, const f
   DN_CHECK_ARG(n > 0 && n % 4 == 0, "dn_ddim_sched_step: n=%lld must be a positive multiple of 4", (long long)n);
   DN_CHECK_ARG((((uintptr_t)x | (uintptr_t)eps | (uintptr_t)noise) & 15) == 0, "dn_ddim_sched_step: x, eps and noise must be 16-byte aligned");
   DN_CHECK_ARG(eta_on || !noise, "dn_ddim_sched_step: injected noise needs eta_on (eta = 0 draws none)");
-  // (row stride 0: `noise` is this step's row whatever the step index)
-  return dn_ddim_sched_step_launch(x, eps, 0, n, coef, steps, step_index, eta_on != 0, noise, 0, eta_on ? seed : 0, nullptr, 0, (hipStream_t)stream);
+  SchedStep u = {SCHED_DDIM, x, 0, n, eps};
+  u.coef = coef; u.steps = steps; u.counter = step_index; u.eta_on = eta_on != 0;
+  u.src = sched_noise(noise, 0, eta_on ? seed : 0, nullptr, 0);  // (row stride 0: `noise` is this step's row whatever the step index)
+  return sched_step_launch("dn_ddim_sched_loop", u, stream);
 }
 
 extern "C" int dn_ddim_sched_step_keyed(float* x, const float* eps, const uint64_t* keys, int32_t B, int32_t T, int32_t Z, const float* coef,
@@ -1062,25 +944,10 @@ extern "C" int dn_ddim_sched_step_keyed(float* x, const float* eps, const uint64
   DN_CHECK_ARG((((uintptr_t)x | (uintptr_t)eps) & 15) == 0 && ((uintptr_t)keys & 7) == 0,
                "dn_ddim_sched_step_keyed: x and eps must be 16-byte, keys 8-byte aligned");
   const int64_t row_quads = (int64_t)T * (Z >> 2);
-  return dn_ddim_sched_step_launch(x, eps, 0, (int64_t)B * row_quads * 4, coef, steps, step_index, 1, nullptr, 0, 0, keys, row_quads,
-                                   (hipStream_t)stream);
-}
-
-// (engine.hip: the update of dn_gaussian_loop; x, eps, noise: the whole batch's; [elem0, elem0 + n_elem): this launch's elements)
-// keys != NULL (the keyed entries): the whole batch's keys, row_quads = T Z / 4 quads per utterance; noise and seed are not read
-int dn_gaussian_sched_step_launch(float* x, const float* eps, int64_t elem0, int64_t n_elem, const float* table, const int32_t* steps,
-                                  const int32_t* counter, int n_steps, int sampler, int clip, float eta, const float* noise, int64_t noise_row,
-                                  uint64_t seed, const uint64_t* keys, int64_t row_quads, hipStream_t stream) {
-  DN_CHECK_ARG(elem0 % 4 == 0 && n_elem % 4 == 0 && n_elem > 0, "dn_gaussian_loop: the latent width must be a multiple of 4");
-  const dim3 grid(ew_grid(n_elem >> 2)), block(256);
-  if (keys)
-    hipLaunchKernelGGL(gaussian_sched_step_kernel<true>, grid, block, 0, stream, x, eps, elem0 >> 2, n_elem >> 2, table, steps, counter, n_steps,
-                       sampler, clip, eta, SchedNoise{nullptr, 0, 0, keys, row_quads});
-  else
-    hipLaunchKernelGGL(gaussian_sched_step_kernel<false>, grid, block, 0, stream, x, eps, elem0 >> 2, n_elem >> 2, table, steps, counter, n_steps,
-                       sampler, clip, eta, SchedNoise{noise, noise_row, seed, nullptr, 0});
-  DN_CHECK_LAUNCH("dn_gaussian_loop step");
-  return DN_OK;
+  SchedStep u = {SCHED_DDIM, x, 0, (int64_t)B * row_quads * 4, eps};
+  u.coef = coef; u.steps = steps; u.counter = step_index; u.eta_on = 1;
+  u.src = sched_noise(nullptr, 0, 0, keys, row_quads);
+  return sched_step_launch("dn_ddim_sched_loop", u, stream);
 }
 
 // what the four dn_gaussian_* entries check of the update's own arguments
@@ -1097,9 +964,10 @@ extern "C" int dn_gaussian_sched_step(float* x, const float* eps, int64_t n, con
   DN_CHECK_ARG(n > 0 && n % 4 == 0, "dn_gaussian_sched_step: n=%lld must be a positive multiple of 4", (long long)n);
   DN_CHECK_ARG((((uintptr_t)x | (uintptr_t)eps | (uintptr_t)noise) & 15) == 0, "dn_gaussian_sched_step: x, eps and noise must be 16-byte aligned");
   if (const int rc = dn_gaussian_sched_args("dn_gaussian_sched_step", n_steps, sampler, eta)) return rc;
-  // (row stride 0: `noise` is this step's row whatever the step index)
-  return dn_gaussian_sched_step_launch(x, eps, 0, n, table, nullptr, step_index, n_steps, sampler, clip_denoised != 0, eta, noise, 0, seed, nullptr,
-                                       0, (hipStream_t)stream);
+  SchedStep u = {SCHED_GAUSSIAN, x, 0, n, eps};
+  u.coef = table; u.counter = step_index; u.n_steps = n_steps; u.sampler = sampler; u.clip = clip_denoised != 0; u.eta = eta;
+  u.src = sched_noise(noise, 0, seed, nullptr, 0);  // (row stride 0: `noise` is this step's row whatever the step index)
+  return sched_step_launch("dn_gaussian_loop", u, stream);
 }
 
 extern "C" int dn_gaussian_sched_step_keyed(float* x, const float* eps, const uint64_t* keys, int32_t B, int32_t T, int32_t Z, const float* table,
@@ -1112,52 +980,16 @@ extern "C" int dn_gaussian_sched_step_keyed(float* x, const float* eps, const ui
                "dn_gaussian_sched_step_keyed: x and eps must be 16-byte, keys 8-byte aligned");
   if (const int rc = dn_gaussian_sched_args("dn_gaussian_sched_step_keyed", n_steps, sampler, eta)) return rc;
   const int64_t row_quads = (int64_t)T * (Z >> 2);
-  return dn_gaussian_sched_step_launch(x, eps, 0, (int64_t)B * row_quads * 4, table, steps, step_index, n_steps, sampler, clip_denoised != 0, eta,
-                                       nullptr, 0, 0, keys, row_quads, (hipStream_t)stream);
-}
-
-// (engine.hip: the update of dn_guided_ddim_loop; n_elem = B*T*latent of the B-row latent; both / xin hold 2 n_elem floats when guided)
-// keys != NULL (dn_guided_ddim_loop_keyed; eta on): the B keys, row_quads = T Z / 4 quads per utterance; noise and seed are not read
-int dn_guided_sched_step_launch(float* x, float* xin, const float* both, int64_t n_elem, int guided, float scale, const float* coef,
-                                const int32_t* steps, const int32_t* counter, int eta_on, const float* noise, int64_t noise_row, uint64_t seed,
-                                const uint64_t* keys, int64_t row_quads, hipStream_t stream) {
-  DN_CHECK_ARG(n_elem % 4 == 0 && n_elem > 0, "dn_guided_ddim_loop: the latent width must be a multiple of 4");
-  const dim3 grid(ew_grid(n_elem >> 2)), block(256);
-  const SchedNoise src = keys ? SchedNoise{nullptr, 0, 0, keys, row_quads} : SchedNoise{noise, noise_row, seed, nullptr, 0};
-#define DN_GUIDED_STEP(G, E) \
-  hipLaunchKernelGGL((guided_sched_step_kernel<G, E, false>), grid, block, 0, stream, x, xin, both, n_elem >> 2, scale, coef, steps, counter, src)
-  if (keys) {
-    if (guided)
-      hipLaunchKernelGGL((guided_sched_step_kernel<true, true, true>), grid, block, 0, stream, x, xin, both, n_elem >> 2, scale, coef, steps, counter, src);
-    else
-      hipLaunchKernelGGL((guided_sched_step_kernel<false, true, true>), grid, block, 0, stream, x, xin, both, n_elem >> 2, scale, coef, steps, counter, src);
-  } else if (guided) {
-    if (eta_on) DN_GUIDED_STEP(true, true); else DN_GUIDED_STEP(true, false);
-  } else {
-    if (eta_on) DN_GUIDED_STEP(false, true); else DN_GUIDED_STEP(false, false);
-  }
-#undef DN_GUIDED_STEP
-  DN_CHECK_LAUNCH("dn_guided_ddim_loop step");
-  return DN_OK;
-}
-
-// (engine.hip: the update of dn_guided_dpm_loop; n_elem = B*T*latent of the B-row latent -- x and hist; both / xin hold 2 n_elem floats when guided)
-int dn_guided_dpm_step_launch(float* x, float* xin, const float* both, float* hist, int64_t n_elem, int guided, float scale, const float* coef,
-                              const int32_t* counter, hipStream_t stream) {
-  DN_CHECK_ARG(n_elem % 4 == 0 && n_elem > 0, "dn_guided_dpm_loop: the latent width must be a multiple of 4");
-  const dim3 grid(ew_grid(n_elem >> 2)), block(256);
-  if (guided)
-    hipLaunchKernelGGL(guided_dpm_step_kernel<true>, grid, block, 0, stream, x, xin, both, hist, n_elem >> 2, scale, coef, counter);
-  else
-    hipLaunchKernelGGL(guided_dpm_step_kernel<false>, grid, block, 0, stream, x, xin, both, hist, n_elem >> 2, scale, coef, counter);
-  DN_CHECK_LAUNCH("dn_guided_dpm_loop step");
-  return DN_OK;
+  SchedStep u = {SCHED_GAUSSIAN, x, 0, (int64_t)B * row_quads * 4, eps};
+  u.coef = table; u.steps = steps; u.counter = step_index; u.n_steps = n_steps; u.sampler = sampler; u.clip = clip_denoised != 0; u.eta = eta;
+  u.src = sched_noise(nullptr, 0, 0, keys, row_quads);
+  return sched_step_launch("dn_gaussian_loop", u, stream);
 }
 
 extern "C" int dn_q_sample(const float* x, const float* noise, float* out, void* out_act, int32_t act_dtype, int32_t ld_act, int32_t M,
                            int32_t C, int32_t ld, int32_t T, const float* coef_a, const float* coef_b, const int32_t* t, void* stream) {
   DN_CHECK_ARG(x && noise && out && coef_a && coef_b && t && M > 0 && C > 0 && ld >= C && T > 0, "dn_q_sample: bad args");
-  hipLaunchKernelGGL(q_sample_kernel, dim3(ew_grid((int64_t)M * C)), dim3(256), 0, (hipStream_t)stream, x, noise, out, out_act, act_dtype,
+  hipLaunchKernelGGL(q_sample_kernel, dim3(pw_grid((int64_t)M * C)), dim3(256), 0, (hipStream_t)stream, x, noise, out, out_act, act_dtype,
                      ld_act, M, C, ld, T, coef_a, coef_b, t);
   DN_CHECK_LAUNCH("dn_q_sample");
   return DN_OK;
@@ -1182,7 +1014,7 @@ extern "C" int dn_argmax_units(const float* logits, int32_t ld, int32_t M, int32
 
 extern "C" int dn_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream) {
   DN_CHECK_ARG(out && n > 0, "dn_randn: bad args");
-  hipLaunchKernelGGL(randn_kernel, dim3(ew_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, out, n, seed, offset);
+  hipLaunchKernelGGL(randn_kernel, dim3(pw_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, out, n, seed, offset);
   DN_CHECK_LAUNCH("dn_randn");
   return DN_OK;
 }
@@ -1192,7 +1024,7 @@ extern "C" int dn_randn_keyed(float* out, const uint64_t* keys, int32_t B, int32
   DN_CHECK_ARG(B > 0 && T > 0 && Z > 0 && Z % 4 == 0, "dn_randn_keyed: B=%d T=%d must be positive, Z=%d a positive multiple of 4", B, T, Z);
   DN_CHECK_ARG(((uintptr_t)out & 15) == 0 && ((uintptr_t)keys & 7) == 0, "dn_randn_keyed: out must be 16-byte, keys 8-byte aligned");
   const int64_t row_quads = (int64_t)T * (Z >> 2), nquad = (int64_t)B * row_quads;
-  hipLaunchKernelGGL(randn_keyed_kernel, dim3(ew_grid(nquad)), dim3(256), 0, (hipStream_t)stream, out, keys, nquad, row_quads, stream_id);
+  hipLaunchKernelGGL(randn_keyed_kernel, dim3(pw_grid(nquad)), dim3(256), 0, (hipStream_t)stream, out, keys, nquad, row_quads, stream_id);
   DN_CHECK_LAUNCH("dn_randn_keyed");
   return DN_OK;
 }
@@ -1205,7 +1037,7 @@ extern "C" int dn_chain_start(const float* params, int32_t ldp, const uint64_t* 
   DN_CHECK_ARG((((uintptr_t)params | (uintptr_t)x | (uintptr_t)z_out) & 15) == 0 && ((uintptr_t)keys & 7) == 0,
                "dn_chain_start: params, x and z_out must be 16-byte, keys 8-byte aligned");
   const int64_t row_quads = (int64_t)T * (Z >> 2), nquad = (int64_t)B * row_quads;
-  hipLaunchKernelGGL(chain_start_kernel, dim3(ew_grid(nquad)), dim3(256), 0, (hipStream_t)stream, params, ldp, keys, nquad, row_quads, Z,
+  hipLaunchKernelGGL(chain_start_kernel, dim3(pw_grid(nquad)), dim3(256), 0, (hipStream_t)stream, params, ldp, keys, nquad, row_quads, Z,
                      coef_a, coef_b, t, x, z_out);
   DN_CHECK_LAUNCH("dn_chain_start");
   return DN_OK;
@@ -1214,7 +1046,7 @@ extern "C" int dn_chain_start(const float* params, int32_t ldp, const uint64_t* 
 extern "C" int dn_convert_rows(const void* src, int32_t src_dtype, int32_t lds, void* dst, int32_t dst_dtype, int32_t ldd, int32_t M,
                                int32_t C, void* stream) {
   DN_CHECK_ARG(src && dst && M > 0 && C > 0 && lds >= C && ldd >= C, "dn_convert_rows: bad args");
-  hipLaunchKernelGGL(convert_rows_kernel, dim3(ew_grid((int64_t)M * ldd)), dim3(256), 0, (hipStream_t)stream, src, src_dtype, lds, dst,
+  hipLaunchKernelGGL(convert_rows_kernel, dim3(pw_grid((int64_t)M * ldd)), dim3(256), 0, (hipStream_t)stream, src, src_dtype, lds, dst,
                      dst_dtype, ldd, M, C);
   DN_CHECK_LAUNCH("dn_convert_rows");
   return DN_OK;
@@ -1223,7 +1055,7 @@ extern "C" int dn_convert_rows(const void* src, int32_t src_dtype, int32_t lds, 
 extern "C" int dn_gaussian_step(const DnGaussianStep* p, void* stream) {
   DN_CHECK_ARG(p && p->x && p->model_out && p->sample && p->t && p->table, "dn_gaussian_step: null argument");
   DN_CHECK_ARG(p->N > 0 && p->inner > 0 && (p->sampler == 0 || p->sampler == 1), "dn_gaussian_step: bad shape / sampler");
-  hipLaunchKernelGGL(gaussian_step_kernel, dim3(ew_grid((int64_t)p->N * p->inner)), dim3(256), 0, (hipStream_t)stream, *p);
+  hipLaunchKernelGGL(gaussian_step_kernel, dim3(pw_grid((int64_t)p->N * p->inner)), dim3(256), 0, (hipStream_t)stream, *p);
   DN_CHECK_LAUNCH("dn_gaussian_step");
   return DN_OK;
 }
@@ -1231,7 +1063,7 @@ extern "C" int dn_gaussian_step(const DnGaussianStep* p, void* stream) {
 extern "C" int dn_gaussian_moments(const DnGaussianMoments* p, void* stream) {
   DN_CHECK_ARG(p && p->x && p->t && p->table && (p->model_out || p->x_start), "dn_gaussian_moments: null argument");
   DN_CHECK_ARG(p->N > 0 && p->inner > 0, "dn_gaussian_moments: bad shape");
-  hipLaunchKernelGGL(gaussian_moments_kernel, dim3(ew_grid((int64_t)p->N * p->inner)), dim3(256), 0, (hipStream_t)stream, *p);
+  hipLaunchKernelGGL(gaussian_moments_kernel, dim3(pw_grid((int64_t)p->N * p->inner)), dim3(256), 0, (hipStream_t)stream, *p);
   DN_CHECK_LAUNCH("dn_gaussian_moments");
   return DN_OK;
 }
@@ -1242,8 +1074,8 @@ extern "C" int dn_cmlm_step(const float* logits, int32_t* tokens, float* scores,
                "dn_cmlm_step: bad args (T=%d must be <= 2048)", T);
   const int remask = (step + 1) < max_step;
   const float p = (float)(1.0 - (double)(step + 1) / (double)max_step);  // the Python float of the reference, cast to the scores' fp32
-  hipLaunchKernelGGL(cmlm_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, tokens, scores, predicted, T, V, p, remask, unk, pad,
-                     (const int32_t*)nullptr, max_step);
+  hipLaunchKernelGGL(cmlm_step_kernel<false>, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, 0.f, tokens, scores, predicted, T, V, p, remask, unk,
+                     pad, (const int32_t*)nullptr, max_step);
   DN_CHECK_LAUNCH("dn_cmlm_step");
   return DN_OK;
 }
@@ -1252,8 +1084,8 @@ extern "C" int dn_cmlm_step_dev(const float* logits, int32_t* tokens, float* sco
                                 const int32_t* step_dev, int32_t max_step, int32_t unk, int32_t pad, void* stream) {
   DN_CHECK_ARG(logits && tokens && scores && predicted && step_dev && B > 0 && T > 0 && T <= 2048 && V > 1 && max_step > 0,
                "dn_cmlm_step_dev: bad args (T=%d must be <= 2048)", T);
-  hipLaunchKernelGGL(cmlm_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, tokens, scores, predicted, T, V, 0.f, 0, unk, pad,
-                     step_dev, max_step);
+  hipLaunchKernelGGL(cmlm_step_kernel<false>, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, 0.f, tokens, scores, predicted, T, V, 0.f, 0, unk,
+                     pad, step_dev, max_step);
   DN_CHECK_LAUNCH("dn_cmlm_step_dev");
   return DN_OK;
 }
@@ -1265,8 +1097,8 @@ extern "C" int dn_cmlm_guided_step(const float* logits2, float scale, int32_t* t
   DN_CHECK_ARG(scale > 0.f, "dn_cmlm_guided_step: guidance scale %g must be > 0 (nat_gen.py:180: without it the loop runs dn_cmlm_step on one pass)", (double)scale);
   const int remask = (step + 1) < max_step;
   const float p = (float)(1.0 - (double)(step + 1) / (double)max_step);
-  hipLaunchKernelGGL(cmlm_guided_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits2, scale, tokens, scores, predicted, B, T, V, p, remask,
-                     unk, pad, (const int32_t*)nullptr, max_step);
+  hipLaunchKernelGGL(cmlm_step_kernel<true>, dim3(B), dim3(256), 0, (hipStream_t)stream, logits2, scale, tokens, scores, predicted, T, V, p, remask, unk,
+                     pad, (const int32_t*)nullptr, max_step);
   DN_CHECK_LAUNCH("dn_cmlm_guided_step");
   return DN_OK;
 }
@@ -1276,8 +1108,8 @@ extern "C" int dn_cmlm_guided_step_dev(const float* logits2, float scale, int32_
   DN_CHECK_ARG(logits2 && tokens && scores && predicted && step_dev && B > 0 && T > 0 && T <= 2048 && V > 1 && max_step > 0,
                "dn_cmlm_guided_step_dev: bad args (T=%d must be <= 2048)", T);
   DN_CHECK_ARG(scale > 0.f, "dn_cmlm_guided_step_dev: guidance scale %g must be > 0", (double)scale);
-  hipLaunchKernelGGL(cmlm_guided_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits2, scale, tokens, scores, predicted, B, T, V, 0.f, 0,
-                     unk, pad, step_dev, max_step);
+  hipLaunchKernelGGL(cmlm_step_kernel<true>, dim3(B), dim3(256), 0, (hipStream_t)stream, logits2, scale, tokens, scores, predicted, T, V, 0.f, 0, unk,
+                     pad, step_dev, max_step);
   DN_CHECK_LAUNCH("dn_cmlm_guided_step_dev");
   return DN_OK;
 }

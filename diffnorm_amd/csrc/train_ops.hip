@@ -14,12 +14,6 @@
 
 namespace dn {
 
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 static inline int ew_blocks(int64_t n4) {
   const int64_t b = (n4 + 255) / 256;
   return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
@@ -180,8 +174,8 @@ __global__ __launch_bounds__(256, 3) void rmsnorm_bwd_kernel(const float* __rest
       ss += xv[i].x * xv[i].x + xv[i].y * xv[i].y + xv[i].z * xv[i].z + xv[i].w * xv[i].w;
       dot += G[i].x * dv[i].x * xv[i].x + G[i].y * dv[i].y * xv[i].y + G[i].z * dv[i].z * xv[i].z + G[i].w * dv[i].w * xv[i].w;
     }
-    ss = wave_sum64(ss);
-    dot = wave_sum64(dot);
+    ss = wave_sum(ss);
+    dot = wave_sum(dot);
     const float r = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
     const float sr = s * r, k = r * r * dot;
 #pragma unroll
@@ -363,11 +357,11 @@ __global__ __launch_bounds__(256) void lsce_kernel(const float* __restrict__ log
     if (ov > bestv || (ov == bestv && oi < best)) { bestv = ov; best = oi; }
     mx = fmaxf(mx, __shfl_xor(mx, o, 64));
   }
-  sum = wave_sum64(sum);
+  sum = wave_sum(sum);
   float se = 0.f;
 #pragma unroll
   for (int i = 0; i < 16; ++i) se += (i * 64 + lane) < V ? expf(v[i] - mx) : 0.f;
-  se = wave_sum64(se);
+  se = wave_sum(se);
   const float lse = mx + logf(se);
   const int tg = target[m];
   const bool valid = tg != 0;
@@ -430,7 +424,7 @@ __global__ __launch_bounds__(256) void masked_mse_kernel(const float* __restrict
     }
     if (dpred_act && c < ld_act) store4(dpred_act, (int64_t)m * ld_act + c, act_dtype, g.x, g.y, g.z, g.w);
   }
-  sq = wave_sum64(sq);
+  sq = wave_sum(sq);
   if (lane == 0 && sq_rows) sq_rows[m] = sq;
 }
 
@@ -439,7 +433,7 @@ constexpr int kVecSumBlocks = 256;
 __global__ __launch_bounds__(256) void vec_sum_partial_kernel(const float* __restrict__ v, int64_t n, float* __restrict__ partial) {
   float s = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) s += v[i];
-  s = wave_sum64(s);
+  s = wave_sum(s);
   __shared__ float ws[4];
   if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
   __syncthreads();
@@ -447,7 +441,7 @@ __global__ __launch_bounds__(256) void vec_sum_partial_kernel(const float* __res
 }
 __global__ __launch_bounds__(256) void vec_sum_final_kernel(const float* __restrict__ partial, float* __restrict__ out, int accumulate) {
   float s = partial[threadIdx.x];  // kVecSumBlocks == blockDim
-  s = wave_sum64(s);
+  s = wave_sum(s);
   __shared__ float ws[4];
   if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
   __syncthreads();
@@ -666,7 +660,7 @@ __global__ __launch_bounds__(256) void time_cond_bwd_ds_kernel(const int32_t* __
     const float* wr = W + (int64_t)c * nfeat;
     float s = 0.f;
     for (int k = lane; k < nfeat; k += 64) s += feat[k] * wr[k];
-    s = wave_sum64(s);
+    s = wave_sum(s);
     if (lane == 0) {
       const float z = s + bias[c];
       const float sg = 1.0f / (1.0f + expf(-z));
@@ -718,7 +712,7 @@ __global__ __launch_bounds__(256) void time_cond_bwd_freq_kernel(const int32_t* 
     const float tf = (float)times[b];
     const float ang = __fmul_rn(__fmul_rn(__fmul_rn(tf, wf[j]), 2.0f), 3.14159265358979323846f);
     float v = (ps * cosf(ang) - pc * sinf(ang)) * (6.28318530717958647692f * tf);
-    v = wave_sum64(v);
+    v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) total += (red[0] + red[1]) + (red[2] + red[3]);

@@ -244,12 +244,6 @@ __global__ __launch_bounds__(256) void embed_kernel(const float* dict, const int
   *reinterpret_cast<float4*>(out + bf * E + 4 * v) = *reinterpret_cast<const float4*>(dict + (int64_t)code * E + 4 * v);
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // LayerNorm over the channels of every valid frame, in place (eps 1e-5, biased variance).  One wave per frame.
 __global__ __launch_bounds__(256) void layernorm_kernel(float* x, const int32_t* lengths, int B, int Tmax, int H, const float* g, const float* bta) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;

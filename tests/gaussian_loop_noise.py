@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE ONLY: the counter / key layout of dn_gaussian_loop's in-kernel draws, restated on the host with
-oracle/philox_normal.py (imported, never edited).  gaussian_sched_step_kernel draws through the scheduled loops' sched_normal4:
+oracle/philox_normal.py (imported, never edited).  the generic Gaussian update (sched_step_kernel under GaussRule) draws through the scheduled loops' sched_normal4:
 
 * seed-drawn:  Philox4x32-10 under key (seed low, seed high), counter (quad low, quad high, chain position i, "DPMP"), the quad of
                the WHOLE [B, T, Z] batch -- philox_normal.step_noise, as dn_ddim_sched_loop;

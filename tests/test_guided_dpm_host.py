@@ -142,14 +142,15 @@ def test_the_new_entries_are_bound_and_declared():
 
 
 def test_the_update_kernels_of_pointwise_compile_without_scratch():
-    """tools/check_resources.py on csrc/pointwise.hip (hipcc cross-compiles: no GPU needed): no kernel of the unit, the two forms of
-    guided_dpm_step_kernel among them, spills or keeps a stack object."""
+    """tools/check_resources.py on csrc/pointwise.hip (hipcc cross-compiles: no GPU needed): no kernel of the unit, the guided and
+    unguided forms of the 2M update (sched_step_kernel under Dpm2mRule) among them, spills or keeps a stack object."""
     import importlib.util
     import shutil
 
     if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
         pytest.skip("hipcc not available")
-    assert "guided_dpm_step_kernel" in open(os.path.join(ROOT, "diffnorm_amd", "csrc", "pointwise.hip")).read()
+    src = open(os.path.join(ROOT, "diffnorm_amd", "csrc", "pointwise.hip")).read()
+    assert "sched_step_kernel" in src and "sched_launch_source<Dpm2mRule, false>" in src
     spec = importlib.util.spec_from_file_location("check_resources", os.path.join(ROOT, "tools", "check_resources.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)

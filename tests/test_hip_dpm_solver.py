@@ -154,6 +154,112 @@ def test_update_kernel_alone(eng, n):
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
 
 
+# The scheduled DDIM and generic Gaussian updates run the same kernel template as the 2M update, guided and unguided, so its launch
+# geometry is pinned through their public single-step entries too, on the grid above: one quad, part of a block, across a block, a
+# second grid-stride trip.  Every case draws or clips: (entry, keyword arguments of its launch).
+PREFIX = 1020
+SEED = 0x5EED0123456789AB
+SCHED_CASES = [("ddim", dict(eta=0.0)), ("ddim", dict(eta=0.5, seed=SEED)),
+               ("gaussian", dict(sampler=0, clip=0, eta=0.0, seed=SEED)), ("gaussian", dict(sampler=0, clip=1, eta=0.0, seed=SEED)),
+               ("gaussian", dict(sampler=1, clip=0, eta=0.5, seed=SEED)), ("gaussian", dict(sampler=1, clip=1, eta=0.5, seed=SEED))]
+KEYS = [0xE220A8397B1DCDAF, 1 << 63, 0x0123456789ABCDEF]
+ROW = 1  # of 5: not the last row, its timestep is not 0 -- the row draws
+_tables = {}
+
+
+def sched_tables(sched, entry, eta):
+    """-> (steps, coefficient rows) on the device: 5 rows of `scheduler.ddim_schedule` / of the cosine "ddim5" respacing."""
+    key = (entry, eta if entry == "ddim" else None)
+    if key not in _tables:
+        if entry == "ddim":
+            _tables[key] = sched.ddim_schedule(50, sampling_steps=5, eta=eta, device=DEV)
+        else:
+            from diffnorm_amd.diffusion import create_diffusion
+
+            _tables[key] = create_diffusion("ddim5", noise_schedule="cosine", learn_sigma=False, diffusion_steps=100).device_schedule(None, DEV)
+    return _tables[key]
+
+
+def sched_step_alone(lib, sched, entry, x, eps, n, eta=0.0, seed=0, sampler=0, clip=0, keys=None, shape=None):
+    """dn_ddim_sched_step / dn_gaussian_sched_step (keys: the keyed entries on `shape` = (B, T, Z)) at row ROW, in place on x"""
+    from diffnorm_amd import _lib
+
+    steps, rows = sched_tables(sched, entry, eta)
+    assert steps.shape[0] == 5 and int(steps[ROW]) != 0
+    idx = torch.tensor([ROW], dtype=torch.int32, device=DEV)
+    k64 = None if keys is None else torch.tensor([k - (1 << 64) if k >> 63 else k for k in keys], dtype=torch.int64, device=DEV)
+
+    def run():
+        s = _lib.current_stream()
+        if entry == "ddim" and keys is None:
+            return lib.dn_ddim_sched_step(x.data_ptr(), eps.data_ptr(), n, rows.data_ptr(), steps.data_ptr(), idx.data_ptr(), int(eta != 0), seed, None, s)
+        if entry == "ddim":
+            return lib.dn_ddim_sched_step_keyed(x.data_ptr(), eps.data_ptr(), k64.data_ptr(), *shape, rows.data_ptr(), steps.data_ptr(), idx.data_ptr(), s)
+        if keys is None:
+            return lib.dn_gaussian_sched_step(x.data_ptr(), eps.data_ptr(), n, rows.data_ptr(), idx.data_ptr(), 5, sampler, clip, eta, seed, None, s)
+        return lib.dn_gaussian_sched_step_keyed(x.data_ptr(), eps.data_ptr(), k64.data_ptr(), *shape, rows.data_ptr(), steps.data_ptr(), idx.data_ptr(), 5,
+                                                sampler, clip, eta, s)
+
+    assert on_stream(run) == 0, lib.dn_last_error()
+
+
+def sentinel_padded(v, tail=64, sentinel=12345.0):
+    return torch.cat([v.reshape(-1), torch.full((tail,), sentinel)]).to(DEV)
+
+
+@pytest.mark.parametrize("n", [4, 1020, 4100, GRID_CAP_ELEMS + 12])
+def test_sched_step_kernels_alone(eng, n):
+    """Nothing behind n is written and eps is not modified; and the prefix property, bit for bit: the first PREFIX elements of the
+    n-element launch are the PREFIX-element launch on the same prefix (the update is element-wise and the draw counter is the quad
+    index from 0, so this holds for the seeded rows too)."""
+    from diffnorm_amd import _lib
+
+    _, sched = eng
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(n)
+    m = max(n, PREFIX)
+    x0, eps = 2.0 * torch.randn(m, generator=g), torch.randn(m, generator=g)  # (|x0| up to ~10: the clip is reached)
+    outs = {}
+    for entry, kw in SCHED_CASES:
+        got = {}
+        for count in {n, PREFIX}:
+            x, ev = sentinel_padded(x0[:count]), sentinel_padded(eps[:count])
+            sched_step_alone(lib, sched, entry, x, ev, count, **kw)
+            x, ev = x.cpu(), ev.cpu()
+            assert (x[count:] == 12345.0).all() and (ev[count:] == 12345.0).all() and torch.equal(ev[:count], eps[:count]), (entry, kw, count)
+            assert torch.isfinite(x).all() and not torch.equal(x[:count], x0[:count])
+            got[count] = x[:count]
+        k = min(n, PREFIX)
+        assert torch.equal(got[n][:k], got[PREFIX][:k]), (entry, kw, n)
+        outs[(entry, tuple(sorted(kw.items())))] = got[n]
+    assert len({tuple(v[:4].tolist()) for v in outs.values()}) == len(SCHED_CASES)  # every case is an update of its own (eta, sampler, clip)
+
+
+@pytest.mark.parametrize("B", [1, 3])
+def test_keyed_sched_step_kernels_alone(eng, B):
+    """The keyed entries along whole utterances: T = 5, Z = 4 -- an utterance of the B-row launch is the launch of that utterance
+    alone under its key, bit for bit, and nothing behind the batch is written."""
+    from diffnorm_amd import _lib
+
+    _, sched = eng
+    lib = _lib.load()
+    Tk, Zk = 5, 4
+    g = torch.Generator().manual_seed(40 + B)
+    x0, eps = 2.0 * torch.randn(B, Tk, Zk, generator=g), torch.randn(B, Tk, Zk, generator=g)
+    for entry, kw in (("ddim", dict(eta=0.5)), ("gaussian", dict(sampler=0, clip=1)), ("gaussian", dict(sampler=1, clip=0, eta=0.5))):
+        x, ev = sentinel_padded(x0), sentinel_padded(eps)
+        sched_step_alone(lib, sched, entry, x, ev, x0.numel(), keys=KEYS[:B], shape=(B, Tk, Zk), **kw)
+        x, ev = x.cpu(), ev.cpu()
+        assert (x[x0.numel():] == 12345.0).all() and torch.equal(ev[:x0.numel()], eps.reshape(-1)) and (ev[x0.numel():] == 12345.0).all()
+        whole = x[:x0.numel()].view(B, Tk, Zk)
+        for b in range(B):
+            xb, eb = sentinel_padded(x0[b]), sentinel_padded(eps[b])
+            sched_step_alone(lib, sched, entry, xb, eb, Tk * Zk, keys=[KEYS[b]], shape=(1, Tk, Zk), **kw)
+            assert torch.equal(xb.cpu()[:Tk * Zk].view(Tk, Zk), whole[b]), (entry, kw, B, b)
+        if B == 3:
+            assert not torch.equal(whole[0] - x0[0], whole[1] - x0[1])  # (the utterances draw under their own keys)
+
+
 def test_update_kernel_entry_refuses_bad_arguments():
     from diffnorm_amd import _lib
 

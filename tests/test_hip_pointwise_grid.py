@@ -567,13 +567,13 @@ def cmlm_inputs(T, step, max_step):
     return cond, tok, scores, groups
 
 
-def cmlm_run(entry, logits_d, tok, scores, step, max_step):
+def cmlm_run(entry, logits_d, tok, scores, step, max_step, V=None):
     """-> (tokens, scores, predicted) of dn_cmlm_step (`entry` "host") or dn_cmlm_step_dev ("dev") on copies of tok / scores"""
     L, lib = _lib()
     B, T = tok.shape
     t_d, s_d = tok.to(DEV).int().contiguous(), scores.to(DEV).contiguous()
     pred = torch.full((B, T), -1, dtype=torch.int32, device=DEV)
-    args = (B, T, CM["V"])
+    args = (B, T, CM["V"] if V is None else V)
     if entry == "host":
         L.check(lib.dn_cmlm_step(logits_d, t_d.data_ptr(), s_d.data_ptr(), pred.data_ptr(), *args, step, max_step, CM["unk"], CM["pad"], _stream()),
                 "dn_cmlm_step")
@@ -667,6 +667,70 @@ def test_cmlm_step_short_rows_and_both_entries_in_step(ops):
             want_masked = sum(max(G._boundary(int(n), step, max_step), 0) for n in out["host"][2].ne(pad).sum(1)) if step + 1 < max_step else 0
             assert n_masked == want_masked, (max_step, step, n_masked)
             state = {e: out[e][:2] for e in out}
+
+
+def narrow_inputs(T, V, step, max_step):
+    """Every position of three ragged rows masked (rows of T, T // 2 and 2 tokens where T allows; T = 1: one masked, one eos, one
+    pad), logits whose column 0 stands clear of the rest: by 1 .. 1.5 at the positions the iteration re-masks, by 3 .. 5 at those
+    it keeps, so a gap stands at every re-mask boundary.  The margins are CHECKED by the caller, not assumed."""
+    unk, pad, eos = CM["unk"], CM["pad"], CM["eos"]
+    g = torch.Generator().manual_seed(7000 + 10 * T + V + step)
+    logits = 0.1 * torch.randn(3, T, V, generator=g)
+    tok = torch.full((3, T), pad)
+    for b, n in enumerate([T, T // 2, 2] if T >= 4 else [1, 1, 0]):
+        if n:
+            tok[b, :n] = unk
+            tok[b, n - 1] = eos if (T >= 4 or b == 1) else unk
+        masked = int(tok[b].eq(unk).sum())
+        k = max(G._boundary(n, step, max_step), 0) if step + 1 < max_step else 0
+        low = torch.randperm(masked, generator=g)[:k]
+        rise = 3.0 + 2.0 * torch.rand(T, generator=g)
+        rise[low] = 1.0 + 0.5 * torch.rand(k, generator=g)
+        logits[b, :, 0] += rise
+    return logits, tok
+
+
+# Both mask-predict kernels share one body: a single position (T = 1: nothing to rank), the rank loop's second turn (T = 257), and
+# vocabularies narrower than a wave (V = 2: 62 idle lanes; V = 65: one lane takes a second column), against the host restatements.
+@pytest.mark.parametrize("T,V", [(1, 2), (1, 65), (33, 65), (257, 2), (257, 65)])
+def test_cmlm_steps_at_one_position_and_narrow_vocabularies(ops, T, V):
+    L, lib = _lib()
+    max_step, unk, pad, B = 10, CM["unk"], CM["pad"], 3
+    for step in (0, 4, 9):
+        logits, tok = narrow_inputs(T, V, step, max_step)
+        zeros = torch.zeros(B, T)
+        # ---- the kernel that keeps the scores
+        m_arg, gap, nz, _ = G.kept_margins(logits, tok, zeros, step, max_step, unk, pad)
+        assert m_arg >= G.MARGIN and gap >= G.MARGIN and nz == 0, (T, V, step, m_arg, gap, nz)
+        ref_tok, ref_sc, ref_pred = G.kept_update(logits, tok, zeros, step, max_step, unk, pad)
+        if T > 1 and step + 1 < max_step:
+            assert bool(ref_tok.eq(unk).any())  # (something is re-masked)
+        buf, addr = guarded(logits)
+        for entry in ("host", "dev"):
+            got_tok, got_sc, got_pred = cmlm_run(entry, addr, tok, zeros, step, max_step, V=V)
+            assert got_tok.tolist() == ref_tok.tolist() and got_pred.tolist() == ref_pred.tolist(), (T, V, step, entry)
+            np.testing.assert_allclose(got_sc.numpy(), ref_sc.numpy(), rtol=1e-5, atol=2e-6)
+        # ---- the guided kernel: cond and null chosen so that cond + scale (cond - null) is `logits` up to rounding
+        scale = 3.0
+        null = 0.5 * torch.randn(B, T, V, generator=torch.Generator().manual_seed(T + V))
+        cond = (logits + scale * null) / (1 + scale)
+        scaled = cond + scale * (cond - null)
+        m_arg, gap, nz = G.margins(scaled, tok, step, max_step, unk, pad)
+        assert m_arg >= G.MARGIN and gap >= G.MARGIN and nz == 0, (T, V, step, m_arg, gap, nz)
+        ref_tok, ref_sc, ref_pred = G.guided_update(scaled, tok, step, max_step, unk, pad)
+        buf2, addr2 = guarded(torch.cat([cond.reshape(-1), null.reshape(-1)]))
+        step_d = torch.tensor([step], dtype=torch.int32, device=DEV)
+        for entry in ("host", "dev"):
+            t_d, s_d = tok.to(DEV).int().contiguous(), torch.full((B, T), 7.0, device=DEV)  # stale scores: the kernel starts from zero
+            pred = torch.full((B, T), -1, dtype=torch.int32, device=DEV)
+            if entry == "host":
+                L.check(lib.dn_cmlm_guided_step(addr2, scale, t_d.data_ptr(), s_d.data_ptr(), pred.data_ptr(), B, T, V, step, max_step, unk, pad,
+                                                _stream()), "dn_cmlm_guided_step")
+            else:
+                L.check(lib.dn_cmlm_guided_step_dev(addr2, scale, t_d.data_ptr(), s_d.data_ptr(), pred.data_ptr(), B, T, V, step_d.data_ptr(), max_step,
+                                                    unk, pad, _stream()), "dn_cmlm_guided_step_dev")
+            assert t_d.cpu().long().tolist() == ref_tok.tolist() and pred.cpu().long().tolist() == ref_pred.tolist(), (T, V, step, entry)
+            np.testing.assert_allclose(s_d.cpu().numpy(), ref_sc.numpy(), rtol=1e-5, atol=2e-6)
 
 
 # ------------------------------------------------------------------------------------------------------------ refused arguments
