@@ -129,6 +129,12 @@ class HubertConfig(C.Structure):
                [(n, C.c_int32) for n in ("dim", "ffn", "layers", "heads", "conv_pos", "conv_pos_groups", "dtype", "has_proj")]
 
 
+class FbankConfig(C.Structure):
+    _fields_ = [("sample_rate", C.c_float), ("n_mels", C.c_int32), ("frame_length", C.c_int32), ("frame_shift", C.c_int32), ("n_fft", C.c_int32),
+                ("low_freq", C.c_float), ("high_freq", C.c_float), ("preemphasis", C.c_float), ("remove_dc_offset", C.c_int32),
+                ("input_scale", C.c_float), ("norm_means", C.c_int32), ("norm_vars", C.c_int32), ("cmvn", C.c_int32)]
+
+
 class RelAttnParams(C.Structure):
     _fields_ = [("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("out", C.c_void_p),
                 ("ldq", C.c_int32), ("ldk", C.c_int32), ("ldv", C.c_int32), ("ldo", C.c_int32),
@@ -351,6 +357,13 @@ SYMBOLS = {
     "dn_hubert_forward": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "dn_hubert_set_profile": (C.c_int, [_vp, _i32]),
     "dn_hubert_stage_times": (C.c_int, [_vp, C.POINTER(C.c_float), _i32]),
+    "dn_fbank_tables": (C.c_int, [C.POINTER(FbankConfig), _vp, _vp]),
+    "dn_fbank_twiddles": (C.c_int, [_i32, _vp]),
+    "dn_fbank_create": (C.c_int, [_vp, _vp, _i32, _vp]),
+    "dn_fbank_destroy": (None, [_vp]),
+    "dn_fbank_out_frames": (_i32, [_vp, _i32]),
+    "dn_fbank_workspace_bytes": (_sz, [_vp, _i32, _i32]),
+    "dn_fbank_forward": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "dn_set_option": (C.c_int, [C.c_char_p, _i32]),
     "dn_get_option": (C.c_int, [C.c_char_p, _vp, _vp]),
 }

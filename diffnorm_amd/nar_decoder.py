@@ -273,10 +273,12 @@ class _HipEncoder:
     dict (encoder_out [S, B, D], encoder_padding_mask [B, S] -- an empty list when nothing is padded, s2t_transformer.py:364-373), with
     the batch-major copy and the subsampled lengths the decoder engine wants riding along; reorder_encoder_out as upstream (:387-420)."""
 
-    def __init__(self, engine):  # a NarEncoderEngine or a ConformerEncoderEngine
-        self.engine = engine
+    def __init__(self, engine, fbank=None):  # a NarEncoderEngine or a ConformerEncoderEngine; fbank: a FbankEngine in front of it
+        self.engine, self.fbank = engine, fbank
 
     def __call__(self, src_tokens, src_lengths=None):
+        if self.fbank is not None:  # src_tokens [B, L] waveforms, src_lengths in samples -> features; their lengths stay on the device
+            src_tokens, src_lengths = self.fbank.forward(src_tokens, src_lengths)
         x, lens = self.engine.forward(src_tokens, src_lengths)
         S = x.shape[1]
         pad = torch.arange(S, device=x.device)[None, :] >= lens[:, None]
@@ -482,18 +484,31 @@ class NARS2UTDecoderModel:
     allow_length_beam = True
 
     def __init__(self, decoder_state_dict, dim=512, ffn=2048, layers=6, heads=8, vocab=1004, pad=1, unk=3, dtype="bf16", device="cuda:0",
-                 use_graph: bool = True, encoder_state_dict=None, encoder_kw=None, eos: int = 2, encoder_arch: str = "transformer"):
+                 use_graph: bool = True, encoder_state_dict=None, encoder_kw=None, eos: int = 2, encoder_arch: str = "transformer",
+                 waveform_input=None):
         """encoder_state_dict (S2TTransformerEncoder.state_dict() names; encoder_kw = NarEncoderEngine's sizes): with it `forward_encoder`
         runs the speech encoder on the HIP engine from [B, L, 80] features, as NARS2UTTransformerModel.forward_encoder does (:566-567);
         without it the encoder output is a tensor the caller supplies.  encoder_arch "conformer": the state dict is
-        S2TConformerEncoder.state_dict()'s and encoder_kw ConformerEncoderEngine's sizes (the recipe's --arch nar_s2ut_conformer)."""
+        S2TConformerEncoder.state_dict()'s and encoder_kw ConformerEncoderEngine's sizes (the recipe's --arch nar_s2ut_conformer).
+        waveform_input (a diffnorm_amd.fbank.FbankConfig, or True for the recipe's: 16 kHz, 80 bins, utterance CMVN): the encoder takes
+        src_tokens [B, L] waveforms with src_lengths in samples and runs the Kaldi fbank + CMVN front end (FbankEngine) in front of the
+        speech encoder, so `generate()` works from waveforms; unset, it takes [B, L, 80] features as before."""
         if encoder_arch not in ("transformer", "conformer"):
             raise ValueError(f"encoder_arch {encoder_arch!r}: 'transformer' or 'conformer'")
+        if waveform_input and encoder_state_dict is None:
+            raise ValueError("waveform_input needs the speech encoder on the engine (encoder_state_dict)")
         self.engine = NarDecoderEngine(decoder_state_dict, dim, ffn, layers, heads, vocab, pad=pad, dtype=dtype, device=device)
         if encoder_state_dict is not None:
             kw = dict(dim=dim, heads=heads, dtype=dtype, device=device)
             kw.update(encoder_kw or {})
-            self.encoder = _HipEncoder((ConformerEncoderEngine if encoder_arch == "conformer" else NarEncoderEngine)(encoder_state_dict, **kw))
+            fb = None
+            if waveform_input:
+                from .fbank import FbankConfig, FbankEngine
+
+                fb = FbankEngine(FbankConfig() if waveform_input is True else waveform_input, device=device)
+                if fb.n_mels != kw.get("input_dim", 80):
+                    raise ValueError(f"waveform_input: {fb.n_mels} mel bins, but the speech encoder takes {kw.get('input_dim', 80)} features per frame")
+            self.encoder = _HipEncoder((ConformerEncoderEngine if encoder_arch == "conformer" else NarEncoderEngine)(encoder_state_dict, **kw), fb)
         else:
             self.encoder = _GivenEncoder()
         self.pad, self.unk, self.eos, self.device = pad, unk, eos, self.engine.device

@@ -1307,6 +1307,55 @@ int dn_hubert_forward(DnHubert* m, const float* wave, const int32_t* lengths, in
 int dn_hubert_set_profile(DnHubert* m, int32_t on);
 int dn_hubert_stage_times(DnHubert* m, float* ms, int32_t cap);
 
+/* ------------------------------------------------------------------ Kaldi fbank + utterance CMVN: waveform -> S2UT source features */
+/* The first box of the S2UT leg: get_fbank (fairseq/data/audio/audio_utils.py:242-277), i.e. torchaudio.compliance.kaldi.fbank(waveform,
+ * num_mel_bins=80, sample_frequency=sr) at its defaults with dither 0 (the deterministic torchaudio form; pyKaldi's own default adds
+ * random dither 1.0), then UtteranceCMVN.__call__ (fairseq/data/audio/feature_transforms/utterance_cmvn.py:30-41), which
+ * examples/speech_to_speech/preprocessing/prep_s2ut_data.py:73 puts in every S2UT config.  Kernels: csrc/fbank.hip.
+ *   frames    snip_edges: m = 1 + (n - frame_length) / frame_shift for n >= frame_length, else 0; frame i = x[i shift, i shift + length)
+ *   per frame subtract the frame's mean (remove_dc_offset) -> f[j] -= preemphasis f[j - 1] with f[-1] := f[0] -> Povey window
+ *             (0.5 - 0.5 cos(2 pi j / (length - 1)))^0.85 -> zero-pad to n_fft -> |rfft|^2 -> n_mels triangular filters in the mel
+ *             domain (mel(f) = 1127 ln(1 + f / 700), n_mels + 2 equally spaced points from low_freq to high_freq, Nyquist bin weight 0)
+ *             -> log(max(energy, FLT_EPSILON))
+ *   CMVN      per utterance and column over its own frames: mean, var = E[x^2] - mean^2, y = (x - mean) / sqrt(max(var, 1e-10))
+ * All arithmetic fp32 (the CMVN sums in double); a result depends on the utterance's own samples and length only, not on B, L, the row
+ * or the neighbours, and no sample at or behind lengths[b] is read.  Refused (-1 with dn_last_error): n_fft other than 256 / 512 /
+ * 1024 or below frame_length, frame_shift outside [1, frame_length], n_mels outside [1, 128], low_freq < 0, high_freq above Nyquist
+ * or not above low_freq (0 = Nyquist).  The rest of torchaudio's signature (dither, use_energy, htk_compat, vtln, other windows,
+ * snip_edges False, subtract_mean) has no field here: diffnorm_amd/fbank.py refuses it by name.                                 */
+typedef struct DnFbank DnFbank;
+typedef struct {
+  float sample_rate;
+  int32_t n_mels, frame_length, frame_shift, n_fft; /* the last three in samples; n_fft >= frame_length */
+  float low_freq, high_freq;                        /* Hz; high_freq 0 = Nyquist */
+  float preemphasis;
+  int32_t remove_dc_offset;
+  float input_scale;             /* samples are multiplied by it: 1.0 for int16-scale input (what the reference feeds), 32768.0 for [-1, 1] */
+  int32_t norm_means, norm_vars; /* the two halves of UtteranceCMVN */
+  int32_t cmvn;                  /* 0: the raw log-mel energies are the output */
+} DnFbankConfig;
+/* The one place the tables are computed (host code, no GPU needed), in double, rounded once: window fp32 [frame_length], mel fp32
+ * [n_mels][n_fft / 2 + 1] (torchaudio's get_mel_banks with a zero Nyquist column; at most two non-zero weights per bin).          */
+int dn_fbank_tables(const DnFbankConfig* cfg, float* window, float* mel);
+/* tw fp32 [n_fft / 2][2] = (cos, -sin)(2 pi k / n_fft): the transform's twiddle factors, in double, rounded once (host code). */
+int dn_fbank_twiddles(int32_t n_fft, float* tw);
+/* tables: device pointers to { window, mel, twiddles }, each a verbatim copy of what the two functions above filled FOR THIS cfg (they
+ * must outlive the handle).  The handle derives each filter's non-zero bin range from cfg by the code that fills the mel table and
+ * never reads the tables on the host: a mel table from anywhere else is summed over the wrong bins -- it is not a way to bring
+ * other filters.                                                                                                              */
+int dn_fbank_create(const DnFbankConfig* cfg, const void* const* tables, int32_t n_tables, DnFbank** out);
+void dn_fbank_destroy(DnFbank* m);
+/* frames of L samples (0 when L < frame_length) */
+int32_t dn_fbank_out_frames(const DnFbank* m, int32_t L);
+size_t dn_fbank_workspace_bytes(const DnFbank* m, int32_t B, int32_t L);
+/* wave fp32 [B, L] (anything, NaN included, at and behind an utterance's samples), lengths int32 [B] on the device (samples; clamped to
+ * [0, L]) -> out fp32 [B, Lf, n_mels], Lf = dn_fbank_out_frames(m, L), out_lengths int32 [B]; rows at or behind out_lengths[b] are
+ * written as zeros.  An utterance shorter than one frame (or empty) is a handled case: out_lengths[b] = 0, zero rows, return 0.
+ * Stream-ordered, no allocation, no synchronisation with the host: it can be captured in a graph.  workspace: 256-byte aligned,
+ * dn_fbank_workspace_bytes(m, B, L); every argument is checked before the first launch (a refused call has written nothing). */
+int dn_fbank_forward(DnFbank* m, const float* wave, const int32_t* lengths, int32_t B, int32_t L, float* out, int32_t* out_lengths,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
