@@ -20,7 +20,7 @@ GEMM_TAG_SHIFT, GEMM_TILE_SHIFT, GEMM_BAND_SHIFT = 8, 16, 24
 GEMM_FAT_STAMPS, GEMM_NO_SHARED_ROWS, GEMM_TAPS_INNER, GEMM_TERM_OUTER = 1 << 20, 1 << 21, 1 << 22, 1 << 23
 # tile variants of dn_conv_gemm (DN_TILE_*)
 (TILE_128X128, TILE_256X128, TILE_256X256, TILE_256X352, TILE_ROW, TILE_256X256_W4, TILE_256X256_W8, TILE_256X192,
- TILE_256X128_2WG) = range(1, 10)
+ TILE_256X128_2WG, TILE_256X128_SR) = range(1, 11)
 
 
 class DiffNormHipError(RuntimeError):
@@ -246,8 +246,11 @@ SYMBOLS = {
     "dn_transpose_slices": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "dn_repack_weights": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     "dn_ffn_fold": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "dn_ffn_fold_kblocked": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "dn_eps_set_ffn_fold": (C.c_int, [_vp, _vp, _vp]),
     "dn_vae_set_ffn_fold": (C.c_int, [_vp, _vp, _vp]),
+    "dn_eps_set_ffn_fold_kblocked": (C.c_int, [_vp, _vp]),
+    "dn_vae_set_ffn_fold_kblocked": (C.c_int, [_vp, _vp]),
     "dn_wgrad_reduce": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "dn_conv_weight_grad_tn": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "dn_conv_weight_grad_tn_x3": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),

@@ -43,7 +43,7 @@ const OptDef kOpts[dn::OPT_COUNT] = {
     {"wgrad_k192", "DN_WGRAD_K192", nullptr},              // 1: the weight-gradient kernel on 192 k-columns per tile where that fills the chip better (default off: faster alone, slower beside the data-gradient chain)
     {"wgrad_prio", "DN_WGRAD_PRIO", nullptr},              // 1: the weight-gradient stream at the lowest priority (read when the stream is created; measured level, default off)
     {"wgrad_tn_x3", "DN_WGRAD_TN_X3", nullptr},            // split-operand (bf16x3) weight gradients: 0 from transposed copies (default 1: straight from the row-major split rows) ("wgrad_tn" covers the 2-byte modes only)
-    {"ffn_fold", "DN_FFN_FOLD", nullptr},                  // sampling engines: 0 = the FFN causal conv and its output projection as two contractions (default 1, in DN_BF16 0: one folded three-tap contraction; 2 / 3: the same forced to the 256 x 128 / 256 x 256 tile, A/B timing)
+    {"ffn_fold", "DN_FFN_FOLD", nullptr},                  // sampling engines: 0 = the FFN causal conv and its output projection as two contractions (the default in DN_BF16); one folded three-tap contraction: 5 = on the tile the engine's route rule picks (the default otherwise), 1 = the tile the route table chooses (term-outer; 128 x 128 at [32,512]), 2 / 3 / 4 = forced to the 256 x 128 / 256 x 256 / 256 x 128 shared-row tile, A/B timing
     {"nar_cg_fold", "DN_NAR_CG_FOLD", nullptr},            // guided NAR decoder pass: 0 = the null half's encoder attention evaluated literally against S copies of the null key / value (default 1: the broadcast addition of the constant row c_l)
 };
 std::atomic<int> g_opt[dn::OPT_COUNT];

@@ -92,8 +92,9 @@ struct TransformerW {
   const void *qkv_W, *out_W, *ffin_W, *ffconv_W, *ffout_W, *pred_W, *ffconv_Wkb, *ffin_Wkb, *qkv_Wkb;
   const float *ffin_b, *ffconv_b, *ffout_b, *g1, *g2, *pred_gamma;
   const void* fold_W;
+  const void* fold_Wkb;  // fold_W K-blocked, [depth][3][padk(inner)/32][padn(D)][32] (2-byte types; dn_ffn_fold_kblocked) or NULL
   const float* fold_b;
-  int fold_default;  // option ffn_fold when unset: 1, but 0 in DN_BF16 (the two-stage form there: DESIGN 11)
+  int fold_default;  // option ffn_fold when unset: 5 (folded, routed by run_transformer), but 0 in DN_BF16 (the two-stage form there: DESIGN 11)
 };
 constexpr int kTransformerTensors = 15;
 

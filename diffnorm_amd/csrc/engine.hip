@@ -143,8 +143,22 @@ struct TfBufs { void *xn, *qkv, *ao, *gg, *fc; float* ssq; };
 inline int ssq_ld(int Dp) { const int n = Dp / 64; return n <= 8 ? 8 : (n + 3) / 4 * 4; }
 
 // Option ffn_fold (default on, off in DN_BF16: TransformerW.fold_default): with folded weights attached, the FFN's causal conv and output projection run as one contraction.
-// 1: on the tile the route table chooses; 2 / 3: forced to 256 x 128 / 256 x 256 (A/B timing); 0: two stages.
+// 5: on the tile fold_route picks; 1: on the tile the route table chooses (term-outer: 128 x 128 at [32,512]); 2 / 3 / 4: forced to
+// 256 x 128 / 256 x 256 / the 256 x 128 shared-row tile (A/B timing); 0: two stages.
+enum { FOLD_OFF = 0, FOLD_TABLE = 1, FOLD_256X128 = 2, FOLD_256X256 = 3, FOLD_SR = 4, FOLD_ROUTED = 5 };
 inline int ffn_fold_mode(const TransformerW& w) { return w.fold_W && w.fold_b ? option_or(OPT_FFN_FOLD, w.fold_default) : 0; }
+
+// Does the folded contraction (M rows, N = Dp columns, K = 3 x ip) go to the 256 x 128 shared-row tile?  Long and at most 512
+// columns wide -- one to four column tiles, where 256-column tiles leave CUs idle -- with enough 256 x 128 tiles to give every CU
+// one; a half-batch launch of the two-stream chain counts double (its twin runs beside it).  With taps_inner = 2 whatever M is:
+// a batch and its shards then sum every output in one order, as for the other tap-inner tiles.  Measured: DESIGN 11.
+constexpr bool kFoldSrRouted = true;
+inline bool fold_route(int dtype, int M, int Dp, int ip, int32_t gemm_flags) {
+  if (!kFoldSrRouted || !dn::dn_is16(dtype) || Dp > 512 || 3L * ip < 1024) return false;
+  if (option_or(OPT_TAPS_INNER, 1) == 2) return true;
+  const long twin = (gemm_flags & DN_GEMM_TWIN) ? 2 : 1;
+  return (long)((M + 255) / 256) * ((Dp + 127) / 128) * twin >= 256;
+}
 
 TfBufs plan_tf(const TransformerW& w, int M, int es, Arena& ar) {
   const int hd = w.heads * w.dim_head;
@@ -238,6 +252,32 @@ int run_transformer(const TransformerW& w, int dtype, float* xres, int B, int T,
   // option qkv_192: the projection's 3 x 512 columns are 8 x 192 but 6 x 256 -- at [32,512] 512 tiles of 256 x 192 are two full rounds
   // of the chip, 384 tiles of 256 x 256 one and a half
   const int fold = ffn_fold_mode(w);
+  // The folded contraction of layer l, row-major operands: three taps of the GEGLU output against W'_j, closing the residual.
+  // Its tile: the route table's (128 x 128 at [32,512]: 512 workgroups over the two half-batch streams, two per CU), one forced by
+  // the option, or -- FOLD_ROUTED, where fold_route says so -- the 256 x 128 shared-row tile; decided once per call.
+  int fold_tile = fold == FOLD_256X128 ? DN_TILE_256X128 : fold == FOLD_256X256 ? DN_TILE_256X256 : fold == FOLD_SR ? DN_TILE_256X128_SR : 0;
+  if (fold == FOLD_ROUTED && fold_route(dtype, M, Dp, ip, gemm_flags)) fold_tile = DN_TILE_256X128_SR;
+  auto fold_params = [&](int l) {
+    DnGemmParams p = gemm_base(dtype, M, Dp, ip, T, gemm_flags);
+    p.n_terms = 3;
+    for (int j = 0; j < 3; ++j) {
+      p.terms[j].A = tb.gg; p.terms[j].lda = ip; p.terms[j].shift = 2 - j;
+      p.terms[j].W = eoff(w.fold_W, ((size_t)l * 3 + j) * Dn * ip, es);
+    }
+    p.bias = w.fold_b + (size_t)l * Dp;
+    p.flags |= DN_TAG_FFN_CONV << DN_GEMM_TAG_SHIFT;
+    if (fold_tile && !fuse) p.flags |= fold_tile << DN_GEMM_TILE_SHIFT;
+    return p;
+  };
+  // Where it lands on the shared-row tile (2-byte types, split norm, taps_inner not 0: dn_conv_gemm_tile says) its operands go
+  // K-blocked when the engine has the K-blocked copy of the folded weights; DN_KBLOCK=0 keeps them row-major.
+  bool fold_kb = false;
+  if (fold && fold_tile == DN_TILE_256X128_SR && !fuse && w.fold_Wkb && kblock_mode() != 0 && dn::dn_is16(dtype)) {
+    DnGemmParams q = fold_params(0);
+    q.epilogue = DN_EPI_RESADD;
+    if (split) { q.norm_out = tb.xn; q.norm_split = 1; }
+    fold_kb = dn_conv_gemm_tile(&q) == DN_TILE_256X128_SR;
+  }
   const bool qkv_192 = option_or(OPT_QKV_192, 0) != 0 && dn::dn_is16(dtype) && (3 * hd) % 192 == 0 && M >= 2048;
   for (int l = 0; l < w.depth; ++l) {
     {  // to_q ; to_kv in one contraction (:930-931,945)
@@ -326,21 +366,16 @@ int run_transformer(const TransformerW& w, int dtype, float* xres, int B, int T,
         p.bias = w.ffin_b + (size_t)l * 2 * ip;
         p.epilogue = DN_EPI_GEGLU; p.out = tb.gg; p.ldo = ip;
         if (mid2 & 2) p.flags |= DN_TILE_256X128_2WG << DN_GEMM_TILE_SHIFT;
+        p.out_layout = fold_kb ? DN_LAYOUT_OUT_KBLOCKED : 0;
         if (scaled) set_row_scale(p, tb, Dp, D, rb ? rb + (size_t)l * rb_layer + 3 * hd + (cx ? hd : 0) : nullptr, rb_ld);
         DN_TRY(dn_conv_gemm(&p, s));
       }
-      DnGemmParams p = gemm_base(dtype, M, Dp, ip, T, gemm_flags);
-      p.n_terms = 3;
-      for (int j = 0; j < 3; ++j) {
-        p.terms[j].A = tb.gg; p.terms[j].lda = ip; p.terms[j].shift = 2 - j;
-        p.terms[j].W = eoff(w.fold_W, ((size_t)l * 3 + j) * Dn * ip, es);
-      }
-      p.bias = w.fold_b + (size_t)l * Dp;
-      p.flags |= DN_TAG_FFN_CONV << DN_GEMM_TAG_SHIFT;
-      // The route table sends it to the 128 x 128 tile at [32,512] (512 workgroups over the two half-batch streams, two per CU);
-      // forcing 256 x 128 (one per CU) measured level with it, 256 x 256 (half the CUs idle) 10 % slower per step: DESIGN 11
-      const int fold_tile = fold == 2 ? DN_TILE_256X128 : fold == 3 ? DN_TILE_256X256 : 0;
-      if (fold_tile && !fuse) p.flags |= fold_tile << DN_GEMM_TILE_SHIFT;
+      DnGemmParams p = fold_params(l);
+      if (fold_kb)  // both operands as whole cache lines: the GEGLU output above, the weights from their K-blocked copy
+        for (int j = 0; j < 3; ++j) {
+          p.terms[j].W = eoff(w.fold_Wkb, ((size_t)l * 3 + j) * Dn * ip, es);
+          p.terms[j].layout = DN_LAYOUT_A_KBLOCKED | DN_LAYOUT_W_KBLOCKED;
+        }
       DN_TRY(close_residual(p));
     } else {
     // CausalConv1d(inner, inner, 3) (:894), set up first: when it runs on one of the two 256-row tiles its operands go K-blocked --
@@ -498,13 +533,25 @@ extern "C" int dn_eps_create(const DnEpsConfig* cfg, const void* const* weights,
 extern "C" int dn_eps_set_ffn_fold(DnEps* m, const void* fold_W, const float* fold_b) {
   DN_CHECK_ARG(m && (fold_W != nullptr) == (fold_b != nullptr), "dn_eps_set_ffn_fold: null engine, or one of the two buffers without the other");
   DN_CHECK_ARG(((uintptr_t)fold_W & 127) == 0 && ((uintptr_t)fold_b & 15) == 0, "dn_eps_set_ffn_fold: fold_W 128-byte, fold_b 16-byte aligned");
-  m->tf.fold_W = fold_W; m->tf.fold_b = fold_b;
-  m->tf.fold_default = m->cfg.dtype == DN_BF16 ? 0 : 1;
+  m->tf.fold_W = fold_W; m->tf.fold_b = fold_b; m->tf.fold_Wkb = nullptr;
+  m->tf.fold_default = m->cfg.dtype == DN_BF16 ? FOLD_OFF : FOLD_ROUTED;
   for (StepGraph* g : {&m->loop_graph, &m->guided_graph}) {  // a captured step holds the launches of the other form
     if (g->exec) (void)hipGraphExecDestroy((hipGraphExec_t)g->exec);
     g->exec = nullptr;
   }
   m->table_ws = nullptr;
+  return DN_OK;
+}
+
+// see include/diffnorm_hip.h
+extern "C" int dn_eps_set_ffn_fold_kblocked(DnEps* m, const void* fold_Wkb) {
+  DN_CHECK_ARG(m && (!fold_Wkb || (m->tf.fold_W && dn::dn_is16(m->cfg.dtype))) && ((uintptr_t)fold_Wkb & 127) == 0,
+               "dn_eps_set_ffn_fold_kblocked: null engine, no folded weights attached, not a 2-byte arithmetic, or fold_Wkb not 128-byte aligned");
+  m->tf.fold_Wkb = fold_Wkb;
+  for (StepGraph* g : {&m->loop_graph, &m->guided_graph}) {  // a captured step holds the other operand layout
+    if (g->exec) (void)hipGraphExecDestroy((hipGraphExec_t)g->exec);
+    g->exec = nullptr;
+  }
   return DN_OK;
 }
 
@@ -1633,8 +1680,15 @@ extern "C" void dn_vae_destroy(DnVae* m) { delete m; }
 extern "C" int dn_vae_set_ffn_fold(DnVae* m, const void* fold_W, const float* fold_b) {
   DN_CHECK_ARG(m && (fold_W != nullptr) == (fold_b != nullptr), "dn_vae_set_ffn_fold: null engine, or one of the two buffers without the other");
   DN_CHECK_ARG(((uintptr_t)fold_W & 127) == 0 && ((uintptr_t)fold_b & 15) == 0, "dn_vae_set_ffn_fold: fold_W 128-byte, fold_b 16-byte aligned");
-  m->tf.fold_W = fold_W; m->tf.fold_b = fold_b;
-  m->tf.fold_default = m->cfg.dtype == DN_BF16 ? 0 : 1;
+  m->tf.fold_W = fold_W; m->tf.fold_b = fold_b; m->tf.fold_Wkb = nullptr;
+  m->tf.fold_default = m->cfg.dtype == DN_BF16 ? FOLD_OFF : FOLD_ROUTED;
+  return DN_OK;
+}
+
+extern "C" int dn_vae_set_ffn_fold_kblocked(DnVae* m, const void* fold_Wkb) {
+  DN_CHECK_ARG(m && (!fold_Wkb || (m->tf.fold_W && dn::dn_is16(m->cfg.dtype))) && ((uintptr_t)fold_Wkb & 127) == 0,
+               "dn_vae_set_ffn_fold_kblocked: null engine, no folded weights attached, not a 2-byte arithmetic, or fold_Wkb not 128-byte aligned");
+  m->tf.fold_Wkb = fold_Wkb;
   return DN_OK;
 }
 

@@ -856,18 +856,26 @@ constexpr int ROWB2 = 64;
 // split norm's producer) do not run on it.
 // HALO (TAPS, three taps with shifts 2d, d, 0): as on the 256 x 352 tile, the taps share one staged copy of the tile's rows plus
 // the H = 16 * ceil(2d / 16) rows in front of them (decided per tile and, with shifts scaled by the group, per group: 2d <= 128).
+// BNB = 128 (TAPS and HALO, 2-byte types, RESADD: DN_TILE_256X128_SR): the shared-row form on 128 columns, for a long three-tap
+// contraction too narrow to fill the chip with 256-column tiles (the folded FFN: N = 512).  Eight waves as 4 x 2 of 64 x 64 (the
+// layout of the wider forms at half the columns): 8 fragment reads per 16 MFMAs, against 10 for 8 x 1 waves of 32 x 128, and the
+// epilogue's 64 x 64 slabs and 64-aligned wave columns (the split norm's producer) as they are.  A weight K-tile is 8 KiB, one
+// 16-row piece per wave; per 64-byte K-chunk the workgroup stages 256 x 64 B of rows once and 3 x 128 x 64 B of weights = 40 KiB
+// per 3 x 512 matrix cycles (26 B/cycle per CU, under the ~30 of the fill path; three shifted copies would be 36).  LDS: a 4-slot
+// weight ring of 32 KiB and the two 24 KiB row slots, 80 KiB; the epilogue's eight slabs (136 KiB) set the allocation.
 template <typename E, int EPI, bool TAPS, int BNB = 256, bool HALO = false>
 __global__ __launch_bounds__(512, 1) void conv_gemm_big_kernel(const DnGemmParams p) {
-  static_assert(!HALO || (TAPS && BNB == 256 && !std::is_same<E, BF16X3>::value), "shared staging: tap-inner order on the 256 x 256 tile");
+  static_assert(!HALO || (TAPS && (BNB == 256 || BNB == 128) && !std::is_same<E, BF16X3>::value), "shared staging: tap-inner order on the 256 x 256 and 256 x 128 tiles");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   if constexpr (std::is_same<E, F16>::value) f16_saturate();  // stores of a value beyond 65504 clamp instead of becoming inf
   constexpr int ES = Elem<E>::bytes;
   constexpr int KT = ROWB2 / ES;
-  static_assert(BNB == 256 || BNB == 192, "tile width");
+  static_assert(BNB == 256 || BNB == 192 || BNB == 128, "tile width");
   constexpr int BMB = 256, STAGES = 4;
   constexpr int TILE = BNB * ROWB2;               // the weight tile (16 KiB at 256 columns); the row tile follows it
   constexpr int STAGE_BYTES = TILE + 256 * ROWB2;
-  constexpr int PER_STAGE = 4;                    // DMA pieces per wave per stage (2 W + 2 A, 16 rows each) ...
+  constexpr int WPW = BNB == 128 ? 1 : 2;         // weight pieces (16 rows each) per wave per stage: 128 columns are one piece for each of the 8 waves
+  constexpr int PER_STAGE = WPW + 2;              // DMA pieces per wave per stage (WPW W + 2 A, 16 rows each) ...
   constexpr int PER_LATE = BNB == 256 ? 4 : 3;    // ... waves 4-7 of the 192-column tile: 1 W + 2 A
   constexpr int NTW = BNB / 32;                   // 16-column accumulator tiles per wave
 
@@ -900,7 +908,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_big_kernel(const DnGemmParam
     m = m < p.M ? m : p.M - 1;
     a_row[i] = m;
     a_t[i] = m % p.T;
-    int n = n0 + (BNB == 256 || wave < 4 ? wave * 32 + i * 16 : 128 + (wave - 4) * 16) + srow;  // (192: waves 4-7 stage one piece, i = 0)
+    int n = n0 + (BNB == 128 ? wave * 16 : BNB == 256 || wave < 4 ? wave * 32 + i * 16 : 128 + (wave - 4) * 16) + srow;  // (192: waves 4-7 stage one piece, i = 0; 128: every wave)
     w_row[i] = n < w_rows ? n : w_rows - 1;
   }
   const int ktiles_per_term = p.K / KT;
@@ -974,8 +982,8 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_big_kernel(const DnGemmParam
   };
   const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lptr_t)smem);
   auto stage = [&](int slot) {
-    const bool one_w = BNB != 256 && wave >= 4;  // uniform
-    const uint32_t wbase = lds_base + slot * STAGE_BYTES + (one_w ? 8192 + (wave - 4) * 1024 : wave * 2048);
+    const bool one_w = BNB == 128 || (BNB != 256 && wave >= 4);  // uniform
+    const uint32_t wbase = lds_base + slot * STAGE_BYTES + (BNB == 128 ? wave * 1024 : one_w ? 8192 + (wave - 4) * 1024 : wave * 2048);
     const uint32_t abase = lds_base + slot * STAGE_BYTES + TILE + wave * 2048;
     if constexpr (TAPS) {
 #pragma unroll
@@ -1083,13 +1091,13 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_big_kernel(const DnGemmParam
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) glds16(w_ptr[i] + tap_woff, lds_base + t * TILE + wave * 2048 + i * 1024);
+        for (int i = 0; i < WPW; ++i) glds16(w_ptr[i] + tap_woff, lds_base + t * TILE + wave * (WPW * 1024) + i * 1024);
         tap_woff += tap_wstride;
       }
       tap_woff = 0;
 #pragma unroll
-      for (int i = 0; i < 2; ++i) w_ptr[i] += w_inc;
-      pipe_sync<4>();  // chunk 0 and the first weight tile have landed
+      for (int i = 0; i < WPW; ++i) w_ptr[i] += w_inc;
+      pipe_sync<2 * WPW>();  // chunk 0 and the first weight tile have landed (the weight tiles of K-tiles 1 and 2 may be in flight)
     }
   }
   if (!shared_rows) {
@@ -1171,13 +1179,13 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_big_kernel(const DnGemmParam
       for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const uint4*>(sa + i * 16 * ROWB2);
     }
     if constexpr (STAGE) {
-      const uint32_t wbase = lds_base + fill * TILE + wave * 2048;
+      const uint32_t wbase = lds_base + fill * TILE + wave * (WPW * 1024);
 #pragma unroll
-      for (int i = 0; i < 2; ++i) glds16(w_ptr[i] + tap_woff, wbase + i * 1024);
+      for (int i = 0; i < WPW; ++i) glds16(w_ptr[i] + tap_woff, wbase + i * 1024);
       if constexpr (TAP == 2) {
         tap_woff = 0;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) w_ptr[i] += w_inc;
+        for (int i = 0; i < WPW; ++i) w_ptr[i] += w_inc;
       } else {
         tap_woff += tap_wstride;
       }
@@ -1211,9 +1219,11 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_big_kernel(const DnGemmParam
     auto adv = [&]() { slot = slot == STAGES - 1 ? 0 : slot + 1; fill = fill == STAGES - 1 ? 0 : fill + 1; };
     const int chunks = ktiles_per_term;  // >= 2 (launch_big)
     for (int c = 0; c + 1 < chunks; ++c) {
-      ktile_h(late_c, T0{}, std::true_type{}, integral_constant<int, 6>{}, slot, fill, aslot); adv();
-      ktile_h(late_c, T1{}, std::true_type{}, integral_constant<int, 7>{}, slot, fill, aslot); adv();
-      ktile_h(late_c, T2{}, std::true_type{}, integral_constant<int, 2>{}, slot, fill, aslot); adv();
+      // what each wait leaves in flight (W = the WPW weight pieces of one K-tile): tap 0: W, W, 2 row pieces; tap 1: W, 2 row pieces, W,
+      // the halo piece; tap 2: this K-tile's W
+      ktile_h(late_c, T0{}, std::true_type{}, integral_constant<int, 2 * WPW + 2>{}, slot, fill, aslot); adv();
+      ktile_h(late_c, T1{}, std::true_type{}, integral_constant<int, 2 * WPW + 3>{}, slot, fill, aslot); adv();
+      ktile_h(late_c, T2{}, std::true_type{}, integral_constant<int, WPW>{}, slot, fill, aslot); adv();
       aslot ^= 1;
     }
     ktile_h(late_c, T0{}, std::false_type{}, integral_constant<int, 3>{}, slot, fill, aslot); adv();
@@ -1245,7 +1255,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_big_kernel(const DnGemmParam
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // slab reads done before the second half overwrites it
   };
   half(std::integral_constant<int, 0>{});
-  half(std::integral_constant<int, 1>{});
+  if constexpr (NTW > 4) half(std::integral_constant<int, 1>{});  // (128 columns: a wave's tile is the one 64 x 64 half)
 }
 
 // ------------------------------------------------------------------------------------------ 256 x 128 tile, two workgroups per CU
@@ -2326,6 +2336,15 @@ static inline bool routes_to_352(const DnGemmParams& p, int force) {
   return tiles_fat >= 100 && 1.3 * fill(tiles_fat) >= fill(tiles_big);
 }
 
+// Can this contraction run on the 256 x 128 shared-row tile (DN_TILE_256X128_SR)?  2-byte types, RESADD without the whole-row
+// norm (the split norm's producer is fine), the three taps (2d, d, 0) of one causal conv in tap-inner order -- so option
+// taps_inner = 0 and DN_GEMM_TERM_OUTER keep a contraction off it, like the other tap-inner tiles -- and two K-chunks or more.
+// Row-major or K-blocked operands.  The tile runs where the caller asks for it (the tile bits of flags): the one contraction it is
+// for, the engines' folded feed-forward block, is routed by run_transformer (engine.hip), which knows what else shares the chip.
+static inline bool sr_tile_ok(const DnGemmParams& p, bool taps) {
+  return dn_is16(p.dtype) && p.epilogue == DN_EPI_RESADD && !(p.norm_out && !p.norm_split) && taps && big_taps_share_rows(p, 32);
+}
+
 // The tile variant a contraction runs on (DN_TILE_*); -1 = K-blocked operands with a tile forced that does not take them.
 // force: forced_tile(p); taps: terms_are_taps(p).
 static inline int choose_tile(const DnGemmParams& p, int force, bool taps) {
@@ -2369,6 +2388,7 @@ static inline int choose_tile(const DnGemmParams& p, int force, bool taps) {
     return sm > ss ? DN_TILE_256X128 : DN_TILE_128X128;
   }
   if (routes_to_352(p, force)) return DN_TILE_256X352;
+  if (force == DN_TILE_256X128_SR && sr_tile_ok(p, taps)) return DN_TILE_256X128_SR;
   // DN_TAPS_INNER=2: the taps of a causal conv run on the 64-byte-K-tile kernels (tap-inner order, shared rows) WHATEVER M is, so a
   // batch and its shards sum every output in the same order -- bit-for-bit sharding invariance at the fast order's speed on
   // large batches (small ones pay for 256-row tiles); the sharded driver's default (normalize.py).
@@ -2471,11 +2491,12 @@ static inline Route route(const DnGemmParams& p) {
   const bool conv_epi = p.epilogue == DN_EPI_BIAS || p.epilogue == DN_EPI_FILM_GATE;
   const bool big = r.tile == DN_TILE_256X256 && conv_epi && p.dtype != DN_BF16X3;
   const bool fat = r.tile == DN_TILE_256X352 || r.tile == DN_TILE_256X256_W4 || r.tile == DN_TILE_256X256_W8;
-  r.taps_inner = taps && (big || fat);
-  r.shared_rows = r.taps_inner && (big ? big_taps_share_rows(p, ROWB2 / (dn_is16(p.dtype) ? 2 : 4))
-                                       : r.tile == DN_TILE_256X352 && p.epilogue == DN_EPI_BIAS && taps_share_rows(p));
+  const bool sr = r.tile == DN_TILE_256X128_SR;  // (choose_tile: only for taps that can share their rows)
+  r.taps_inner = taps && (big || fat || sr);
+  r.shared_rows = r.taps_inner && (sr || (big ? big_taps_share_rows(p, ROWB2 / (dn_is16(p.dtype) ? 2 : 4))
+                                              : r.tile == DN_TILE_256X352 && p.epilogue == DN_EPI_BIAS && taps_share_rows(p)));
   const int forced_band = (p.flags >> DN_GEMM_BAND_SHIFT) & 0xff;  // a band forced by the caller (tests)
-  const bool banded = (r.tile >= DN_TILE_128X128 && r.tile <= DN_TILE_256X256) || r.tile == DN_TILE_256X128_2WG;
+  const bool banded = (r.tile >= DN_TILE_128X128 && r.tile <= DN_TILE_256X256) || r.tile == DN_TILE_256X128_2WG || sr;
   r.band = banded && forced_band == 0 ? choose_band(p, r.tile) : forced_band;
   return r;
 }
@@ -2520,6 +2541,15 @@ static int launch_big(const DnGemmParams& p, const Route& r, hipStream_t s) {
     if (r.taps_inner) return launch_kernel<conv_gemm_big_kernel<E, EPI, true>>(p, grid, 512, lds, s);
   }
   return launch_kernel<conv_gemm_big_kernel<E, EPI, false, BNB>>(p, grid, 512, lds, s);
+}
+
+// The 256 x 128 shared-row form of the same kernel (route(): taps-inner, shared rows)
+template <typename E, int EPI>
+static int launch_sr(const DnGemmParams& p, hipStream_t s) {
+  constexpr int ring = 4 * 128 * ROWB2 + 2 * (256 + 128) * ROWB2, unshared = 4 * (128 + 256) * ROWB2, slabs = 8 * 64 * EP_LD * 4;
+  constexpr int lds = slabs > ring && slabs > unshared ? slabs : ring > unshared ? ring : unshared;
+  const dim3 grid(((p.M + 255) / 256) * ((p.N + 127) / 128), p.groups);
+  return launch_kernel<conv_gemm_big_kernel<E, EPI, true, 128, true>>(p, grid, 512, lds, s);
 }
 
 template <typename E, int EPI>
@@ -2577,6 +2607,9 @@ static int launch(const DnGemmParams& p0, hipStream_t s) {
       break;
     case DN_TILE_256X128_2WG:
       if constexpr (half && EPI != DN_EPI_RESADD && EPI != DN_EPI_POSEMB) return launch_mid2<E, EPI>(p, s);
+      break;
+    case DN_TILE_256X128_SR:
+      if constexpr (half && EPI == DN_EPI_RESADD) return launch_sr<E, EPI>(p, s);
       break;
     case DN_TILE_256X256_W4:  // (the forced-only hand-scheduled 256 x 256 forms: kept for bf16)
       if constexpr (std::is_same<E, BF16>::value) return launch_fat<E, EPI, 8>(p, r, s);

@@ -97,6 +97,7 @@ struct FoldArgs {
   int64_t conv_W_ls, conv_b_ls, out_W_ls, out_b_ls;  // elements between the layers' sources
   int dim, inner, ip, in_n, Dp, Dn;
   void* W;   // [depth][3][Dn][ip] in the operand format
+  void* Wkb; // [depth][3][ip/32][Dn][32], 2-byte types, or NULL: the same values K-blocked (packing.kblock's layout)
   float* b;  // [depth][Dp]
 };
 
@@ -128,6 +129,9 @@ __global__ __launch_bounds__(64) void ffn_fold_w_kernel(FoldArgs a) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = (n0 + r < a.dim && c + i < a.inner) ? acc[r][i] : 0.f;
     store8<DT>(a.W, (((int64_t)blockIdx.z * a.Dn) + n0 + r) * a.ip + c, make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]));
+    if constexpr (DT == DN_BF16 || DT == DN_F16) {  // the lane's 8 columns lie inside one 32-column block
+      if (a.Wkb) store8<DT>(a.Wkb, ((((int64_t)blockIdx.z * (a.ip / 32)) + (c >> 5)) * a.Dn + n0 + r) * 32 + (c & 31), make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]));
+    }
   }
 }
 
@@ -167,16 +171,26 @@ extern "C" int dn_repack_weights(const float* master, const DnRepackDesc* descs,
 extern "C" int dn_ffn_fold(const float* conv_W, const float* conv_b, const float* out_W, const float* out_b, int64_t conv_W_stride,
                            int64_t conv_b_stride, int64_t out_W_stride, int64_t out_b_stride, int32_t depth, int32_t dim, int32_t inner,
                            int32_t dtype, void* fold_W, float* fold_b, void* stream) {
+  return dn_ffn_fold_kblocked(conv_W, conv_b, out_W, out_b, conv_W_stride, conv_b_stride, out_W_stride, out_b_stride, depth, dim, inner, dtype,
+                              fold_W, fold_b, nullptr, stream);
+}
+
+// see include/diffnorm_hip.h
+extern "C" int dn_ffn_fold_kblocked(const float* conv_W, const float* conv_b, const float* out_W, const float* out_b, int64_t conv_W_stride,
+                                    int64_t conv_b_stride, int64_t out_W_stride, int64_t out_b_stride, int32_t depth, int32_t dim,
+                                    int32_t inner, int32_t dtype, void* fold_W, float* fold_b, void* fold_Wkb, void* stream) {
   DN_CHECK_ARG(conv_W && conv_b && out_W && out_b && fold_W && fold_b, "dn_ffn_fold: null argument");
   DN_CHECK_ARG(depth >= 1 && 3 * depth <= 65535 && dim >= 1 && inner >= 1, "dn_ffn_fold: depth=%d dim=%d inner=%d", depth, dim, inner);
   DN_CHECK_ARG(dtype == DN_F32 || dtype == DN_BF16 || dtype == DN_BF16X3 || dtype == DN_F16, "dn_ffn_fold: dtype=%d", dtype);
   DN_CHECK_ARG((conv_W_stride | out_W_stride) % 4 == 0 && (((uintptr_t)conv_W | (uintptr_t)out_W) & 15) == 0 && ((uintptr_t)fold_W & 127) == 0,
                "dn_ffn_fold: the weight sources must be 16-byte aligned (strides multiples of 4), the folded weights 128-byte aligned");
+  DN_CHECK_ARG(!fold_Wkb || ((dtype == DN_BF16 || dtype == DN_F16) && ((uintptr_t)fold_Wkb & 127) == 0),
+               "dn_ffn_fold_kblocked: the K-blocked copy is for DN_BF16 / DN_F16 (dtype=%d), 128-byte aligned", dtype);
   dn::FoldArgs a;
   a.conv_W = conv_W; a.conv_b = conv_b; a.out_W = out_W; a.out_b = out_b;
   a.conv_W_ls = conv_W_stride; a.conv_b_ls = conv_b_stride; a.out_W_ls = out_W_stride; a.out_b_ls = out_b_stride;
   a.dim = dim; a.inner = inner; a.ip = (inner + 63) / 64 * 64; a.in_n = (inner + 127) / 128 * 128; a.Dp = (dim + 63) / 64 * 64; a.Dn = (dim + 127) / 128 * 128;
-  a.W = fold_W; a.b = fold_b;
+  a.W = fold_W; a.b = fold_b; a.Wkb = fold_Wkb;
   const dim3 grid((a.ip / 8 + 63) / 64, a.Dn / 4, 3 * depth), block(64);
   hipStream_t s = (hipStream_t)stream;
   if (dtype == DN_F32) hipLaunchKernelGGL(dn::ffn_fold_w_kernel<DN_F32>, grid, block, 0, s, a);

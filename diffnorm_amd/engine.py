@@ -147,9 +147,14 @@ class _Engine:
     # ---- the folded feed-forward weights (dn_ffn_fold), kept beside the packed table
     fold_W: Optional[torch.Tensor] = None
     fold_b: Optional[torch.Tensor] = None
+    fold_Wkb: Optional[torch.Tensor] = None  # fold_W K-blocked (2-byte arithmetics): same sums, same bits, written by the same launch
 
     def _tf_dims(self):
         """(dim, depth) of the engine's transformer and the C entry that attaches its folded weights."""
+        raise NotImplementedError
+
+    def _attach_kblocked(self):
+        """The C entry that attaches fold_Wkb."""
         raise NotImplementedError
 
     def _fold_call(self, srcs, strides, depth, layer0):
@@ -157,8 +162,9 @@ class _Engine:
         inner = int(dim * 4 * 2 / 3)
         (_, _), b_shape = packing.ffn_fold_storage(dim, 1, self.dtype)
         w_off = layer0 * self.fold_W[0].numel() * self.fold_W.element_size()
-        _lib.check(self.lib.dn_ffn_fold(*srcs, *strides, depth, dim, inner, self.dtype, self.fold_W.data_ptr() + w_off,
-                                        self.fold_b.data_ptr() + layer0 * b_shape[1] * 4, _lib.current_stream()), "dn_ffn_fold")
+        kb = None if self.fold_Wkb is None else self.fold_Wkb.data_ptr() + w_off  # (the two copies have the same bytes per layer)
+        _lib.check(self.lib.dn_ffn_fold_kblocked(*srcs, *strides, depth, dim, inner, self.dtype, self.fold_W.data_ptr() + w_off,
+                                                 self.fold_b.data_ptr() + layer0 * b_shape[1] * 4, kb, _lib.current_stream()), "dn_ffn_fold")
 
     def _fold_from_state_dict(self, tf_layers, sd):
         """Allocates the folded buffers, forms them layer by layer from the state dict's packed fp32 tensors and attaches them."""
@@ -167,10 +173,14 @@ class _Engine:
         with torch.cuda.device(self.device):
             self.fold_W = torch.empty(w_shape, dtype=w_dtype, device=self.device)
             self.fold_b = torch.empty(b_shape, dtype=torch.float32, device=self.device)
+            if self.dtype in (_lib.DN_BF16, _lib.DN_F16):  # [depth][3][padk(inner)/32][padn(dim)][32]
+                self.fold_Wkb = torch.empty((w_shape[0], 3, w_shape[3] // 32, w_shape[2], 32), dtype=w_dtype, device=self.device)
             for l, layer in enumerate(tf_layers):
                 srcs = [t.to(self.device) for t in packing.ffn_fold_sources(layer, sd)]
                 self._fold_call([t.data_ptr() for t in srcs], (0, 0, 0, 0), 1, l)
         _lib.check(attach(self.handle, self.fold_W.data_ptr(), self.fold_b.data_ptr()), "set_ffn_fold")
+        if self.fold_Wkb is not None:
+            _lib.check(self._attach_kblocked()(self.handle, self.fold_Wkb.data_ptr()), "set_ffn_fold_kblocked")
 
     def _fold_from_flat(self, train_engine, master):
         """The same entry on a training engine's flat fp32 buffer (master or EMA), after its repack: same sources, same bits."""
@@ -182,7 +192,7 @@ class _Engine:
             self._fold_call([master.data_ptr() + 4 * o for o in offs], strides, depth, 0)
 
     def fold_bytes(self) -> int:
-        return 0 if self.fold_W is None else sum(t.numel() * t.element_size() for t in (self.fold_W, self.fold_b))
+        return 0 if self.fold_W is None else sum(t.numel() * t.element_size() for t in (self.fold_W, self.fold_b, self.fold_Wkb) if t is not None)
 
     def refresh_bytes(self) -> int:
         """Bytes the last refresh_from's layout reads from the master plus writes to the packed tensors (0 before the first)."""
@@ -207,6 +217,9 @@ class EpsEngine(_Engine):
 
     def _tf_dims(self):
         return self.cfg.dim, self.cfg.depth, self.lib.dn_eps_set_ffn_fold
+
+    def _attach_kblocked(self):
+        return self.lib.dn_eps_set_ffn_fold_kblocked
 
     def __del__(self):
         if getattr(self, "handle", None) and self.handle.value:
@@ -640,6 +653,9 @@ class VaeEngine(_Engine):
 
     def _tf_dims(self):
         return self._tf[0], self._tf[1], self.lib.dn_vae_set_ffn_fold
+
+    def _attach_kblocked(self):
+        return self.lib.dn_vae_set_ffn_fold_kblocked
 
     def __del__(self):
         if getattr(self, "handle", None) and self.handle.value:

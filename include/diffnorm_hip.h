@@ -90,7 +90,8 @@ typedef struct {
  * L2 -> LDS fill rate, tools/dma_issue_cost.hip) and a causal shift is a plain row offset.  rows = M for A and for
  * out, Np for W.  K-blocked A / W are taken by the 256 x 352 tile and, where the shape does not route there, by the
  * 256 x 256 tile (the contraction then runs on that tile whatever the shape heuristic would have chosen; forcing
- * another tile is DN_EINVAL); dn_conv_gemm_kblocked_ok tells whether the shape routes to the 256 x 352 tile, where the
+ * another tile is DN_EINVAL, except DN_TILE_256X192, DN_TILE_256X128_2WG and DN_TILE_256X128_SR where they
+ * apply); dn_conv_gemm_kblocked_ok tells whether the shape routes to the 256 x 352 tile, where the
  * layout pays.  The GEGLU epilogue can emit K-blocked output (out_layout) on every tile.                          */
 enum { DN_LAYOUT_A_KBLOCKED = 1, DN_LAYOUT_W_KBLOCKED = 2, DN_LAYOUT_OUT_KBLOCKED = 1 };
 
@@ -181,7 +182,10 @@ enum {
   DN_TILE_256X256_W4 = 6,   /* forced only, bf16: the hand-scheduled 256 x 256 form, one wave per SIMD                 */
   DN_TILE_256X256_W8 = 7,   /* forced only, bf16: the same with two waves per SIMD                                     */
   DN_TILE_256X192 = 8,      /* the 256 x 256 kernel on 192 columns: widths a multiple of 192 but ragged on 256         */
-  DN_TILE_256X128_2WG = 9   /* forced only, 2-byte types: 256 x 128 with two workgroups per CU                         */
+  DN_TILE_256X128_2WG = 9,  /* forced only, 2-byte types: 256 x 128 with two workgroups per CU                         */
+  DN_TILE_256X128_SR = 10   /* forced only, 2-byte types, RESADD, three taps (2d, d, 0): the 256 x 256 kernel on 128 columns,
+                               taps innermost in K sharing one staged copy of their rows; takes K-blocked operands. The
+                               engines force it for their folded feed-forward contraction (option "ffn_fold")            */
 };
 
 int dn_conv_gemm(const DnGemmParams* p, void* stream);
@@ -189,7 +193,7 @@ int dn_conv_gemm(const DnGemmParams* p, void* stream);
 /* How dn_conv_gemm runs a contraction; reads the params and the run-time options only.                                */
 typedef struct {
   int32_t tile;        /* DN_TILE_*; -1 = K-blocked operands with a tile forced that does not take them (dn_conv_gemm: DN_EINVAL) */
-  int32_t taps_inner;  /* 1: the taps of a causal conv run innermost in K (tiles 3, 4, 6, 7); 0: term-outer                 */
+  int32_t taps_inner;  /* 1: the taps of a causal conv run innermost in K (tiles 3, 4, 6, 7, 10); 0: term-outer             */
   int32_t shared_rows; /* 1: the taps share one staged copy of the activation rows                                         */
   int32_t band;        /* row-tile band of the tile order (0 / 1 = column tiles fastest)                                   */
 } DnGemmRoute;
@@ -541,6 +545,12 @@ int dn_repack_weights(const float* master, const DnRepackDesc* descs, int32_t n,
 int dn_ffn_fold(const float* conv_W, const float* conv_b, const float* out_W, const float* out_b, int64_t conv_W_stride,
                 int64_t conv_b_stride, int64_t out_W_stride, int64_t out_b_stride, int32_t depth, int32_t dim, int32_t inner,
                 int32_t dtype, void* fold_W, float* fold_b, void* stream);
+/* The same, and from the same fp32 sums a second copy of the weights in the K-blocked layout, fold_Wkb
+ * [depth][3][padk(inner)/32][padn(dim)][32] (DN_BF16 / DN_F16 only, 128-byte aligned): every element is rounded once and stored
+ * twice, so the two copies hold the same bits, refreshed or fresh.  fold_Wkb NULL: dn_ffn_fold.                                 */
+int dn_ffn_fold_kblocked(const float* conv_W, const float* conv_b, const float* out_W, const float* out_b, int64_t conv_W_stride,
+                         int64_t conv_b_stride, int64_t out_W_stride, int64_t out_b_stride, int32_t depth, int32_t dim, int32_t inner,
+                         int32_t dtype, void* fold_W, float* fold_b, void* fold_Wkb, void* stream);
 
 /* The operand transpose of the training engines' weight gradient (autograd of CausalConv1d / nn.Linear, latent_module.py:476-485):
  * dst[j / chunk][row0 + c][j % chunk] = src[b * T + t, c] with j = b * Tp + front + t, zero for pad frames, channels >= C and the tail
@@ -650,10 +660,15 @@ int dn_eps_weights_changed(DnEps* m);
  * the conv's [M, padk(inner)] buffer leaves the workspace plan.  Captured steps are dropped.  After the packed weights were
  * rewritten, dn_ffn_fold into the same buffers refreshes them: the addresses stay attached.                                      */
 int dn_eps_set_ffn_fold(DnEps* m, const void* fold_W, const float* fold_b);
+/* Attaches dn_ffn_fold_kblocked's K-blocked copy (NULL detaches; dn_eps_set_ffn_fold detaches it too, so attach it after).  Where
+ * the folded contraction runs on DN_TILE_256X128_SR (option "ffn_fold") the GEGLU projection then writes its output K-blocked and
+ * the contraction stages whole cache lines of both operands; without the copy that tile reads row-major operands.              */
+int dn_eps_set_ffn_fold_kblocked(DnEps* m, const void* fold_Wkb);
 
 int dn_vae_create(const DnVaeConfig* cfg, const void* const* weights, int32_t n_weights, DnVae** out);
 void dn_vae_destroy(DnVae* m);
 int dn_vae_set_ffn_fold(DnVae* m, const void* fold_W, const float* fold_b); /* as dn_eps_set_ffn_fold, the decoder's transformer */
+int dn_vae_set_ffn_fold_kblocked(DnVae* m, const void* fold_Wkb);           /* as dn_eps_set_ffn_fold_kblocked                    */
 size_t dn_vae_workspace_bytes(const DnVae* m, int32_t B, int32_t T);
 /* encoder WaveNets of encode_feature (latent_module.py:1099-1106): feat fp32 [B,T,dim] -> params fp32 [B,T,2z] */
 int dn_vae_encode_params(DnVae* m, const float* feat, int32_t B, int32_t T, float* params, void* workspace,
@@ -1001,8 +1016,9 @@ int dn_version(void);
  * K-blocked operands), "wgrad_stream", "wgrad_tn", "wgrad_groups" (DN_WGRAD_*: A/B switches of the weight-gradient path),
  * "wgrad_tn_x3" (DN_WGRAD_TN_X3: DN_BF16X3 weight gradients from the row-major split rows; "wgrad_tn" is the 2-byte modes only),
  * "ffn_fold" (DN_FFN_FOLD: sampling engines with folded weights attached -- 0 the FFN's causal conv and output projection as two
- * contractions, 1 [default; DN_BF16 engines default to 0] one folded contraction on the routed tile, 2 / 3 the same forced to the 256 x 128 / 256 x 256
- * tile; like every option it is part of the captured-step cache keys through the option generation).
+ * contractions [the default of DN_BF16 engines]; one folded contraction: 5 [the default otherwise] on the tile run_transformer's
+ * route rule picks, 1 on the tile the route table chooses (term-outer; 128 x 128 at [32,512]), 2 / 3 / 4 forced to the 256 x 128 / 256 x 256 / 256 x 128 shared-row
+ * tile (4 where that tile applies: 2-byte types, split norm, "taps_inner" not 0); like every option it is part of the captured-step cache keys through the option generation).
  * "nar_cg_fold" (DN_NAR_CG_FOLD: the guided NAR decoder pass -- 1 [default] the null half's encoder attention as the addition of
  * the constant row c_l, 0 evaluated literally; it changes the option generation like every option).
  * dn_get_option: *is_set = 0 when the option is neither set nor in the environment (the library's built-in choice applies). */
