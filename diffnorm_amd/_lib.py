@@ -126,7 +126,8 @@ class ConformerEncConfig(C.Structure):
 
 class HubertConfig(C.Structure):
     _fields_ = [("n_conv", C.c_int32), ("conv_dim", C.c_int32), ("conv_kernel", C.c_int32 * 8), ("conv_stride", C.c_int32 * 8)] + \
-               [(n, C.c_int32) for n in ("dim", "ffn", "layers", "heads", "conv_pos", "conv_pos_groups", "dtype", "has_proj")]
+               [(n, C.c_int32) for n in ("dim", "ffn", "layers", "heads", "conv_pos", "conv_pos_groups", "dtype", "has_proj", "wave_norm", "extractor_ln",
+                                           "conv_bias", "pre_norm", "vocab")]
 
 
 class FbankConfig(C.Structure):
@@ -360,6 +361,8 @@ SYMBOLS = {
     "dn_hubert_forward": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "dn_hubert_set_profile": (C.c_int, [_vp, _i32]),
     "dn_hubert_stage_times": (C.c_int, [_vp, C.POINTER(C.c_float), _i32]),
+    "dn_hubert_ctc_forward": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "dn_ctc_greedy": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "dn_fbank_tables": (C.c_int, [C.POINTER(FbankConfig), _vp, _vp]),
     "dn_fbank_twiddles": (C.c_int, [_i32, _vp]),
     "dn_fbank_create": (C.c_int, [_vp, _vp, _i32, _vp]),

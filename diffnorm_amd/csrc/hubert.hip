@@ -12,6 +12,12 @@
 //                                   gather of layer i + 1 (as the subsampler's GLU is), the last one by gelu_rows_kernel
 //   positional conv                 dn_grouped_conv1d below
 //   layers                          dn_conv_gemm / dn_attention launches, nar_common.h's LayerNorm
+// The large form (wav2vec 2.0 / HuBERT large, and the Wav2VecCtc recognisers of the recipe's ASR-BLEU, research/TranSpeech/asr_bleu/
+// utils.py:221-308) is the same pass with DnHubertConfig's appended fields set:
+//   wave_norm                       wave_stats_kernel / wave_combine_kernel; applied by stage_wave
+//   extractor_ln (+ conv_bias)      conv0_ln_kernel; layers 1..: the same contraction with the bias, then ln_gelu_rows_kernel
+//   pre_norm                        the second layer loop of hubert_pass
+//   vocab                           dn_hubert_ctc_forward: encoder.layer_norm, the fp32 head, emit_rows_kernel; dn_ctc_greedy decodes
 #include <new>
 
 #include "common.h"
@@ -48,9 +54,17 @@ __global__ void hubert_lengths_kernel(const int32_t* __restrict__ lengths, int B
 
 // The samples of a frame tile in LDS: ws[i] = wave[b][t0 * s + i], zeros at and behind the utterance's own length (whatever the
 // caller left there never reaches a valid frame, not even through a zero weight)
-__device__ __forceinline__ void stage_wave(float* ws, const float* __restrict__ wave, int64_t L, int b, int len, int t0, int s) {
+// wstat (wave_norm): the utterance's (mean hi, mean lo, rstd) of wave_combine_kernel; the staged sample is then the normalised one,
+// so no normalised copy of the waveform exists anywhere
+__device__ __forceinline__ void stage_wave(float* ws, const float* __restrict__ wave, int64_t L, int b, int len, int t0, int s,
+                                           const float4* __restrict__ wstat = nullptr) {
   const int n = C0_TF * s + C0_KMAX;
   const int64_t base = (int64_t)t0 * s;
+  if (wstat) {
+    const float4 st = wstat[b];
+    for (int i = threadIdx.x; i < n; i += 256) ws[i] = base + i < len ? ((wave[(int64_t)b * L + base + i] - st.x) - st.y) * st.z : 0.f;
+    return;
+  }
   for (int i = threadIdx.x; i < n; i += 256) ws[i] = base + i < len ? wave[(int64_t)b * L + base + i] : 0.f;
 }
 __device__ __forceinline__ float conv0_at(const float* ws, const float (&w)[C0_KMAX]) {
@@ -172,6 +186,212 @@ __global__ __launch_bounds__(256) void masked_copy_kernel(const float* __restric
   }
 }
 
+// ---- wave_norm: F.layer_norm(wave, wave.shape) of one utterance over its own samples (eps 1e-5, biased variance), taken as the
+// GroupNorm pass above takes its statistics: per tile the mean, then the squared deviations FROM THAT MEAN (no E[x^2] - mean^2), the
+// tiles combined in tile order.  The tile sums run in double (a fixed tree over the block), so a constant waveform has deviation 0.
+constexpr int WN_PER = 16, WN_TILE = 256 * WN_PER;  // samples per thread / per tile
+__device__ __forceinline__ double block_sum256(double v, double* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  const double r = red[0];
+  __syncthreads();
+  return r;
+}
+// part[b][tile] = (mean hi, mean lo, M2, 0) of the tile's valid samples
+__global__ __launch_bounds__(256) void wave_stats_kernel(const float* __restrict__ wave, const int32_t* __restrict__ lengths, int L, float4* __restrict__ part) {
+  __shared__ double red[256];
+  const int tile = blockIdx.x, b = blockIdx.y, len = lengths[b] < L ? lengths[b] : L;
+  int n = len - tile * WN_TILE;
+  n = n < 0 ? 0 : n > WN_TILE ? WN_TILE : n;
+  const float* w = wave + (int64_t)b * L + (int64_t)tile * WN_TILE;
+  float x[WN_PER];
+  double sum = 0;
+#pragma unroll
+  for (int k = 0; k < WN_PER; ++k) {
+    const int i = threadIdx.x + 256 * k;
+    x[k] = i < n ? w[i] : 0.f;
+    sum += (double)x[k];
+  }
+  const double mean = n ? block_sum256(sum, red) / n : 0.0;
+  const float mh = (float)mean, ml = (float)(mean - (double)mh);
+  double q = 0;
+#pragma unroll
+  for (int k = 0; k < WN_PER; ++k)
+    if ((int)threadIdx.x + 256 * k < n) {
+      const float d = (x[k] - mh) - ml;
+      q += (double)d * d;
+    }
+  const double m2 = block_sum256(q, red);
+  if (threadIdx.x == 0) part[(int64_t)b * gridDim.x + tile] = make_float4(mh, ml, (float)m2, 0.f);
+}
+// wstat[b] = (mean hi, mean lo, rstd, 0): Chan et al. over the tiles in order, in double
+__global__ void wave_combine_kernel(const float4* __restrict__ part, const int32_t* __restrict__ lengths, int B, int L, int tiles, float4* __restrict__ wstat) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int len = lengths[b] < L ? lengths[b] : L;
+  double n = 0, mean = 0, m2 = 0;
+  for (int t = 0; t < tiles; ++t) {
+    int nb = len - t * WN_TILE;
+    if (nb <= 0) break;
+    nb = nb > WN_TILE ? WN_TILE : nb;
+    const float4 p = part[(int64_t)b * tiles + t];
+    const double d = ((double)p.x + (double)p.y) - mean, tot = n + nb;
+    mean += d * nb / tot;
+    m2 += (double)p.z + d * d * n * nb / tot;
+    n = tot;
+  }
+  float4 o = make_float4(0, 0, 0, 0);
+  if (n > 0) {
+    o.x = (float)mean;
+    o.y = (float)(mean - (double)o.x);
+    o.z = (float)(1.0 / sqrt(m2 / n + 1e-5));
+  }
+  wstat[b] = o;
+}
+
+// ---- extractor_mode "layer_norm" (wav2vec2.py:849-859): Conv1d + bias -> Fp32LayerNorm over the C channels of each frame -> GELU.
+// Layer 0 in one kernel: a wave per frame, lane -> channels lane + 64 i; the taps [16][C] and the tile's (normalised) samples lie in
+// LDS; the norm is row-wise, so there are no cross-tile statistics.  C <= C0_LN_CMAX.
+constexpr int C0_LN_CMAX = 512, C0_LN_NC = C0_LN_CMAX / 64;
+__global__ __launch_bounds__(256) void conv0_ln_kernel(const float* __restrict__ wave, const int32_t* __restrict__ lengths, int L, int T1, int C, int s,
+                                                       const float* __restrict__ w0, const float* __restrict__ bias, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, const float4* __restrict__ wstat, void* __restrict__ y, int dtype) {
+  __shared__ float ws[C0_TF * C0_SMAX + C0_KMAX];
+  __shared__ float wl[C0_KMAX * C0_LN_CMAX];
+  const int b = blockIdx.y, t0 = blockIdx.x * C0_TF;
+  const int nf = T1 - t0 < C0_TF ? T1 - t0 : C0_TF;
+  stage_wave(ws, wave, L, b, lengths[b] < L ? lengths[b] : L, t0, s, wstat);
+  for (int i = threadIdx.x; i < C0_KMAX * C; i += 256) wl[i] = w0[i];
+  __syncthreads();
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, nc = C / 64;
+  float bi[C0_LN_NC], g[C0_LN_NC], be[C0_LN_NC];
+#pragma unroll
+  for (int i = 0; i < C0_LN_NC; ++i) {
+    const int c = lane + 64 * i;
+    bi[i] = i < nc ? bias[c] : 0.f;
+    g[i] = i < nc ? gamma[c] : 0.f;
+    be[i] = i < nc ? beta[c] : 0.f;
+  }
+  for (int f = wv; f < nf; f += 4) {
+    float xs[C0_KMAX], a[C0_LN_NC];
+#pragma unroll
+    for (int j = 0; j < C0_KMAX; ++j) xs[j] = ws[f * s + j];
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < C0_LN_NC; ++i) {
+      a[i] = 0.f;
+      if (i < nc) {
+        float acc = bi[i];
+#pragma unroll
+        for (int j = 0; j < C0_KMAX; ++j) acc = fmaf(wl[j * C + lane + 64 * i], xs[j], acc);
+        a[i] = acc;
+        sum += acc;
+      }
+    }
+    const float mean = wave_sum(sum) / (float)C;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < C0_LN_NC; ++i)
+      if (i < nc) q = fmaf(a[i] - mean, a[i] - mean, q);
+    const float rstd = rsqrtf(wave_sum(q) / (float)C + 1e-5f);
+    const int64_t row = ((int64_t)b * T1 + t0 + f) * C;
+#pragma unroll
+    for (int i = 0; i < C0_LN_NC; ++i)
+      if (i < nc) store_act(y, row + lane + 64 * i, dtype, gelu_exact(fmaf((a[i] - mean) * rstd, g[i], be[i])));
+  }
+}
+
+// Layers 1.. of that mode: y = gelu(LayerNorm(x)) per row, x the contraction's fp32 output (bias in its epilogue) [M, C] -> out_dtype
+// (in place when out_dtype is DN_F32 and y == x: a wave holds its whole row before it stores).  nar_common.h's LayerNorm with a GELU behind it.
+__global__ __launch_bounds__(256) void ln_gelu_rows_kernel(const float* x, void* y, int out_dtype, int M, int C, const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= M) return;
+  const float* xr = x + (int64_t)row * C;
+  float4 v[4];
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int c = (i * 64 + lane) * 4;
+    v[i] = c < C ? *reinterpret_cast<const float4*>(xr + c) : make_float4(0, 0, 0, 0);
+    s += v[i].x + v[i].y + v[i].z + v[i].w;
+  }
+  const float mean = wave_sum(s) / (float)C;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int c = (i * 64 + lane) * 4;
+    if (c < C) {
+      const float a = v[i].x - mean, b = v[i].y - mean, cc = v[i].z - mean, d = v[i].w - mean;
+      q += a * a + b * b + cc * cc + d * d;
+    }
+  }
+  const float rstd = rsqrtf(wave_sum(q) / (float)C + 1e-5f);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int c = (i * 64 + lane) * 4;
+    if (c >= C) continue;
+    const float4 g = *reinterpret_cast<const float4*>(gamma + c), be = *reinterpret_cast<const float4*>(beta + c);
+    store4(y, (int64_t)row * C + c, out_dtype, gelu_exact((v[i].x - mean) * rstd * g.x + be.x), gelu_exact((v[i].y - mean) * rstd * g.y + be.y),
+           gelu_exact((v[i].z - mean) * rstd * g.z + be.z), gelu_exact((v[i].w - mean) * rstd * g.w + be.w));
+  }
+}
+
+// The CTC head's output without its pad columns: out[b][t][v] = e[b S + t][v] for t < len[b], v < V; zero rows behind
+__global__ __launch_bounds__(256) void emit_rows_kernel(const float* __restrict__ e, int ld, const int32_t* __restrict__ len, int B, int S, int V,
+                                                        float* __restrict__ out) {
+  const int64_t n = (int64_t)B * S * V;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int v = (int)(i % V);
+    const int64_t row = i / V;
+    const int t = (int)(row % S), b = (int)(row / S);
+    out[i] = t < len[b] ? e[row * ld + v] : 0.f;
+  }
+}
+
+// dn_ctc_greedy: a workgroup per utterance, 256 frames a round.  A thread takes its frame's arg-max (the first maximum: strict >),
+// the frame is kept iff it is no blank and differs from the frame before it (toks[0] carries the last frame of the round before),
+// and the kept tokens are compacted in order by a ballot prefix inside each wave and the waves' totals across the block.
+__global__ __launch_bounds__(256) void ctc_greedy_kernel(const float* __restrict__ em, const int32_t* __restrict__ lengths, int S, int V, int blank,
+                                                         int32_t* __restrict__ tokens, int32_t* __restrict__ counts) {
+  __shared__ int toks[257], wtot[4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  int len = lengths[b];
+  len = len < 0 ? 0 : len > S ? S : len;
+  const float* e = em + (int64_t)b * S * V;
+  int base = 0;
+  for (int t0 = 0; t0 < len; t0 += 256) {
+    const int t = t0 + tid;
+    int tok = -1;
+    if (t < len) {
+      const float* row = e + (int64_t)t * V;
+      float best = row[0];
+      tok = 0;
+      for (int v = 1; v < V; ++v) {
+        const float x = row[v];
+        if (x > best) { best = x; tok = v; }
+      }
+    }
+    toks[tid + 1] = tok;
+    __syncthreads();
+    const bool keep = t < len && tok != blank && (t == 0 || tok != toks[tid]);
+    const unsigned long long mask = __ballot(keep);
+    if (lane == 0) wtot[wv] = __popcll(mask);
+    __syncthreads();
+    int off = base;
+    for (int w = 0; w < wv; ++w) off += wtot[w];
+    if (keep) tokens[(int64_t)b * S + off + __popcll(mask & ((1ull << lane) - 1ull))] = tok;
+    base += wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    __syncthreads();
+    if (tid == 255) toks[0] = tok;
+  }
+  if (tid == 0) counts[b] = base;
+}
+
 // dn_grouped_conv1d.  A workgroup: GC_NF * (256 / Cg) frames of one group of one sequence; thread -> (output channel co, frame
 // slot fr), GC_NF frames fr + FR i each.  The tile's rows and the k - 1 halo rows lie in LDS once for all taps; the weights stream
 // from [g][tap][ci][co] (co fastest: one coalesced load per (tap, ci), reused for the GC_NF frames).
@@ -269,14 +489,21 @@ struct DnHubert {
   DnHubertConfig cfg;
   const float *conv0_w, *gn_g, *gn_b, *ln_g, *ln_b, *proj_b, *pos_w, *pos_b, *enc_g, *enc_b, *qkv_b, *out_b, *fc1_b, *fc2_b, *lng, *lnb, *zeros;
   const void *conv_W[DN_HUBERT_MAX_CONV], *proj_W, *qkv_W, *out_W, *fc1_W, *fc2_W;
+  const float *conv_b, *cln_g, *cln_b, *head_b;  // extractor_ln: [n_conv][C] each; vocab > 0: the CTC head
+  const void* head_W;
   hipEvent_t ev[DN_HUBERT_STAGES + 1];  // dn_hubert_set_profile: stage boundaries of the last profiled forward
   int n_ev, profile;
 };
 
 extern "C" int dn_hubert_create(const DnHubertConfig* cfg, const void* const* w, int32_t n, DnHubert** out) {
   DN_CHECK_ARG(cfg && cfg->n_conv >= 2 && cfg->n_conv <= DN_HUBERT_MAX_CONV, "dn_hubert_create: 2 .. %d conv layers", DN_HUBERT_MAX_CONV);
-  DN_TRY(check_create("dn_hubert_create", cfg, w, n, 21 + cfg->n_conv, out));
+  DN_TRY(check_create("dn_hubert_create", cfg, w, n, 21 + cfg->n_conv + (cfg->extractor_ln ? 3 : 0) + (cfg->vocab > 0 ? 2 : 0), out));
   const int C = cfg->conv_dim, dh = cfg->dim / cfg->heads;
+  DN_CHECK_ARG(!cfg->extractor_ln || C <= C0_LN_CMAX, "dn_hubert_create: extractor_ln: conv width %d (<= %d)", C, C0_LN_CMAX);
+  DN_CHECK_ARG(!cfg->extractor_ln == !cfg->pre_norm && (cfg->extractor_ln || (!cfg->conv_bias && !cfg->wave_norm)),
+               "dn_hubert_create: the large form is one form: extractor_ln and pre_norm go together, conv_bias and wave_norm only with them");
+  DN_CHECK_ARG(cfg->vocab >= 0 && cfg->vocab <= 4096 && (!cfg->vocab || cfg->pre_norm), "dn_hubert_create: vocab %d (0: no CTC head, <= 4096; the large form only)",
+               cfg->vocab);
   DN_CHECK_ARG(C > 0 && C % 64 == 0 && C <= 1024, "dn_hubert_create: conv width %d must be a multiple of 64, <= 1024", C);
   DN_CHECK_ARG(cfg->conv_kernel[0] >= 1 && cfg->conv_kernel[0] <= C0_KMAX && cfg->conv_stride[0] >= 1 && cfg->conv_stride[0] <= C0_SMAX,
                "dn_hubert_create: first conv kernel %d (<= %d), stride %d (<= %d)", cfg->conv_kernel[0], C0_KMAX, cfg->conv_stride[0], C0_SMAX);
@@ -300,6 +527,10 @@ extern "C" int dn_hubert_create(const DnHubertConfig* cfg, const void* const* w,
   m->qkv_W = t.next_mat(); m->qkv_b = t.next_vec(); m->out_W = t.next_mat(); m->out_b = t.next_vec();
   m->fc1_W = t.next_mat(); m->fc1_b = t.next_vec(); m->fc2_W = t.next_mat(); m->fc2_b = t.next_vec();
   m->lng = t.next_vec(); m->lnb = t.next_vec(); m->zeros = t.next_vec();
+  m->conv_b = m->cln_g = m->cln_b = m->head_b = nullptr;
+  m->head_W = nullptr;
+  if (cfg->extractor_ln) { m->conv_b = t.next_vec(); m->cln_g = t.next_vec(); m->cln_b = t.next_vec(); }
+  if (cfg->vocab > 0) { m->head_W = t.next_mat(); m->head_b = t.next_vec(); }
   *out = m;
   return DN_OK;
 }
@@ -344,9 +575,11 @@ extern "C" int32_t dn_hubert_out_frames(const DnHubert* m, int32_t L) {
 
 namespace {
 struct HubertBufs {
-  int T[DN_HUBERT_MAX_CONV], tiles;
+  int T[DN_HUBERT_MAX_CONV], tiles, wtiles;
   int64_t max_elems;  // the largest buffer, in elements
   float2* part; float4* stat; int32_t* len1;
+  float4 *wpart, *wstat;  // wave_norm
+  float* em;              // vocab > 0: the head's output with its pad columns [B S][vocab -> 4]
   void *y0, *cols, *xn, *qkv, *ao, *h;
   float *y, *x0, *xa, *xb, *hf;
 };
@@ -360,7 +593,8 @@ HubertBufs plan_hubert(const DnHubert* m, int B, int L, Arena& ar) {
   b.tiles = (b.T[0] + C0_TF - 1) / C0_TF;
   size_t cols = 0;
   for (int i = 1; i < c.n_conv; ++i) cols = std::max(cols, (size_t)b.T[i] * c.conv_kernel[i] * C);
-  b.max_elems = (int64_t)B * std::max<int64_t>({(int64_t)b.T[0] * C, (int64_t)cols, (int64_t)S * c.ffn, (int64_t)S * 3 * D});
+  b.max_elems = (int64_t)B * std::max<int64_t>({(int64_t)b.T[0] * C, (int64_t)cols, (int64_t)S * c.ffn, (int64_t)S * 3 * D,
+                                                      (int64_t)S * round_up(c.vocab, 4)});
   b.part = (float2*)ar.take((size_t)B * b.tiles * C * sizeof(float2));
   b.stat = (float4*)ar.take((size_t)B * C * sizeof(float4));
   b.len1 = (int32_t*)ar.take((size_t)B * sizeof(int32_t));
@@ -375,6 +609,14 @@ HubertBufs plan_hubert(const DnHubert* m, int B, int L, Arena& ar) {
   b.ao = ar.take((size_t)B * S * D * es);
   b.hf = (float*)ar.take((size_t)B * S * c.ffn * 4);
   b.h = ar.take((size_t)B * S * c.ffn * es);
+  b.wtiles = (L + WN_TILE - 1) / WN_TILE;
+  b.wpart = b.wstat = nullptr;
+  b.em = nullptr;
+  if (c.wave_norm) {
+    b.wpart = (float4*)ar.take((size_t)B * b.wtiles * sizeof(float4));
+    b.wstat = (float4*)ar.take((size_t)B * sizeof(float4));
+  }
+  if (c.vocab > 0) b.em = (float*)ar.take((size_t)B * S * round_up(c.vocab, 4) * 4);
   return b;
 }
 }  // namespace
@@ -386,19 +628,22 @@ extern "C" size_t dn_hubert_workspace_bytes(const DnHubert* m, int32_t B, int32_
   return a.off + 512;
 }
 
-extern "C" int dn_hubert_forward(DnHubert* m, const float* wave, const int32_t* lengths, int32_t B, int32_t L, int32_t n_layers_run, float* out,
-                                 int32_t* out_lengths, void* workspace, size_t workspace_bytes, void* stream) {
-  DN_CHECK_ARG(m && wave && lengths && out && out_lengths && workspace, "dn_hubert_forward: null argument");
+namespace {
+// The pass behind both entries.  emissions == nullptr: `out` = the output of layer n_layers_run - 1 (dn_hubert_forward).  Else every
+// layer runs, encoder.layer_norm follows in the pre-norm form (TransformerEncoder.forward with layer None, wav2vec2.py:1001-1007), and
+// `out` = emissions fp32 [B, S, vocab] of the CTC head (dn_hubert_ctc_forward).
+int hubert_pass(const char* who, DnHubert* m, const float* wave, const int32_t* lengths, int32_t B, int32_t L, int32_t n_layers_run, bool emissions, float* out,
+                int32_t* out_lengths, void* workspace, size_t workspace_bytes, void* stream) {
   const DnHubertConfig& c = m->cfg;
   const int S = dn_hubert_out_frames(m, L);
-  DN_CHECK_ARG(B > 0 && B <= 65535 && L > 0 && S >= 1, "dn_hubert_forward: B=%d L=%d: the waveform is shorter than one frame of the conv stack", B, L);
-  DN_CHECK_ARG(n_layers_run >= 1 && n_layers_run <= c.layers, "dn_hubert_forward: output layer %d outside 1 .. %d", n_layers_run, c.layers);
+  DN_CHECK_ARG(B > 0 && B <= 65535 && L > 0 && S >= 1, "%s: B=%d L=%d: the waveform is shorter than one frame of the conv stack", who, B, L);
+  DN_CHECK_ARG(n_layers_run >= 1 && n_layers_run <= c.layers, "%s: output layer %d outside 1 .. %d", who, n_layers_run, c.layers);
   hipStream_t s = (hipStream_t)stream;
   Arena ar{(char*)workspace, 0, workspace_bytes};
   const HubertBufs b = plan_hubert(m, B, L, ar);
-  DN_CHECK_ARG(b.max_elems < (int64_t)1 << 31, "dn_hubert_forward: B=%d L=%d: a buffer of %lld elements exceeds 2^31 (rows are indexed in 32 bits): split the batch", B,
-               L, (long long)b.max_elems);
-  DN_TRY(check_workspace("dn_hubert_forward", workspace, workspace_bytes, ar.off));
+  DN_CHECK_ARG(b.max_elems < (int64_t)1 << 31, "%s: B=%d L=%d: a buffer of %lld elements exceeds 2^31 (rows are indexed in 32 bits): split the batch", who,
+               B, L, (long long)b.max_elems);
+  DN_TRY(check_workspace(who, workspace, workspace_bytes, ar.off));
   const int dtype = c.dtype, es = esize(dtype), C = c.conv_dim, D = c.dim, F = c.ffn, H = c.heads, dh = D / H;
   const int sdt = side_dtype(dtype), ses = esize(sdt);
   ConvGeom g;
@@ -418,22 +663,38 @@ extern "C" int dn_hubert_forward(DnHubert* m, const float* wave, const int32_t* 
   hipLaunchKernelGGL(hubert_lengths_kernel, dim3(1), dim3(256), 0, s, lengths, B, L, g, S, b.len1, out_lengths);
   // ---- conv layer 0 + Fp32GroupNorm + GELU (wav2vec2.py:860-866), statistics per utterance over its own frames
   const int T1 = b.T[0], s0 = c.conv_stride[0];
-  hipLaunchKernelGGL(conv0_stats_kernel, dim3(b.tiles, B), dim3(256), 0, s, wave, lengths, b.len1, L, C, s0, m->conv0_w, b.part);
-  hipLaunchKernelGGL(conv0_combine_kernel, dim3((B * C + 255) / 256), dim3(256), 0, s, b.part, b.len1, B, C, b.tiles, b.stat);
-  hipLaunchKernelGGL(conv0_apply_kernel, dim3(b.tiles, B), dim3(256), 0, s, wave, lengths, L, T1, C, s0, m->conv0_w, m->gn_g, m->gn_b, b.stat, b.y0, dtype);
+  if (c.wave_norm) {  // the utterance's own mean and rstd; applied where the first conv stages its samples
+    hipLaunchKernelGGL(wave_stats_kernel, dim3(b.wtiles, B), dim3(256), 0, s, wave, lengths, L, b.wpart);
+    hipLaunchKernelGGL(wave_combine_kernel, dim3((B + 63) / 64), dim3(64), 0, s, b.wpart, lengths, B, L, b.wtiles, b.wstat);
+  }
+  if (c.extractor_ln) {  // conv + bias + Fp32LayerNorm over the channels + GELU, one kernel (wav2vec2.py:849-859)
+    hipLaunchKernelGGL(conv0_ln_kernel, dim3(b.tiles, B), dim3(256), 0, s, wave, lengths, L, T1, C, s0, m->conv0_w, c.conv_bias ? m->conv_b : m->zeros, m->cln_g,
+                       m->cln_b, b.wstat, b.y0, dtype);
+  } else {
+    hipLaunchKernelGGL(conv0_stats_kernel, dim3(b.tiles, B), dim3(256), 0, s, wave, lengths, b.len1, L, C, s0, m->conv0_w, b.part);
+    hipLaunchKernelGGL(conv0_combine_kernel, dim3((B * C + 255) / 256), dim3(256), 0, s, b.part, b.len1, B, C, b.tiles, b.stat);
+    hipLaunchKernelGGL(conv0_apply_kernel, dim3(b.tiles, B), dim3(256), 0, s, wave, lengths, L, T1, C, s0, m->conv0_w, m->gn_g, m->gn_b, b.stat, b.y0, dtype);
+  }
   mark();
   // ---- conv layers 1.. + GELU (:867-868): gathered rows, one contraction each; y holds layer i's pre-activation
   for (int i = 1; i < c.n_conv; ++i) {
     const int k = c.conv_kernel[i], st = c.conv_stride[i], Tin = b.T[i - 1], Tout = b.T[i];
     const int grid = ew_grid((int64_t)B * Tout * k * C / 4);
-    if (i == 1)
+    if (i == 1 || c.extractor_ln)
       hipLaunchKernelGGL((strided_taps_kernel<false>), dim3(grid), dim3(256), 0, s, b.y0, dtype, B, Tin, Tout, C, k, st, b.cols, dtype);
     else
       hipLaunchKernelGGL((strided_taps_kernel<true>), dim3(grid), dim3(256), 0, s, b.y, DN_F32, B, Tin, Tout, C, k, st, b.cols, dtype);
-    DN_TRY(linear(Rows{dtype, B * Tout, Tout, 0, s}, b.cols, k * C, m->conv_W[i], m->zeros, C, DN_EPI_BIAS, b.y, DN_F32));
+    DN_TRY(linear(Rows{dtype, B * Tout, Tout, 0, s}, b.cols, k * C, m->conv_W[i], c.conv_bias ? m->conv_b + (size_t)i * C : m->zeros, C, DN_EPI_BIAS, b.y,
+                  DN_F32));
+    if (c.extractor_ln) {  // the norm sits between the conv and the GELU: one row kernel, into the next gather's input (the last: fp32, in place)
+      const bool last = i + 1 == c.n_conv;
+      hipLaunchKernelGGL(ln_gelu_rows_kernel, dim3((B * Tout + 3) / 4), dim3(256), 0, s, b.y, last ? (void*)b.y : b.y0, last ? DN_F32 : dtype, B * Tout, C,
+                         m->cln_g + (size_t)i * C, m->cln_b + (size_t)i * C);
+    }
   }
   const Rows rc{dtype, B * S, S, C, s}, r{dtype, B * S, S, D, s};
-  hipLaunchKernelGGL(gelu_rows_kernel, dim3(ew_grid((int64_t)rc.M * C / 4)), dim3(256), 0, s, b.y, b.y, DN_F32, (int64_t)rc.M * C / 4);
+  if (!c.extractor_ln)
+    hipLaunchKernelGGL(gelu_rows_kernel, dim3(ew_grid((int64_t)rc.M * C / 4)), dim3(256), 0, s, b.y, b.y, DN_F32, (int64_t)rc.M * C / 4);
   mark();
   // ---- layer_norm, post_extract_proj (hubert.py:445-453)
   if (c.has_proj) {
@@ -445,26 +706,74 @@ extern "C" int dn_hubert_forward(DnHubert* m, const float* wave, const int32_t* 
   // ---- x + gelu(SamePad(pos_conv(x))), encoder.layer_norm (wav2vec2.py:1020-1025); frames outside the utterance are zeros
   DN_TRY(dn_grouped_conv1d(b.x0, m->pos_w, m->pos_b, b.xa, out_lengths, B, S, D, c.conv_pos_groups, c.conv_pos, s));
   mark();
-  float *cur = b.xb, *other = b.xa;
-  norm_both(r, b.xa, m->enc_g, m->enc_b, cur);
-  for (int l = 0; l < n_layers_run; ++l) {  // TransformerSentenceEncoderLayer.forward, layer_norm_first False (:1258-1283)
-    const float* lg = m->lng + (size_t)l * 2 * D;
-    const float* lb = m->lnb + (size_t)l * 2 * D;
-    DN_TRY(linear(r, xn, D, layer_mat(m->qkv_W, l, 3 * D, D, es), m->qkv_b + (size_t)l * 3 * D, 3 * D, DN_EPI_BIAS, b.qkv, sdt));
-    DN_TRY(attention(dtype, H, dh, b.qkv, 3 * D, eoff(b.qkv, D, ses), eoff(b.qkv, 2 * D, ses), 3 * D, B, S, 0, out_lengths, b.ao, s));
-    DN_TRY(linear_resadd(r, b.ao, D, layer_mat(m->out_W, l, D, D, es), m->out_b + (size_t)l * D, cur));
-    norm_both(r, cur, lg, lb, other);  // self_attn_layer_norm BEHIND the residual
+  float *cur = b.xa, *other = b.xb;
+  if (c.pre_norm) {  // no encoder.layer_norm in front of pre-norm layers (:1024): the stream stays in b.xa
+    for (int l = 0; l < n_layers_run; ++l) {  // layer_norm_first True (:1235-1257): x += attn(LN1(x)); x += fc2(gelu(fc1(LN2(x))))
+      const float* lg = m->lng + (size_t)l * 2 * D;
+      const float* lb = m->lnb + (size_t)l * 2 * D;
+      layernorm(r, cur, lg, lb, b.xn, dtype);
+      DN_TRY(linear(r, b.xn, D, layer_mat(m->qkv_W, l, 3 * D, D, es), m->qkv_b + (size_t)l * 3 * D, 3 * D, DN_EPI_BIAS, b.qkv, sdt));
+      DN_TRY(attention(dtype, H, dh, b.qkv, 3 * D, eoff(b.qkv, D, ses), eoff(b.qkv, 2 * D, ses), 3 * D, B, S, 0, out_lengths, b.ao, s));
+      DN_TRY(linear_resadd(r, b.ao, D, layer_mat(m->out_W, l, D, D, es), m->out_b + (size_t)l * D, cur));
+      layernorm(r, cur, lg + D, lb + D, b.xn, dtype);
+      DN_TRY(linear(r, b.xn, D, layer_mat(m->fc1_W, l, F, D, es), m->fc1_b + (size_t)l * F, F, DN_EPI_BIAS, b.hf, DN_F32));
+      hipLaunchKernelGGL(gelu_rows_kernel, dim3(ew_grid((int64_t)r.M * F / 4)), dim3(256), 0, s, b.hf, b.h, dtype, (int64_t)r.M * F / 4);
+      DN_TRY(linear_resadd(r, b.h, F, layer_mat(m->fc2_W, l, D, F, es), m->fc2_b + (size_t)l * D, cur));
+    }
+  } else {
     std::swap(cur, other);
-    DN_TRY(linear(r, xn, D, layer_mat(m->fc1_W, l, F, D, es), m->fc1_b + (size_t)l * F, F, DN_EPI_BIAS, b.hf, DN_F32));
-    hipLaunchKernelGGL(gelu_rows_kernel, dim3(ew_grid((int64_t)r.M * F / 4)), dim3(256), 0, s, b.hf, b.h, dtype, (int64_t)r.M * F / 4);
-    DN_TRY(linear_resadd(r, b.h, F, layer_mat(m->fc2_W, l, D, F, es), m->fc2_b + (size_t)l * D, cur));
-    if (l + 1 < n_layers_run) norm_both(r, cur, lg + D, lb + D, other);  // final_layer_norm
-    else layernorm(r, cur, lg + D, lb + D, other, DN_F32);
-    std::swap(cur, other);
+    norm_both(r, b.xa, m->enc_g, m->enc_b, cur);
+    for (int l = 0; l < n_layers_run; ++l) {  // TransformerSentenceEncoderLayer.forward, layer_norm_first False (:1258-1283)
+      const float* lg = m->lng + (size_t)l * 2 * D;
+      const float* lb = m->lnb + (size_t)l * 2 * D;
+      DN_TRY(linear(r, xn, D, layer_mat(m->qkv_W, l, 3 * D, D, es), m->qkv_b + (size_t)l * 3 * D, 3 * D, DN_EPI_BIAS, b.qkv, sdt));
+      DN_TRY(attention(dtype, H, dh, b.qkv, 3 * D, eoff(b.qkv, D, ses), eoff(b.qkv, 2 * D, ses), 3 * D, B, S, 0, out_lengths, b.ao, s));
+      DN_TRY(linear_resadd(r, b.ao, D, layer_mat(m->out_W, l, D, D, es), m->out_b + (size_t)l * D, cur));
+      norm_both(r, cur, lg, lb, other);  // self_attn_layer_norm BEHIND the residual
+      std::swap(cur, other);
+      DN_TRY(linear(r, xn, D, layer_mat(m->fc1_W, l, F, D, es), m->fc1_b + (size_t)l * F, F, DN_EPI_BIAS, b.hf, DN_F32));
+      hipLaunchKernelGGL(gelu_rows_kernel, dim3(ew_grid((int64_t)r.M * F / 4)), dim3(256), 0, s, b.hf, b.h, dtype, (int64_t)r.M * F / 4);
+      DN_TRY(linear_resadd(r, b.h, F, layer_mat(m->fc2_W, l, D, F, es), m->fc2_b + (size_t)l * D, cur));
+      if (l + 1 < n_layers_run) norm_both(r, cur, lg + D, lb + D, other);  // final_layer_norm
+      else layernorm(r, cur, lg + D, lb + D, other, DN_F32);
+      std::swap(cur, other);
+    }
   }
   mark();
-  hipLaunchKernelGGL(masked_copy_kernel, dim3(ew_grid((int64_t)r.M * D / 4)), dim3(256), 0, s, cur, out_lengths, B, S, D, out);
+  if (emissions) {  // encoder.layer_norm (the head exists in the pre-norm form only) -> proj (wav2vec2_asr.py:494-495); the pad columns stay
+    // in the workspace.  Always the DN_F32 contraction on the fp32 stream, whatever the engine's arithmetic, as dn_kmeans_assign's: a
+    // letter is a decision
+    const int V = c.vocab, Vp = round_up(V, 4);
+    layernorm(r, cur, m->enc_g, m->enc_b, b.xb, DN_F32);
+    DN_TRY(linear(Rows{DN_F32, r.M, S, D, s}, b.xb, D, m->head_W, m->head_b, Vp, DN_EPI_BIAS, b.em, DN_F32));
+    hipLaunchKernelGGL(emit_rows_kernel, dim3(ew_grid((int64_t)r.M * V)), dim3(256), 0, s, b.em, Vp, out_lengths, B, S, V, out);
+  } else {
+    hipLaunchKernelGGL(masked_copy_kernel, dim3(ew_grid((int64_t)r.M * D / 4)), dim3(256), 0, s, cur, out_lengths, B, S, D, out);
+  }
   mark();
-  DN_CHECK_LAUNCH("dn_hubert_forward");
+  DN_CHECK_LAUNCH(who);
+  return DN_OK;
+}
+}  // namespace
+
+extern "C" int dn_hubert_forward(DnHubert* m, const float* wave, const int32_t* lengths, int32_t B, int32_t L, int32_t n_layers_run, float* out,
+                                 int32_t* out_lengths, void* workspace, size_t workspace_bytes, void* stream) {
+  DN_CHECK_ARG(m && wave && lengths && out && out_lengths && workspace, "dn_hubert_forward: null argument");
+  return hubert_pass("dn_hubert_forward", m, wave, lengths, B, L, n_layers_run, false, out, out_lengths, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dn_hubert_ctc_forward(DnHubert* m, const float* wave, const int32_t* lengths, int32_t B, int32_t L, float* emissions, int32_t* out_lengths,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  DN_CHECK_ARG(m && wave && lengths && emissions && out_lengths && workspace, "dn_hubert_ctc_forward: null argument");
+  DN_CHECK_ARG(m->cfg.vocab > 0, "dn_hubert_ctc_forward: the engine was created without a CTC head (vocab 0)");
+  return hubert_pass("dn_hubert_ctc_forward", m, wave, lengths, B, L, m->cfg.layers, true, emissions, out_lengths, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dn_ctc_greedy(const float* emissions, const int32_t* lengths, int32_t B, int32_t S, int32_t V, int32_t blank, int32_t* tokens_out,
+                             int32_t* counts_out, void* stream) {
+  DN_CHECK_ARG(emissions && lengths && tokens_out && counts_out, "dn_ctc_greedy: null argument");
+  DN_CHECK_ARG(B > 0 && S > 0 && V > 0 && blank >= 0 && blank < V, "dn_ctc_greedy: B=%d S=%d V=%d blank=%d (inside the vocabulary)", B, S, V, blank);
+  hipLaunchKernelGGL(ctc_greedy_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, emissions, lengths, S, V, blank, tokens_out, counts_out);
+  DN_CHECK_LAUNCH("dn_ctc_greedy");
   return DN_OK;
 }

@@ -22,7 +22,15 @@ MHUBERT_BASE = SimpleNamespace(conv_feature_layers="[(512,10,5)] + [(512,3,2)] *
                                encoder_embed_dim=768, encoder_ffn_embed_dim=3072, encoder_layers=12, encoder_attention_heads=12, conv_pos=128,
                                conv_pos_groups=16, layer_norm_first=False, layer_type="transformer", required_seq_len_multiple=1,
                                activation_fn="gelu", normalize=False)
+# The large form: a LayerNorm behind every (biased) conv, pre-norm layers, waveform normalisation in the task (wav2vec 2.0 large /
+# LV-60 / XLSR and HuBERT large / xlarge's recipe; the widths here are the large ones)
+_LARGE = dict(conv_feature_layers="[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2", extractor_mode="layer_norm", conv_bias=True, encoder_embed_dim=1024,
+              encoder_ffn_embed_dim=4096, encoder_layers=24, encoder_attention_heads=16, conv_pos=128, conv_pos_groups=16, layer_norm_first=True,
+              layer_type="transformer", activation_fn="gelu", normalize=True)
+WAV2VEC2_LARGE = SimpleNamespace(required_seq_len_multiple=2, **_LARGE)
+HUBERT_LARGE = SimpleNamespace(required_seq_len_multiple=2, **dict(_LARGE, conv_bias=False))
 _FIRST_KMAX = 16  # taps of the first conv the kernel holds (C0_KMAX in csrc/hubert.hip)
+_LN_CMAX = 512    # conv width of the LayerNorm extractor's first-layer kernel (C0_LN_CMAX)
 
 
 def conv_layers(cfg) -> List[Tuple[int, int, int]]:
@@ -36,20 +44,26 @@ def conv_layers(cfg) -> List[Tuple[int, int, int]]:
 
 
 def check_hubert_args(cfg) -> None:
-    """What of HubertModel's variants the engine runs (the mHuBERT-base form); the rest is refused here, on the host."""
+    """What of HubertModel's / Wav2Vec2Model's variants the engine runs, each as a whole: the base form (extractor_mode 'default',
+    post-norm layers, nothing else) exactly as before, and the large form (extractor_mode 'layer_norm' WITH layer_norm_first; with
+    them conv_bias, task normalize and any required_seq_len_multiple, whose appended frames are masked keys that are cut off again).
+    These are the forms released checkpoints have and the goldens pin; a single large-form property on the base form is no model
+    anyone has and stays refused here, on the host, as does everything else."""
     g = lambda k, d: getattr(cfg, k, d)
-    if g("extractor_mode", "default") != "default":
-        raise ValueError(f"hubert: extractor_mode {cfg.extractor_mode!r} (a LayerNorm behind every conv: the large models) is not supported, only 'default'")
-    if g("conv_bias", False):
-        raise ValueError("hubert: conv_bias=True is not supported")
-    if g("layer_norm_first", False):
-        raise ValueError("hubert: layer_norm_first=True (pre-norm layers) is not supported")
+    if g("extractor_mode", "default") not in ("default", "layer_norm"):
+        raise ValueError(f"hubert: extractor_mode {cfg.extractor_mode!r} is not supported, only 'default' and 'layer_norm'")
+    large = g("extractor_mode", "default") == "layer_norm"
+    if bool(g("layer_norm_first", False)) != large:
+        raise ValueError(f"hubert: extractor_mode {g('extractor_mode', 'default')!r} with layer_norm_first={bool(g('layer_norm_first', False))} is not supported: "
+                         "a LayerNorm behind every conv and pre-norm layers go together (the large form)")
+    if g("conv_bias", False) and not large:
+        raise ValueError("hubert: conv_bias=True is supported in the large form only (extractor_mode 'layer_norm' with layer_norm_first)")
     if g("layer_type", "transformer") != "transformer":
         raise ValueError(f"hubert: layer_type {cfg.layer_type!r} is not supported, only 'transformer'")
-    if g("required_seq_len_multiple", 1) != 1:
-        raise ValueError("hubert: required_seq_len_multiple must be 1")
-    if g("normalize", False):
-        raise ValueError("hubert: task normalize=True (waveform layer_norm in the reader) is not supported")
+    if int(g("required_seq_len_multiple", 1)) < 1 or (int(g("required_seq_len_multiple", 1)) != 1 and not large):
+        raise ValueError("hubert: required_seq_len_multiple must be 1 in the base form (at least 1 in the large form)")
+    if g("normalize", False) and not large:
+        raise ValueError("hubert: task normalize=True (waveform layer_norm in the reader) is supported in the large form only")
     if g("activation_fn", "gelu") != "gelu":
         raise ValueError(f"hubert: activation_fn {cfg.activation_fn!r} is not supported, only 'gelu'")
     if g("pos_conv_depth", 1) != 1:
@@ -61,6 +75,8 @@ def check_hubert_args(cfg) -> None:
         raise ValueError("hubert: 2 .. 8 conv layers of one width are supported")
     if layers[0][1] > _FIRST_KMAX or layers[0][2] > 8:
         raise ValueError(f"hubert: first conv kernel {layers[0][1]} (<= {_FIRST_KMAX}) / stride {layers[0][2]} (<= 8)")
+    if g("extractor_mode", "default") == "layer_norm" and layers[0][0] > _LN_CMAX:
+        raise ValueError(f"hubert: extractor_mode 'layer_norm' with conv width {layers[0][0]} (<= {_LN_CMAX})")
 
 
 def out_frames(cfg, L: int) -> int:
@@ -100,15 +116,18 @@ def pack_hubert(sd: Dict[str, torch.Tensor], cfg, dtype: int) -> List[torch.Tens
     has_proj = "post_extract_proj.weight" in sd  # (absent when the conv width is the embed width, hubert.py:264-268)
     if not has_proj and Cw != D:
         raise ValueError(f"hubert: no post_extract_proj in the state dict but conv width {Cw} != embed width {D}")
-    if any(k.startswith("feature_extractor.conv_layers.") and k.endswith(".0.bias") for k in sd):
-        raise ValueError("hubert: conv biases in the state dict (conv_bias=True) are not supported")
-    if "feature_extractor.conv_layers.1.2.1.weight" in sd:
-        raise ValueError("hubert: a LayerNorm behind conv layer 1 (extractor_mode 'layer_norm') is not supported")
+    ext_ln, conv_bias = getattr(cfg, "extractor_mode", "default") == "layer_norm", bool(getattr(cfg, "conv_bias", False))
+    if any(k.startswith("feature_extractor.conv_layers.") and k.endswith(".0.bias") for k in sd) != conv_bias:
+        raise ValueError(f"hubert: conv biases in the state dict do not agree with conv_bias={conv_bias}")
+    if ("feature_extractor.conv_layers.1.2.1.weight" in sd) != ext_ln:
+        raise ValueError(f"hubert: the state dict {'lacks' if ext_ln else 'has'} the LayerNorm behind conv layer 1 (extractor_mode 'layer_norm') but "
+                         f"cfg.extractor_mode is {'layer_norm' if ext_ln else 'default'!r}")
     w0 = g("feature_extractor.conv_layers.0.0.weight")
     assert w0.shape == (Cw, 1, layers[0][1]), w0.shape
     conv0 = torch.zeros(_FIRST_KMAX, Cw)
     conv0[: layers[0][1]] = w0[:, 0, :].t()
-    out = [conv0, g("feature_extractor.conv_layers.0.2.weight").contiguous(), g("feature_extractor.conv_layers.0.2.bias").contiguous()]
+    n0 = "feature_extractor.conv_layers.0.2.1." if ext_ln else "feature_extractor.conv_layers.0.2."
+    out = [conv0, g(n0 + "weight").contiguous(), g(n0 + "bias").contiguous()]
     for i, (_, k, _) in enumerate(layers[1:], 1):
         w = g(f"feature_extractor.conv_layers.{i}.0.weight")
         assert w.shape == (Cw, Cw, k), w.shape
@@ -129,7 +148,34 @@ def pack_hubert(sd: Dict[str, torch.Tensor], cfg, dtype: int) -> List[torch.Tens
         f2W.append(mat(g(p + "fc2.weight"))); f2b.append(g(p + "fc2.bias"))
         lng.append(torch.stack([g(p + "self_attn_layer_norm.weight"), g(p + "final_layer_norm.weight")]))
         lnb.append(torch.stack([g(p + "self_attn_layer_norm.bias"), g(p + "final_layer_norm.bias")]))
-    return out + [stack(t) for t in (qkv_W, qkv_b, so_W, so_b, f1W, f1b, f2W, f2b, lng, lnb)] + [torch.zeros(Cw)]
+    out = out + [stack(t) for t in (qkv_W, qkv_b, so_W, so_b, f1W, f1b, f2W, f2b, lng, lnb)] + [torch.zeros(Cw)]
+    if ext_ln:  # per conv layer: bias (zeros without conv_bias), LayerNorm weight and bias
+        ce = "feature_extractor.conv_layers.{}.{}"
+        out += [stack([g(ce.format(i, "0.bias")) if conv_bias else torch.zeros(Cw) for i in range(len(layers))]),
+                stack([g(ce.format(i, "2.1.weight")) for i in range(len(layers))]), stack([g(ce.format(i, "2.1.bias")) for i in range(len(layers))])]
+    return out
+
+
+def pack_ctc_head(weight: torch.Tensor, bias: torch.Tensor) -> List[torch.Tensor]:
+    """Wav2VecEncoder.proj (Linear(dim -> V)) -> the two entries behind pack_hubert's table: the fp32 weight (the head runs the
+    DN_F32 contraction in every mode) with zero rows up to the contraction's packed height, the bias with zeros up to a multiple of 4
+    (columns the engine never copies into the emissions)."""
+    V = weight.shape[0]
+    return [packing._mat(weight.float(), _lib.DN_F32, cols=weight.shape[1]), packing._vec(bias, (V + 3) // 4 * 4)]
+
+
+def hubert_config(cfg, dtype: int, has_proj: bool, vocab: int = 0) -> "_lib.HubertConfig":
+    """cfg -> DnHubertConfig (include/diffnorm_hip.h)."""
+    layers = conv_layers(cfg)
+    c = _lib.HubertConfig()
+    c.n_conv, c.conv_dim = len(layers), layers[0][0]
+    for i, (_, k, s) in enumerate(layers):
+        c.conv_kernel[i], c.conv_stride[i] = k, s
+    c.dim, c.ffn, c.layers, c.heads = cfg.encoder_embed_dim, cfg.encoder_ffn_embed_dim, cfg.encoder_layers, cfg.encoder_attention_heads
+    c.conv_pos, c.conv_pos_groups, c.dtype, c.has_proj = cfg.conv_pos, cfg.conv_pos_groups, dtype, int(has_proj)
+    c.wave_norm, c.extractor_ln = int(bool(getattr(cfg, "normalize", False))), int(getattr(cfg, "extractor_mode", "default") == "layer_norm")
+    c.conv_bias, c.pre_norm, c.vocab = int(bool(getattr(cfg, "conv_bias", False))), int(bool(getattr(cfg, "layer_norm_first", False))), int(vocab)
+    return c
 
 
 def _as_wave(w) -> torch.Tensor:
@@ -147,15 +193,7 @@ class HubertEngine(_NarEngine):
     def __init__(self, state_dict, cfg=MHUBERT_BASE, dtype="f16", device="cuda:0"):
         self.cfg, self.dim = cfg, cfg.encoder_embed_dim
         self.dtype = _dtype_code(dtype)
-        layers = conv_layers(cfg)
-        c = _lib.HubertConfig()
-        c.n_conv, c.conv_dim = len(layers), layers[0][0]
-        for i, (_, k, s) in enumerate(layers):
-            c.conv_kernel[i], c.conv_stride[i] = k, s
-        c.dim, c.ffn, c.layers, c.heads = cfg.encoder_embed_dim, cfg.encoder_ffn_embed_dim, cfg.encoder_layers, cfg.encoder_attention_heads
-        c.conv_pos, c.conv_pos_groups, c.dtype = cfg.conv_pos, cfg.conv_pos_groups, self.dtype
-        c.has_proj = int("post_extract_proj.weight" in state_dict)
-        self._create(device, pack_hubert(state_dict, cfg, self.dtype), c)
+        self._create(device, pack_hubert(state_dict, cfg, self.dtype), hubert_config(cfg, self.dtype, "post_extract_proj.weight" in state_dict))
 
     def out_frames(self, L: int) -> int:
         return int(self.lib.dn_hubert_out_frames(self.handle, int(L)))
@@ -176,9 +214,8 @@ class HubertEngine(_NarEngine):
             _lib.check(self.lib.dn_hubert_stage_times(self.handle, ms, len(self.STAGES)), "dn_hubert_stage_times")
         return list(ms)
 
-    def forward(self, wave: torch.Tensor, lengths, layer: int):
-        """wave [B, L] (anything finite behind an utterance's samples), lengths [B], layer = output_layer (1-based) ->
-        (features fp32 [B, S, dim] with zero rows behind each utterance's frames, frame counts int32 [B])."""
+    def _inputs(self, wave: torch.Tensor, lengths):
+        """The checks and device copies both passes share -> (wave, lengths int32, S, (workspace pointer, bytes))."""
         B, L = wave.shape
         lengths = torch.as_tensor(lengths)
         if lengths.device.type == "cpu" and (out_frames(self.cfg, int(lengths.min())) < 1 or int(lengths.max()) > L):
@@ -188,9 +225,16 @@ class HubertEngine(_NarEngine):
             raise ValueError(f"HubertEngine.forward: {L} samples are shorter than one frame of the conv stack")
         wave = wave.to(self.device, torch.float32).contiguous()
         ln = lengths.to(self.device, torch.int32).contiguous()
+        return wave, ln, S, self._aligned(self._workspace(int(self.lib.dn_hubert_workspace_bytes(self.handle, B, L))))
+
+    def forward(self, wave: torch.Tensor, lengths, layer: int):
+        """wave [B, L] (anything behind an utterance's samples), lengths [B], layer = output_layer (1-based) -> (features fp32
+        [B, S, dim] with zero rows behind each utterance's frames, frame counts int32 [B]).  In the pre-norm form this is the
+        un-normalised stream for every layer, as HubertModel.extract_features(output_layer=k) hands TransformerEncoder a layer."""
+        B, L = wave.shape
+        wave, ln, S, (wp, wn) = self._inputs(wave, lengths)
         out = torch.empty(B, S, self.dim, dtype=torch.float32, device=self.device)
         lens = torch.empty(B, dtype=torch.int32, device=self.device)
-        wp, wn = self._aligned(self._workspace(int(self.lib.dn_hubert_workspace_bytes(self.handle, B, L))))
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dn_hubert_forward(self.handle, wave.data_ptr(), ln.data_ptr(), B, L, int(layer), out.data_ptr(), lens.data_ptr(), wp, wn,
                                                   _lib.current_stream()), "dn_hubert_forward")
@@ -215,6 +259,11 @@ class HubertFeatureReader:
 
     def _check_chunks(self, n: int):
         bounds = chunk_bounds(n, self.max_chunk)
+        if len(bounds) > 1 and getattr(self.cfg, "normalize", False):
+            # the reference normalises the WHOLE waveform once and cuts it afterwards (hubert_feature_reader.py:47-53); the engine
+            # takes its statistics per forward call, so a chunk would be normalised over its own samples
+            raise ValueError(f"a waveform of {n} samples is more than one chunk of {self.max_chunk}: with task normalize=True the statistics "
+                             "belong to the whole waveform, which the chunk loop does not carry; raise max_chunk")
         for s, e in bounds:
             if out_frames(self.cfg, e - s) < 1:
                 raise ValueError(f"a chunk of {e - s} samples (at {s} of {n}) is shorter than one frame of the conv stack")

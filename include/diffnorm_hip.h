@@ -1262,7 +1262,12 @@ int dn_voc_stage_times(DnVoc* m, float* ms, int32_t cap);
  * would get ALONE (the reader never batches; the reference's batched padding-mask path is not what this reproduces): a result depends
  * on the utterance's own samples and length only, not on B, the row or L.  Kernels and the pass: csrc/hubert.hip.  Supported form
  * (mHuBERT-base): extractor_mode "default", conv_bias False, layer_norm_first False, layer_type "transformer",
- * required_seq_len_multiple 1, task normalize False; every conv layer of the same width.
+ * required_seq_len_multiple 1, task normalize False; every conv layer of the same width. The large form (wav2vec 2.0 / HuBERT
+ * large, and the Wav2VecCtc recognisers of the recipe's ASR-BLEU) is the same engine with the DnHubertConfig fields behind
+ * has_proj set; all of them zero is the base form, bit for bit.  The two forms are accepted as wholes (the ones released
+ * checkpoints have and the goldens pin): extractor_ln and pre_norm go together, conv_bias and wave_norm only with them; any other
+ * mix is refused at create.  required_seq_len_multiple needs no field: the frames it appends are masked keys that are cut off
+ * again (wav2vec2.py:1027-1037, 1063-1065), so nothing is computed for it.
  *
  * Grouped Conv1d with 'same' zero padding of k / 2 frames in front and SamePad's trim behind (an even k drops the last frame;
  * make_conv_pos, fairseq/models/wav2vec/wav2vec2.py:899-915), then GELU and the residual add (TransformerEncoder.extract_features,
@@ -1293,7 +1298,9 @@ int dn_kmeans_assign(const float* feats, const float* centroids, const float* ha
  *   then: layer_norm g, b [C] (HubertModel.layer_norm)   post_extract_proj W [dim][C], b
  *   pos_conv w fp32 [groups][k][Cg][Cg] (weight-norm folded: g v / |v| over dim 2, float64 on the host), bias [dim]
  *   encoder.layer_norm g, b   qkv_W [layers][3 dim][dim] (q ; k ; v), qkv_b   out_W, out_b   fc1_W, fc1_b   fc2_W, fc2_b
- *   ln_g [layers][2][dim] (self_attn_layer_norm ; final_layer_norm), ln_b   zeros [C] (the bias of the bias-free convs)        */
+ *   ln_g [layers][2][dim] (self_attn_layer_norm ; final_layer_norm), ln_b   zeros [C] (the bias of the bias-free convs)
+ *   extractor_ln: conv bias [n_conv][C] (read when conv_bias), conv LayerNorm g [n_conv][C], b [n_conv][C] (entries 1, 2 are not read)
+ *   vocab > 0: proj W fp32 [vocab -> 128][dim], b [vocab -> multiple of 4]                                                                    */
 #define DN_HUBERT_MAX_CONV 8
 typedef struct DnHubert DnHubert;
 typedef struct {
@@ -1301,6 +1308,14 @@ typedef struct {
   int32_t conv_kernel[DN_HUBERT_MAX_CONV], conv_stride[DN_HUBERT_MAX_CONV];
   int32_t dim, ffn, layers, heads, conv_pos, conv_pos_groups, dtype;
   int32_t has_proj; /* 0: no post_extract_proj (conv_dim == dim, hubert.py:264-268); its two table entries are then not read */
+  int32_t wave_norm;    /* task normalize: F.layer_norm(wave, wave.shape) per utterance over its own samples (eps 1e-5), applied where
+                           the first conv stages its samples: mean, then squared deviations from it, per-tile partials combined in order */
+  int32_t extractor_ln; /* extractor_mode "layer_norm": Conv1d (+ bias) -> Fp32LayerNorm over the channels of a frame -> GELU behind
+                           every conv (wav2vec2.py:849-859); conv_dim <= 512 */
+  int32_t conv_bias;    /* with extractor_ln only (HuBERT large has none) */
+  int32_t pre_norm;     /* layer_norm_first: x += attn(LN1(x)); x += fc2(gelu(fc1(LN2(x)))), no encoder.layer_norm in front; it follows
+                           the last layer in dn_hubert_ctc_forward only (TransformerEncoder.forward, layer None, wav2vec2.py:1001-1007) */
+  int32_t vocab;        /* > 0: the CTC head Linear(dim -> vocab) of Wav2VecEncoder (wav2vec2_asr.py:494-495); with pre_norm only */
 } DnHubertConfig;
 int dn_hubert_create(const DnHubertConfig* cfg, const void* const* weights, int32_t n_weights, DnHubert** out);
 void dn_hubert_destroy(DnHubert* m);
@@ -1322,6 +1337,21 @@ int dn_hubert_forward(DnHubert* m, const float* wave, const int32_t* lengths, in
 #define DN_HUBERT_STAGES 5
 int dn_hubert_set_profile(DnHubert* m, int32_t on);
 int dn_hubert_stage_times(DnHubert* m, float* ms, int32_t cap);
+
+/* Wav2VecEncoder.forward in eval mode (wav2vec2_asr.py:473-501; research/TranSpeech/asr_bleu/utils.py:262-266): every layer,
+ * encoder.layer_norm in the pre-norm form, then the head: emissions fp32 [B, S, vocab] = proj(x), rows at or past out_lengths[b]
+ * zeros.  The head is always the DN_F32 contraction on the fp32 stream (a letter is a decision, as a unit is in
+ * dn_kmeans_assign); it writes its pad columns (vocab -> multiple of 4) into the workspace; they never reach `emissions`.
+ * Arguments, refusals and workspace as dn_hubert_forward; the engine must have been created with vocab > 0.  The fifth profiled
+ * stage is then final norm + head + emission copy. */
+int dn_hubert_ctc_forward(DnHubert* m, const float* wave, const int32_t* lengths, int32_t B, int32_t L, float* emissions, int32_t* out_lengths,
+                          void* workspace, size_t workspace_bytes, void* stream);
+/* Best-path CTC decoding (what the recipe's beam-1, lexicon-free, LM-free decoder keeps): tok[t] = the arg-max of frame t (the lowest
+ * index on ties); frame t is kept iff tok[t] != blank and (t == 0 or tok[t] != tok[t - 1]); the kept tokens in order ->
+ * tokens_out[b, :counts_out[b]] (int32 [B, S]; entries behind the count are not written).  emissions fp32 [B, S, V]; frames at and
+ * behind lengths[b] are never read.  One launch for the batch, a workgroup per utterance, any S.                              */
+int dn_ctc_greedy(const float* emissions, const int32_t* lengths, int32_t B, int32_t S, int32_t V, int32_t blank, int32_t* tokens_out,
+                  int32_t* counts_out, void* stream);
 
 /* ------------------------------------------------------------------ Kaldi fbank + utterance CMVN: waveform -> S2UT source features */
 /* The first box of the S2UT leg: get_fbank (fairseq/data/audio/audio_utils.py:242-277), i.e. torchaudio.compliance.kaldi.fbank(waveform,
