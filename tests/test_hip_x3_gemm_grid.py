@@ -28,19 +28,17 @@ K = 32 (one split row group of 128 bytes) is a supported width -- gemm.hip check
 K-tile (pair) -- so it is in the K grid; the width that is refused is one that is no multiple of 32.
 
 Out of scope: the f16 mode, the weight-gradient kernels, timing; no test reads kernel assembly; no sanitizer runs."""
-import ctypes as C
 import math
 
 import pytest
 import torch
 
+import gemm_grid_common as common
+from gemm_grid_common import BAR, BIAS, FILM, GEGLU, NAMES, NAN, POSEMB, RELU, RESADD, SILU, all_nan, epilogue, gelu, padn, seeded, shift_rows  # noqa: F401
+
 gpu = pytest.mark.gpu
 DEV = "cuda:0"
-NAN = float("nan")
 TILES = [0, 1, 2, 3, 8]
-BIAS, SILU, GEGLU, FILM, RESADD, POSEMB, RELU = range(7)  # _lib.EPI_* (asserted in env)
-NAMES = ["bias", "silu", "geglu", "film", "resadd", "posemb", "relu"]
-BAR = {BIAS: 1e-4, RELU: 1e-4, RESADD: 1e-4, POSEMB: 1e-4, SILU: 2e-4, GEGLU: 2e-4, FILM: 2e-4}
 
 
 @pytest.fixture(scope="module")
@@ -52,52 +50,9 @@ def env():
     return ops, packing, _lib
 
 
-def seeded(shape, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
-
-
-def padn(c):
-    return (c + 127) // 128 * 128
-
-
-class Spy:
-    """Stands between ops.conv_gemm and the library: edits the params (fields ops.conv_gemm has no argument for), asks
-    dn_conv_gemm_route about them and hands the call on -- or not (launch=False: the route is all that is wanted)."""
-
-    def __init__(self, lib, launch, edit):
-        self._lib, self._launch, self._edit, self.tile = lib, launch, edit, None
-
-    def __getattr__(self, name):
-        return getattr(self._lib, name)
-
-    def dn_conv_gemm(self, ref, stream):
-        from diffnorm_amd import _lib
-
-        p = ref._obj
-        if self._edit:
-            self._edit(p)
-        r = _lib.GemmRoute()
-        assert self._lib.dn_conv_gemm_route(C.byref(p), C.byref(r)) == 0
-        self.tile = r.tile
-        return self._lib.dn_conv_gemm(ref, stream) if self._launch else 0
-
-
-def call(*args, host=False, launch=True, edit=None, **kw):
-    """ops.conv_gemm(*args, x3=True, **kw) through a Spy; returns the tile dn_conv_gemm_route names.  host: no device is touched
-    (stream 0; the tensors may live on the CPU as long as nothing is launched)."""
-    from diffnorm_amd import _lib, ops
-
-    spy = Spy(_lib.load(), launch, edit)
-    saved = _lib.load, _lib.current_stream
-    _lib.load = lambda: spy
-    if host:
-        _lib.current_stream = lambda: None
-    try:
-        ops.conv_gemm(*args, x3=True, **kw)
-    finally:
-        _lib.load, _lib.current_stream = saved
-    return spy.tile
+def call(*args, **kw):
+    """ops.conv_gemm(*args, x3=True, **kw) through the Spy of gemm_grid_common; returns the tile dn_conv_gemm_route names"""
+    return common.call(*args, x3=True, **kw)
 
 
 def check_route(tile, epi, got):
@@ -115,14 +70,6 @@ def halves(s, weight):
     return (b, a) if weight else (a, b)
 
 
-def shift_rows(a, shift, T):
-    """row m = row m - shift of the same sequence, zero outside it (gemm_kernels.h shift_valid)"""
-    m = torch.arange(a.shape[0])
-    t = m % T
-    valid = (t >= shift) if shift >= 0 else (t - shift < T)
-    return a[(m - shift).clamp(0, a.shape[0] - 1)] * valid.unsqueeze(1).to(a.dtype)
-
-
 def contract(terms, T, K, rows):
     """terms: (split activations [M, 2 lda], split weights [>= rows, 2 K], shift).  Returns the accumulator three ways: float64 of
     (hi + lo) (hi + lo); float64 of the three products; fp32 of the three products (one float32 matmul each, summed in fp32)."""
@@ -135,38 +82,6 @@ def contract(terms, T, K, rows):
         for a, w in ((ah, wl), (al, wh), (ah, wh)):
             p32 = p32 + a.float() @ w.float().t()
     return val, p64, p32
-
-
-def gelu(x):
-    return 0.5 * x * (1 + torch.special.erf(x * 0.7071067811865476))
-
-
-def epilogue(acc, epi, bias=None, res=None, ga=None, be=None, pos=None, scale=None, rbias=None):
-    """The epilogue of wave_epilogue_impl in acc's dtype (float64 or float32); side inputs are per row ([M, n]) or per column ([n])."""
-    c = lambda t: t.to(acc.dtype)
-    v = acc
-    if scale is not None:  # split norm, consumer side
-        v = v * c(scale).unsqueeze(1)
-        if rbias is not None:
-            v = v + c(rbias)
-    if bias is not None:
-        v = v + c(bias)
-    if epi == GEGLU:  # packed columns: tiles of [8 value | 8 gate]
-        v = v.view(v.shape[0], -1, 2, 8)
-        return (gelu(v[:, :, 1]) * v[:, :, 0]).reshape(v.shape[0], -1)
-    if epi == SILU:
-        return v * torch.sigmoid(v)
-    if epi == RELU:
-        return v.clamp_min(0)
-    if epi == FILM:
-        if ga is not None:
-            v = v * c(ga) + c(be)
-        return torch.tanh(v) * torch.sigmoid(v) + c(res)
-    if epi == RESADD:
-        return v + c(res)
-    if epi == POSEMB:
-        return v + c(pos)
-    return v
 
 
 WORST = {}
@@ -186,10 +101,6 @@ def judge(test, case, got, val, p64, p32, bar, K, n_terms):
           f"measured {e3:.3e} ratio {e3 / bound:.3f} | worst so far {w[0]:.3f} {w[1]:.3f}")
     assert e_val <= v_bar, (case, e_val, v_bar)
     assert e3 <= bound, (case, e3, bound, emu)
-
-
-def all_nan(t):
-    return bool(torch.isnan(t.float()).all().item())
 
 
 # ------------------------------------------------------------------------------------------ one contraction with an epilogue
