@@ -6,3 +6,14 @@ scheduler.py (noise schedules), latent_module.py (host mirror of the reference m
 fairseq_plugin/ (register_model / register_task / register_criterion surface).
 """
 __version__ = "0.1.0"
+
+_ENGINES = {"Resampler": "resample", "FbankEngine": "fbank", "HubertFeatureReader": "hubert", "AsrTranscriber": "asr"}
+
+
+def __getattr__(name):
+    """The engines by name, imported at first use (importing the package stays as light as it was)."""
+    if name in _ENGINES:
+        import importlib
+
+        return getattr(importlib.import_module("." + _ENGINES[name], __name__), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

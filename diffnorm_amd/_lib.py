@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdiffnorm_hip.so")
 
 DN_F32, DN_BF16, DN_BF16X3, DN_F16 = 0, 1, 2, 3
+DN_I16 = 16  # a sample format of dn_resample_forward's input, no arithmetic mode
 EPI_BIAS, EPI_SILU, EPI_GEGLU, EPI_FILM_GATE, EPI_RESADD, EPI_POSEMB, EPI_RELU = range(7)
 DN_MAX_TERMS = 8
 TAG_FFN_CONV, TAG_WN_DILATED, TAG_FFN_CONV_WGRAD = 1, 2, 3
@@ -134,6 +135,10 @@ class FbankConfig(C.Structure):
     _fields_ = [("sample_rate", C.c_float), ("n_mels", C.c_int32), ("frame_length", C.c_int32), ("frame_shift", C.c_int32), ("n_fft", C.c_int32),
                 ("low_freq", C.c_float), ("high_freq", C.c_float), ("preemphasis", C.c_float), ("remove_dc_offset", C.c_int32),
                 ("input_scale", C.c_float), ("norm_means", C.c_int32), ("norm_vars", C.c_int32), ("cmvn", C.c_int32)]
+
+
+class ResampleConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("orig", "new_", "width", "K", "force_global")]
 
 
 class RelAttnParams(C.Structure):
@@ -370,6 +375,12 @@ SYMBOLS = {
     "dn_fbank_out_frames": (_i32, [_vp, _i32]),
     "dn_fbank_workspace_bytes": (_sz, [_vp, _i32, _i32]),
     "dn_fbank_forward": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "dn_resample_create": (C.c_int, [_vp, _vp, _i32, _vp]),
+    "dn_resample_destroy": (None, [_vp]),
+    "dn_resample_out_length": (C.c_int64, [_vp, C.c_int64]),
+    "dn_resample_tile": (_i32, [_vp]),
+    "dn_resample_workspace_bytes": (_sz, [_vp, _i32, _i32]),
+    "dn_resample_forward": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "dn_set_option": (C.c_int, [C.c_char_p, _i32]),
     "dn_get_option": (C.c_int, [C.c_char_p, _vp, _vp]),
 }

@@ -5,8 +5,9 @@ engine: waveform -> per-utterance layer_norm -> wav2vec 2.0 encoder -> Linear to
 `Wav2VecCtcEngine` is dn_hubert_ctc_forward + dn_ctc_greedy of libdiffnorm_hip.so (include/diffnorm_hip.h; csrc/hubert.hip): the
 HuBERT / wav2vec 2.0 engine with a CTC head, one forward, one head contraction and one decode launch for a ragged batch, every
 utterance computed as if alone (the reference transcribes one file at a time).  `AsrTranscriber` restates ASRGenerator's surface
-without its downloads; `hf_to_fairseq_state_dict` maps a Hugging Face Wav2Vec2ForCTC state dict onto the fairseq names.  Reading audio
-files, resampling and BLEU are not done here: waveforms arrive as tensors at the model's sample rate (the vocoder emits 16 kHz).
+without its downloads; `hf_to_fairseq_state_dict` maps a Hugging Face Wav2Vec2ForCTC state dict onto the fairseq names.  BLEU and
+audio files other than 16-bit PCM WAV are not done here: waveforms arrive as tensors at the model's sample rate (the vocoder emits
+16 kHz) or at any other integer rate named with `sample_rate`, converted on the device first as utils.py:231-237 does on the host.
 """
 import re
 from typing import Dict, List, Sequence
@@ -14,7 +15,8 @@ from typing import Dict, List, Sequence
 import torch
 
 from . import _lib
-from .hubert import WAV2VEC2_LARGE, HubertEngine, _as_wave, check_hubert_args, hubert_config, out_frames, pack_ctc_head, pack_hubert
+from .hubert import (WAV2VEC2_LARGE, HubertEngine, _as_wave, _resampled, _resampler_of, check_hubert_args, hubert_config, out_frames, pack_ctc_head,
+                     pack_hubert)
 
 _W2V, _PROJ = "w2v_encoder.w2v_model.", "w2v_encoder.proj."
 FAIRSEQ_SPECIALS = ["<s>", "<pad>", "</s>", "<unk>"]
@@ -109,6 +111,7 @@ class AsrTranscriber:
         if post_process not in ("collapse", "none"):
             raise NotImplementedError(f"post_process {post_process!r} (only 'collapse' and 'none')")
         self.engine, self.tokens, self.post_process = engine, list(tokens), post_process
+        self._resamplers = None
         self.blank_token = self.tokens[0]
         self.sil_token = "|" if "|" in self.tokens else self.tokens[2]
         if engine is not None and (engine.vocab != len(self.tokens) or engine.blank != 0):
@@ -117,9 +120,22 @@ class AsrTranscriber:
     def text(self, ids: Sequence[int]) -> str:
         return post_process([self.tokens[int(i)] for i in ids], self.post_process, self.sil_token)
 
-    def transcribe(self, waves: Sequence) -> List[str]:
+    def resampler(self, sample_rate):
+        """The cached Resampler from `sample_rate` to the model's rate (cfg.sample_rate, 16 000 where the config carries none); None
+        when there is nothing to convert."""
+        return None if sample_rate is None else _resampler_of(self, self.engine.cfg, self.engine.device, sample_rate)
+
+    def transcribe(self, waves: Sequence, sample_rate=None) -> List[str]:
         """A ragged batch of waveforms (1-D, at the model's sample rate) -> one string each: one forward, one head contraction, one
-        decode launch, then one copy of the token ids to the host."""
+        decode launch, then one copy of the token ids to the host.  sample_rate: the waveforms' rate when it is not the model's
+        (utils.py:231-237): they are resampled on the device first ([n] or [n, C], fp32 or int16, as Resampler.forward takes them)."""
+        _, _, tokens, counts = self.forward(waves, sample_rate=sample_rate)
+        tokens, counts = tokens.cpu(), counts.cpu()
+        return [self.text(tokens[j, : int(counts[j])].tolist()) for j in range(len(waves))]
+
+    def forward(self, waves: Sequence, sample_rate=None):
+        """The engine's forward on the padded batch transcribe() builds -> (emissions, frame counts, token ids, token counts)."""
+        waves = _resampled(self.resampler(sample_rate), waves)
         waves = [_as_wave(w) for w in waves]
         lens = torch.tensor([w.numel() for w in waves], dtype=torch.int32)
         for n in lens.tolist():
@@ -128,9 +144,7 @@ class AsrTranscriber:
         batch = torch.zeros(len(waves), int(lens.max()), device=waves[0].device if all(w.device == waves[0].device for w in waves) else "cpu")
         for j, w in enumerate(waves):
             batch[j, : w.numel()] = w
-        _, _, tokens, counts = self.engine.forward(batch, lens)
-        tokens, counts = tokens.cpu(), counts.cpu()
-        return [self.text(tokens[j, : int(counts[j])].tolist()) for j in range(len(waves))]
+        return self.engine.forward(batch, lens)
 
 
 _HF_LAYER = {"attention.q_proj": "self_attn.q_proj", "attention.k_proj": "self_attn.k_proj", "attention.v_proj": "self_attn.v_proj",

@@ -6,7 +6,8 @@ torchaudio.compliance.kaldi.fbank(waveform, num_mel_bins=80, sample_frequency=sr
 `FbankEngine` is dn_fbank_* of libdiffnorm_hip.so (include/diffnorm_hip.h; csrc/fbank.hip).  The device path is the deterministic
 torchaudio form, dither 0 (pyKaldi's own default adds random dither 1.0).  A batch gives every utterance what it gets alone, bit for
 bit, and nothing at or behind an utterance's own samples is read.  Waveforms arrive as tensors or arrays at the configured sample
-rate; decoding, resampling and channel selection are not done here.
+rate, or at any other integer rate named with `sample_rate`, which is converted on the device first (diffnorm_amd/resample.py);
+decoding audio files other than 16-bit PCM WAV is not done here.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -139,15 +140,29 @@ class FbankEngine(_NarEngine):
         self.cfg = cfg if cfg is not None else FbankConfig()
         self.n_mels = int(self.cfg.n_mels)
         self.frames_per_workgroup = POINTS_PER_WORKGROUP // self.cfg.fft_size
+        self._resamplers = None
         self._create(device, [torch.from_numpy(t) for t in host_tables(self.cfg)], self.cfg.c_struct())
 
     def out_frames(self, L: int) -> int:
         return int(self.lib.dn_fbank_out_frames(self.handle, int(L)))
 
-    def forward(self, wave, lengths=None):
+    def resampler(self, sample_rate):
+        """The cached Resampler from `sample_rate` to the configured rate; None when there is nothing to convert."""
+        if self._resamplers is None:
+            from .resample import ResamplerCache
+
+            self._resamplers = ResamplerCache(self.cfg.sample_rate, self.device)
+        return self._resamplers.get(sample_rate)
+
+    def forward(self, wave, lengths=None, sample_rate=None):
         """wave [B, L] with lengths [B] in samples (host or device; anything, NaN included, may lie behind an utterance's samples), or
         a list of 1-D waveforms of unequal length, padded here -> (feats fp32 [B, Lf, n_mels] with zero rows behind each utterance's
-        frames, frame counts int32 [B] on the device).  An utterance shorter than one frame gets zero frames, not an error."""
+        frames, frame counts int32 [B] on the device).  An utterance shorter than one frame gets zero frames, not an error.
+        sample_rate: the rate of `wave` when it is not the configured one -- the batch goes through Resampler.forward first (which
+        also takes int16 and [B, L, C] input and hands on [-1, 1]-scaled mono for int16) and the features are those of its output."""
+        rs = self.resampler(sample_rate) if sample_rate is not None else None
+        if rs is not None:
+            wave, lengths = rs.forward(wave, lengths)
         if not isinstance(wave, torch.Tensor):
             waves = [_as_wave(w) for w in wave]
             if not waves:

@@ -6,7 +6,8 @@ pretrained/hubert_feature_reader.py) and scripts/prepare/quantize_unit.sh (quant
 padding_mask=None, mask=False, output_layer=k) (fairseq/models/hubert/hubert.py:429-476, 529-545) in eval mode, with the reader's
 contract that an utterance is run ALONE -- a batch gives every utterance exactly that.  `HubertFeatureReader` is the reader's chunk
 loop over it, `KMeansQuantizer` the unit assignment, `dump_features` the `{split}.manifest.tsv` + `.npy` layout diffnorm_amd/data.py
-reads.  Waveforms arrive as tensors or arrays at the model's sample rate; decoding and resampling audio files is not done here.
+reads.  Waveforms arrive as tensors or arrays at the model's sample rate, or at any other integer rate named with `sample_rate`,
+which is converted on the device first (diffnorm_amd/resample.py); decoding audio files other than 16-bit PCM WAV is not done here.
 """
 from types import SimpleNamespace
 from typing import Dict, Iterable, List, Sequence, Tuple
@@ -241,6 +242,25 @@ class HubertEngine(_NarEngine):
         return out, lens
 
 
+def _resampler_of(owner, cfg, device, sample_rate):
+    """owner's cached Resampler from `sample_rate` to cfg's own rate (16 000 where cfg carries none); None: nothing to convert."""
+    if sample_rate is None:
+        return None
+    if getattr(owner, "_resamplers", None) is None:
+        from .resample import ResamplerCache
+
+        owner._resamplers = ResamplerCache(getattr(cfg, "sample_rate", 16000), device)
+    return owner._resamplers.get(sample_rate)
+
+
+def _resampled(rs, waves: Sequence) -> Sequence:
+    """The waveforms as they are (rs None), or each one's own samples of the resampled batch, on the device."""
+    if rs is None:
+        return waves
+    out, lens = rs.forward(list(waves))
+    return [out[i, :n] for i, n in enumerate(lens.tolist())]
+
+
 def chunk_bounds(n: int, max_chunk: int) -> List[Tuple[int, int]]:
     """The reader's chunk loop (hubert_feature_reader.py:52-53): [start, start + max_chunk) over n samples."""
     return [(s, min(s + max_chunk, n)) for s in range(0, n, max_chunk)]
@@ -256,6 +276,12 @@ class HubertFeatureReader:
             raise ValueError(f"layer {layer} outside 1 .. {cfg.encoder_layers}")
         self.cfg, self.layer, self.max_chunk = cfg, layer, int(max_chunk)
         self.engine = engine if engine is not None else HubertEngine(state_dict, cfg, dtype=dtype, device=device)
+        self._resamplers = None
+
+    def resampler(self, sample_rate):
+        """The cached Resampler from `sample_rate` to the model's rate (cfg.sample_rate, 16 000 where the config carries none); None
+        when there is nothing to convert."""
+        return None if sample_rate is None else _resampler_of(self, self.cfg, self.engine.device, sample_rate)
 
     def _check_chunks(self, n: int):
         bounds = chunk_bounds(n, self.max_chunk)
@@ -269,12 +295,16 @@ class HubertFeatureReader:
                 raise ValueError(f"a chunk of {e - s} samples (at {s} of {n}) is shorter than one frame of the conv stack")
         return bounds
 
-    def get_feats(self, wave) -> torch.Tensor:
+    def get_feats(self, wave, sample_rate=None) -> torch.Tensor:
         """One waveform [n] -> features [T, dim] on the engine's device."""
-        return self.get_feats_batch([wave])[0]
+        return self.get_feats_batch([wave], sample_rate=sample_rate)[0]
 
-    def get_feats_batch(self, waves: Sequence) -> List[torch.Tensor]:
-        """A ragged batch of waveforms, one chunk round at a time: round r runs chunk r of every waveform that has one as one batch."""
+    def get_feats_batch(self, waves: Sequence, sample_rate=None) -> List[torch.Tensor]:
+        """A ragged batch of waveforms, one chunk round at a time: round r runs chunk r of every waveform that has one as one batch.
+        sample_rate: the waveforms' rate when it is not the model's -- they are resampled on the device first ([n] or [n, C], fp32 or
+        int16, as Resampler.forward takes them) and the chunk loop runs over the resampled waveforms, as the reference's reader
+        sees audio its loader has already converted."""
+        waves = _resampled(self.resampler(sample_rate), waves)
         waves = [_as_wave(w) for w in waves]
         bounds = [self._check_chunks(w.numel()) for w in waves]
         parts: List[List[torch.Tensor]] = [[] for _ in waves]
@@ -332,15 +362,17 @@ class KMeansQuantizer:
         return units
 
 
-def dump_features(reader: HubertFeatureReader, items: Iterable[Tuple[str, object]], out_features_path: str, batch: int = 8) -> str:
+def dump_features(reader: HubertFeatureReader, items: Iterable[Tuple[str, object]], out_features_path: str, batch: int = 8, sample_rate=None) -> str:
     """(file id, waveform) pairs -> `{out_features_path}/{id}.feat.npy` and the `{split}.manifest.tsv` beside it, through
-    data.write_feature_manifest: the layout load_samples / load_normalization_inputs read.  Returns the manifest path."""
+    data.write_feature_manifest: the layout load_samples / load_normalization_inputs read.  Returns the manifest path.
+    sample_rate: the waveforms' rate when it is not the model's (get_feats_batch resamples each group on the device)."""
     items = list(items)
+    rate = {} if sample_rate is None else {"sample_rate": sample_rate}  # (a reader without the keyword keeps working at its own rate)
 
     def feats():
         for s in range(0, len(items), batch):
             group = items[s: s + batch]
-            for (fid, _), f in zip(group, reader.get_feats_batch([w for _, w in group])):
+            for (fid, _), f in zip(group, reader.get_feats_batch([w for _, w in group], **rate)):
                 yield fid, f.cpu().numpy()
 
     return data.write_feature_manifest(out_features_path, feats())

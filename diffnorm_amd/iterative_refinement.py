@@ -83,7 +83,9 @@ class IterativeRefinementGenerator:
         return (before == tokens).all(dim=1), after_out._replace(output_tokens=tokens, output_scores=scores, attn=attn)
 
     @torch.no_grad()
-    def generate(self, models, sample, prefix_tokens=None, constraints=None):
+    def generate(self, models, sample, prefix_tokens=None, constraints=None, sample_rate=None):
+        # sample_rate (or sample["net_input"]["sample_rate"]): the rate of waveform src_tokens when it is not the model's own; a
+        # waveform-input model (NARS2UTDecoderModel(waveform_input=...)) resamples the batch on the device first
         if constraints is not None:
             raise NotImplementedError("Constrained decoding with the IterativeRefinementGenerator is not supported")
         if not self.retain_dropout:
@@ -105,7 +107,11 @@ class IterativeRefinementGenerator:
             assert self.beam_size == 1, "beam search is not supported with true length"
             target_length = sample["target"].ne(self.pad).sum(dim=1)
 
-        encoder_out = model.forward_encoder([src_tokens, src_lengths])
+        sample_rate = sample["net_input"].get("sample_rate") if sample_rate is None else sample_rate
+        if sample_rate is None:
+            encoder_out = model.forward_encoder([src_tokens, src_lengths])
+        else:
+            encoder_out = model.forward_encoder([src_tokens, src_lengths], sample_rate=sample_rate)
         if self.speech_source:
             assert not self.use_true_length, "the speech-source generator has no true-length option"
             state = model.initialize_output_tokens(encoder_out, src_lengths)

@@ -276,9 +276,11 @@ class _HipEncoder:
     def __init__(self, engine, fbank=None):  # a NarEncoderEngine or a ConformerEncoderEngine; fbank: a FbankEngine in front of it
         self.engine, self.fbank = engine, fbank
 
-    def __call__(self, src_tokens, src_lengths=None):
+    def __call__(self, src_tokens, src_lengths=None, sample_rate=None):
+        if sample_rate is not None and self.fbank is None:
+            raise ValueError("sample_rate belongs to waveform input (waveform_input=...): features have no sample rate to convert")
         if self.fbank is not None:  # src_tokens [B, L] waveforms, src_lengths in samples -> features; their lengths stay on the device
-            src_tokens, src_lengths = self.fbank.forward(src_tokens, src_lengths)
+            src_tokens, src_lengths = self.fbank.forward(src_tokens, src_lengths, sample_rate=sample_rate)
         x, lens = self.engine.forward(src_tokens, src_lengths)
         S = x.shape[1]
         pad = torch.arange(S, device=x.device)[None, :] >= lens[:, None]
@@ -585,8 +587,9 @@ class NARS2UTDecoderModel:
     def eval(self):
         return self
 
-    def forward_encoder(self, encoder_inputs):
-        return self.encoder(*encoder_inputs)
+    def forward_encoder(self, encoder_inputs, sample_rate=None):
+        """sample_rate: the rate of waveform input when it is not the fbank front end's own (resampled on the device first)."""
+        return self.encoder(*encoder_inputs) if sample_rate is None else self.encoder(*encoder_inputs, sample_rate=sample_rate)
 
     def _prepared(self, enc):
         """The engine's view of an encoder output, cached in the dict: batch-major fp32 copy -> cross keys / values; source lengths."""

@@ -1402,6 +1402,47 @@ size_t dn_fbank_workspace_bytes(const DnFbank* m, int32_t B, int32_t L);
 int dn_fbank_forward(DnFbank* m, const float* wave, const int32_t* lengths, int32_t B, int32_t L, float* out, int32_t* out_lengths,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ sample-rate conversion in front of the three waveform front ends */
+/* What the reference's loaders do before a model sees audio: torchaudio.functional.resample(waveform, sample_rate, 16000) in the ASR
+ * loader (examples/speech_to_speech/asr_bleu/utils.py:231-237; research/TranSpeech/asr_bleu/utils.py:237) and the `to_mono` step of
+ * convert_waveform (fairseq/data/audio/audio_utils.py:22-72: the mean over the channels).  The filter is torchaudio's windowed-sinc
+ * polyphase bank, stated in diffnorm_amd/resample.py (resample_tables), which is where it is computed: in float64, rounded once.
+ * With orig and new divided by their gcd, width = ceil(lowpass_filter_width * orig / (min(orig, new) * rolloff)), K = 2 width + orig:
+ *   out[b, i * new + p] = sum_{k < K} bank[p][k] * x_b[i * orig + k - width],  x_b = 0 outside [0, lengths[b]),
+ * for i * new + p < out_length(lengths[b]) = ceil(new * lengths[b] / orig).  The sum runs over k in ascending order as fp32 FMAs from
+ * zero on every path and in every tile: an utterance's output depends on its own samples and length only, not on B, L, the row or
+ * the neighbours.  Kernel: csrc/resample.hip.                                                                                   */
+#define DN_I16 16 /* a SAMPLE FORMAT of dn_resample_forward's input (16-bit PCM, scaled by 2^-15 in the load); no arithmetic mode */
+typedef struct DnResample DnResample;
+typedef struct {
+  int32_t orig, new_;       /* the rates divided by their gcd, both >= 1 */
+  int32_t width, K;         /* as above; K = 2 width + orig */
+  int32_t force_global;     /* != 0: read the bank from global memory even where it fits in LDS (the two paths give identical bits) */
+} DnResampleConfig;
+/* tables: device pointers to { bank fp32 [new][K], the same bank transposed fp32 [K][new] } (they must outlive the handle).  The
+ * bank is staged in LDS beside the input span when new * (K | 1) <= 8192 floats (32 KiB beside a span of at most 32 KiB); a larger
+ * bank (441 : 160, 441 : 320) is read from the transposed copy in global memory, lanes on consecutive phases.  Refused: a
+ * configuration whose one-frame span K (+ 1 / 32 skew) exceeds the 8192 staged floats.  (torchaudio.functional.resample's
+ * _get_sinc_resample_kernel, which asr_bleu/utils.py:231-237 reaches, is the table's definition.)                                */
+int dn_resample_create(const DnResampleConfig* cfg, const void* const* tables, int32_t n_tables, DnResample** out);
+void dn_resample_destroy(DnResample* m);
+/* ceil(new * L / orig) in 64-bit arithmetic (torchaudio's target_length, reached from asr_bleu/utils.py:231-237); 0 for L <= 0 */
+int64_t dn_resample_out_length(const DnResample* m, int64_t L);
+/* output samples per workgroup tile: frames_per_tile * new, about 1024 (the geometry the tests name their edges from; no reference
+ * counterpart, the reference's resampler is one conv1d call)                                                                   */
+int32_t dn_resample_tile(const DnResample* m);
+/* 0: the forward needs no workspace; the entry exists for the engines' common calling pattern (asr_bleu/utils.py:231-237 has none) */
+size_t dn_resample_workspace_bytes(const DnResample* m, int32_t B, int32_t L);
+/* in: [B, L, channels] interleaved samples, in_dtype DN_F32 or DN_I16 (anything, NaN included, at and behind an utterance's samples:
+ * they are never read); a sample is converted (int16 * 2^-15, exact) and the channels are summed in fp32 in channel order and divided
+ * by their count as part of the load (convert_waveform's to_mono, audio_utils.py:49-50; channels 1: the sample itself).
+ * lengths int32 [B] on the device (clamped to [0, L]) -> out fp32 [B, Lo], Lo = dn_resample_out_length(m, L), zeros at and behind
+ * out_lengths[b] = dn_resample_out_length(m, lengths[b]), which is written on the device.  An empty utterance is a handled case.
+ * Stream-ordered, no allocation, no synchronisation with the host.  Replaces torchaudio.functional.resample at
+ * asr_bleu/utils.py:231-237.  Every argument is checked before the launch (a refused call has written nothing).                  */
+int dn_resample_forward(DnResample* m, const void* in, int32_t in_dtype, int32_t channels, const int32_t* lengths, int32_t B, int32_t L, float* out,
+                        int32_t* out_lengths, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
