@@ -7,7 +7,8 @@ fairseq_plugin/ (register_model / register_task / register_criterion surface).
 """
 __version__ = "0.1.0"
 
-_ENGINES = {"Resampler": "resample", "FbankEngine": "fbank", "HubertFeatureReader": "hubert", "AsrTranscriber": "asr"}
+_ENGINES = {"Resampler": "resample", "FbankEngine": "fbank", "HubertFeatureReader": "hubert", "AsrTranscriber": "asr",
+            "KMeansQuantizer": "hubert", "KMeansTrainer": "kmeans", "learn_kmeans": "kmeans"}
 
 
 def __getattr__(name):

@@ -359,6 +359,10 @@ SYMBOLS = {
     "dn_grouped_conv1d": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dn_kmeans_workspace_bytes": (_sz, [_i32, _i32]),
     "dn_kmeans_assign": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "dn_kmeans_workspace_bytes_train": (_sz, [_i32, _i32]),
+    "dn_kmeans_accumulate": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dn_kmeans_update": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "dn_kmeans_min_dist": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "dn_hubert_create": (C.c_int, [_vp, _vp, _i32, _vp]),
     "dn_hubert_destroy": (None, [_vp]),
     "dn_hubert_out_frames": (_i32, [_vp, _i32]),

@@ -1292,6 +1292,31 @@ size_t dn_kmeans_workspace_bytes(int32_t M, int32_t n_centroids);
 int dn_kmeans_assign(const float* feats, const float* centroids, const float* half_norm, int32_t M, int32_t D, int32_t n_centroids,
                      int32_t* units, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Learning that codebook: one step of sklearn.cluster.MiniBatchKMeans (cluster_kmeans.py / learn_kmeans.py of the reference) is
+ * dn_kmeans_assign -> dn_kmeans_accumulate -> dn_kmeans_update (diffnorm_amd/csrc/kmeans.hip).  D a multiple of 32 (<= 4096),
+ * n <= 8192; feats, centers, sums 16-byte aligned; every workspace is dn_kmeans_workspace_bytes_train(M, n), 256-byte aligned.
+ *
+ * dn_kmeans_accumulate: sums[j][:] = sum of the rows with labels[m] == j (double [n, D]), counts[j] their number, inertia[0] =
+ * sum_m |x_m - c_labels[m]|^2 from the differences, in double.  centers: the packed fp32 matrix dn_kmeans_assign reads (row stride D).
+ * A stable counting sort of the row indices by label, then one wave per (cluster, 256 columns) adds that cluster's rows in ascending
+ * row index: no floating-point atomics, the same bits on every call and for every M; an empty cluster gets count 0 and sums 0.  A
+ * label outside [0, n) is never used as an index: its row is left out (callers check labels they did not get from dn_kmeans_assign).
+ *
+ * dn_kmeans_update: for every cluster with counts[j] > 0, c_j <- (c_j w_j + sums[j]) / (w_j + counts[j]) in double, rounded once to
+ * fp32, w_j += counts[j] (weight_sums double [n]), half_norm[j] <- -|c_j|^2 / 2 of the rounded centre, in double, rounded once.  The
+ * other clusters keep their bits.
+ *
+ * dn_kmeans_min_dist (k-means++ seeding): d2[m][j] = |x_m - cands[j]|^2 (differences, double accumulation, rounded once to fp32) for
+ * k <= 16 candidates (cands fp32 [k, D]); pot[j] = sum_m min(mind2[m], d2[m][j]) in double, summed in a fixed order; commit >= 0
+ * also stores mind2[m] <- min(mind2[m], d2[m][commit]) (commit -1: mind2 is only read).                                          */
+size_t dn_kmeans_workspace_bytes_train(int32_t M, int32_t n_clusters);
+int dn_kmeans_accumulate(const float* feats, const int32_t* labels, const float* centers, int32_t M, int32_t D, int32_t n_clusters, double* sums,
+                         int32_t* counts, double* inertia, void* workspace, size_t workspace_bytes, void* stream);
+int dn_kmeans_update(float* centers, float* half_norm, double* weight_sums, const double* sums, const int32_t* counts, int32_t n_clusters, int32_t D,
+                     void* stream);
+int dn_kmeans_min_dist(const float* feats, int32_t M, int32_t D, const float* cands, int32_t k, int32_t commit, float* mind2, double* pot,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* Packed tensors (diffnorm_amd/hubert.py::pack_hubert; matrices [rows -> 128][K] in cfg.dtype, everything else fp32):
  *   0 conv0_w fp32 [16][C] (tap j of channel c at [j][c], zero rows behind the kernel)   1 GroupNorm gamma [C]   2 beta [C]
  *   3 .. n_conv + 1: conv layer i >= 1 as [C][k_i C], column j C + c = weight[o][c][j]
