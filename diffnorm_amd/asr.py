@@ -133,6 +133,20 @@ class AsrTranscriber:
         tokens, counts = tokens.cpu(), counts.cpu()
         return [self.text(tokens[j, : int(counts[j])].tolist()) for j in range(len(waves))]
 
+    def score(self, waves: Sequence, references: Sequence[str], sample_rate=None, unit: str = "word"):
+        """transcribe() followed by the error rate against `references` -> (transcripts, metrics.ErrorRate): word error rate
+        (unit "word": str.split() tokens) or character error rate (unit "char": code points), the distances on the device
+        (metrics.wer / metrics.cer).  The transcripts are what transcribe() returns (stripped, lower case); the references are
+        compared as they are given: case and punctuation are the caller's."""
+        from . import metrics
+
+        if unit not in ("word", "char"):
+            raise ValueError(f"AsrTranscriber.score: unit {unit!r} ('word' or 'char')")
+        if len(references) != len(waves):
+            raise ValueError(f"AsrTranscriber.score: {len(references)} references for {len(waves)} waveforms")
+        hyps = self.transcribe(waves, sample_rate=sample_rate)
+        return hyps, (metrics.wer if unit == "word" else metrics.cer)(hyps, list(references), device=self.engine.device)
+
     def forward(self, waves: Sequence, sample_rate=None):
         """The engine's forward on the padded batch transcribe() builds -> (emissions, frame counts, token ids, token counts)."""
         waves = _resampled(self.resampler(sample_rate), waves)

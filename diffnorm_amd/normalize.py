@@ -76,7 +76,8 @@ def tsv_line(it: Utterance, pred_units: Sequence[int]) -> str:
 def normalize(ddim_sample: Callable, utterances: Sequence[Utterance], start_step: int = 50, batch_size: int = 100,
               device="cuda:0", group=None, sampling_steps: Optional[int] = None, eta: float = 0.0, seed: int = 0,
               solver: Optional[str] = None, noise_seed: Optional[int] = None, max_tokens: Optional[int] = None,
-              max_sentences: Optional[int] = None, pad_multiple: int = 1, keyed_steps: bool = False) -> Optional[List[str]]:
+              max_sentences: Optional[int] = None, pad_multiple: int = 1, keyed_steps: bool = False,
+              unit_changes: Optional[list] = None) -> Optional[List[str]]:
     """Runs `ddim_sample(feat, input_mask=..., ref_units=..., start_step=...)` (LatentDiscreteModel.ddim_sample) over this
     rank's batches and gathers the TSV lines of all ranks in utterance order (every rank returns the full list).
     `sampling_steps` (evaluations per chain instead of start_step-1), `eta`, `seed` and `solver` ("dpmpp_2m": the second-order
@@ -90,10 +91,15 @@ def normalize(ddim_sample: Callable, utterances: Sequence[Utterance], start_step
     `pad_multiple` > 1 also rounds the consecutive batches' T up.  `keyed_steps` (needs `noise_seed`): a stochastic chain
     (`eta` != 0) draws its per-step noise from the utterance's key as well (the sampler's `keyed_steps=True`; `seed` is not used),
     so it keeps the same promises; without it `noise_seed` refuses `eta` != 0.  With the five unset this is the reference's batching
-    and noise."""
+    and noise.
+
+    `unit_changes`: a list that receives one `(audio_id, errors, n_ref, n_hyp)` per utterance, in utterance order, on every rank
+    (gathered as the lines are): the edit distance between the de-duplicated predicted units and the utterance's `reduce_tgt_unit`
+    -- how far normalisation moved the units -- computed on the device from the batch's prediction (metrics.unit_changes) before
+    it is brought to the host.  The returned lines do not depend on it."""
     if noise_seed is not None or max_tokens is not None or max_sentences is not None or pad_multiple != 1 or keyed_steps:
         return _normalize_keyed(ddim_sample, utterances, start_step, batch_size, device, group, sampling_steps, eta, solver,
-                                noise_seed, max_tokens, max_sentences, pad_multiple, keyed_steps)
+                                noise_seed, max_tokens, max_sentences, pad_multiple, keyed_steps, unit_changes)
     rank, world = sharding.rank_world(group)
     # A run must give the same results on any number of ranks (and whatever sizes the last batches have).  The 2-byte / f32
     # contractions' fast K order (taps of a causal conv innermost, one staged copy of the rows, on the two 256-row tiles) sums in a
@@ -109,7 +115,7 @@ def normalize(ddim_sample: Callable, utterances: Sequence[Utterance], start_step
     chosen = _lib.get_option("taps_inner")
     batches = sharding.batch_indices(len(utterances), batch_size)
     mine = sharding.my_batches(len(batches), rank, world)
-    local = []
+    local, changes = [], []
     extra = {}
     if sampling_steps is not None:
         extra["sampling_steps"] = sampling_steps
@@ -123,13 +129,24 @@ def normalize(ddim_sample: Callable, utterances: Sequence[Utterance], start_step
             feat, ref_units, lens = assemble_batch(items, device)
             mask = torch.arange(feat.shape[1], device=lens.device).view(1, -1) < lens.view(-1, 1)
             pred, _, _, _ = ddim_sample(feat, input_mask=mask, cond_scale=1.0, ref_units=ref_units, start_step=start_step, **extra)
+            if unit_changes is not None:
+                changes.append(_batch_changes(items, pred, ref_units, lens))
             local.append([tsv_line(it, p.tolist()) for it, p in zip(items, pred)])
     per_batch = sharding.gather_in_order(local, mine, len(batches), group)
+    if unit_changes is not None:
+        unit_changes.extend(c for got in sharding.gather_in_order(changes, mine, len(batches), group) for c in got)
     return [line for lines in per_batch for line in lines]
 
 
+def _batch_changes(items, pred, ref_units, lens) -> List[tuple]:
+    """(audio_id, errors, n_ref, n_hyp) of a batch, from its prediction while that is still on the device."""
+    from . import metrics
+
+    return [(it.audio_id,) + c for it, c in zip(items, metrics.unit_changes(pred, ref_units, lens))]
+
+
 def _normalize_keyed(ddim_sample, utterances, start_step, batch_size, device, group, sampling_steps, eta, solver, noise_seed,
-                     max_tokens, max_sentences, pad_multiple, keyed_steps=False) -> List[str]:
+                     max_tokens, max_sentences, pad_multiple, keyed_steps=False, unit_changes=None) -> List[str]:
     """normalize() with per-utterance noise keys and, under `max_tokens`, frame-budget batches (see normalize)."""
     if noise_seed is None and keyed_steps:
         raise ValueError("normalize: keyed_steps draws the per-step noise from the utterances' keys: set noise_seed")
@@ -165,7 +182,7 @@ def _normalize_keyed(ddim_sample, utterances, start_step, batch_size, device, gr
     if keyed_steps:
         extra["keyed_steps"] = True
     chosen = _lib.get_option("taps_inner")
-    local = []
+    local, changes = [], []
     with _lib.option("taps_inner", 2 if chosen is None else chosen):  # routing by shape, as normalize()
         for b in mine:
             items = [utterances[i] for i in batches[b]]
@@ -174,10 +191,18 @@ def _normalize_keyed(ddim_sample, utterances, start_step, batch_size, device, gr
             keys = sharding.utterance_keys(noise_seed, batches[b])
             pred, _, _, _ = ddim_sample(feat, input_mask=mask, cond_scale=1.0, ref_units=ref_units, start_step=start_step,
                                         noise_keys=keys, **extra)
+            if unit_changes is not None:
+                changes.append(_batch_changes(items, pred, ref_units, lens))
             local.append([tsv_line(it, p.tolist()) for it, p in zip(items, pred)])
     per_batch = sharding.gather_in_order(local, mine, len(batches), group)
     lines = [None] * len(utterances)  # back to utterance order
     for ids, got in zip(batches, per_batch):
         for i, line in zip(ids, got):
             lines[i] = line
+    if unit_changes is not None:
+        ordered = [None] * len(utterances)
+        for ids, got in zip(batches, sharding.gather_in_order(changes, mine, len(batches), group)):
+            for i, c in zip(ids, got):
+                ordered[i] = c
+        unit_changes.extend(ordered)
     return lines

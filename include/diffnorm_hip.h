@@ -1468,6 +1468,35 @@ size_t dn_resample_workspace_bytes(const DnResample* m, int32_t B, int32_t L);
 int dn_resample_forward(DnResample* m, const void* in, int32_t in_dtype, int32_t channels, const int32_t* lengths, int32_t B, int32_t L, float* out,
                         int32_t* out_lengths, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ scores over integer sequences: edit distance, run-length reduction */
+/* What says how good a result is: the share of units normalisation changed, and the word / character error rate of a vocoder -> ASR
+ * loop.  Both are a unit-cost Levenshtein distance (substitution, insertion, deletion cost 1 each) over integer sequences; units are
+ * compared after run-length de-duplication.  Replaces the `editdistance.eval(hyp_words, ref_words)` calls of fairseq's WER scorer
+ * (fairseq/scoring/wer.py:50-58) and the reference's own one-thread-per-pair kernel's role (fairseq/clib/libnat_cuda), and the
+ * per-utterance Python loop of diff_norm_synthesis.py:25-46 (reduce_token).  Kernels: csrc/metrics.hip, written for gfx950: one
+ * wavefront per pair, the shorter sequence's columns in per-lane register strips, rows skewed one step per lane, the strip boundary
+ * handed on by a DPP wave shift; pairs whose shorter side exceeds 2048 tokens are swept in panels of 2048 columns with the panel's
+ * last column in the workspace.  Integer arithmetic, no atomics: bit-identical between calls and independent of B, of the pair's
+ * position and of lda / ldb.                                                                                                      */
+#define DN_EDIT_DISTANCE_MAX_LEN 8192
+/* bytes dn_edit_distance needs for B pairs with rows of max_len_a / max_len_b tokens (0 for arguments it would refuse) */
+size_t dn_edit_distance_workspace_bytes(int32_t B, int32_t max_len_a, int32_t max_len_b);
+/* a int32 [B, lda], b int32 [B, ldb], a_len / b_len int32 [B] on the device (clamped to [0, lda] / [0, ldb]; elements at or behind a
+ * length are never read) -> dist int32 [B]: dist[i] = Levenshtein(a[i, :a_len[i]], b[i, :b_len[i]]); an empty side gives the other
+ * side's length.  lda, ldb in 1 .. DN_EDIT_DISTANCE_MAX_LEN (refused beyond).  panel_cols: 0 = the kernel's own (2048); otherwise a
+ * multiple of 64 up to 2048: the columns of a panel, so that the workspace path can be run on short pairs (the results are the
+ * same numbers).  workspace: 4-byte aligned, dn_edit_distance_workspace_bytes(B, lda, ldb).  Stream-ordered, no allocation, no
+ * synchronisation with the host; every argument is checked before the launch.                                                   */
+int dn_edit_distance(const int32_t* a, int32_t lda, const int32_t* a_len, const int32_t* b, int32_t ldb, const int32_t* b_len, int32_t B,
+                     int32_t* dist, int32_t panel_cols, void* workspace, size_t workspace_bytes, void* stream);
+/* Batched run-length de-duplication, the device form of reduce_token (diff_norm_synthesis.py:25-46): units int32 [B, ld], lengths
+ * int32 [B] (clamped to [0, ld]) -> reduced int32 [B, ld]: row b holds its runs' values in order, zeros at and behind
+ * reduced_len[b]; reduced_len int32 [B]; durations int32 [B, ld]: the runs' lengths; first int32 [B, ld]: the index of each run's
+ * first frame (both zero behind reduced_len[b]; either may be null).  One pass, one wavefront per row, no atomics; the outputs must
+ * not alias the input.                                                                                                            */
+int dn_reduce_units(const int32_t* units, const int32_t* lengths, int32_t B, int32_t ld, int32_t* reduced, int32_t* reduced_len,
+                    int32_t* durations, int32_t* first, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
