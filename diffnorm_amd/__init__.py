@@ -2,7 +2,7 @@
 
 Layout: csrc/ (HIP kernels + C-ABI engine -> libdiffnorm_hip.so), _lib.py (ctypes binding), ops.py
 (op-level wrappers), packing.py (state-dict -> packed weights), engine.py (engine handles),
-scheduler.py (noise schedules), metrics.py (edit distance, unit / word / character error rates), latent_module.py (host mirror of the reference modules),
+scheduler.py (noise schedules), metrics.py (edit distance, unit / word / character error rates, BLEU), latent_module.py (host mirror of the reference modules),
 fairseq_plugin/ (register_model / register_task / register_criterion surface).
 """
 __version__ = "0.1.0"
@@ -10,7 +10,7 @@ __version__ = "0.1.0"
 _ENGINES = {"Resampler": "resample", "FbankEngine": "fbank", "HubertFeatureReader": "hubert", "AsrTranscriber": "asr",
             "KMeansQuantizer": "hubert", "KMeansTrainer": "kmeans", "learn_kmeans": "kmeans",
             "ErrorRate": "metrics", "edit_distance": "metrics", "reduce_units": "metrics", "unit_error_rate": "metrics", "wer": "metrics",
-            "cer": "metrics"}
+            "cer": "metrics", "BleuScore": "metrics", "bleu_stats": "metrics", "bleu": "metrics", "unit_bleu": "metrics"}
 
 
 def __getattr__(name):

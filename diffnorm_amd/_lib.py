@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, "libdiffnorm_hip.so")
 
 DN_F32, DN_BF16, DN_BF16X3, DN_F16 = 0, 1, 2, 3
 EDIT_DISTANCE_MAX_LEN = 8192  # DN_EDIT_DISTANCE_MAX_LEN
+BLEU_ORDER, BLEU_STATS = 4, 10  # DN_BLEU_ORDER, DN_BLEU_STATS
 DN_I16 = 16  # a sample format of dn_resample_forward's input, no arithmetic mode
 EPI_BIAS, EPI_SILU, EPI_GEGLU, EPI_FILM_GATE, EPI_RESADD, EPI_POSEMB, EPI_RELU = range(7)
 DN_MAX_TERMS = 8
@@ -389,6 +390,8 @@ SYMBOLS = {
     "dn_edit_distance_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "dn_edit_distance": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _sz, _vp]),
     "dn_reduce_units": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "dn_bleu_stats_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "dn_bleu_stats": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
     "dn_set_option": (C.c_int, [C.c_char_p, _i32]),
     "dn_get_option": (C.c_int, [C.c_char_p, _vp, _vp]),
 }

@@ -147,6 +147,21 @@ class AsrTranscriber:
         hyps = self.transcribe(waves, sample_rate=sample_rate)
         return hyps, (metrics.wer if unit == "word" else metrics.cer)(hyps, list(references), device=self.engine.device)
 
+    def asr_bleu(self, waves: Sequence, references: Sequence[str], sample_rate=None, lowercase: bool = True, smooth: str = "exp"):
+        """transcribe() followed by BLEU against `references` -> (transcripts, metrics.BleuScore): ASR-BLEU as
+        compute_asr_bleu.py:138-153 forms it, the n-gram statistics on the device (metrics.bleu).  The transcripts are what
+        transcribe() returns; lowercase lowers both sides before they are compared (the recipe lowers the transcripts).  Tokens are
+        str.split(): punctuation in the references is the caller's to normalise."""
+        from . import metrics
+
+        metrics._check_smooth(smooth)
+        if isinstance(references, str):
+            raise ValueError("AsrTranscriber.asr_bleu: a list of reference strings is expected, not one string")
+        if len(references) != len(waves):
+            raise ValueError(f"AsrTranscriber.asr_bleu: {len(references)} references for {len(waves)} waveforms")
+        hyps = self.transcribe(waves, sample_rate=sample_rate)
+        return hyps, metrics.bleu(hyps, list(references), smooth=smooth, lowercase=lowercase, device=self.engine.device)
+
     def forward(self, waves: Sequence, sample_rate=None):
         """The engine's forward on the padded batch transcribe() builds -> (emissions, frame counts, token ids, token counts)."""
         waves = _resampled(self.resampler(sample_rate), waves)

@@ -1,11 +1,23 @@
-"""Scores of the recipe's results, computed on the device: the unit error rate of normalisation and the word / character error
-rate of a vocoder -> ASR loop.
+"""Scores of the recipe's results, computed on the device: the unit error rate of normalisation, the word / character error
+rate of a vocoder -> ASR loop, and BLEU of the decoded units (unit BLEU) and of the re-transcribed speech (ASR-BLEU).
 
-Both are a unit-cost Levenshtein distance over integer sequences (dn_edit_distance of libdiffnorm_hip.so: one wavefront per pair,
-csrc/metrics.hip), units after run-length de-duplication (dn_reduce_units, the device form of normalize.reduce_token).  They
-replace the `editdistance.eval` calls of fairseq's WER scorer (fairseq/scoring/wer.py:50-58) and the per-utterance loop of
-diff_norm_synthesis.py:25-46.  Substitution / insertion / deletion counts, alignments, weighted costs and BLEU are not done here.
-Everything is integer arithmetic: a result is exact, and depends on the pair alone."""
+The error rates are a unit-cost Levenshtein distance over integer sequences (dn_edit_distance of libdiffnorm_hip.so: one wavefront
+per pair, csrc/metrics.hip), units after run-length de-duplication (dn_reduce_units, the device form of normalize.reduce_token).
+They replace the `editdistance.eval` calls of fairseq's WER scorer (fairseq/scoring/wer.py:50-58) and the per-utterance loop of
+diff_norm_synthesis.py:25-46.  Substitution / insertion / deletion counts, alignments and weighted costs are not done here.
+
+BLEU's device part is the per-pair clipped n-gram statistics over integer ids (dn_bleu_stats: one workgroup per pair, one sort of
+the n-gram start positions, csrc/bleu.hip), the integers fairseq's libbleu defines (fairseq/clib/libbleu/libbleu.cpp:73-109,138-156)
+and a single-reference sacreBLEU sums; the score over their sums is closed-form float64 arithmetic on the host (BleuScore).  It
+replaces the sacrebleu.corpus_bleu calls of research/utils/unit_bleu.py:91,106 and research/TranSpeech/asr_bleu/compute_asr_bleu.py:153.
+smooth="none" is fairseq's Scorer.score (fairseq/scoring/bleu.py:132-151); smooth="exp" restates sacreBLEU's default smoothing and is
+pinned to that statement and to worked cases, NOT to `sacrebleu` (the module is not available to this project).  Not done here:
+sacreBLEU's `13a` tokeniser (tokens are str.split(); text normalisation is the caller's, as for `wer` -- for unit strings and CTC
+transcripts of letters and apostrophes `13a` changes nothing, for references with punctuation it does), several references per item,
+orders above 4, chrF, and a BLEU hook inside normalize().
+
+Everything on the device is integer arithmetic: a result is exact, and depends on the pair alone."""
+import math
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
@@ -254,3 +266,180 @@ def unit_changes(pred: Sequence[torch.Tensor], ref_units: torch.Tensor, ref_len:
     ref_len = ref_len.to(dev, torch.int32)
     er = _error_rate(edit_distance(red, ref_units, rlen, ref_len), rlen, ref_len)
     return list(zip(er.errors, er.ref_len, er.hyp_len))
+
+
+# ------------------------------------------------------------------------------------------ BLEU
+BLEU_ORDER = _lib.BLEU_ORDER
+SMOOTHINGS = ("exp", "none")
+
+
+def bleu_stats(hyp, ref, hyp_len=None, ref_len=None, device=None) -> torch.Tensor:
+    """BLEU's per-pair statistics of B pairs -> int32 [B, 10] on the device: hyp_len, ref_len, then match_n, count_n for n = 1 .. 4
+    with count_n = max(hyp_len - n + 1, 0) and match_n = sum over distinct n-grams of min(count in hyp, count in ref)
+    (libbleu.cpp:73-109).  hyp, ref: the input forms of `edit_distance` (device tensors with lengths, host tensors, lists of
+    sequences; rows hold at most 8192 tokens; the same host checks, one pinned upload).  Any int32 token values: only equality of
+    tokens matters.  One launch, exact, and a row depends on its pair alone."""
+    (h, hl, r, rl), device = _sides([("hyp", hyp, hyp_len), ("ref", ref, ref_len)], device)
+    B = h.shape[0]
+    if r.shape[0] != B:
+        raise ValueError(f"bleu_stats: {B} rows of hyp against {r.shape[0]} rows of ref")
+    lib = _lib.load()
+    stats = torch.empty(B, _lib.BLEU_STATS, dtype=torch.int32, device=device)
+    nbytes = lib.dn_bleu_stats_workspace_bytes(B, h.shape[1], r.shape[1])
+    ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(lib.dn_bleu_stats(h.data_ptr(), h.shape[1], hl.data_ptr(), r.data_ptr(), r.shape[1], rl.data_ptr(), B, stats.data_ptr(),
+                                     ws.data_ptr(), ws.numel() * 4, _lib.current_stream()), "dn_bleu_stats")
+    return stats
+
+
+def _check_smooth(smooth: str) -> str:
+    if smooth not in SMOOTHINGS:
+        raise ValueError(f"smooth {smooth!r} ('exp' or 'none')")
+    return smooth
+
+
+def bleu_precisions(matches: Sequence[int], counts: Sequence[int], smooth: str = "exp") -> List[float]:
+    """The four n-gram precisions of summed statistics.  "none": m_n / c_n, 0 where c_n = 0 (Scorer.precision, bleu.py:138-147).
+    "exp": walk n = 1 .. 4 with k = 1, stop at the first c_n = 0 (the rest stay 0); where m_n = 0, k <- 2k and p_n = 1 / (k c_n)."""
+    _check_smooth(smooth)
+    if smooth == "none":
+        return [m / c if c > 0 else 0.0 for m, c in zip(matches, counts)]
+    out, k = [0.0] * len(matches), 1
+    for n, (m, c) in enumerate(zip(matches, counts)):
+        if c == 0:
+            break
+        if m == 0:
+            k *= 2
+            out[n] = 1 / (k * c)
+        else:
+            out[n] = m / c
+    return out
+
+
+def bleu_brevity(hyp_len: int, ref_len: int, smooth: str = "exp") -> float:
+    """min(1, exp(1 - ref_len / hyp_len)) (Scorer.brevity, bleu.py:149-151); 0.0 for an empty hypothesis, where that line divides by
+    zero.  Under "exp": 1 if hyp_len >= ref_len, else exp(1 - ref_len / hyp_len) -- the same number."""
+    _check_smooth(smooth)
+    if hyp_len == 0:
+        return 0.0
+    if smooth == "none":
+        return min(1, math.exp(1 - ref_len / hyp_len))
+    return 1.0 if hyp_len >= ref_len else math.exp(1 - ref_len / hyp_len)
+
+
+def bleu_score(matches: Sequence[int], counts: Sequence[int], hyp_len: int, ref_len: int, smooth: str = "exp") -> float:
+    """BLEU (0 - 100) of summed statistics: BP * exp(sum_n ln p_n / 4) * 100, in float64, ln 0 = -inf.
+    "none" (Scorer.score, bleu.py:132-136): any m_n = 0 or c_n = 0 gives 0.0.  "exp" (sacreBLEU's default rule, restated): 0.0 if
+    m_1 = 0; zero matches of a higher order are smoothed (bleu_precisions), an order the hypothesis is too short for (c_n = 0) keeps
+    p_n = 0, so a hypothesis of fewer than 4 tokens scores 0.0.  An empty hypothesis gives 0.0.  Where no m_n and no c_n is zero
+    the two rules are the same number."""
+    ps = bleu_precisions(matches, counts, smooth)
+    if hyp_len == 0 or matches[0] == 0 or any(p <= 0 for p in ps):
+        return 0.0
+    psum = sum(math.log(p) for p in ps)
+    return bleu_brevity(hyp_len, ref_len, smooth) * math.exp(psum / len(ps)) * 100
+
+
+@dataclass
+class BleuScore:
+    """Per-item BLEU statistics: `matches` [B][4] and `totals` [B][4] (the clipped matches and the hypothesis's n-grams of order
+    1 .. 4) with the items' hypothesis and reference lengths.  `score` is the corpus BLEU of the SUMMED statistics (not a mean of
+    the items), `item_scores` each item scored alone (unit_bleu.py:91); both under `smooth`."""
+    matches: List[List[int]]
+    totals: List[List[int]]
+    hyp_len: List[int]
+    ref_len: List[int]
+    smooth: str = "exp"
+
+    def __post_init__(self):
+        _check_smooth(self.smooth)
+        self.matches, self.totals = ([[int(v) for v in row] for row in x] for x in (self.matches, self.totals))
+        self.hyp_len, self.ref_len = ([int(v) for v in x] for x in (self.hyp_len, self.ref_len))
+        if not len(self.matches) == len(self.totals) == len(self.hyp_len) == len(self.ref_len):
+            raise ValueError(f"BleuScore: {len(self.matches)} rows of matches, {len(self.totals)} of totals, {len(self.hyp_len)} hypothesis "
+                             f"and {len(self.ref_len)} reference lengths")
+        if any(len(row) != BLEU_ORDER for row in self.matches + self.totals):
+            raise ValueError(f"BleuScore: every row of matches and totals holds {BLEU_ORDER} orders")
+
+    def __add__(self, other: "BleuScore") -> "BleuScore":
+        if not isinstance(other, BleuScore):
+            return NotImplemented
+        if other.smooth != self.smooth:
+            raise ValueError(f"BleuScore: smooth {self.smooth!r} + smooth {other.smooth!r}")
+        return BleuScore(self.matches + other.matches, self.totals + other.totals, self.hyp_len + other.hyp_len, self.ref_len + other.ref_len,
+                         self.smooth)
+
+    @property
+    def total_matches(self) -> List[int]:
+        return [sum(row[n] for row in self.matches) for n in range(BLEU_ORDER)]
+
+    @property
+    def total_counts(self) -> List[int]:
+        return [sum(row[n] for row in self.totals) for n in range(BLEU_ORDER)]
+
+    @property
+    def total_hyp_len(self) -> int:
+        return sum(self.hyp_len)
+
+    @property
+    def total_ref_len(self) -> int:
+        return sum(self.ref_len)
+
+    @property
+    def precisions(self) -> List[float]:
+        return bleu_precisions(self.total_matches, self.total_counts, self.smooth)
+
+    @property
+    def brevity_penalty(self) -> float:
+        return float(bleu_brevity(self.total_hyp_len, self.total_ref_len, self.smooth))
+
+    @property
+    def score(self) -> float:
+        return bleu_score(self.total_matches, self.total_counts, self.total_hyp_len, self.total_ref_len, self.smooth)
+
+    @property
+    def item_scores(self) -> List[float]:
+        return [bleu_score(m, c, h, r, self.smooth) for m, c, h, r in zip(self.matches, self.totals, self.hyp_len, self.ref_len)]
+
+    def format(self) -> str:
+        """One line in the shape of Scorer.result_string (bleu.py:153-168)."""
+        ratio = self.total_hyp_len / self.total_ref_len if self.total_ref_len else 0.0
+        return "BLEU4 = {:2.2f}, {:2.1f}/{:2.1f}/{:2.1f}/{:2.1f} (BP={:.3f}, ratio={:.3f}, syslen={}, reflen={})".format(
+            self.score, *[p * 100 for p in self.precisions], self.brevity_penalty, ratio, self.total_hyp_len, self.total_ref_len)
+
+
+def _bleu_score(stats: torch.Tensor, smooth: str) -> BleuScore:
+    rows = stats.cpu().tolist()  # one copy back
+    return BleuScore([r[2::2] for r in rows], [r[3::2] for r in rows], [r[0] for r in rows], [r[1] for r in rows], smooth)
+
+
+def unit_bleu(hyp_units, ref_units, reduce: bool = False, hyp_len=None, ref_len=None, smooth: str = "exp", device=None) -> BleuScore:
+    """BLEU between unit sequences (lists of sequences, or padded tensors with hyp_len / ref_len) -> BleuScore; with reduce=True
+    after run-length de-duplication of BOTH sides on the device (unit_bleu.py scores the unit strings as they are decoded)."""
+    _check_smooth(smooth)
+    (h, hl, r, rl), device = _sides([("hyp_units", hyp_units, hyp_len), ("ref_units", ref_units, ref_len)], device)
+    if h.shape[0] != r.shape[0]:
+        raise ValueError(f"unit_bleu: {h.shape[0]} hypotheses against {r.shape[0]} references")
+    if reduce:
+        h, hl, _, _ = reduce_units(h, hl)
+        r, rl, _, _ = reduce_units(r, rl)
+    return _bleu_score(bleu_stats(h, r, hl, rl), smooth)
+
+
+def bleu(hyps: Sequence[str], refs: Sequence[str], smooth: str = "exp", lowercase: bool = False, device=None) -> BleuScore:
+    """Corpus BLEU of `hyps` against one reference each -> BleuScore: the statistics of the str.split() tokens of every pair on the
+    device (words -> ids through one dictionary over the batch on the host), the score from their sums.  lowercase: str.lower() of
+    both sides first (unit_bleu.py:91,106 pass lowercase=True).  Punctuation and any other text normalisation are left to the caller:
+    sacreBLEU's `13a` tokeniser is not applied."""
+    _check_smooth(smooth)
+    if isinstance(hyps, str) or isinstance(refs, str):
+        raise ValueError("bleu: lists of strings are expected, not one string")
+    if len(hyps) != len(refs):
+        raise ValueError(f"bleu: {len(hyps)} hypotheses against {len(refs)} references")
+    if not len(hyps):
+        return BleuScore([], [], [], [], smooth)
+    if lowercase:
+        hyps, refs = [s.lower() for s in hyps], [s.lower() for s in refs]
+    h, r = word_ids(hyps, refs)
+    return _bleu_score(bleu_stats(h, r, device=device), smooth)

@@ -1497,6 +1497,33 @@ int dn_edit_distance(const int32_t* a, int32_t lda, const int32_t* a_len, const 
 int dn_reduce_units(const int32_t* units, const int32_t* lengths, int32_t B, int32_t ld, int32_t* reduced, int32_t* reduced_len,
                     int32_t* durations, int32_t* first, void* stream);
 
+/* ------------------------------------------------------------------ scores over integer sequences: BLEU's clipped n-gram statistics */
+/* The two headline scores of the recipe are BLEU: of the decoded units (research/utils/unit_bleu.py:91,106) and of the re-transcribed
+ * speech (research/TranSpeech/asr_bleu/compute_asr_bleu.py:153).  What belongs on the device are the per-pair statistics over integer
+ * ids that fairseq's own scorer defines (fairseq/clib/libbleu/libbleu.cpp:73-109,138-156: bleu_addngram / bleu_add), the integers a
+ * single-reference corpus BLEU sums: the two lengths and, for n = 1 .. DN_BLEU_ORDER,
+ *   count_n = max(hyp_len - n + 1, 0)                                  the hypothesis's n-grams
+ *   match_n = sum over distinct n-grams g of min(count_hyp(g), count_ref(g))   how many of them the reference covers (clipped)
+ * The score over them (fairseq/scoring/bleu.py:132-151) is closed-form host arithmetic over the summed integers: diffnorm_amd/metrics.py.
+ * Kernel: csrc/bleu.hip, one workgroup per pair: both rows in LDS, ONE bitonic sort of the hyp_len + ref_len start positions by their
+ * 4-token key (full lexicographic comparison of the tokens as signed integers, a below-everything mark where a row has ended), after
+ * which the equal n-grams of every order are contiguous; one pass of run boundaries and per-run hypothesis / reference counts serves
+ * the four orders.  Exact for any int32 token values (only equality matters), no hash, no floating point, no atomics: bit-identical
+ * between calls and independent of B, of the pair's position, of ld_hyp / ld_ref and of what lies behind the lengths.               */
+#define DN_BLEU_ORDER 4
+#define DN_BLEU_STATS 10 /* hyp_len, ref_len, match1, count1, ..., match4, count4 */
+/* bytes dn_bleu_stats needs (0 for arguments it would refuse).  Every pair up to 8192 + 8192 tokens is sorted in LDS, so this is a
+ * token size; the entry exists for the common calling pattern                                                                    */
+size_t dn_bleu_stats_workspace_bytes(int32_t B, int32_t ld_hyp, int32_t ld_ref);
+/* hyp int32 [B, ld_hyp], ref int32 [B, ld_ref], hyp_len / ref_len int32 [B] on the device (clamped to [0, ld_hyp] / [0, ld_ref];
+ * elements at or behind a length are never read) -> stats int32 [B, DN_BLEU_STATS]: row i = the clamped hyp_len, ref_len, then
+ * match_n, count_n for n = 1 .. 4 of the pair (hyp[i, :hyp_len[i]], ref[i, :ref_len[i]]); an empty side gives zero matches.
+ * ld_hyp, ld_ref in 1 .. DN_EDIT_DISTANCE_MAX_LEN (refused beyond).  workspace: non-null, dn_bleu_stats_workspace_bytes(B, ld_hyp,
+ * ld_ref) bytes, not touched.  Stream-ordered, no allocation, no synchronisation with the host; every argument is checked before the
+ * launch.  Replaces bleu_add (libbleu.cpp:138-156) per pair, without its trimming of pad / eos and without its hash.               */
+int dn_bleu_stats(const int32_t* hyp, int32_t ld_hyp, const int32_t* hyp_len, const int32_t* ref, int32_t ld_ref, const int32_t* ref_len, int32_t B,
+                  int32_t* stats, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
