@@ -468,3 +468,17 @@ def current_stream():
     import torch
 
     return torch.cuda.current_stream().cuda_stream
+
+
+def alloc_workspace(nbytes: int, device):
+    """A uint8 device tensor behind which `nbytes` bytes lie at a 256-byte aligned address, wherever the allocator put it."""
+    import torch
+
+    return torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=device)
+
+
+def aligned(t):
+    """(the first 256-byte aligned address inside tensor `t`, the bytes of `t` behind it): a workspace as the C entries take it."""
+    p = t.data_ptr()
+    a = (p + 255) & ~255
+    return a, t.numel() * t.element_size() - (a - p)

@@ -183,6 +183,23 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// (count, mean, M2 = sum of squared deviations from the mean) of a run of values, merged chunk by chunk in double in the caller's
+// chunk order (Chan et al.): what the GroupNorm, waveform and CMVN statistics kernels combine their tiles with
+struct ChanAcc {
+  double n = 0, mean = 0, m2 = 0;
+  __host__ __device__ void add(int nb, double mean_b, double m2_b) {  // a chunk of nb > 0 values
+    const double d = mean_b - mean, tot = n + nb;
+    mean += d * nb / tot;
+    m2 += m2_b + d * d * n * nb / tot;
+    n = tot;
+  }
+  // the mean as two floats, hi + lo: (x - hi) - lo in fp32 subtracts it to double accuracy
+  __host__ __device__ void split(float& hi, float& lo) const {
+    hi = (float)mean;
+    lo = (float)(mean - (double)hi);
+  }
+};
+
 // Reductions over the four lanes {l, l^16, l^32, l^48} with the gfx950 half/row swaps instead of ds_bpermute:
 // v_permlane32_swap(a, b) exchanges lanes 32-63 of a with lanes 0-31 of b, v_permlane16_swap the odd 16-lane rows of a
 // with the even rows of b; fed the same value twice they leave {x[l], x[l^32]} resp. {x[l], x[l^16]} in the two results.

@@ -1,12 +1,13 @@
 // Host-side orchestration of the DiffNorm hot path on top of the op-level C ABI: sub-model
-// descriptors (WaveNet, conditionable transformer), the workspace bump allocator, and the packed
-// weight order shared with diffnorm_amd/packing.py.
+// descriptors (WaveNet, conditionable transformer), the workspace bump allocator and its check, the
+// engines' stage timer, and the packed weight order shared with diffnorm_amd/packing.py.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
 
 #include "../../include/diffnorm_hip.h"
+#include "common.h"
 
 namespace dn {
 
@@ -54,6 +55,61 @@ struct Arena {  // bump allocator over the caller's workspace; base == nullptr o
     off = a + bytes;
     if (!base) return reinterpret_cast<void*>(a + 256);  // non-null dummy while measuring
     return off <= cap ? base + a : nullptr;
+  }
+};
+
+// After the plan: the caller's workspace is aligned and holds what the plan took.  `hint` (the function that sizes the workspace)
+// follows the message in brackets.
+inline int check_workspace(const char* who, const void* workspace, size_t bytes, size_t required, const char* hint = nullptr) {
+  DN_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", who);
+  if (required > bytes) {
+    if (hint) dn_set_error("%s: workspace %zu < required %zu (%s)", who, bytes, required, hint);
+    else dn_set_error("%s: workspace %zu < required %zu", who, bytes, required);
+    return DN_EWORKSPACE;
+  }
+  return DN_OK;
+}
+
+// Stage timing of an engine's forward (dn_voc_set_profile, dn_hubert_set_profile): events at the stage boundaries, created by the
+// first enable(.., on), recorded by the forward's mark()s while switched on (`cursor` counts them from 0 in every forward), read back
+// as the milliseconds between neighbours.
+struct StageTimer {
+  static constexpr int kMaxEvents = 16;
+  hipEvent_t ev[kMaxEvents];
+  int n_ev = 0, profile = 0;
+
+  int enable(const char* who, int need, int on) {
+    DN_CHECK_ARG(need >= 2 && need <= kMaxEvents, "%s: %d stage boundaries (2 .. %d)", who, need, kMaxEvents);
+    if (on && !n_ev)
+      for (int i = 0; i < need; ++i) {
+        if (hipEventCreate(&ev[i]) != hipSuccess) {
+          dn_set_error("%s: hipEventCreate failed", who);
+          return DN_ELAUNCH;
+        }
+        n_ev = i + 1;
+      }
+    profile = on ? 1 : 0;
+    return DN_OK;
+  }
+  void mark(int& cursor, hipStream_t s) {
+    if (profile && cursor < n_ev) (void)hipEventRecord(ev[cursor++], s);
+  }
+  // waits for the last profiled forward; ms[i] = its stage i; returns the number of stages (n_ev - 1)
+  int read(const char* who, float* ms, int cap) {
+    DN_CHECK_ARG(ms && n_ev, "%s: profiling was not switched on (the engine's set_profile)", who);
+    const int n = n_ev - 1;
+    DN_CHECK_ARG(cap >= n, "%s: room for %d values needed", who, n);
+    bool ok = hipEventSynchronize(ev[n]) == hipSuccess;
+    for (int i = 0; i < n && ok; ++i) ok = hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]) == hipSuccess;
+    if (!ok) {
+      dn_set_error("%s: no profiled forward has run", who);
+      return DN_ELAUNCH;
+    }
+    return n;
+  }
+  void destroy() {
+    for (int i = 0; i < n_ev; ++i) (void)hipEventDestroy(ev[i]);
+    n_ev = profile = 0;
   }
 };
 

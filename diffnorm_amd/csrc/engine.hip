@@ -677,15 +677,11 @@ extern "C" int dn_eps_forward(DnEps* m, const float* x, const int32_t* t, const 
   DN_CHECK_ARG(m->cfg.dim_prompt == 0, "dn_eps_forward: this model is conditioned on a prompt: use dn_eps_forward_cond");
   DN_CHECK_ARG(B > 0 && T > 0, "dn_eps_forward: B=%d T=%d", B, T);
   DN_CHECK_ARG(T <= m->cfg.max_pos, "dn_eps_forward: T=%d exceeds the positional table (%d)", T, m->cfg.max_pos);
-  DN_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "dn_eps_forward: workspace must be 256-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const int Bt = shared_t ? 1 : B;
   Arena ar{(char*)workspace, 0, workspace_bytes};
   EpsBufs b = plan_eps(m, B, T, Bt, ar);
-  if (ar.off > workspace_bytes) {
-    dn_set_error("dn_eps_forward: workspace %zu < required %zu", workspace_bytes, ar.off);
-    return DN_EWORKSPACE;
-  }
+  DN_TRY(check_workspace("dn_eps_forward", workspace, workspace_bytes, ar.off));
   DN_TRY(eps_cond_rows(m, t, Bt, b.cond, b.gb, b.gbh, s));
   return eps_core(m, x, b.gb, shared_t ? 0 : m->n_row, lengths, B, T, eps_out, b, s);
 }
@@ -1292,14 +1288,10 @@ extern "C" int dn_eps_forward_cond_ex(DnEps* m, const float* x, const int32_t* t
   DN_CHECK_ARG(!time_table || table_n > 0, "dn_eps_forward_cond: a time table needs its row count");
   DN_CHECK_ARG(m->cfg.dim_prompt > 0, "dn_eps_forward_cond: the model was created without a prompt branch (cfg.dim_prompt == 0)");
   DN_CHECK_ARG(B > 0 && T > 0 && Tp > 0 && T <= m->cfg.max_pos, "dn_eps_forward_cond: B=%d T=%d Tp=%d", B, T, Tp);
-  DN_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "dn_eps_forward_cond: workspace must be 256-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   Arena ar{(char*)workspace, 0, workspace_bytes};
   const CondBufs b = plan_eps_cond(m, B, T, Tp, ar);
-  if (ar.off > workspace_bytes) {
-    dn_set_error("dn_eps_forward_cond: workspace %zu < required %zu", workspace_bytes, ar.off);
-    return DN_EWORKSPACE;
-  }
+  DN_TRY(check_workspace("dn_eps_forward_cond", workspace, workspace_bytes, ar.off));
   const DnEpsConfig& c = m->cfg;
   const int dtype = c.dtype, es = esize(dtype), M = B * T;
   const int D = c.dim, Dp = padk(D), Dn = padn(D), z = c.latent, zp = padk(z), C = D * c.cond_mult, P = c.dim_prompt, Pp = padk(P);
@@ -1742,15 +1734,11 @@ extern "C" size_t dn_vae_workspace_bytes(const DnVae* m, int32_t B, int32_t T) {
 extern "C" int dn_vae_encode_params(DnVae* m, const float* feat, int32_t B, int32_t T, float* params, void* workspace,
                                     size_t workspace_bytes, void* stream) {
   DN_CHECK_ARG(m && feat && params && workspace && B > 0 && T > 0, "dn_vae_encode_params: bad argument");
-  DN_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "dn_vae_encode_params: workspace must be 256-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const int dtype = m->cfg.dtype, M = B * T;
   Arena ar{(char*)workspace, 0, workspace_bytes};
   VaeBufs b = plan_vae_enc(m, M, ar);
-  if (ar.off > workspace_bytes) {
-    dn_set_error("dn_vae_encode_params: workspace %zu < required %zu", workspace_bytes, ar.off);
-    return DN_EWORKSPACE;
-  }
+  DN_TRY(check_workspace("dn_vae_encode_params", workspace, workspace_bytes, ar.off));
   DN_TRY(dn_convert_rows(feat, DN_F32, m->cfg.dim, b.in_act, dtype, padk(m->cfg.dim), M, m->cfg.dim, s));
   const void* cur = b.in_act;
   for (int n = 0; n < m->n_wave; ++n) {
@@ -1771,17 +1759,13 @@ extern "C" int dn_vae_encode_params(DnVae* m, const float* feat, int32_t B, int3
 extern "C" int dn_vae_decode(DnVae* m, const float* latent, const int32_t* lengths, int32_t B, int32_t T, float* recon, float* logits,
                              int32_t* units, void* workspace, size_t workspace_bytes, void* stream) {
   DN_CHECK_ARG(m && latent && lengths && workspace && B > 0 && T > 0, "dn_vae_decode: bad argument");
-  DN_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "dn_vae_decode: workspace must be 256-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const int dtype = m->cfg.dtype, M = B * T, D = m->cfg.dim, Dp = padk(D), z = m->cfg.z, V = m->cfg.vocab;
   const bool want_lm = logits != nullptr || units != nullptr;
   const bool dense_recon = recon != nullptr && Dp == D;  // to_pred can write the caller's buffer directly
   Arena ar{(char*)workspace, 0, workspace_bytes};
   VaeBufs b = plan_vae_dec(m, M, !dense_recon, want_lm && !logits, ar);
-  if (ar.off > workspace_bytes) {
-    dn_set_error("dn_vae_decode: workspace %zu < required %zu", workspace_bytes, ar.off);
-    return DN_EWORKSPACE;
-  }
+  DN_TRY(check_workspace("dn_vae_decode", workspace, workspace_bytes, ar.off));
   DN_TRY(dn_convert_rows(latent, DN_F32, z, b.in_act, dtype, padk(z), M, z, s));
   const void* cur = b.in_act;
   for (int n = 0; n < m->n_wave; ++n) {

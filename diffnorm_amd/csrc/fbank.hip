@@ -207,22 +207,18 @@ __global__ __launch_bounds__(256) void cmvn_combine_kernel(const double2* __rest
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= B * M) return;
   const int b = i / M, m = i - b * M;
-  double n = 0, mean = 0, m2 = 0;
+  ChanAcc a;
   for (int c = 0; c < chunks; ++c) {
     int nb = out_len[b] - c * FB_CHUNK;
     if (nb <= 0) break;
     nb = nb > FB_CHUNK ? FB_CHUNK : nb;
     const double2 p = part[((int64_t)b * chunks + c) * M + m];
-    const double d = p.x - mean, tot = n + nb;
-    mean += d * nb / tot;
-    m2 += p.y + d * d * n * nb / tot;
-    n = tot;
+    a.add(nb, p.x, p.y);
   }
   float4 o = make_float4(0.f, 0.f, 1.f, 0.f);
-  if (n > 0) {
-    const double var = m2 / n;
-    o.x = (float)mean;
-    o.y = (float)(mean - (double)o.x);
+  if (a.n > 0) {
+    const double var = a.m2 / a.n;
+    a.split(o.x, o.y);
     o.z = (float)sqrt(var > 1e-10 ? var : 1e-10);
   }
   stat[i] = o;
@@ -372,13 +368,10 @@ extern "C" int dn_fbank_forward(DnFbank* m, const float* wave, const int32_t* le
   DN_CHECK_ARG(Lf == 0 || out != nullptr, "dn_fbank_forward: null output");
   FbBufs b{nullptr, nullptr, 0};
   if (cmvn) {
-    DN_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0, "dn_fbank_forward: the workspace must be 256-byte aligned");
+    DN_CHECK_ARG(workspace, "dn_fbank_forward: null workspace (CMVN needs one)");
     Arena ar{(char*)workspace, 0, workspace_bytes};
     b = plan_fbank(m, B, Lf, ar);
-    if (ar.off > workspace_bytes) {
-      dn_set_error("dn_fbank_forward: workspace %zu < required %zu", workspace_bytes, ar.off);
-      return DN_EWORKSPACE;
-    }
+    DN_TRY(check_workspace("dn_fbank_forward", workspace, workspace_bytes, ar.off));
   }
   hipLaunchKernelGGL(fbank_lengths_kernel, dim3((B + 255) / 256), dim3(256), 0, s, lengths, B, L, g.W, g.S, out_lengths);
   if (Lf > 0)

@@ -1,7 +1,7 @@
 // The mHuBERT front end of the recipe (scripts/prepare/feature_dump.sh -> examples/textless_nlp/gslm/speech2unit/pretrained/
 // hubert_feature_reader.py; scripts/prepare/quantize_unit.sh -> quantize_with_kmeans.py): HubertModel.extract_features(source,
-// padding_mask=None, mask=False, output_layer=k) (fairseq/models/hubert/hubert.py:429-476, 529-545), eval mode, and the k-means
-// assignment behind it.  ConvFeatureExtractionModel (fairseq/models/wav2vec/wav2vec2.py:819-896, mode "default", no conv bias) ->
+// padding_mask=None, mask=False, output_layer=k) (fairseq/models/hubert/hubert.py:429-476, 529-545), eval mode (the k-means
+// assignment behind it is kmeans.hip's).  ConvFeatureExtractionModel (fairseq/models/wav2vec/wav2vec2.py:819-896, mode "default", no conv bias) ->
 // LayerNorm -> post_extract_proj -> pos_conv + residual -> LayerNorm (TransformerEncoder.extract_features, :1009-1076,
 // layer_norm_first False) -> post-norm TransformerSentenceEncoderLayers (:1258-1283).  The reader runs one utterance at a time, so a
 // batch here gives every utterance what it gets alone: per-utterance GroupNorm statistics, zeros outside [0, len) in the positional
@@ -11,11 +11,11 @@
 //                                   the subsampler's form in nar_common.h) on dn_conv_gemm; the GELU behind layer i is applied by the
 //                                   gather of layer i + 1 (as the subsampler's GLU is), the last one by gelu_rows_kernel
 //   positional conv                 dn_grouped_conv1d below
-//   layers                          dn_conv_gemm / dn_attention launches, nar_common.h's LayerNorm
+//   layers                          nar_common.h's LayerNorm and self_attention_block; dn_conv_gemm for the FFN
 // The large form (wav2vec 2.0 / HuBERT large, and the Wav2VecCtc recognisers of the recipe's ASR-BLEU, research/TranSpeech/asr_bleu/
 // utils.py:221-308) is the same pass with DnHubertConfig's appended fields set:
 //   wave_norm                       wave_stats_kernel / wave_combine_kernel; applied by stage_wave
-//   extractor_ln (+ conv_bias)      conv0_ln_kernel; layers 1..: the same contraction with the bias, then ln_gelu_rows_kernel
+//   extractor_ln (+ conv_bias)      conv0_ln_kernel; layers 1..: the same contraction with the bias, then nar_common.h's LayerNorm + GELU
 //   pre_norm                        the second layer loop of hubert_pass
 //   vocab                           dn_hubert_ctc_forward: encoder.layer_norm, the fp32 head, emit_rows_kernel; dn_ctc_greedy decodes
 #include <new>
@@ -32,9 +32,6 @@ namespace {
 constexpr int C0_KMAX = 16;   // taps of the first conv held in registers (zero weights behind the kernel)
 constexpr int C0_SMAX = 8;    // its largest stride
 constexpr int C0_TF = 256;    // frames per tile, counted from frame 0 of each utterance
-
-// nn.GELU() (erf form) in fp32
-__device__ __forceinline__ float gelu_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
 __host__ __device__ __forceinline__ int conv_frames(int len, int k, int s) { return len >= k ? (len - k) / s + 1 : 0; }
 
@@ -106,22 +103,18 @@ __global__ __launch_bounds__(256) void conv0_combine_kernel(const float2* __rest
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= B * C) return;
   const int b = i / C, c = i - b * C;
-  double n = 0, mean = 0, m2 = 0;
+  ChanAcc a;
   for (int t = 0; t < tiles; ++t) {
     int nb = len1[b] - t * C0_TF;
     if (nb <= 0) break;
     nb = nb > C0_TF ? C0_TF : nb;
     const float2 p = part[((int64_t)b * tiles + t) * C + c];
-    const double d = (double)p.x - mean, tot = n + nb;
-    mean += d * nb / tot;
-    m2 += (double)p.y + d * d * n * nb / tot;
-    n = tot;
+    a.add(nb, (double)p.x, (double)p.y);
   }
   float4 o = make_float4(0, 0, 0, 0);
-  if (n > 0) {
-    o.x = (float)mean;
-    o.y = (float)(mean - (double)o.x);
-    o.z = (float)(1.0 / sqrt(m2 / n + 1e-5));
+  if (a.n > 0) {
+    a.split(o.x, o.y);
+    o.z = (float)(1.0 / sqrt(a.m2 / a.n + 1e-5));
   }
   stat[i] = o;
 }
@@ -233,22 +226,18 @@ __global__ void wave_combine_kernel(const float4* __restrict__ part, const int32
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   const int len = lengths[b] < L ? lengths[b] : L;
-  double n = 0, mean = 0, m2 = 0;
+  ChanAcc a;
   for (int t = 0; t < tiles; ++t) {
     int nb = len - t * WN_TILE;
     if (nb <= 0) break;
     nb = nb > WN_TILE ? WN_TILE : nb;
     const float4 p = part[(int64_t)b * tiles + t];
-    const double d = ((double)p.x + (double)p.y) - mean, tot = n + nb;
-    mean += d * nb / tot;
-    m2 += (double)p.z + d * d * n * nb / tot;
-    n = tot;
+    a.add(nb, (double)p.x + (double)p.y, (double)p.z);
   }
   float4 o = make_float4(0, 0, 0, 0);
-  if (n > 0) {
-    o.x = (float)mean;
-    o.y = (float)(mean - (double)o.x);
-    o.z = (float)(1.0 / sqrt(m2 / n + 1e-5));
+  if (a.n > 0) {
+    a.split(o.x, o.y);
+    o.z = (float)(1.0 / sqrt(a.m2 / a.n + 1e-5));
   }
   wstat[b] = o;
 }
@@ -302,42 +291,6 @@ __global__ __launch_bounds__(256) void conv0_ln_kernel(const float* __restrict__
 #pragma unroll
     for (int i = 0; i < C0_LN_NC; ++i)
       if (i < nc) store_act(y, row + lane + 64 * i, dtype, gelu_exact(fmaf((a[i] - mean) * rstd, g[i], be[i])));
-  }
-}
-
-// Layers 1.. of that mode: y = gelu(LayerNorm(x)) per row, x the contraction's fp32 output (bias in its epilogue) [M, C] -> out_dtype
-// (in place when out_dtype is DN_F32 and y == x: a wave holds its whole row before it stores).  nar_common.h's LayerNorm with a GELU behind it.
-__global__ __launch_bounds__(256) void ln_gelu_rows_kernel(const float* x, void* y, int out_dtype, int M, int C, const float* __restrict__ gamma,
-                                                           const float* __restrict__ beta) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= M) return;
-  const float* xr = x + (int64_t)row * C;
-  float4 v[4];
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = (i * 64 + lane) * 4;
-    v[i] = c < C ? *reinterpret_cast<const float4*>(xr + c) : make_float4(0, 0, 0, 0);
-    s += v[i].x + v[i].y + v[i].z + v[i].w;
-  }
-  const float mean = wave_sum(s) / (float)C;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = (i * 64 + lane) * 4;
-    if (c < C) {
-      const float a = v[i].x - mean, b = v[i].y - mean, cc = v[i].z - mean, d = v[i].w - mean;
-      q += a * a + b * b + cc * cc + d * d;
-    }
-  }
-  const float rstd = rsqrtf(wave_sum(q) / (float)C + 1e-5f);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = (i * 64 + lane) * 4;
-    if (c >= C) continue;
-    const float4 g = *reinterpret_cast<const float4*>(gamma + c), be = *reinterpret_cast<const float4*>(beta + c);
-    store4(y, (int64_t)row * C + c, out_dtype, gelu_exact((v[i].x - mean) * rstd * g.x + be.x), gelu_exact((v[i].y - mean) * rstd * g.y + be.y),
-           gelu_exact((v[i].z - mean) * rstd * g.z + be.z), gelu_exact((v[i].w - mean) * rstd * g.w + be.w));
   }
 }
 
@@ -467,32 +420,13 @@ extern "C" int dn_grouped_conv1d(const float* x, const float* w, const float* bi
   return DN_OK;
 }
 
-extern "C" size_t dn_kmeans_workspace_bytes(int32_t M, int32_t n_centroids) {
-  if (M <= 0 || n_centroids <= 0) return 0;
-  return (size_t)M * round_up(n_centroids, 4) * sizeof(float) + 512;
-}
-
-extern "C" int dn_kmeans_assign(const float* feats, const float* centroids, const float* half_norm, int32_t M, int32_t D, int32_t n_centroids,
-                                int32_t* units, void* workspace, size_t workspace_bytes, void* stream) {
-  DN_CHECK_ARG(feats && centroids && half_norm && units && workspace, "dn_kmeans_assign: null argument");
-  DN_CHECK_ARG(M > 0 && D > 0 && D % 32 == 0 && n_centroids > 0, "dn_kmeans_assign: M=%d D=%d (a multiple of 32) centroids=%d", M, D, n_centroids);
-  const int N = round_up(n_centroids, 4);
-  DN_CHECK_ARG((int64_t)M * std::max(N, D) < (int64_t)1 << 31, "dn_kmeans_assign: M=%d: a buffer exceeds 2^31 elements", M);
-  DN_TRY(check_workspace("dn_kmeans_assign", workspace, workspace_bytes, (size_t)M * N * sizeof(float)));
-  hipStream_t s = (hipStream_t)stream;
-  float* scores = (float*)workspace;
-  DN_TRY(linear(Rows{DN_F32, M, M, 0, s}, feats, D, centroids, half_norm, N, DN_EPI_BIAS, scores, DN_F32));  // x . c_j - |c_j|^2 / 2
-  return dn_argmax_units(scores, N, M, n_centroids, 0, units, stream);  // the first maximum wins: ties go to the lowest index
-}
-
 struct DnHubert {
   DnHubertConfig cfg;
   const float *conv0_w, *gn_g, *gn_b, *ln_g, *ln_b, *proj_b, *pos_w, *pos_b, *enc_g, *enc_b, *qkv_b, *out_b, *fc1_b, *fc2_b, *lng, *lnb, *zeros;
   const void *conv_W[DN_HUBERT_MAX_CONV], *proj_W, *qkv_W, *out_W, *fc1_W, *fc2_W;
   const float *conv_b, *cln_g, *cln_b, *head_b;  // extractor_ln: [n_conv][C] each; vocab > 0: the CTC head
   const void* head_W;
-  hipEvent_t ev[DN_HUBERT_STAGES + 1];  // dn_hubert_set_profile: stage boundaries of the last profiled forward
-  int n_ev, profile;
+  StageTimer timer;  // dn_hubert_set_profile: the DN_HUBERT_STAGES + 1 stage boundaries of the last profiled forward
 };
 
 extern "C" int dn_hubert_create(const DnHubertConfig* cfg, const void* const* w, int32_t n, DnHubert** out) {
@@ -518,7 +452,6 @@ extern "C" int dn_hubert_create(const DnHubertConfig* cfg, const void* const* w,
   DnHubert* m = new (std::nothrow) DnHubert();
   DN_CHECK_ARG(m != nullptr, "dn_hubert_create: out of host memory");
   m->cfg = *cfg;
-  m->n_ev = m->profile = 0;
   TableCursor t{w, 0};
   m->conv0_w = t.next_vec(); m->gn_g = t.next_vec(); m->gn_b = t.next_vec();
   for (int i = 1; i < cfg->n_conv; ++i) m->conv_W[i] = t.next_mat();
@@ -537,34 +470,19 @@ extern "C" int dn_hubert_create(const DnHubertConfig* cfg, const void* const* w,
 
 extern "C" void dn_hubert_destroy(DnHubert* m) {
   if (!m) return;
-  for (int i = 0; i < m->n_ev; ++i) (void)hipEventDestroy(m->ev[i]);
+  m->timer.destroy();
   delete m;
 }
 
 extern "C" int dn_hubert_set_profile(DnHubert* m, int32_t on) {
   DN_CHECK_ARG(m, "dn_hubert_set_profile: null engine");
-  if (on && !m->n_ev)
-    for (int i = 0; i <= DN_HUBERT_STAGES; ++i) {
-      if (hipEventCreate(&m->ev[i]) != hipSuccess) {
-        dn_set_error("dn_hubert_set_profile: hipEventCreate failed");
-        return DN_ELAUNCH;
-      }
-      m->n_ev = i + 1;
-    }
-  m->profile = on ? 1 : 0;
-  return DN_OK;
+  return m->timer.enable("dn_hubert_set_profile", DN_HUBERT_STAGES + 1, on);
 }
 
 extern "C" int dn_hubert_stage_times(DnHubert* m, float* ms, int32_t cap) {
-  DN_CHECK_ARG(m && ms && m->n_ev == DN_HUBERT_STAGES + 1, "dn_hubert_stage_times: profiling was not switched on (dn_hubert_set_profile)");
-  DN_CHECK_ARG(cap >= DN_HUBERT_STAGES, "dn_hubert_stage_times: room for %d values needed", DN_HUBERT_STAGES);
-  bool ok = hipEventSynchronize(m->ev[DN_HUBERT_STAGES]) == hipSuccess;
-  for (int i = 0; i < DN_HUBERT_STAGES && ok; ++i) ok = hipEventElapsedTime(&ms[i], m->ev[i], m->ev[i + 1]) == hipSuccess;
-  if (!ok) {
-    dn_set_error("dn_hubert_stage_times: no profiled forward has run");
-    return DN_ELAUNCH;
-  }
-  return DN_OK;
+  DN_CHECK_ARG(m && m->timer.n_ev == DN_HUBERT_STAGES + 1, "dn_hubert_stage_times: profiling was not switched on (dn_hubert_set_profile)");
+  const int n = m->timer.read("dn_hubert_stage_times", ms, cap);
+  return n < 0 ? n : DN_OK;
 }
 
 extern "C" int32_t dn_hubert_out_frames(const DnHubert* m, int32_t L) {
@@ -645,12 +563,11 @@ int hubert_pass(const char* who, DnHubert* m, const float* wave, const int32_t* 
                B, L, (long long)b.max_elems);
   DN_TRY(check_workspace(who, workspace, workspace_bytes, ar.off));
   const int dtype = c.dtype, es = esize(dtype), C = c.conv_dim, D = c.dim, F = c.ffn, H = c.heads, dh = D / H;
-  const int sdt = side_dtype(dtype), ses = esize(sdt);
   ConvGeom g;
   g.n = c.n_conv;
   for (int i = 0; i < DN_HUBERT_MAX_CONV; ++i) { g.k[i] = c.conv_kernel[i]; g.s[i] = c.conv_stride[i]; }
   int ei = 0;
-  auto mark = [&]() { if (m->profile && ei < m->n_ev) (void)hipEventRecord(m->ev[ei++], s); };
+  auto mark = [&]() { m->timer.mark(ei, s); };
   // LayerNorm of x into the fp32 stream `y32` and, as the next contraction's A operand, into xn; in DN_F32 the two are one
   const void* xn = b.xn;
   auto norm_both = [&](const Rows& rr, const float* x, const float* gm, const float* bt, float* y32) {
@@ -688,8 +605,7 @@ int hubert_pass(const char* who, DnHubert* m, const float* wave, const int32_t* 
                   DN_F32));
     if (c.extractor_ln) {  // the norm sits between the conv and the GELU: one row kernel, into the next gather's input (the last: fp32, in place)
       const bool last = i + 1 == c.n_conv;
-      hipLaunchKernelGGL(ln_gelu_rows_kernel, dim3((B * Tout + 3) / 4), dim3(256), 0, s, b.y, last ? (void*)b.y : b.y0, last ? DN_F32 : dtype, B * Tout, C,
-                         m->cln_g + (size_t)i * C, m->cln_b + (size_t)i * C);
+      layernorm_gelu(Rows{dtype, B * Tout, Tout, C, s}, b.y, m->cln_g + (size_t)i * C, m->cln_b + (size_t)i * C, last ? (void*)b.y : b.y0, last ? DN_F32 : dtype);
     }
   }
   const Rows rc{dtype, B * S, S, C, s}, r{dtype, B * S, S, D, s};
@@ -707,18 +623,25 @@ int hubert_pass(const char* who, DnHubert* m, const float* wave, const int32_t* 
   DN_TRY(dn_grouped_conv1d(b.x0, m->pos_w, m->pos_b, b.xa, out_lengths, B, S, D, c.conv_pos_groups, c.conv_pos, s));
   mark();
   float *cur = b.xa, *other = b.xb;
+  // the two halves of layer l, on the normalised rows `in` and the residual stream x: x += out_proj(attention(qkv(in))) over the
+  // utterance's own frames, and x += fc2(gelu(fc1(in))) (fc1 lands in fp32, the GELU rounds it to the operand type)
+  auto self_attn = [&](int l, const void* in, float* x) {
+    return self_attention_block(r, H, dh, in, layer_mat(m->qkv_W, l, 3 * D, D, es), m->qkv_b + (size_t)l * 3 * D, layer_mat(m->out_W, l, D, D, es),
+                                m->out_b + (size_t)l * D, b.qkv, b.ao, out_lengths, x);
+  };
+  auto ffn = [&](int l, const void* in, float* x) {
+    DN_TRY(linear(r, in, D, layer_mat(m->fc1_W, l, F, D, es), m->fc1_b + (size_t)l * F, F, DN_EPI_BIAS, b.hf, DN_F32));
+    hipLaunchKernelGGL(gelu_rows_kernel, dim3(ew_grid((int64_t)r.M * F / 4)), dim3(256), 0, s, b.hf, b.h, dtype, (int64_t)r.M * F / 4);
+    return linear_resadd(r, b.h, F, layer_mat(m->fc2_W, l, D, F, es), m->fc2_b + (size_t)l * D, x);
+  };
   if (c.pre_norm) {  // no encoder.layer_norm in front of pre-norm layers (:1024): the stream stays in b.xa
     for (int l = 0; l < n_layers_run; ++l) {  // layer_norm_first True (:1235-1257): x += attn(LN1(x)); x += fc2(gelu(fc1(LN2(x))))
       const float* lg = m->lng + (size_t)l * 2 * D;
       const float* lb = m->lnb + (size_t)l * 2 * D;
       layernorm(r, cur, lg, lb, b.xn, dtype);
-      DN_TRY(linear(r, b.xn, D, layer_mat(m->qkv_W, l, 3 * D, D, es), m->qkv_b + (size_t)l * 3 * D, 3 * D, DN_EPI_BIAS, b.qkv, sdt));
-      DN_TRY(attention(dtype, H, dh, b.qkv, 3 * D, eoff(b.qkv, D, ses), eoff(b.qkv, 2 * D, ses), 3 * D, B, S, 0, out_lengths, b.ao, s));
-      DN_TRY(linear_resadd(r, b.ao, D, layer_mat(m->out_W, l, D, D, es), m->out_b + (size_t)l * D, cur));
+      DN_TRY(self_attn(l, b.xn, cur));
       layernorm(r, cur, lg + D, lb + D, b.xn, dtype);
-      DN_TRY(linear(r, b.xn, D, layer_mat(m->fc1_W, l, F, D, es), m->fc1_b + (size_t)l * F, F, DN_EPI_BIAS, b.hf, DN_F32));
-      hipLaunchKernelGGL(gelu_rows_kernel, dim3(ew_grid((int64_t)r.M * F / 4)), dim3(256), 0, s, b.hf, b.h, dtype, (int64_t)r.M * F / 4);
-      DN_TRY(linear_resadd(r, b.h, F, layer_mat(m->fc2_W, l, D, F, es), m->fc2_b + (size_t)l * D, cur));
+      DN_TRY(ffn(l, b.xn, cur));
     }
   } else {
     std::swap(cur, other);
@@ -726,14 +649,10 @@ int hubert_pass(const char* who, DnHubert* m, const float* wave, const int32_t* 
     for (int l = 0; l < n_layers_run; ++l) {  // TransformerSentenceEncoderLayer.forward, layer_norm_first False (:1258-1283)
       const float* lg = m->lng + (size_t)l * 2 * D;
       const float* lb = m->lnb + (size_t)l * 2 * D;
-      DN_TRY(linear(r, xn, D, layer_mat(m->qkv_W, l, 3 * D, D, es), m->qkv_b + (size_t)l * 3 * D, 3 * D, DN_EPI_BIAS, b.qkv, sdt));
-      DN_TRY(attention(dtype, H, dh, b.qkv, 3 * D, eoff(b.qkv, D, ses), eoff(b.qkv, 2 * D, ses), 3 * D, B, S, 0, out_lengths, b.ao, s));
-      DN_TRY(linear_resadd(r, b.ao, D, layer_mat(m->out_W, l, D, D, es), m->out_b + (size_t)l * D, cur));
+      DN_TRY(self_attn(l, xn, cur));
       norm_both(r, cur, lg, lb, other);  // self_attn_layer_norm BEHIND the residual
       std::swap(cur, other);
-      DN_TRY(linear(r, xn, D, layer_mat(m->fc1_W, l, F, D, es), m->fc1_b + (size_t)l * F, F, DN_EPI_BIAS, b.hf, DN_F32));
-      hipLaunchKernelGGL(gelu_rows_kernel, dim3(ew_grid((int64_t)r.M * F / 4)), dim3(256), 0, s, b.hf, b.h, dtype, (int64_t)r.M * F / 4);
-      DN_TRY(linear_resadd(r, b.h, F, layer_mat(m->fc2_W, l, D, F, es), m->fc2_b + (size_t)l * D, cur));
+      DN_TRY(ffn(l, xn, cur));
       if (l + 1 < n_layers_run) norm_both(r, cur, lg + D, lb + D, other);  // final_layer_norm
       else layernorm(r, cur, lg + D, lb + D, other, DN_F32);
       std::swap(cur, other);

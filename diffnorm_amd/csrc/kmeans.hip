@@ -1,6 +1,8 @@
 // Learning the unit quantizer (examples/textless_nlp/gslm/speech2unit/clustering/cluster_kmeans.py, examples/hubert/simple_kmeans/
-// learn_kmeans.py: sklearn.cluster.MiniBatchKMeans) on the device.  One mini-batch step is assign -> accumulate -> update; the
-// assignment is dn_kmeans_assign (hubert.hip).  Here:
+// learn_kmeans.py: sklearn.cluster.MiniBatchKMeans) on the device, and applying it (ApplyKmeans, examples/hubert/simple_kmeans/
+// dump_km_label.py:20-53).  One mini-batch step is assign -> accumulate -> update.  Here:
+//   dn_kmeans_assign       the nearest centre of every row: scores x . c_j - |c_j|^2 / 2 by one DN_F32 contraction, then the first
+//                          maximum of each row (dn_argmax_units)
 //   dn_kmeans_accumulate   per-cluster column sums, member counts and the inertia of a labelled batch, without floating-point atomics
 //                          and without a one-hot contraction: a stable counting sort of the row indices by label
 //                            km_hist_kernel   histogram of the labels of KM_ROWS rows per workgroup (LDS integer atomics)
@@ -249,6 +251,24 @@ inline size_t min_dist_bytes(int M) { return (size_t)((M + MD_ROWS - 1) / MD_ROW
 
 }  // namespace
 }  // namespace dn
+
+extern "C" size_t dn_kmeans_workspace_bytes(int32_t M, int32_t n_centroids) {
+  if (M <= 0 || n_centroids <= 0) return 0;
+  return (size_t)M * round_up(n_centroids, 4) * sizeof(float) + 512;
+}
+
+extern "C" int dn_kmeans_assign(const float* feats, const float* centroids, const float* half_norm, int32_t M, int32_t D, int32_t n_centroids,
+                                int32_t* units, void* workspace, size_t workspace_bytes, void* stream) {
+  DN_CHECK_ARG(feats && centroids && half_norm && units && workspace, "dn_kmeans_assign: null argument");
+  DN_CHECK_ARG(M > 0 && D > 0 && D % 32 == 0 && n_centroids > 0, "dn_kmeans_assign: M=%d D=%d (a multiple of 32) centroids=%d", M, D, n_centroids);
+  const int N = round_up(n_centroids, 4);
+  DN_CHECK_ARG((int64_t)M * std::max(N, D) < (int64_t)1 << 31, "dn_kmeans_assign: M=%d: a buffer exceeds 2^31 elements", M);
+  DN_TRY(check_workspace("dn_kmeans_assign", workspace, workspace_bytes, (size_t)M * N * sizeof(float)));
+  hipStream_t s = (hipStream_t)stream;
+  float* scores = (float*)workspace;
+  DN_TRY(linear(Rows{DN_F32, M, M, 0, s}, feats, D, centroids, half_norm, N, DN_EPI_BIAS, scores, DN_F32));  // x . c_j - |c_j|^2 / 2
+  return dn_argmax_units(scores, N, M, n_centroids, 0, units, stream);  // the first maximum wins: ties go to the lowest index
+}
 
 extern "C" size_t dn_kmeans_workspace_bytes_train(int32_t M, int32_t n_clusters) {
   if (M <= 0 || n_clusters <= 0 || n_clusters > KM_NMAX) return 0;

@@ -1,5 +1,6 @@
-// What the NAR decoder and the two speech encoders share (nar_decoder.hip, nar_encoder.hip, conformer_encoder.hip): the LayerNorm
-// kernel, the Conv1dSubsampler, and the few host helpers their passes are written in.  Internal linkage, one copy per unit.
+// What the NAR decoder, the two speech encoders and the HuBERT front end share (nar_decoder.hip, nar_encoder.hip,
+// conformer_encoder.hip, hubert.hip; kmeans.hip takes `linear` for the assignment's scores): the LayerNorm kernel, the
+// Conv1dSubsampler, and the few host helpers their passes are written in.  Internal linkage, one copy per unit.
 #pragma once
 #include <algorithm>
 
@@ -9,10 +10,15 @@
 namespace dn {
 namespace {
 
-// LayerNorm (eps 1e-5, biased variance, affine): x fp32 [M, ldx] -> y [M, ldy] in out_dtype (pad columns zeroed).  One wave per
-// row, D <= 1024 in registers.
-__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int ldx, void* __restrict__ y, int ldy, int out_dtype, int M,
-                                                        int D, const float* __restrict__ gamma, const float* __restrict__ beta) {
+// nn.GELU() (erf form) in fp32
+__device__ __forceinline__ float gelu_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
+
+// LayerNorm (eps 1e-5, biased variance, affine): x fp32 [M, ldx] -> y [M, ldy] in out_dtype (pad columns zeroed); GELU: the exact
+// GELU behind the affine.  One wave per row, D <= 1024 in registers.  y may be x itself (fp32, ldy == ldx): a wave holds its whole
+// row before it stores, and neither pointer is __restrict__.
+template <bool GELU>
+__global__ __launch_bounds__(256) void layernorm_kernel(const float* x, int ldx, void* y, int ldy, int out_dtype, int M, int D,
+                                                        const float* __restrict__ gamma, const float* __restrict__ beta) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= M) return;
   const float* xr = x + (int64_t)row * ldx;
@@ -44,6 +50,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
       const float4 g = *reinterpret_cast<const float4*>(gamma + c), be = *reinterpret_cast<const float4*>(beta + c);
       o[0] = (v[i].x - mean) * rstd * g.x + be.x; o[1] = (v[i].y - mean) * rstd * g.y + be.y;
       o[2] = (v[i].z - mean) * rstd * g.z + be.z; o[3] = (v[i].w - mean) * rstd * g.w + be.w;
+      if (GELU) { o[0] = gelu_exact(o[0]); o[1] = gelu_exact(o[1]); o[2] = gelu_exact(o[2]); o[3] = gelu_exact(o[3]); }
     }
     store4(y, (int64_t)row * ldy + c, out_dtype, o[0], o[1], o[2], o[3]);
   }
@@ -92,7 +99,11 @@ inline const void* layer_mat(const void* W, int l, int N, int K, int es) { retur
 struct Rows { int dtype, M, T, D; hipStream_t s; };
 
 inline void layernorm(const Rows& r, const float* x, const float* gamma, const float* beta, void* y, int out_dtype) {
-  hipLaunchKernelGGL(layernorm_kernel, dim3((r.M + 3) / 4), dim3(256), 0, r.s, x, r.D, y, r.D, out_dtype, r.M, r.D, gamma, beta);
+  hipLaunchKernelGGL((layernorm_kernel<false>), dim3((r.M + 3) / 4), dim3(256), 0, r.s, x, r.D, y, r.D, out_dtype, r.M, r.D, gamma, beta);
+}
+// y = gelu(LayerNorm(x)); in place when y == x and out_dtype is DN_F32
+inline void layernorm_gelu(const Rows& r, const float* x, const float* gamma, const float* beta, void* y, int out_dtype) {
+  hipLaunchKernelGGL((layernorm_kernel<true>), dim3((r.M + 3) / 4), dim3(256), 0, r.s, x, r.D, y, r.D, out_dtype, r.M, r.D, gamma, beta);
 }
 
 // out[M, N] = epilogue(A[M, K] W^T + bias) in out_dtype; A and out dense
@@ -141,14 +152,14 @@ inline int attention(int dtype, int heads, int dh, const void* q, int ldq, const
   return dn_attention(&a, s);
 }
 
-// After the plan: the caller's workspace is aligned and holds what the plan took
-inline int check_workspace(const char* who, const void* workspace, size_t bytes, size_t required) {
-  DN_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", who);
-  if (required > bytes) {
-    dn_set_error("%s: workspace %zu < required %zu", who, bytes, required);
-    return DN_EWORKSPACE;
-  }
-  return DN_OK;
+// x += out_W attention(qkv_W xn + qkv_b) + out_b: the self-attention of a layer on the normalised rows xn [M, D] and the fp32
+// residual stream x, through qkv [M, 3 D] (q ; k ; v) and ao [M, D]; the keys are the sequence's own frames, lengths[b] of them valid
+inline int self_attention_block(const Rows& r, int heads, int dh, const void* xn, const void* qkv_W, const float* qkv_b, const void* out_W,
+                                const float* out_b, void* qkv, void* ao, const int32_t* lengths, float* x) {
+  const int D = r.D, sdt = side_dtype(r.dtype), ses = esize(sdt);
+  DN_TRY(linear(r, xn, D, qkv_W, qkv_b, 3 * D, DN_EPI_BIAS, qkv, sdt));
+  DN_TRY(attention(r.dtype, heads, dh, qkv, 3 * D, eoff(qkv, D, ses), eoff(qkv, 2 * D, ses), 3 * D, r.M / r.T, r.T, 0, lengths, ao, r.s));
+  return linear_resadd(r, ao, D, out_W, out_b, x);
 }
 
 // What every *_create here asks of its arguments and of the fields the three configs share

@@ -287,10 +287,8 @@ static int decoder_pass(const char* who, DnNar* m, int halves, const int32_t* to
     const float* g = m->ln_g + (size_t)l * 3 * D;
     const float* be = m->ln_b + (size_t)l * 3 * D;
     layernorm(all, b.x, g, be, b.xn, dtype);  // self_attn_layer_norm (pre-norm, :421-423)
-    DN_TRY(linear(all, b.xn, D, layer_mat(m->qkv_W, l, 3 * D, D, es), m->qkv_b + (size_t)l * 3 * D, 3 * D, DN_EPI_BIAS, b.qkv, sdt));  // q ; k ; v
-    DN_TRY(attention(dtype, H, dh, b.qkv, 3 * D, eoff(b.qkv, D, ses), eoff(b.qkv, 2 * D, ses), 3 * D, halves * B, T, 0, b.tlen, b.ao,
-                     s));  // full context, keys = non-pad tokens
-    DN_TRY(linear_resadd(all, b.ao, D, layer_mat(m->so_W, l, D, D, es), m->so_b + (size_t)l * D, b.x));
+    DN_TRY(self_attention_block(all, H, dh, b.xn, layer_mat(m->qkv_W, l, 3 * D, D, es), m->qkv_b + (size_t)l * 3 * D, layer_mat(m->so_W, l, D, D, es),
+                                m->so_b + (size_t)l * D, b.qkv, b.ao, b.tlen, b.x));  // full context, keys = non-pad tokens
     layernorm(cross, b.x, g + D, be + D, b.xn, dtype);  // encoder_attn_layer_norm (:447-449)
     DN_TRY(linear(cross, b.xn, D, layer_mat(m->cq_W, l, D, D, es), m->cq_b + (size_t)l * D, D, DN_EPI_BIAS, b.cq, sdt));
     const void* kv = eoff(ckv, (size_t)l * B * S * 2 * D, ses);

@@ -105,15 +105,12 @@ extern "C" int dn_nar_encoder_forward(DnNarEnc* m, const float* feats, const int
   hipLaunchKernelGGL(enc_embed_kernel, dim3(ew_grid((int64_t)r.M * D)), dim3(256), 0, s, b.sub.y1, src_lengths, 2, B, S, D, m->pos, c.pad, sqrtf((float)D), b.x,
                      out_lengths);
   // ---- pre-norm encoder layers
-  const int sdt = side_dtype(dtype), ses = esize(sdt);
   for (int l = 0; l < c.layers; ++l) {
     const float* g = m->ln_g + (size_t)l * 2 * D;
     const float* be = m->ln_b + (size_t)l * 2 * D;
     layernorm(r, b.x, g, be, b.xn, dtype);  // self_attn_layer_norm (:194-196)
-    DN_TRY(linear(r, b.xn, D, layer_mat(m->qkv_W, l, 3 * D, D, es), m->qkv_b + (size_t)l * 3 * D, 3 * D, DN_EPI_BIAS, b.qkv, sdt));  // q ; k ; v
-    DN_TRY(attention(dtype, H, dh, b.qkv, 3 * D, eoff(b.qkv, D, ses), eoff(b.qkv, 2 * D, ses), 3 * D, B, S, 0, out_lengths, b.ao,
-                     s));  // key_padding_mask (:197-204)
-    DN_TRY(linear_resadd(r, b.ao, D, layer_mat(m->so_W, l, D, D, es), m->so_b + (size_t)l * D, b.x));
+    DN_TRY(self_attention_block(r, H, dh, b.xn, layer_mat(m->qkv_W, l, 3 * D, D, es), m->qkv_b + (size_t)l * 3 * D, layer_mat(m->so_W, l, D, D, es),
+                                m->so_b + (size_t)l * D, b.qkv, b.ao, out_lengths, b.x));  // key_padding_mask (:197-204)
     DN_TRY(ffn_block(r, b.x, b.xn, b.h, F, g + D, be + D, layer_mat(m->fc1_W, l, F, D, es), m->fc1_b + (size_t)l * F, layer_mat(m->fc2_W, l, D, F, es),
                      m->fc2_b + (size_t)l * D, DN_EPI_RELU));  // final_layer_norm, relu(fc1), fc2 (:210-215)
   }

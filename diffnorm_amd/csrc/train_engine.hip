@@ -1059,14 +1059,9 @@ Ctx make_ctx(const FlatParams& p, int B, int T, const Plan& pl, hipStream_t s, b
 // Lays `plan` out over the caller's workspace; `sizer` names the function that tells how large it has to be.
 template <typename PlanFn>
 int plan_workspace(void* ws, size_t ws_bytes, const char* who, const char* sizer, PlanFn plan) {
-  DN_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", who);
   Arena ar{(char*)ws, 0, ws_bytes};
   plan(ar);
-  if (ar.off > ws_bytes) {
-    dn_set_error("%s: workspace %zu < required %zu (%s)", who, ws_bytes, ar.off, sizer);
-    return DN_EWORKSPACE;
-  }
-  return DN_OK;
+  return check_workspace(who, ws, ws_bytes, ar.off, sizer);
 }
 
 int check_batch(const DnVaeTrain* m, const DnVaeTrainBatch* b, void* ws, size_t ws_bytes, VaePlan* pl, const char* who) {

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "common.h"
+#include "engine.h"
 
 namespace dn {
 namespace voc {
@@ -304,11 +305,8 @@ struct DnVoc {
   const float *ln1g, *ln1b, *ln2g, *ln2b, *pw, *pb;
   int up_total;
   int64_t max_elems_per_frame;                 // widest activation per input frame: max over layers of (frames per input frame) * C
-  hipEvent_t ev[16];
-  int n_ev, profile;
+  dn::StageTimer timer;                        // dn_voc_set_profile: the stage boundaries of the last profiled forward
 };
-
-static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 extern "C" int dn_voc_conv_tile(int32_t dtype, int32_t C_in, int32_t C_out, int32_t k) {
   const char* e = conv_shape_error(dtype, C_in, C_out, k, 1);
@@ -401,42 +399,38 @@ extern "C" int dn_voc_create(const DnVocConfig* c, const void* const* weights, i
     delete m;
     return DN_EINVAL;
   }
-  m->n_ev = 0;
-  m->profile = 0;
   *out = m;
   return DN_OK;
 }
 
 extern "C" void dn_voc_destroy(DnVoc* m) {
   if (!m) return;
-  for (int i = 0; i < m->n_ev; ++i) (void)hipEventDestroy(m->ev[i]);
+  m->timer.destroy();
   delete m;
 }
 
 extern "C" int32_t dn_voc_upsample(const DnVoc* m) { return m ? m->up_total : 0; }
 
-// five activation buffers of the widest layer, the scan and the per-row frame counts
-extern "C" size_t dn_voc_workspace_bytes(const DnVoc* m, int32_t B, int32_t Lmax0) {
-  if (!m || B < 1 || Lmax0 < 1) return 0;
-  const size_t buf = align256((size_t)B * Lmax0 * m->max_elems_per_frame * sizeof(float));
-  return 5 * buf + align256((size_t)B * (Lmax0 + 1) * sizeof(int32_t)) + 2 * align256((size_t)B * sizeof(int32_t)) + 256;
-}
-
 namespace {
-struct Workspace {
+// five activation buffers of the widest layer, the scan [B][Lmax + 1] and the per-row frame counts
+struct VocBufs {
   float* buf[5];
-  int32_t *cum, *frames, *ones;
+  int32_t *cum, *frames;
 };
-int carve(const DnVoc* m, int B, int Lmax0, void* ws, size_t ws_bytes, Workspace& w, const char* who) {
-  DN_CHECK_ARG(ws && ((uintptr_t)ws & 255) == 0 && ws_bytes >= dn_voc_workspace_bytes(m, B, Lmax0), "%s: workspace of %zu bytes (256-byte aligned) needed, %zu given", who,
-               dn_voc_workspace_bytes(m, B, Lmax0), ws_bytes);
-  char* p = reinterpret_cast<char*>(ws);
-  const size_t buf = align256((size_t)B * Lmax0 * m->max_elems_per_frame * sizeof(float));
-  for (int i = 0; i < 5; ++i, p += buf) w.buf[i] = reinterpret_cast<float*>(p);
-  w.cum = reinterpret_cast<int32_t*>(p); p += align256((size_t)B * (Lmax0 + 1) * sizeof(int32_t));
-  w.frames = reinterpret_cast<int32_t*>(p); p += align256((size_t)B * sizeof(int32_t));
-  w.ones = reinterpret_cast<int32_t*>(p);
-  return DN_OK;
+VocBufs plan_voc(const DnVoc* m, int B, int Lmax, dn::Arena& ar) {
+  VocBufs w;
+  for (int i = 0; i < 5; ++i) w.buf[i] = (float*)ar.take((size_t)B * Lmax * m->max_elems_per_frame * sizeof(float));
+  w.cum = (int32_t*)ar.take((size_t)B * (Lmax + 1) * sizeof(int32_t));
+  w.frames = (int32_t*)ar.take((size_t)B * sizeof(int32_t));
+  return w;
+}
+// The plan over the caller's workspace.  A pass takes exactly dn_voc_workspace_bytes: one byte less is refused, and with
+// DN_EINVAL, as a bad workspace of the vocoder's always has been.
+int plan_voc_checked(const char* who, const DnVoc* m, int B, int Lmax, void* ws, size_t ws_bytes, VocBufs& w) {
+  DN_CHECK_ARG(ws, "%s: null workspace", who);
+  dn::Arena ar{(char*)ws, 0, ws_bytes};
+  w = plan_voc(m, B, Lmax, ar);
+  return dn::check_workspace(who, ws, ws_bytes, ar.off) == DN_OK ? DN_OK : DN_EINVAL;
 }
 int run_layer(int dtype, const DnVocLayer& l, const float* x, float* out, int ldo, const float* res, const int32_t* lengths, int len_mul, int Lmax, int B,
               float slope, int post, float div, hipStream_t st) {
@@ -450,19 +444,20 @@ int run_layer(int dtype, const DnVocLayer& l, const float* x, float* out, int ld
 }
 }  // namespace
 
-#define DN_VOC_TRY(x)          \
-  do {                         \
-    const int rc__ = (x);      \
-    if (rc__ != DN_OK) return rc__; \
-  } while (0)
+extern "C" size_t dn_voc_workspace_bytes(const DnVoc* m, int32_t B, int32_t Lmax0) {
+  if (!m || B < 1 || Lmax0 < 1) return 0;
+  dn::Arena a{nullptr, 0, 0};
+  (void)plan_voc(m, B, Lmax0, a);
+  return a.off;
+}
 
 extern "C" int dn_voc_durations(DnVoc* m, const int32_t* codes, const int32_t* lengths, int32_t B, int32_t Tmax, int32_t* durations, int32_t* sums,
                                 void* workspace, size_t workspace_bytes, void* stream) {
   DN_CHECK_ARG(m && codes && lengths && durations && sums, "dn_voc_durations: null argument");
   DN_CHECK_ARG(m->cfg.dur_hidden > 0, "dn_voc_durations: the model has no duration predictor (dur_predictor_params)");
   DN_CHECK_ARG(B >= 1 && Tmax >= 1, "dn_voc_durations: B = %d, Tmax = %d", B, Tmax);
-  Workspace w;
-  DN_VOC_TRY(carve(m, B, Tmax, workspace, workspace_bytes, w, "dn_voc_durations"));
+  VocBufs w;
+  DN_TRY(plan_voc_checked("dn_voc_durations", m, B, Tmax, workspace, workspace_bytes, w));
   hipStream_t st = (hipStream_t)stream;
   const int E = m->cfg.embedding_dim, H = m->cfg.dur_hidden;
   scan_kernel<<<B, 64, 0, st>>>(nullptr, lengths, Tmax, Tmax, 1, w.cum, w.frames, nullptr, nullptr);
@@ -470,9 +465,9 @@ extern "C" int dn_voc_durations(DnVoc* m, const int32_t* codes, const int32_t* l
   embed_kernel<<<(unsigned)((nvec + 255) / 256), 256, 0, st>>>(m->dict, codes, lengths, w.cum, w.frames, B, Tmax, Tmax, E, m->cfg.num_embeddings, w.buf[0]);
   DN_CHECK_LAUNCH("dn_voc_durations: embedding");
   const unsigned row_blocks = (unsigned)((B * Tmax + 3) / 4);
-  DN_VOC_TRY(run_layer(DN_F32, m->p1, w.buf[0], w.buf[1], H, nullptr, w.frames, 1, Tmax, B, 1.f, DN_VOC_POST_RELU, 1.f, st));
+  DN_TRY(run_layer(DN_F32, m->p1, w.buf[0], w.buf[1], H, nullptr, w.frames, 1, Tmax, B, 1.f, DN_VOC_POST_RELU, 1.f, st));
   layernorm_kernel<<<row_blocks, 256, 0, st>>>(w.buf[1], w.frames, B, Tmax, H, m->ln1g, m->ln1b);
-  DN_VOC_TRY(run_layer(DN_F32, m->p2, w.buf[1], w.buf[2], H, nullptr, w.frames, 1, Tmax, B, 1.f, DN_VOC_POST_RELU, 1.f, st));
+  DN_TRY(run_layer(DN_F32, m->p2, w.buf[1], w.buf[2], H, nullptr, w.frames, 1, Tmax, B, 1.f, DN_VOC_POST_RELU, 1.f, st));
   layernorm_kernel<<<row_blocks, 256, 0, st>>>(w.buf[2], w.frames, B, Tmax, H, m->ln2g, m->ln2b);
   duration_kernel<<<row_blocks, 256, 0, st>>>(w.buf[2], w.frames, B, Tmax, H, m->pw, m->pb, durations, nullptr);
   scan_kernel<<<B, 64, 0, st>>>(durations, lengths, Tmax, 0x7fffffff, 1, nullptr, nullptr, sums, nullptr);
@@ -482,34 +477,12 @@ extern "C" int dn_voc_durations(DnVoc* m, const int32_t* codes, const int32_t* l
 
 extern "C" int dn_voc_set_profile(DnVoc* m, int32_t on) {
   DN_CHECK_ARG(m, "dn_voc_set_profile: null engine");
-  if (on && !m->n_ev) {
-    const int need = m->cfg.n_ups + 3;
-    for (int i = 0; i < need; ++i) {
-      if (hipEventCreate(&m->ev[i]) != hipSuccess) {
-        dn_set_error("dn_voc_set_profile: hipEventCreate failed");
-        return DN_ELAUNCH;
-      }
-      m->n_ev = i + 1;
-    }
-  }
-  m->profile = on ? 1 : 0;
-  return DN_OK;
+  return m->timer.enable("dn_voc_set_profile", m->cfg.n_ups + 3, on);
 }
 
 extern "C" int dn_voc_stage_times(DnVoc* m, float* ms, int32_t cap) {
-  DN_CHECK_ARG(m && ms && m->n_ev, "dn_voc_stage_times: profiling was not switched on (dn_voc_set_profile)");
-  const int n = m->n_ev - 1;
-  DN_CHECK_ARG(cap >= n, "dn_voc_stage_times: room for %d values needed", n);
-  if (hipEventSynchronize(m->ev[n]) != hipSuccess) {
-    dn_set_error("dn_voc_stage_times: no profiled forward has run");
-    return DN_ELAUNCH;
-  }
-  for (int i = 0; i < n; ++i)
-    if (hipEventElapsedTime(&ms[i], m->ev[i], m->ev[i + 1]) != hipSuccess) {
-      dn_set_error("dn_voc_stage_times: no profiled forward has run");
-      return DN_ELAUNCH;
-    }
-  return n;
+  DN_CHECK_ARG(m, "dn_voc_stage_times: null engine");
+  return m->timer.read("dn_voc_stage_times", ms, cap);
 }
 
 extern "C" int dn_voc_forward(DnVoc* m, const int32_t* codes, const int32_t* lengths, const int32_t* durations, int32_t B, int32_t Tmax, int32_t Lmax0,
@@ -518,39 +491,39 @@ extern "C" int dn_voc_forward(DnVoc* m, const int32_t* codes, const int32_t* len
   DN_CHECK_ARG(B >= 1 && Tmax >= 1 && Lmax0 >= 1, "dn_voc_forward: B = %d, Tmax = %d, Lmax0 = %d", B, Tmax, Lmax0);
   DN_CHECK_ARG(durations || Lmax0 >= Tmax, "dn_voc_forward: without durations every unit is one frame: Lmax0 = %d < Tmax = %d", Lmax0, Tmax);
   DN_CHECK_ARG((int64_t)Lmax0 * m->up_total < (int64_t)1 << 31, "dn_voc_forward: %d frames x %d samples overflow a row's int32 indices", Lmax0, m->up_total);
-  Workspace w;
-  DN_VOC_TRY(carve(m, B, std::max(Lmax0, Tmax), workspace, workspace_bytes, w, "dn_voc_forward"));
-  // the scan is [B][Tmax + 1]; carve sized it for max(Lmax0, Tmax) + 1 per row
+  VocBufs w;
+  DN_TRY(plan_voc_checked("dn_voc_forward", m, B, std::max(Lmax0, Tmax), workspace, workspace_bytes, w));
+  // the scan is [B][Tmax + 1]; the plan sized it for max(Lmax0, Tmax) + 1 per row
   hipStream_t st = (hipStream_t)stream;
   const DnVocConfig& c = m->cfg;
   const int dt = c.dtype, E = c.embedding_dim;
   int ei = 0;
-  auto mark = [&]() { if (m->profile && ei < m->n_ev) (void)hipEventRecord(m->ev[ei++], st); };
+  auto mark = [&]() { m->timer.mark(ei, st); };
   mark();
   scan_kernel<<<B, 64, 0, st>>>(durations, lengths, Tmax, Lmax0, m->up_total, w.cum, w.frames, nullptr, wav_lengths);
   const int64_t nvec = (int64_t)B * Lmax0 * (E / 4);
   embed_kernel<<<(unsigned)((nvec + 255) / 256), 256, 0, st>>>(m->dict, codes, lengths, w.cum, w.frames, B, Tmax, Lmax0, E, c.num_embeddings, w.buf[1]);
   DN_CHECK_LAUNCH("dn_voc_forward: embedding");
-  DN_VOC_TRY(run_layer(dt, m->pre, w.buf[1], w.buf[0], m->pre.C_out, nullptr, w.frames, 1, Lmax0, B, 1.f, DN_VOC_POST_NONE, 1.f, st));
+  DN_TRY(run_layer(dt, m->pre, w.buf[1], w.buf[0], m->pre.C_out, nullptr, w.frames, 1, Lmax0, B, 1.f, DN_VOC_POST_NONE, 1.f, st));
   mark();
   float *cur = w.buf[0], *X = w.buf[1], *T = w.buf[2], *H = w.buf[3], *S = w.buf[4];
   int mul = 1, L = Lmax0, ri = 0;
   for (int i = 0; i < c.n_ups; ++i) {
     const DnVocLayer& up = m->ups[i];
     // [L, u * C] rows of the polyphase conv are the [L * u, C] activation in memory
-    DN_VOC_TRY(run_layer(dt, up, cur, X, up.C_out, nullptr, w.frames, mul, L, B, 0.1f, DN_VOC_POST_NONE, 1.f, st));
+    DN_TRY(run_layer(dt, up, cur, X, up.C_out, nullptr, w.frames, mul, L, B, 0.1f, DN_VOC_POST_NONE, 1.f, st));
     mul *= c.up_rates[i];
     L *= c.up_rates[i];
     const int ch = up.C_in / 2;
     for (int j = 0; j < c.n_kernels; ++j) {
       const float* h = X;
       for (int pr = 0; pr < 3; ++pr, ri += 2) {
-        DN_VOC_TRY(run_layer(dt, m->res[ri], h, T, ch, nullptr, w.frames, mul, L, B, 0.1f, DN_VOC_POST_NONE, 1.f, st));
+        DN_TRY(run_layer(dt, m->res[ri], h, T, ch, nullptr, w.frames, mul, L, B, 0.1f, DN_VOC_POST_NONE, 1.f, st));
         if (pr < 2) {
-          DN_VOC_TRY(run_layer(dt, m->res[ri + 1], T, H, ch, h, w.frames, mul, L, B, 0.1f, DN_VOC_POST_RES, 1.f, st));
+          DN_TRY(run_layer(dt, m->res[ri + 1], T, H, ch, h, w.frames, mul, L, B, 0.1f, DN_VOC_POST_RES, 1.f, st));
           h = H;
         } else {  // the block's output joins the stage's sum; the last one divides by the number of blocks, once
-          DN_VOC_TRY(run_layer(dt, m->res[ri + 1], T, S, ch, h, w.frames, mul, L, B, 0.1f, j ? DN_VOC_POST_RES_ACC : DN_VOC_POST_RES,
+          DN_TRY(run_layer(dt, m->res[ri + 1], T, S, ch, h, w.frames, mul, L, B, 0.1f, j ? DN_VOC_POST_RES_ACC : DN_VOC_POST_RES,
                                j == c.n_kernels - 1 ? (float)c.n_kernels : 1.f, st));
         }
       }
@@ -558,7 +531,7 @@ extern "C" int dn_voc_forward(DnVoc* m, const int32_t* codes, const int32_t* len
     std::swap(cur, S);
     mark();
   }
-  DN_VOC_TRY(run_layer(dt, m->post, cur, wav, 1, nullptr, w.frames, mul, L, B, 0.01f, DN_VOC_POST_TANH, 1.f, st));
+  DN_TRY(run_layer(dt, m->post, cur, wav, 1, nullptr, w.frames, mul, L, B, 0.01f, DN_VOC_POST_TANH, 1.f, st));
   mark();
   return DN_OK;
 }

@@ -76,14 +76,10 @@ class _Engine:
 
     def _workspace(self, nbytes: int) -> torch.Tensor:
         if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+            self._ws = _lib.alloc_workspace(nbytes, self.device)
         return self._ws
 
-    @staticmethod
-    def _aligned(ws: torch.Tensor):
-        p = ws.data_ptr()
-        a = (p + 255) & ~255
-        return a, ws.numel() - (a - p)
+    _aligned = staticmethod(_lib.aligned)
 
     def _aligned_workspace(self, nbytes):
         return self._aligned(self._workspace(int(nbytes)))
@@ -271,7 +267,7 @@ class EpsEngine(_Engine):
         """The time half of the conditioning rows of timesteps t0 .. t0 + n_t - 1 (dn_eps_cond_time_table): fp32 [n_t, n_cond]."""
         n_cond = len(packing.eps_cond_modules(self.cfg)) * 2 * packing.padk(self.cfg.dim)
         table = torch.empty(n_t, n_cond, dtype=torch.float32, device=self.device)
-        ws = torch.empty(int(self.lib.dn_eps_cond_time_table_workspace_bytes(self.handle, n_t)) + 256, dtype=torch.uint8, device=self.device)
+        ws = _lib.alloc_workspace(self.lib.dn_eps_cond_time_table_workspace_bytes(self.handle, n_t), self.device)
         wp, wn = self._aligned(ws)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dn_eps_cond_time_table(self.handle, int(t0), int(n_t), table.data_ptr(), wp, wn, _lib.current_stream()),
@@ -557,7 +553,7 @@ class EpsEngine(_Engine):
         n = int(st.numel())
         n_cond = len(packing.eps_cond_modules(self.cfg)) * 2 * packing.padk(self.cfg.dim)
         table = torch.empty(n, n_cond, dtype=torch.float32, device=self.device)
-        ws = torch.empty(int(self.lib.dn_eps_cond_time_table_workspace_bytes(self.handle, n)) + 256, dtype=torch.uint8, device=self.device)
+        ws = _lib.alloc_workspace(self.lib.dn_eps_cond_time_table_workspace_bytes(self.handle, n), self.device)
         wp, wn = self._aligned(ws)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dn_eps_cond_time_table_steps(self.handle, st.data_ptr(), n, table.data_ptr(), wp, wn, _lib.current_stream()),

@@ -353,12 +353,11 @@ class KMeansQuantizer:
         units = torch.empty(M, dtype=torch.int32, device=self.device)
         if M == 0:
             return units
-        nbytes = int(self.lib.dn_kmeans_workspace_bytes(M, self.n))
-        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
-        wp = (ws.data_ptr() + 255) & ~255
+        ws = _lib.alloc_workspace(self.lib.dn_kmeans_workspace_bytes(M, self.n), self.device)
+        wp, wn = _lib.aligned(ws)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dn_kmeans_assign(feats.data_ptr(), self.centers.data_ptr(), self.half.data_ptr(), M, D, self.n, units.data_ptr(), wp,
-                                                 ws.numel() - (wp - ws.data_ptr()), _lib.current_stream()), "dn_kmeans_assign")
+                                                 wn, _lib.current_stream()), "dn_kmeans_assign")
         return units
 
 

@@ -132,16 +132,6 @@ class _HostRows:
 
 
 # ---------------------------------------------------------------- bindings of the three kernels
-def _aligned(nbytes: int, device) -> Tuple[torch.Tensor, int]:
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-    return ws, (ws.data_ptr() + 255) & ~255
-
-
-def _ws_args(workspace: torch.Tensor) -> Tuple[int, int]:
-    wp = (workspace.data_ptr() + 255) & ~255
-    return wp, workspace.numel() * workspace.element_size() - (wp - workspace.data_ptr())
-
-
 def _check_feats(feats: torch.Tensor, who: str) -> Tuple[int, int]:
     if feats.dim() != 2 or feats.dtype != torch.float32 or not feats.is_contiguous() or not feats.is_cuda:
         raise ValueError(f"{who}: feats must be a contiguous fp32 [M, D] device tensor")
@@ -170,8 +160,8 @@ def accumulate(feats: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor,
     sums, counts, inertia = out or (torch.empty(n, D, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
                                     torch.empty(1, dtype=torch.float64, device=dev))
     if workspace is None:
-        workspace = torch.empty(workspace_bytes(M, n) + 256, dtype=torch.uint8, device=dev)
-    wp, nb = _ws_args(workspace)
+        workspace = _lib.alloc_workspace(workspace_bytes(M, n), dev)
+    wp, nb = _lib.aligned(workspace)
     with torch.cuda.device(dev):
         _lib.check(lib.dn_kmeans_accumulate(feats.data_ptr(), labels.data_ptr(), centers.data_ptr(), M, D, n, sums.data_ptr(), counts.data_ptr(),
                                             inertia.data_ptr(), wp, nb, _lib.current_stream()), "dn_kmeans_accumulate")
@@ -200,8 +190,8 @@ def min_dist(feats: torch.Tensor, cands: torch.Tensor, mind2: torch.Tensor, comm
     dev = feats.device
     pot = torch.empty(k, dtype=torch.float64, device=dev) if pot is None else pot
     if workspace is None:
-        workspace = torch.empty(workspace_bytes(M, 1) + 256, dtype=torch.uint8, device=dev)
-    wp, nb = _ws_args(workspace)
+        workspace = _lib.alloc_workspace(workspace_bytes(M, 1), dev)
+    wp, nb = _lib.aligned(workspace)
     with torch.cuda.device(dev):
         _lib.check(_lib.load().dn_kmeans_min_dist(feats.data_ptr(), M, D, cands.data_ptr(), k, commit, mind2.data_ptr(), pot.data_ptr(), wp, nb,
                                                   _lib.current_stream()), "dn_kmeans_min_dist")
@@ -254,8 +244,8 @@ class KMeansTrainer:
     def _reserve(self, rows: int):
         if rows > self._rows:
             self._labels = torch.empty(rows, dtype=torch.int32, device=self.device)
-            self._assign_ws = torch.empty(int(self.lib.dn_kmeans_workspace_bytes(rows, self.n)) + 256, dtype=torch.uint8, device=self.device)
-            self._train_ws = torch.empty(workspace_bytes(rows, self.n) + 256, dtype=torch.uint8, device=self.device)
+            self._assign_ws = _lib.alloc_workspace(self.lib.dn_kmeans_workspace_bytes(rows, self.n), self.device)
+            self._train_ws = _lib.alloc_workspace(workspace_bytes(rows, self.n), self.device)
             self._rows = rows
 
     def _device_feats(self, feats) -> torch.Tensor:
@@ -278,7 +268,7 @@ class KMeansTrainer:
         rng = np.random.RandomState(seed)
         first = int(rng.randint(M))
         draws = torch.from_numpy(rng.uniform(size=(max(self.n - 1, 1), trials))).to(self.device)
-        ws = torch.empty(workspace_bytes(M, 1) + 256, dtype=torch.uint8, device=self.device)
+        ws = _lib.alloc_workspace(workspace_bytes(M, 1), self.device)
         mind2 = torch.full((M,), float("inf"), dtype=torch.float32, device=self.device)
         pot, pot1 = torch.empty(trials, dtype=torch.float64, device=self.device), torch.empty(1, dtype=torch.float64, device=self.device)
         picks = torch.empty(self.n, dtype=torch.int64, device=self.device)
@@ -304,7 +294,7 @@ class KMeansTrainer:
     def _assign(self, x: torch.Tensor) -> torch.Tensor:
         M = x.shape[0]
         self._reserve(M)
-        wp, nb = _ws_args(self._assign_ws)
+        wp, nb = _lib.aligned(self._assign_ws)
         _lib.check(self.lib.dn_kmeans_assign(x.data_ptr(), self.centers.data_ptr(), self.half.data_ptr(), M, self.D, self.n, self._labels.data_ptr(), wp, nb,
                                              _lib.current_stream()), "dn_kmeans_assign")
         return self._labels[:M]

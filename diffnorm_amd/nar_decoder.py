@@ -313,7 +313,7 @@ class NarDecoderEngine(_NarEngine):
         B, S, D = enc_out.shape
         assert D == self.dim and enc_out.is_contiguous() and enc_out.dtype == torch.float32 and enc_out.device == self.device
         tdt = self._kv_dtype
-        raw = torch.empty(int(self.lib.dn_nar_cross_kv_bytes(self.handle, B, S)) + 256, dtype=torch.uint8, device=self.device)
+        raw = _lib.alloc_workspace(self.lib.dn_nar_cross_kv_bytes(self.handle, B, S), self.device)
         off = (-raw.data_ptr()) % 256
         ckv = raw[off: off + self.layers * B * S * 2 * D * tdt.itemsize].view(tdt).view(self.layers, B, S, 2 * D)
         wp, wn = self._ws_for(B, 1, S)
@@ -366,8 +366,7 @@ class NarDecoderEngine(_NarEngine):
         """dn_nar_null_cross: the fp32 [layers, dim] table of c_l = W_o (W_v emb[null_token] + b_v) + b_o, formed on the device in the
         engine's arithmetic, once per engine and token.  -> a view of the table (it lives in a buffer this engine keeps)."""
         if self.null_token != int(null_token):
-            n = int(self.lib.dn_nar_null_cross_bytes(self.handle))
-            buf = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
+            buf = _lib.alloc_workspace(self.lib.dn_nar_null_cross_bytes(self.handle), self.device)
             wp, wn = self._aligned(buf)
             with torch.cuda.device(self.device):
                 _lib.check(self.lib.dn_nar_null_cross(self.handle, int(null_token), wp, wn, _lib.current_stream()), "dn_nar_null_cross")
@@ -433,7 +432,7 @@ class _IterationGraph:
         self.ckv = torch.empty(eng.layers, B, S, 2 * eng.dim, dtype=eng._kv_dtype, device=dev)
         self.slen = torch.empty(B, dtype=torch.int32, device=dev)
         self._src_id = None
-        self._ws = torch.empty(eng._pass_bytes(B, T, S, scale is not None) + 256, dtype=torch.uint8, device=dev)
+        self._ws = _lib.alloc_workspace(eng._pass_bytes(B, T, S, scale is not None), dev)
 
     def load(self, enc, tokens, scores=None, step=None):
         """The state the next run() starts from; `enc` has been through the model's _prepared()."""

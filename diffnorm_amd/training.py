@@ -201,10 +201,8 @@ class _FlatEngine:
         """(256-byte aligned address, bytes behind it) of the workspace, grown to `need` bytes."""
         if self._ws is None or self._ws.numel() < need + 256:
             self._ws = None
-            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-        p = self._ws.data_ptr()
-        a = (p + 255) & ~255
-        return a, self._ws.numel() - (a - p)
+            self._ws = _lib.alloc_workspace(need, self.device)
+        return _lib.aligned(self._ws)
 
 
 class VaeTrainEngine(_FlatEngine):

@@ -183,6 +183,23 @@ def test_workspace_regrowth_large_small_large():
     assert all(torch.equal(a, b) for a, b in zip(first, third))
 
 
+def test_stage_times_of_a_profiled_forward():
+    """set_profile(True), one forward: stage_times() gives one finite, non-negative ms per stage of HubertEngine.STAGES; switched off
+    again, the next forward returns the same bits."""
+    import math
+
+    eng = engine("f32")
+    waves = [R.make_wave(3000, 300), R.make_wave(1999, 301)]
+    base = run(eng, waves, 3)
+    eng.set_profile(True)
+    profiled = run(eng, waves, 3)
+    times = eng.stage_times()
+    eng.set_profile(False)
+    assert len(times) == len(eng.STAGES) == 5 and all(math.isfinite(t) and t >= 0.0 for t in times), times
+    after = run(eng, waves, 3)
+    assert all(torch.equal(a, b) and torch.equal(a, c) for a, b, c in zip(base, profiled, after))
+
+
 @pytest.mark.parametrize("dtype", ["f32", "f16"])
 def test_chunked_reader_equals_the_chunks_alone(dtype):
     from diffnorm_amd import hubert

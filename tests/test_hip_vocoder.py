@@ -133,3 +133,21 @@ def test_workspace_regrowth_and_recreation(tiny_sd, engines):
     assert not handle.value, "the engine was not destroyed with its last reference"
     fresh2 = V.CodeHiFiGANVocoder(tiny_sd, R.TINY_CFG, dtype="f32")
     assert torch.equal(fresh2.generate([torch.tensor([4, 5])], dur_prediction=True)[0], small[0])
+
+
+def test_stage_times_of_a_profiled_forward(engines):
+    """set_profile(True), one forward: stage_times() gives n_ups + 2 finite, non-negative ms (embedding + conv_pre, each upsampling stage,
+    conv_post); switched off again, the next forward returns the same bits."""
+    import math
+
+    voc = engines["f32"]
+    units = [torch.tensor(u) for u in R.TINY_UNITS]
+    base = voc.generate(units, dur_prediction=True)
+    voc.engine.set_profile(True)
+    profiled = voc.generate(units, dur_prediction=True)
+    times = voc.engine.stage_times()
+    voc.engine.set_profile(False)
+    assert len(times) == len(R.TINY_CFG["upsample_rates"]) + 2 and all(math.isfinite(t) and t >= 0.0 for t in times), times
+    after = voc.generate(units, dur_prediction=True)
+    for a, b, c in zip(base, profiled, after):
+        assert torch.equal(a, b) and torch.equal(a, c)
