@@ -139,7 +139,8 @@ def attention(q, k, v, out, B, T, heads, dim_head, lengths: Optional[torch.Tenso
 def rel_attention(q, k, v, pos, bias_u, bias_v, lengths, heads: int, pos_zero_row: int, x3: bool = False):
     """dn_rel_attention: q, k, v [B, T, heads * dk] and pos [rows, heads * dk] (offset d at row pos_zero_row + d) in one element type
     (fp32, bf16 or fp16; x3: fp32 tensors, DN_BF16X3 mode), bias_u / bias_v fp32 [heads, dk], lengths int32 [B] (each in [1, T]) or
-    None -> out [B, T, heads * dk] in that type (x3: fp32, read back from the split rows)."""
+    None -> out [B, T, heads * dk] in that type (x3: fp32, read back from the split rows, whose row stride is heads * dk rounded up
+    to a multiple of 32)."""
     from . import packing
 
     B, T, hd = q.shape
@@ -150,16 +151,18 @@ def rel_attention(q, k, v, pos, bias_u, bias_v, lengths, heads: int, pos_zero_ro
     q, k, v, pos = (t.contiguous() for t in (q, k, v, pos))
     a = _lib.RelAttnParams()
     a.dtype = _lib.DN_BF16X3 if x3 else _code(q)
-    out = torch.empty((B, T, 2 * hd), dtype=torch.bfloat16, device=q.device) if x3 else torch.empty_like(q)
+    ldo = -(-hd // 32) * 32 if x3 else hd  # split rows come in groups of 32 elements: a narrower output gets padded rows
+    out = torch.empty((B, T, 2 * ldo), dtype=torch.bfloat16, device=q.device) if x3 else torch.empty_like(q)
     a.q, a.k, a.v, a.out, a.pos = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), pos.data_ptr()
-    a.ldq = a.ldk = a.ldv = a.ldo = a.ldp = hd
+    a.ldq = a.ldk = a.ldv = a.ldp = hd
+    a.ldo = ldo
     a.B, a.T, a.heads, a.dim_head = B, T, heads, hd // heads
     a.lengths = _lib.ptr(None if lengths is None else lengths.to(q.device, torch.int32).contiguous())
     a.scale, a.pos_zero_row, a.pos_rows = (hd // heads) ** -0.5, pos_zero_row, pos.shape[0]
     bu, bv = bias_u.to(q.device, torch.float32).contiguous(), bias_v.to(q.device, torch.float32).contiguous()
     a.bias_u, a.bias_v = bu.data_ptr(), bv.data_ptr()
     _lib.check(_lib.load().dn_rel_attention(C.byref(a), _stream()), "dn_rel_attention")
-    return packing.unsplit_rows(out) if x3 else out
+    return packing.unsplit_rows(out)[..., :hd].contiguous() if x3 else out
 
 
 def glu_dwconv(x, w, shift, dtype: Optional[int] = None):

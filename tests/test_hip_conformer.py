@@ -63,7 +63,7 @@ def _attn_ref(q, k, v, pos, u, vb, lens, H, Tmax, rnd=None):
 
 @pytest.mark.parametrize("mode", ["f32", "x3", "f16", "bf16"])
 @pytest.mark.parametrize("T", [1, 17, 64, 65, 130, 300])
-@pytest.mark.parametrize("dk", [16, 64])
+@pytest.mark.parametrize("dk", [16, 32, 64])
 def test_rel_attention_matches_float64(mode, T, dk):
     """dn_rel_attention against the float64 restatement of score = ((q + u) k + (q + v) P(i - j)) / sqrt(dk) on the operands the device
     holds.  Bar: FWD_TOL of the attention grid for the mode, relative to the output's max; in the 2-byte modes the maximum of that and
@@ -130,6 +130,19 @@ def test_rel_attention_c_abi_refuses_a_table_that_is_too_short():
             _lib.check(_lib.load().dn_rel_attention(C.byref(a), _lib.current_stream()), "dn_rel_attention")
 
 
+def _glu_dwconv_ref(xs, w, shift):
+    """float64 swish(depthwise_conv(glu(xs)) + shift) on xs [B, S, 2 C] (float64, what the device holds), w [C, k], shift [C]."""
+    C, k = w.shape
+    y = torch.nn.functional.glu(xs, dim=-1).transpose(1, 2)
+    y = torch.nn.functional.conv1d(y, w.double()[:, None, :], None, 1, k // 2, 1, C) + shift.double()[None, :, None]
+    return torch.nn.functional.silu(y).transpose(1, 2)
+
+
+def _glu_dwconv_bound(mode, scale):
+    """1e-5 x scale in fp32 arithmetic; the 2-byte modes add one unit roundoff of the format, the split-row store of x3 2^-16."""
+    return (1e-5 + UNIT.get(mode, 2.0 ** -16 if mode == "x3" else 0.0)) * scale
+
+
 @pytest.mark.parametrize("mode", ["f32", "x3", "f16", "bf16"])
 @pytest.mark.parametrize("S", [1, 14, 15, 16, 100])
 @pytest.mark.parametrize("k,C", [(3, 64), (31, 64), (31, 512), (3, 512)])
@@ -142,14 +155,11 @@ def test_glu_dwconv_matches_float64(mode, S, k, C):
     B = 3
     x = _randn(7 * S + k + C, B, S, 2 * C)
     w, shift = _randn(11 + k + C, C, k) * k ** -0.5, 0.3 * _randn(13 + k + C, C)
-    xs = _rt(x, mode)
-    y = torch.nn.functional.glu(xs, dim=-1).transpose(1, 2)
-    y = torch.nn.functional.conv1d(y, w.double()[:, None, :], None, 1, k // 2, 1, C) + shift.double()[None, :, None]
-    want = torch.nn.functional.silu(y).transpose(1, 2)
+    want = _glu_dwconv_ref(_rt(x, mode), w, shift)
     scale = want.abs().max().item()
     got = ops.glu_dwconv(x.to(STORE[mode]).to(DEV), w.to(DEV), shift.to(DEV), dtype=_lib.DN_BF16X3 if mode == "x3" else None)
     err = (got.double().cpu() - want).abs().max().item()
-    bound = (1e-5 + UNIT.get(mode, 2.0 ** -16 if mode == "x3" else 0.0)) * scale
+    bound = _glu_dwconv_bound(mode, scale)
     print(f"glu_dwconv {mode} k={k} C={C} S={S}: bound {bound:.3e} measured {err:.3e}")
     assert got.shape == (B, S, C) and err < bound
 
